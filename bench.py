@@ -30,6 +30,12 @@ reference's codec family: byte shuffle + zstd-5 per 64^3 chunk through libzstd).
 the GPU's and the port's output on the same 256^3 volume against the clean volume.  `bm4dnet`
 (config 3's learned stage, measured at the full 1024^3) and `encoded` (compression ratios of the
 encode legs next to shuffle + zstd-5 on sampled chunks) are extra keys outside `value`.
+
+`--dump-outputs DIR` (--mode volumes) writes what rank 0's last timed step computed as DIR/<name>.npy
+(float32 / float64, under 64 MB in all): the denoised volume, the DCT indices and the two encode legs'
+chunk sizes, offsets and packed streams -- all of an array when it is small, else a fixed seeded sample of
+its elements in index order.  The input volume is a function of --size and the rank, so two builds run
+with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -132,6 +138,45 @@ def synth_clean(shape, seed):
 def psnr_db(a, ref, peak):
     mse = float(np.mean((np.asarray(a, np.float64) - np.asarray(ref, np.float64)) ** 2))
     return float("inf") if mse == 0.0 else 10.0 * np.log10(peak * peak / mse)
+
+
+DUMP_LIMIT = 64 << 20     # bytes of all --dump-outputs files together
+DUMP_SEED = 0xD0D0
+
+
+def dump_sample(a, k, tag, dtype):
+    """a flattened, as `dtype`; when it holds more than k elements, a fixed seeded sample of k of them
+    (index order; the sample depends on the element count and `tag` only)."""
+    a = a.ravel()
+    if a.size > k:
+        rng = np.random.default_rng([DUMP_SEED, tag])
+        a = a[np.sort(rng.choice(a.size, size=k, replace=False))]
+    return a.astype(dtype)
+
+
+def timed_outputs(denoised, indices=None, *encodes):
+    """--dump-outputs of the volumes mode: the denoised uint16 volume (host array); `indices` = (count,
+    device buffer) of the DCT leg's int32 indices; `encodes` = (name, chunks, streams, offsets, sizes)
+    device buffers of each encode leg, as exabm4d_codec_encode_dev filled them."""
+    out = {"denoised": dump_sample(denoised, 1 << 22, 0, np.float32)}
+    if indices is not None:
+        n, buf = indices
+        out["dct_indices"] = dump_sample(buf.download((n,), np.int32), 1 << 21, 1, np.float64)
+    for tag, (name, n, d_enc, d_off, d_sz) in enumerate(encodes, 2):
+        off = d_off.download((n + 1,), np.uint64)
+        out[f"{name}_sizes"] = d_sz.download((n,), np.uint32).astype(np.float64)
+        out[f"{name}_offsets"] = off.astype(np.float64)
+        out[f"{name}_stream"] = dump_sample(d_enc.download((int(off[-1]),), np.uint8), 1 << 20, tag, np.float32)
+    return out
+
+
+def write_outputs(path, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes is over the {DUMP_LIMIT}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def profile_record(kernel, shape, live_ms):
@@ -824,7 +869,14 @@ def main():
     ap.add_argument("--bm4dnet-tune", type=int, default=256,
                     help="edge of the volume the reference-like path (fast=False, MIOpen's own defaults, a fresh "
                          "child process: ~20 s of solver selection) is measured on; 0 disables")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="--mode volumes: write what rank 0's last timed step computed to DIR/<name>.npy "
+                         "(float32 / float64, seeded samples of the large arrays, under 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode != "volumes":
+        ap.error("--dump-outputs needs --mode volumes")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))     # every mode: volumes, slabs, chunks
@@ -967,6 +1019,11 @@ def main():
     sl = (slice(0, min(64, shape[0])),)
     resid = out[sl].astype(np.float32) - vol[sl].astype(np.float32)
     resid_std = float(resid.std())
+    if args.dump_outputs and rank == 0:
+        # the buffers still hold the last timed step's results (the end-to-end leg reuses d_out later)
+        legs = () if args.no_encode else ((nblk * 512, d_idx), ("encode_u16", nchunks, d_enc16, d_off16, d_sz16),
+                                          ("encode_idx", nchunks_i, d_enc32, d_off32, d_sz32))
+        write_outputs(args.dump_outputs, timed_outputs(out, *legs))
     encoded = None
     if not args.no_encode:
         sz16 = d_sz16.download((nchunks,), np.uint32).astype(np.uint64)

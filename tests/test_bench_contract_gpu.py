@@ -64,6 +64,60 @@ def test_default_line_has_the_contract_keys():
 
 
 @pytest.mark.gpu
+def test_dump_outputs_are_the_timed_steps_results(tmp_path):
+    """--dump-outputs: the same arrays whatever the step counts (the inputs are seeded, the path is
+    deterministic), float32 / float64 only, under 64 MB; at 64^3 nothing is sampled, so the two coded
+    streams decode (C oracle) to the dumped volume and indices."""
+    import numpy as np
+    from oracle import codec_oracle
+    base = ("--cpu-sample", "0", "--end-to-end", "0")
+    d = _run(*base, "--dump-outputs", str(tmp_path / "a"))
+    assert d["steps"] == 2
+    d = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "64", "--steps", "1",
+                        "--warmup", "0", "--bm4dnet", "0", *base, "--dump-outputs", str(tmp_path / "b")],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert d.returncode == 0, d.stderr[-2000:]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"denoised.npy", "dct_indices.npy", "encode_u16_sizes.npy", "encode_u16_offsets.npy",
+            "encode_u16_stream.npy", "encode_idx_sizes.npy", "encode_idx_offsets.npy",
+            "encode_idx_stream.npy"} <= set(names)
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n, a in got.items():
+        assert a.dtype in (np.float32, np.float64), n
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{n}.npy")), n
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["denoised"].size == 64 ** 3 and got["dct_indices"].size == 64 ** 3
+    for leg, typesize, want in (("encode_u16", 2, got["denoised"]), ("encode_idx", 4, got["dct_indices"])):
+        sizes, offsets, stream = got[f"{leg}_sizes"], got[f"{leg}_offsets"], got[f"{leg}_stream"]
+        assert sizes.size == 1 and offsets[0] == 0 and stream.size == offsets[-1] >= sizes[0] > 0
+        vals, used = codec_oracle.decode(stream[:int(sizes[0])].astype(np.uint8), 64 ** 3, typesize)
+        assert used == sizes[0] and np.array_equal(vals.astype(np.float64), want.astype(np.float64)), leg
+
+
+def test_dump_sample_is_fixed_and_exact():
+    """CPU: the sampler behind --dump-outputs takes all of a small array, a fixed sample of a large one
+    in index order, and converts without loss."""
+    import numpy as np
+    import bench
+    small = np.arange(1000, dtype=np.uint16)
+    assert np.array_equal(bench.dump_sample(small, 1000, 0, np.float32), small)
+    big = np.arange(1 << 20, dtype=np.int32) - (1 << 19)
+    a = bench.dump_sample(big, 4096, 1, np.float64)
+    assert a.dtype == np.float64 and a.size == 4096 and np.all(np.diff(a) > 0) and np.all(np.isin(a, big))
+    assert np.array_equal(a, bench.dump_sample(big.copy(), 4096, 1, np.float64))
+    assert not np.array_equal(a, bench.dump_sample(big, 4096, 2, np.float64))
+
+
+@pytest.mark.parametrize("args", [["--steps", "0"], ["--mode", "slabs", "--dump-outputs", "x"]])
+def test_bench_rejects_what_it_cannot_honour(args):
+    """CPU: no timed step, or a dump outside --mode volumes, is an argument error before any GPU work."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True,
+                         text=True, timeout=120, cwd=ROOT)
+    assert out.returncode == 2 and "error" in out.stderr, out.stderr[-2000:]
+
+
+@pytest.mark.gpu
 def test_no_encode_flag_says_so():
     d = _run("--no-encode", "--cpu-sample", "0")
     assert d["config"]["encode"] == "none" and "encode_u16" not in d["phase_ms"] and "cpu_baseline" not in d

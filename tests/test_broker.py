@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from aind_exaspim_image_compression import _native, bm4d as B, broker
+from util import socket_dir
 
 
 def test_default_device_rules(monkeypatch):
@@ -85,8 +86,14 @@ def _worker(args):
     return ok
 
 
-def test_broker_protocol_coalesces_forked_workers(monkeypatch, tmp_path):
-    monkeypatch.setenv(broker.ENV_DIR, str(tmp_path))
+@pytest.fixture
+def sock_dir(tmp_path):
+    with socket_dir(tmp_path, room=3) as d:                # room: the "s1/" sub-directories of one test
+        yield d
+
+
+def test_broker_protocol_coalesces_forked_workers(monkeypatch, sock_dir):
+    monkeypatch.setenv(broker.ENV_DIR, str(sock_dir))
     monkeypatch.setenv("EXABM4D_DEVICE", "0")
     fake = _FakeContext()
     monkeypatch.setattr(_native, "context", lambda device=None: fake)
@@ -129,11 +136,11 @@ class _OverlapContext(_FakeContext):
                 _OverlapContext.inside -= 1
 
 
-def test_two_calls_in_flight_and_one_slot(monkeypatch, tmp_path):
+def test_two_calls_in_flight_and_one_slot(monkeypatch, sock_dir):
     """slots=2: the clients are cut into two groups whose calls overlap (one group's workers do their host
     work while the other group's call runs); slots=1 is the lockstep form.  Same answers either way."""
     for slots, want_overlap in ((2, True), (1, False)):
-        d = tmp_path / f"s{slots}"
+        d = sock_dir / f"s{slots}"
         d.mkdir()
         monkeypatch.setenv(broker.ENV_DIR, str(d))
         monkeypatch.setenv("EXABM4D_DEVICE", "0")
@@ -158,8 +165,8 @@ def test_two_calls_in_flight_and_one_slot(monkeypatch, tmp_path):
         assert (_OverlapContext.most >= 2) == want_overlap
 
 
-def test_broker_reports_errors_instead_of_hanging(monkeypatch, tmp_path):
-    monkeypatch.setenv(broker.ENV_DIR, str(tmp_path))
+def test_broker_reports_errors_instead_of_hanging(monkeypatch, sock_dir):
+    monkeypatch.setenv(broker.ENV_DIR, str(sock_dir))
 
     class Failing:
         def denoise_f32_host_v(self, *a, **k):

@@ -11,7 +11,7 @@ import sys
 import numpy as np
 import pytest
 
-from util import psnr, synth_volume
+from util import psnr, socket_dir, synth_volume
 
 pytestmark = pytest.mark.gpu
 HELPER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers", "fork_workers.py")
@@ -35,11 +35,12 @@ def test_broker_coalesces_the_workers_single_patch_calls(oracle, tmp_path, monke
     HIP context), 24 single-patch bm4d() calls, one GPU-owner process that batches what is pending.  Every
     volume of a batched call has its own fixed-point unit, so the teachers are the oracle's bit for bit,
     whatever a patch happened to be batched with."""
-    monkeypatch.setenv("EXABM4D_BROKER_DIR", str(tmp_path))
     out = tmp_path / "teachers.npy"
-    r = subprocess.run([sys.executable, HELPER, "broker", str(out), "8", "24"], capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, (r.stderr[-2000:], open(next(tmp_path.glob("*.log"))).read()[-2000:])
+    with socket_dir(tmp_path) as d:
+        monkeypatch.setenv("EXABM4D_BROKER_DIR", str(d))
+        r = subprocess.run([sys.executable, HELPER, "broker", str(out), "8", "24"], capture_output=True,
+                           text=True, timeout=900)
+        assert r.returncode == 0, (r.stderr[-2000:], open(next(d.glob("*.log"))).read()[-2000:])
     got = np.load(out)
     assert got.shape == (24, 64, 64, 64)
     for i in (0, 7, 23):

@@ -1,4 +1,10 @@
-"""Shared synthetic-data helpers for the tests (deterministic, numpy only)."""
+"""Shared helpers for the tests: deterministic synthetic data (numpy only), a directory for sockets."""
+import contextlib
+import os
+import pathlib
+import shutil
+import tempfile
+
 import numpy as np
 
 
@@ -43,3 +49,19 @@ def metric_inputs(seed, shape=(40, 36, 44)):
     pred_u16 = np.rint(pred_f32).astype(np.uint16)
     fg = clean > 1000
     return pred_u16, pred_f32, raw, target, fg
+
+
+@contextlib.contextmanager
+def socket_dir(tmp_path, room=0):
+    """A directory for the broker's AF_UNIX socket (plus `room` bytes of sub-directories): tmp_path when the
+    socket path fits in the 107 bytes such a path may hold, else a fresh short directory under /tmp -- pytest's
+    tmp_path under a long TMPDIR or user name goes past the limit."""
+    from aind_exaspim_image_compression import broker
+    if len(str(tmp_path)) + room + 1 + len(os.path.basename(broker.socket_path(0))) <= 107:
+        yield pathlib.Path(tmp_path)
+        return
+    d = tempfile.mkdtemp(prefix="exb-", dir="/tmp")
+    try:
+        yield pathlib.Path(d)
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
