@@ -11,6 +11,13 @@
 // x[b][s][c], s = (d, h, w) flattened, c fastest; groups of C / G consecutive channels.  C % 4 == 0 and
 // (C / G) % 4 == 0: a float4 of channels never straddles a group.  fp32 data, fp64 statistics; the partial sums
 // are combined in a fixed order, so the result is a deterministic function of the input.
+//
+// The statistics are formed around pivots, so that their rounding scales with the spread of a group and not
+// with its mean (a sum of squares formed around zero and a variance taken as E[x^2] - mean^2 lose (mean / std)^2
+// ulp): each thread sums x - k and (x - k)^2 in fp32 per channel, k = the channel's value at spatial row 0 of
+// the sample; it then moves its four channels' sums in fp64 to the group's reference p (the pivot of the group's
+// first channel), sum (x - p) = S' + n d and sum (x - p)^2 = Q' + 2 d S' + n d^2 with d = k - p, and the
+// fixed-order reduction adds those.  A non-finite value makes the group's variance NaN, and the group NaN.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -20,7 +27,16 @@ namespace exabm4d {
 
 constexpr int GN_THREADS = 256;
 
-// Partial sums of one (sample, chunk of rows): part[((b * nchunk + chunk) * G + g) * 2 + {0: sum, 1: sum of squares}]
+// Partial sums of one (sample, chunk of rows) about the group's reference p:
+// part[((b * nchunk + chunk) * G + g) * 2 + {0: sum of (x - p), 1: sum of (x - p)^2}]
+__device__ __forceinline__ float group_pivot(const float* x, size_t spatial, int C, int b, int c0, const float* cbias) {
+    return x[(size_t)b * spatial * C + c0] + (cbias ? cbias[c0] : 0.0f);
+}
+__device__ __forceinline__ void acc_shifted(float4& s, float4& q, const float4 v, const float4 k) {
+    const float dx = v.x - k.x, dy = v.y - k.y, dz = v.z - k.z, dw = v.w - k.w;
+    s.x += dx; s.y += dy; s.z += dz; s.w += dw;
+    q.x += dx * dx; q.y += dy * dy; q.z += dz * dz; q.w += dw * dw;
+}
 __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const float* __restrict__ x, size_t spatial, int C,
                                                              int G, int nchunk, size_t rows_per_chunk,
                                                              double* __restrict__ part,
@@ -34,30 +50,43 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const float* __res
     const size_t r0 = (size_t)chunk * rows_per_chunk;
     const size_t r1 = r0 + rows_per_chunk < spatial ? r0 + rows_per_chunk : spatial;
     const float4* base = reinterpret_cast<const float4*>(x + (size_t)b * spatial * C) + lane;
-    float s0 = 0.0f, s1 = 0.0f, q0 = 0.0f, q1 = 0.0f;     // two accumulators each: shorter dependency chains
     const float4 cb = cbias ? reinterpret_cast<const float4*>(cbias)[lane] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     auto ld = [&](size_t row) {
         float4 v = base[row * lanes];
         v.x += cb.x; v.y += cb.y; v.z += cb.z; v.w += cb.w;
         return v;
     };
+    const float4 k = ld(0);                          // the four channels' pivots
+    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 s0 = zero, s1 = zero, q0 = zero, q1 = zero;   // two accumulators each: shorter dependency chains
+    int cnt = 0;                                     // rows this thread visits
     size_t r = r0 + rsub;
     for (; r + rows_per_iter < r1; r += 2 * (size_t)rows_per_iter) {
-        const float4 a = ld(r);
-        const float4 c = ld(r + rows_per_iter);
-        s0 += (a.x + a.y) + (a.z + a.w);
-        q0 += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
-        s1 += (c.x + c.y) + (c.z + c.w);
-        q1 += (c.x * c.x + c.y * c.y) + (c.z * c.z + c.w * c.w);
+        acc_shifted(s0, q0, ld(r), k);
+        acc_shifted(s1, q1, ld(r + rows_per_iter), k);
+        cnt += 2;
     }
     if (r < r1) {
-        const float4 a = ld(r);
-        s0 += (a.x + a.y) + (a.z + a.w);
-        q0 += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
+        acc_shifted(s0, q0, ld(r), k);
+        cnt += 1;
+    }
+    // to the group's reference p in fp64: sum (x - p) = S' + n d, sum (x - p)^2 = Q' + 2 d S' + n d^2, d = k - p
+    const int cpg = C / G;
+    const double p = (double)group_pivot(x, spatial, C, b, (4 * lane / cpg) * cpg, cbias);
+    const double n = (double)cnt;
+    const float kk[4] = {k.x, k.y, k.z, k.w};
+    const float sa[4] = {s0.x, s0.y, s0.z, s0.w}, sb[4] = {s1.x, s1.y, s1.z, s1.w};
+    const float qa[4] = {q0.x, q0.y, q0.z, q0.w}, qb[4] = {q1.x, q1.y, q1.z, q1.w};
+    double st = 0.0, qt = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const double d = (double)kk[j] - p, sj = (double)sa[j] + (double)sb[j], qj = (double)qa[j] + (double)qb[j];
+        st += sj + n * d;
+        qt += qj + 2.0 * d * sj + n * d * d;
     }
     __shared__ double sh[GN_THREADS][2];
-    sh[threadIdx.x][0] = (double)s0 + (double)s1;
-    sh[threadIdx.x][1] = (double)q0 + (double)q1;
+    sh[threadIdx.x][0] = st;
+    sh[threadIdx.x][1] = qt;
     __syncthreads();
     // thread g sums its group's entries in a fixed order: lanes [g * lanes / G, (g + 1) * lanes / G) of every row slot
     if ((int)threadIdx.x < G) {
@@ -68,9 +97,9 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const float* __res
                 s += sh[rs * lanes + l][0];
                 q += sh[rs * lanes + l][1];
             }
-        double* p = part + (((size_t)b * nchunk + chunk) * G + g) * 2;
-        p[0] = s;
-        p[1] = q;
+        double* pp = part + (((size_t)b * nchunk + chunk) * G + g) * 2;
+        pp[0] = s;
+        pp[1] = q;
     }
 }
 
@@ -78,19 +107,20 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const float* __res
 __global__ void gn_params_kernel(const double* __restrict__ part, int batch, int C, int G, int nchunk,
                                  double count, const float* __restrict__ gamma, const float* __restrict__ beta,
                                  float eps, float* __restrict__ a, float* __restrict__ shift,
-                                 const float* __restrict__ cbias) {
+                                 const float* __restrict__ cbias, const float* __restrict__ x, size_t spatial) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= batch * C) return;
-    const int b = i / C, c = i - b * C, g = c / (C / G);
+    const int b = i / C, c = i - b * C, cpg = C / G, g = c / cpg;
     double s = 0.0, q = 0.0;
     for (int k = 0; k < nchunk; k++) {
         const double* p = part + (((size_t)b * nchunk + k) * G + g) * 2;
         s += p[0];
         q += p[1];
     }
-    const double mean = s / count;
-    double var = q / count - mean * mean;
-    var = var > 0.0 ? var : 0.0;
+    const double m = s / count;                      // the mean of x - p
+    double var = q / count - m * m;
+    var = var < 0.0 ? 0.0 : var;                     // (a NaN stays NaN: a non-finite input makes the group NaN)
+    const double mean = (double)group_pivot(x, spatial, C, b, g * cpg, cbias) + m;
     const float rstd = (float)(1.0 / sqrt(var + (double)eps));
     const float ga = gamma ? gamma[c] : 1.0f, be = beta ? beta[c] : 0.0f;
     const float av = rstd * ga;
@@ -254,7 +284,8 @@ hipError_t launch_groupnorm_lrelu_ndhwc(const float* x, float* y, int batch, siz
                        C, G, (int)nchunk, rows_per_chunk, part, cbias);
     const int total = batch * C;
     hipLaunchKernelGGL(gn_params_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, part, batch, C, G,
-                       (int)nchunk, (double)spatial * (double)(C / G), gamma, beta, eps, a, shift, cbias);
+                       (int)nchunk, (double)spatial * (double)(C / G), gamma, beta, eps, a, shift, cbias, x,
+                       spatial);
     const size_t n4 = spatial * (size_t)lanes;
     size_t blocks = (n4 + GN_THREADS - 1) / GN_THREADS;
     const size_t cap = (8192 + (size_t)batch - 1) / (size_t)batch;

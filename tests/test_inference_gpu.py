@@ -142,8 +142,9 @@ def test_ndhwc_shadow_matches_the_reference_cpu_output_and_leaves_the_model_alon
                                    (33, 32, 4, 4, 4), (2, 96, 8, 8, 8)])
 def test_fused_groupnorm_leakyrelu_on_ndhwc(shape):
     """The BM4DNet stage's GroupNorm + LeakyReLU pairs as one NDHWC kernel pair (csrc/nn_kernels.hip) against
-    the framework's two modules: fp64 statistics here, Welford in fp32 there -- agreement to a few ulp of
-    the normalised values; the fused result is a deterministic function of its input; 96 channels (24 float4
+    the framework's two modules at mean/std ~ 0.5: fp64 reductions of fp32 sums around per-channel pivots here,
+    Welford in fp32 there -- agreement to 2e-5 (3e-5 with the bias; the fp64 reference and a bound that holds at
+    any mean/std: tests/test_nn_kernels_gpu.py); the fused result is a deterministic function of its input; 96 channels (24 float4
     lanes do not divide a workgroup) take the framework's path through the same module."""
     b, c = shape[:2]
     g = torch.Generator().manual_seed(sum(shape))
