@@ -29,6 +29,7 @@ c_vp = ctypes.c_void_p
 KEY_EMPTY = 0xFFFFFFFF
 DATA_EXP_AUTO = -2 ** 31    # exabm4d.h EXABM4D_DATA_EXP_AUTO: E per volume from the data (fp32 entry points)
 DATA_EXP_U16 = 17           # exabm4d.h EXABM4D_DATA_EXP_U16: the uint16 pipelines' fixed E
+DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2   # exabm4d.h exabm4d_dtype: element types of the *_dt_dev entries
 
 
 class Params(ctypes.Structure):
@@ -121,6 +122,10 @@ SIGNATURES = {
                                                 c_vp]),
     "exabm4d_maxpool2_ndhwc_dev": (_I, [_CTX, c_vp, c_vp, c_vp, _I, _I, _I, _I, _I]),
     "exabm4d_upsample2_trilinear_ndhwc_dev": (_I, [_CTX, c_vp, c_vp, c_vp, _I, _I, _I, _I, _I]),
+    "exabm4d_groupnorm_lrelu_ndhwc_dt_dev": (_I, [_CTX, c_vp, _I, c_vp, c_vp, _I, _SZ, _I, _I, c_vp, c_vp, _F, _F,
+                                                   c_vp, _SZ, c_vp]),
+    "exabm4d_maxpool2_ndhwc_dt_dev": (_I, [_CTX, c_vp, _I, c_vp, c_vp, _I, _I, _I, _I, _I]),
+    "exabm4d_upsample2_trilinear_ndhwc_dt_dev": (_I, [_CTX, c_vp, _I, c_vp, c_vp, _I, _I, _I, _I, _I]),
     "exabm4d_host_register": (_I, [_CTX, c_vp, ctypes.c_size_t]),
     "exabm4d_host_unregister": (_I, [_CTX, c_vp]),
     "exabm4d_transform_forward_u16_dev": (_I, [_CTX, _TP, c_vp, c_vp, _SZ]),
@@ -471,23 +476,25 @@ class Context:
 
     # -- BM4DNet stage ---------------------------------------------------------------------------
     def groupnorm_lrelu_ndhwc(self, stream, x, y, batch, spatial, channels, groups, gamma, beta, eps, slope,
-                              workspace, workspace_bytes, conv_bias=None):
-        """GroupNorm + LeakyReLU on an NDHWC fp32 tensor (x, y, gamma, beta, workspace: device pointers or
-        objects with ``data_ptr()``; ``stream``: the HIP stream handle to run on).  ValueError where the
-        fused kernels do not apply (see the header)."""
-        self._check(lib().exabm4d_groupnorm_lrelu_ndhwc_dev(
-            self.handle, int(stream), _ptr(x), _ptr(y), int(batch), int(spatial), int(channels), int(groups),
-            _ptr(gamma) if gamma is not None else None, _ptr(beta) if beta is not None else None,
+                              workspace, workspace_bytes, conv_bias=None, dtype=DTYPE_F32):
+        """GroupNorm + LeakyReLU on an NDHWC tensor of ``dtype`` (a DTYPE_* code; x, y, gamma, beta, workspace:
+        device pointers or objects with ``data_ptr()``; gamma, beta and conv_bias fp32 for every dtype;
+        ``stream``: the HIP stream handle to run on).  ValueError where the fused kernels do not apply (see the
+        header)."""
+        self._check(lib().exabm4d_groupnorm_lrelu_ndhwc_dt_dev(
+            self.handle, int(stream), int(dtype), _ptr(x), _ptr(y), int(batch), int(spatial), int(channels),
+            int(groups), _ptr(gamma) if gamma is not None else None, _ptr(beta) if beta is not None else None,
             float(eps), float(slope), _ptr(workspace), int(workspace_bytes),
             _ptr(conv_bias) if conv_bias is not None else None))
 
-    def maxpool2_ndhwc(self, stream, x, y, batch, d, h, w, channels):
-        self._check(lib().exabm4d_maxpool2_ndhwc_dev(self.handle, int(stream), _ptr(x), _ptr(y), int(batch), int(d),
-                                                     int(h), int(w), int(channels)))
+    def maxpool2_ndhwc(self, stream, x, y, batch, d, h, w, channels, dtype=DTYPE_F32):
+        self._check(lib().exabm4d_maxpool2_ndhwc_dt_dev(self.handle, int(stream), int(dtype), _ptr(x), _ptr(y),
+                                                        int(batch), int(d), int(h), int(w), int(channels)))
 
-    def upsample2_trilinear_ndhwc(self, stream, x, y, batch, d, h, w, channels):
-        self._check(lib().exabm4d_upsample2_trilinear_ndhwc_dev(self.handle, int(stream), _ptr(x), _ptr(y),
-                                                                int(batch), int(d), int(h), int(w), int(channels)))
+    def upsample2_trilinear_ndhwc(self, stream, x, y, batch, d, h, w, channels, dtype=DTYPE_F32):
+        self._check(lib().exabm4d_upsample2_trilinear_ndhwc_dt_dev(self.handle, int(stream), int(dtype), _ptr(x),
+                                                                   _ptr(y), int(batch), int(d), int(h), int(w),
+                                                                   int(channels)))
 
     def host_register(self, addr, nbytes):
         """Page-lock caller memory that host entry points copy from / to repeatedly (see the header)."""

@@ -13,6 +13,7 @@ buffers that stay in HBM, and only the uint16 result comes back.  The U-Net itse
 Reference quirk kept on purpose (inference.py:91-103): the first ``trim``
 voxels along every axis receive zero weight and come out as ``transform.inverse(0)``.
 """
+import contextlib
 import itertools
 import os
 
@@ -26,6 +27,18 @@ from aind_exaspim_image_compression.machine_learning.transforms import (
     with_offset,
 )
 from aind_exaspim_image_compression.machine_learning.unet3d import N2V2UNet, UNet
+
+# predict(precision=...): the autocast dtype of the forward passes (None: fp32, no autocast)
+PRECISIONS = {"fp32": None, "fp16": torch.float16, "bf16": torch.bfloat16}
+# element types of libexabm4d's NDHWC entries; the half-width ones only for a reduced-precision shadow's modules
+_NATIVE_DTYPES = {torch.float32: _native.DTYPE_F32, torch.float16: _native.DTYPE_F16,
+                  torch.bfloat16: _native.DTYPE_BF16}
+
+
+def _native_dtype(dtype, half):
+    """The libexabm4d element-type code for tensors of ``dtype``, or None where the NDHWC modules fall back."""
+    code = _NATIVE_DTYPES.get(dtype)
+    return code if code == _native.DTYPE_F32 or half else None
 
 
 def _model_device(model):
@@ -45,8 +58,8 @@ def _miopen_defaults():
     """Once per process, before its first convolution (``predict`` / ``load_model`` call it): make MIOpen
     pick the tuned solvers for the BM4DNet U-Net without a search.
       * a per-user MIOpen user-db directory (``$XDG_CACHE_HOME/exabm4d/miopen/torch-<version>``) seeded with
-        the find-db records shipped in ``miopen_db/`` (12 KB of text MIOpen wrote during one exhaustive
-        search on an MI355X) -- unless the caller already chose ``MIOPEN_USER_DB_PATH``; searches the caller
+        the find-db records shipped in ``miopen_db/`` (27 KB of text MIOpen wrote during exhaustive searches
+        on an MI355X, fp32, fp16 and bf16) -- unless the caller already chose ``MIOPEN_USER_DB_PATH``; searches the caller
         runs later (``tune_model``) persist there too, so they are paid once per machine, not per process;
       * ``MIOPEN_FIND_MODE=2`` (FAST) unless the caller set the variable: a find-db hit selects the recorded
         solver at once, a miss falls back to heuristics instead of timing every solver (17 s per process
@@ -87,17 +100,21 @@ class FusedGroupNormLeakyReLU(torch.nn.Module):
     the activation and a layout copy back (45 % of the forward's kernel time).  Falls back to the framework's
     two modules for anything the kernels do not take (training, other dtypes / layouts / channel counts)."""
 
-    def __init__(self, norm, act, conv_bias=None):
+    def __init__(self, norm, act, conv_bias=None, half=False):
         """``conv_bias``: the bias of the convolution in front, taken over from it (the caller sets that
-        convolution's ``bias`` to None): added inside the kernels instead of in a pass of its own."""
+        convolution's ``bias`` to None): added inside the kernels instead of in a pass of its own.
+        ``half``: also take fp16 / bf16 tensors (the half-width kernels; gamma, beta and the bias stay fp32) --
+        for the shadow ``predict(precision="fp16" | "bf16")`` builds; otherwise those fall back as before."""
         super().__init__()
         self.norm, self.act = norm, act
         self.conv_bias = conv_bias
+        self.half = half
         self._ws = None
 
     def forward(self, x):
         n = self.norm
-        fused = (not self.training and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5
+        code = _native_dtype(x.dtype, self.half)
+        fused = (not self.training and x.is_cuda and code is not None and x.dim() == 5
                  and x.is_contiguous(memory_format=torch.channels_last_3d) and not torch.is_grad_enabled()
                  and n.num_channels % 4 == 0 and (n.num_channels // n.num_groups) % 4 == 0
                  and 256 % (n.num_channels // 4) == 0 and n.num_groups <= 32 and x.shape[0] <= 65535)
@@ -113,7 +130,7 @@ class FusedGroupNormLeakyReLU(torch.nn.Module):
         ctx = _native.context(x.device.index or 0)
         ctx.groupnorm_lrelu_ndhwc(torch.cuda.current_stream(x.device).cuda_stream, x, x, b, spatial, c,
                                   n.num_groups, n.weight, n.bias, n.eps, self.act.negative_slope,
-                                  self._ws, need, self.conv_bias)
+                                  self._ws, need, self.conv_bias, dtype=code)
         return x
 
 
@@ -125,11 +142,13 @@ class _ResampleNDHWC(torch.nn.Module):
     """The U-Net's ``MaxPool3d(2)`` and ``Upsample(scale_factor=2, mode="trilinear", align_corners=True)`` on
     NDHWC tensors through ``libexabm4d`` (csrc/nn_kernels.hip: a float4 of channels per thread).  PyTorch's own
     kernels for the two walk an NDHWC tensor through generic strides (3.8 ms per call on this U-Net's tensors);
-    anything else -- other parameters, layouts, dtypes, training -- runs ``inner`` on an NCDHW copy."""
+    anything else -- other parameters, layouts, dtypes, training -- runs ``inner`` on an NCDHW copy.  ``half``: as
+    for ``FusedGroupNormLeakyReLU``, fp16 / bf16 tensors run natively too."""
 
-    def __init__(self, inner):
+    def __init__(self, inner, half=False):
         super().__init__()
         self.inner = inner
+        self.half = half
         m = inner
         if isinstance(m, torch.nn.MaxPool3d):
             ok = (_all_equal(m.kernel_size, 2) and _all_equal(m.stride if m.stride is not None else m.kernel_size, 2)
@@ -144,35 +163,35 @@ class _ResampleNDHWC(torch.nn.Module):
             self.kind = None
 
     def forward(self, x):
+        code = _native_dtype(x.dtype, self.half)
         native = (self.kind is not None and not self.training and not torch.is_grad_enabled() and x.is_cuda
-                  and x.dtype == torch.float32 and x.dim() == 5 and x.shape[1] % 4 == 0
+                  and code is not None and x.dim() == 5 and x.shape[1] % 4 == 0
                   and x.is_contiguous(memory_format=torch.channels_last_3d)
                   and (self.kind == "up" or min(x.shape[2:]) >= 2))
         if not native:
             return self.inner(x.contiguous())
         b, c, d, h, w = (int(v) for v in x.shape)
         out_dims = (d // 2, h // 2, w // 2) if self.kind == "pool" else (2 * d, 2 * h, 2 * w)
-        y = torch.empty((b, c) + out_dims, dtype=torch.float32, device=x.device,
-                        memory_format=torch.channels_last_3d)
+        y = torch.empty((b, c) + out_dims, dtype=x.dtype, device=x.device, memory_format=torch.channels_last_3d)
         ctx = _native.context(x.device.index or 0)
         stream = torch.cuda.current_stream(x.device).cuda_stream
         if self.kind == "pool":
-            ctx.maxpool2_ndhwc(stream, x, y, b, d, h, w, c)
+            ctx.maxpool2_ndhwc(stream, x, y, b, d, h, w, c, dtype=code)
         else:
-            ctx.upsample2_trilinear_ndhwc(stream, x, y, b, d, h, w, c)
+            ctx.upsample2_trilinear_ndhwc(stream, x, y, b, d, h, w, c, dtype=code)
         return y
 
 
-def _fuse_norm_act(module):
+def _fuse_norm_act(module, half=False):
     """Replace every (GroupNorm, LeakyReLU) neighbour pair inside ``nn.Sequential`` containers of ``module`` by
     a ``FusedGroupNormLeakyReLU`` + ``Identity`` (same positions: the copy's parameters are the pair's), and
     put every ``MaxPool3d`` / ``Upsample`` behind ``_ResampleNDHWC``.  For the private copy ``_ndhwc_shadow`` makes;
-    its ``state_dict`` keys are not the model's any more."""
+    its ``state_dict`` keys are not the model's any more.  ``half``: the new modules take fp16 / bf16 too."""
     for name, child in list(module.named_children()):
         if isinstance(child, (torch.nn.MaxPool3d, torch.nn.Upsample)):
-            setattr(module, name, _ResampleNDHWC(child).train(module.training))
+            setattr(module, name, _ResampleNDHWC(child, half).train(module.training))
         else:
-            _fuse_norm_act(child)
+            _fuse_norm_act(child, half)
     if isinstance(module, torch.nn.Sequential):
         for i in range(len(module) - 1):
             a, b = module[i], module[i + 1]
@@ -181,21 +200,23 @@ def _fuse_norm_act(module):
                 bias = None
                 if isinstance(conv, torch.nn.Conv3d) and conv.bias is not None and conv.out_channels == a.num_channels:
                     bias, conv.bias = conv.bias, None             # added inside the fused kernels instead
-                module[i] = FusedGroupNormLeakyReLU(a, b, bias).train(module.training)   # (a new module starts in training mode)
+                module[i] = FusedGroupNormLeakyReLU(a, b, bias, half).train(module.training)   # (a new module starts in training mode)
                 module[i + 1] = torch.nn.Identity()
     return module
 
 
-def _ndhwc_shadow(model, fuse=True):
+def _ndhwc_shadow(model, fuse=True, half=False):
     """An NDHWC (channels_last_3d) copy of an eval-mode fp32 module for the forward passes of one ``predict``
     call: MIOpen's implicit-GEMM solvers for NDHWC weights run this U-Net at 51 TFLOP/s against 30 for the
     default layout, and (``fuse``) its GroupNorm + LeakyReLU pairs run as the fused NDHWC kernels of
     ``libexabm4d`` instead of converting the layout there and back around PyTorch's GroupNorm.  The caller's
     model is not touched (52 MB copied per call); same fp32 arithmetic, results differ by summation order
-    (tests at 2e-3 against the golden patch)."""
+    (tests at 2e-3 against the golden patch).  ``half``: for forward passes under an fp16 / bf16 autocast
+    (``predict(precision=...)``): the parameters stay fp32, the fused modules also take the half-width tensors
+    autocast's convolutions produce."""
     import copy
     shadow = copy.deepcopy(model).to(memory_format=torch.channels_last_3d)
-    return _fuse_norm_act(shadow) if fuse else shadow
+    return _fuse_norm_act(shadow, half) if fuse else shadow
 
 
 def tune_model(model):
@@ -228,7 +249,7 @@ def quick_start(model):
 
 
 def predict(img, model, transform, batch_size=32, patch_size=64, overlap=12, trim=5,
-            verbose=True, fast=True):
+            verbose=True, fast=True, precision="fp32"):
     """Denoise a 3-D image by overlapping-patch inference; returns uint16 counts.
 
     Parameters follow the reference (inference.py:28-67): ``img`` is a 3-D array (leading
@@ -236,7 +257,18 @@ def predict(img, model, transform, batch_size=32, patch_size=64, overlap=12, tri
     ``(B,1,P,P,P)`` float32 CUDA tensor), ``transform`` the IntensityTransform the model was
     trained with.  ``fast`` (not in the reference; default on): an eval-mode ``nn.Module`` runs its forward
     passes through an NDHWC copy of itself with MIOpen's tuned solvers (``_miopen_defaults``,
-    ``_ndhwc_shadow``; fp32 throughout); ``fast=False`` calls ``model`` exactly as given."""
+    ``_ndhwc_shadow``; fp32 throughout); ``fast=False`` calls ``model`` exactly as given.
+
+    ``precision`` (not in the reference; default ``"fp32"``): ``"fp32"``, ``"fp16"`` or ``"bf16"``, the
+    arithmetic of the network's forward passes; anything else is a ValueError.  ``"fp32"`` is the path
+    described above.  ``"fp16"`` / ``"bf16"`` run the forward passes under ``torch.autocast`` of that dtype: the
+    NDHWC copy's convolutions in half precision, its GroupNorm + LeakyReLU pairs, max-pools and up-samplings
+    through the half-width kernels of ``libexabm4d`` (parameters fp32); with ``fast=False`` or a callable,
+    autocast around each call only.  The input patches, the residual sum ``x + logits`` (autocast leaves the
+    addition to type promotion: fp32), the network's output and the stitching stay fp32."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {sorted(PRECISIONS)}, not {precision!r}")
+    amp_dtype = PRECISIONS[precision]
     _miopen_defaults()
     img = np.asarray(img)
     while img.ndim > 3:
@@ -250,9 +282,15 @@ def predict(img, model, transform, batch_size=32, patch_size=64, overlap=12, tri
     dev = _model_device(model)
     ctx = _native.context(dev.index or 0)
     run = model
+    shadowed = False
     if fast and isinstance(model, torch.nn.Module) and not model.training and \
             all(p.dtype == torch.float32 for p in model.parameters()) and any(True for _ in model.parameters()):
-        run = _ndhwc_shadow(model)
+        run = _ndhwc_shadow(model, half=amp_dtype is not None)
+        shadowed = True
+    # the shadow's forward passes share one autocast region (its weights are cast once per call, not per batch);
+    # a caller's module or callable gets autocast around each call
+    amp = (lambda: torch.autocast("cuda", dtype=amp_dtype)) if amp_dtype is not None else contextlib.nullcontext
+    loop_amp, call_amp = (amp, contextlib.nullcontext) if shadowed else (contextlib.nullcontext, amp)
 
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
@@ -273,21 +311,22 @@ def predict(img, model, transform, batch_size=32, patch_size=64, overlap=12, tri
             pbar = tqdm(total=len(starts), desc="Denoise")
         batch = torch.empty((batch_size, 1, patch_size, patch_size, patch_size),
                             dtype=torch.float32, device=dev)
-        for b0 in range(0, len(starts), batch_size):
-            chunk = np.asarray(starts[b0:b0 + batch_size], dtype=np.int32)
-            nb = len(chunk)
-            ctx.tile_gather(vol, shape, chunk, patch_size, batch)      # inference.py:153-168
-            # A short last batch is run at full size (rows beyond nb hold the previous batch's
-            # patches and are dropped): MIOpen then sees ONE input shape per volume instead of
-            # paying a solver search -- seconds -- for the tail's.  Only for modules in eval mode,
-            # whose output rows do not depend on the rest of the batch.
-            full = nb < batch_size and b0 > 0 and not getattr(model, "training", True)
-            with torch.no_grad():
-                out = run(batch if full else batch[:nb])[:nb]          # inference.py:171-173
-            out = out.to(torch.float32).contiguous()
-            ctx.tile_accumulate(out, chunk, patch_size, trim, accum_pred, accum_wgt, shape)
-            if pbar is not None:
-                pbar.update(nb)
+        with loop_amp():
+            for b0 in range(0, len(starts), batch_size):
+                chunk = np.asarray(starts[b0:b0 + batch_size], dtype=np.int32)
+                nb = len(chunk)
+                ctx.tile_gather(vol, shape, chunk, patch_size, batch)      # inference.py:153-168
+                # A short last batch is run at full size (rows beyond nb hold the previous batch's
+                # patches and are dropped): MIOpen then sees ONE input shape per volume instead of
+                # paying a solver search -- seconds -- for the tail's.  Only for modules in eval mode,
+                # whose output rows do not depend on the rest of the batch.
+                full = nb < batch_size and b0 > 0 and not getattr(model, "training", True)
+                with torch.no_grad(), call_amp():
+                    out = run(batch if full else batch[:nb])[:nb]      # inference.py:171-173
+                out = out.to(torch.float32).contiguous()
+                ctx.tile_accumulate(out, chunk, patch_size, trim, accum_pred, accum_wgt, shape)
+                if pbar is not None:
+                    pbar.update(nb)
         del vol
         result = torch.empty(shape, dtype=torch.int16, device=dev)
         ctx.tile_finalize(transform.native_struct(), accum_pred, accum_wgt, result, n)

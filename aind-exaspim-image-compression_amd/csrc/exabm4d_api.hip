@@ -1326,11 +1326,19 @@ size_t exabm4d_groupnorm_workspace_bytes(int batch, size_t spatial, int channels
     if (batch < 1 || channels < 1 || groups < 1) return 0;
     return groupnorm_workspace_bytes(batch, spatial, channels, groups);
 }
-int exabm4d_groupnorm_lrelu_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, float* y, int batch,
-                                      size_t spatial, int channels, int groups, const float* gamma,
-                                      const float* beta, float eps, float slope, void* workspace,
-                                      size_t workspace_bytes, const float* conv_bias) {
+// The fp32 entries are the dtype-coded ones with EXABM4D_DTYPE_F32; the element type picks the template
+// instance of nn_kernels.hip (_Float16 / __bf16 storage for fp16 / bf16, 8-byte four-channel vectors).
+static bool nn_dtype_ok(int dtype) {
+    return dtype == EXABM4D_DTYPE_F32 || dtype == EXABM4D_DTYPE_F16 || dtype == EXABM4D_DTYPE_BF16;
+}
+static uintptr_t nn_align_mask(int dtype) { return dtype == EXABM4D_DTYPE_F32 ? 15u : 7u; }
+
+int exabm4d_groupnorm_lrelu_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* x, void* y,
+                                         int batch, size_t spatial, int channels, int groups, const float* gamma,
+                                         const float* beta, float eps, float slope, void* workspace,
+                                         size_t workspace_bytes, const float* conv_bias) {
     if (!ctx || !x || !y || !workspace) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (!nn_dtype_ok(dtype)) return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_ndhwc: unknown dtype");
     if (conv_bias && ((uintptr_t)conv_bias & 15u) != 0)
         return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_ndhwc: conv_bias must be 16-byte aligned");
     if (batch < 1 || batch > 65535 || spatial < 1 || channels < 4 || groups < 1 || groups > 32 ||
@@ -1340,37 +1348,89 @@ int exabm4d_groupnorm_lrelu_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const 
                     "256 % (channels / 4) == 0 and groups <= 32 (use the framework's GroupNorm otherwise)");
     if (workspace_bytes < groupnorm_workspace_bytes(batch, spatial, channels, groups))
         return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_ndhwc: workspace too small");
-    if ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)workspace) & 15u) != 0)
-        return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_ndhwc: 16-byte aligned tensors expected");
+    if ((((uintptr_t)x | (uintptr_t)y) & nn_align_mask(dtype)) != 0 || ((uintptr_t)workspace & 15u) != 0)
+        return fail(ctx, EXABM4D_ERR_INVALID,
+                    dtype == EXABM4D_DTYPE_F32 ? "groupnorm_lrelu_ndhwc: 16-byte aligned tensors expected"
+                                               : "groupnorm_lrelu_ndhwc: 8-byte aligned tensors and a 16-byte "
+                                                 "aligned workspace expected");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_groupnorm_lrelu_ndhwc(x, y, batch, spatial, channels, groups, gamma, beta, eps, slope,
-                                              workspace, (hipStream_t)hip_stream, conv_bias));
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (dtype == EXABM4D_DTYPE_F32)
+        HIP_TRY(ctx, launch_groupnorm_lrelu_ndhwc(static_cast<const float*>(x), static_cast<float*>(y), batch,
+                                                  spatial, channels, groups, gamma, beta, eps, slope, workspace, s,
+                                                  conv_bias));
+    else if (dtype == EXABM4D_DTYPE_F16)
+        HIP_TRY(ctx, launch_groupnorm_lrelu_ndhwc(static_cast<const _Float16*>(x), static_cast<_Float16*>(y), batch,
+                                                  spatial, channels, groups, gamma, beta, eps, slope, workspace, s,
+                                                  conv_bias));
+    else
+        HIP_TRY(ctx, launch_groupnorm_lrelu_ndhwc(static_cast<const __bf16*>(x), static_cast<__bf16*>(y), batch,
+                                                  spatial, channels, groups, gamma, beta, eps, slope, workspace, s,
+                                                  conv_bias));
     return EXABM4D_OK;
 }
+int exabm4d_groupnorm_lrelu_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, float* y, int batch,
+                                      size_t spatial, int channels, int groups, const float* gamma,
+                                      const float* beta, float eps, float slope, void* workspace,
+                                      size_t workspace_bytes, const float* conv_bias) {
+    return exabm4d_groupnorm_lrelu_ndhwc_dt_dev(ctx, hip_stream, EXABM4D_DTYPE_F32, x, y, batch, spatial, channels,
+                                                groups, gamma, beta, eps, slope, workspace, workspace_bytes,
+                                                conv_bias);
+}
 
-static int nn_resample_checks(exabm4d_ctx* ctx, const void* x, const void* y, int batch, int d, int h, int w,
-                              int channels) {
+static int nn_resample_checks(exabm4d_ctx* ctx, int dtype, const void* x, const void* y, int batch, int d, int h,
+                              int w, int channels) {
     if (!ctx || !x || !y) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (!nn_dtype_ok(dtype)) return fail(ctx, EXABM4D_ERR_INVALID, "NDHWC resampling: unknown dtype");
     if (batch < 1 || d < 1 || h < 1 || w < 1 || channels < 4 || channels % 4 != 0)
         return fail(ctx, EXABM4D_ERR_UNSUPPORTED, "NDHWC resampling: sizes >= 1 and channels % 4 == 0");
-    if ((((uintptr_t)x | (uintptr_t)y) & 15u) != 0)
-        return fail(ctx, EXABM4D_ERR_INVALID, "NDHWC resampling: 16-byte aligned tensors expected");
+    if ((((uintptr_t)x | (uintptr_t)y) & nn_align_mask(dtype)) != 0)
+        return fail(ctx, EXABM4D_ERR_INVALID,
+                    dtype == EXABM4D_DTYPE_F32 ? "NDHWC resampling: 16-byte aligned tensors expected"
+                                               : "NDHWC resampling: 8-byte aligned tensors expected");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return EXABM4D_OK;
+}
+int exabm4d_maxpool2_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* x, void* y, int batch,
+                                  int d, int h, int w, int channels) {
+    int rc = nn_resample_checks(ctx, dtype, x, y, batch, d, h, w, channels);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (dtype == EXABM4D_DTYPE_F32)
+        HIP_TRY(ctx, launch_maxpool2_ndhwc(static_cast<const float*>(x), static_cast<float*>(y), batch, d, h, w,
+                                           channels, s));
+    else if (dtype == EXABM4D_DTYPE_F16)
+        HIP_TRY(ctx, launch_maxpool2_ndhwc(static_cast<const _Float16*>(x), static_cast<_Float16*>(y), batch, d, h,
+                                           w, channels, s));
+    else
+        HIP_TRY(ctx, launch_maxpool2_ndhwc(static_cast<const __bf16*>(x), static_cast<__bf16*>(y), batch, d, h, w,
+                                           channels, s));
+    return EXABM4D_OK;
+}
+int exabm4d_upsample2_trilinear_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* x, void* y,
+                                             int batch, int d, int h, int w, int channels) {
+    int rc = nn_resample_checks(ctx, dtype, x, y, batch, d, h, w, channels);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (dtype == EXABM4D_DTYPE_F32)
+        HIP_TRY(ctx, launch_upsample2_trilinear_ndhwc(static_cast<const float*>(x), static_cast<float*>(y), batch,
+                                                      d, h, w, channels, s));
+    else if (dtype == EXABM4D_DTYPE_F16)
+        HIP_TRY(ctx, launch_upsample2_trilinear_ndhwc(static_cast<const _Float16*>(x), static_cast<_Float16*>(y),
+                                                      batch, d, h, w, channels, s));
+    else
+        HIP_TRY(ctx, launch_upsample2_trilinear_ndhwc(static_cast<const __bf16*>(x), static_cast<__bf16*>(y),
+                                                      batch, d, h, w, channels, s));
     return EXABM4D_OK;
 }
 int exabm4d_maxpool2_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, float* y, int batch, int d,
                                int h, int w, int channels) {
-    int rc = nn_resample_checks(ctx, x, y, batch, d, h, w, channels);
-    if (rc) return rc;
-    HIP_TRY(ctx, launch_maxpool2_ndhwc(x, y, batch, d, h, w, channels, (hipStream_t)hip_stream));
-    return EXABM4D_OK;
+    return exabm4d_maxpool2_ndhwc_dt_dev(ctx, hip_stream, EXABM4D_DTYPE_F32, x, y, batch, d, h, w, channels);
 }
 int exabm4d_upsample2_trilinear_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, float* y, int batch,
                                           int d, int h, int w, int channels) {
-    int rc = nn_resample_checks(ctx, x, y, batch, d, h, w, channels);
-    if (rc) return rc;
-    HIP_TRY(ctx, launch_upsample2_trilinear_ndhwc(x, y, batch, d, h, w, channels, (hipStream_t)hip_stream));
-    return EXABM4D_OK;
+    return exabm4d_upsample2_trilinear_ndhwc_dt_dev(ctx, hip_stream, EXABM4D_DTYPE_F32, x, y, batch, d, h, w,
+                                                    channels);
 }
 
 // Page-lock caller memory that host entry points will copy from / to many times (the broker: every worker's

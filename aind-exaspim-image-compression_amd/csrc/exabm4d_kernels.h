@@ -116,15 +116,18 @@ hipError_t launch_normalize_zconv(const long long* num, const double* qscale, co
                                   uint16_t* match16 = nullptr, float match_offset = 0.0f,
                                   int* match_written = nullptr);
 // BM4DNet stage: GroupNorm + LeakyReLU on an NDHWC tensor x[batch][spatial][C] (nn_kernels.hip); y may be x.
-// Requires C % 4 == 0, (C / G) % 4 == 0, 256 % (C / 4) == 0, G <= 32.
+// Requires C % 4 == 0, (C / G) % 4 == 0, 256 % (C / 4) == 0, G <= 32.  T: float, _Float16 or __bf16 (the
+// storage of torch.bfloat16); gamma, beta, cbias and the workspace's statistics are fp32 / fp64 for all three.
 size_t groupnorm_workspace_bytes(int batch, size_t spatial, int C, int G);
-hipError_t launch_groupnorm_lrelu_ndhwc(const float* x, float* y, int batch, size_t spatial, int C, int G,
+template <typename T>
+hipError_t launch_groupnorm_lrelu_ndhwc(const T* x, T* y, int batch, size_t spatial, int C, int G,
                                         const float* gamma, const float* beta, float eps, float slope,
                                         void* workspace, hipStream_t s, const float* cbias = nullptr);
-// MaxPool3d(2) (floor) and trilinear x2 up-sampling (align_corners) on NDHWC fp32 tensors, C % 4 == 0
-hipError_t launch_maxpool2_ndhwc(const float* x, float* y, int batch, int D, int H, int W, int C, hipStream_t s);
-hipError_t launch_upsample2_trilinear_ndhwc(const float* x, float* y, int batch, int D, int H, int W, int C,
-                                            hipStream_t s);
+// MaxPool3d(2) (floor) and trilinear x2 up-sampling (align_corners) on NDHWC tensors of T (as above), C % 4 == 0
+template <typename T>
+hipError_t launch_maxpool2_ndhwc(const T* x, T* y, int batch, int D, int H, int W, int C, hipStream_t s);
+template <typename T>
+hipError_t launch_upsample2_trilinear_ndhwc(const T* x, T* y, int batch, int D, int H, int W, int C, hipStream_t s);
 // staged entry point: num_f = fl32(fl64(num) 2^(E - 43))
 hipError_t launch_num_to_float(const long long* num, const double* qscale, float* out, size_t nvox, int batch,
                                hipStream_t s);

@@ -9,8 +9,10 @@
 // for normalisation and activation, all on the layout the convolutions produce and consume.
 //
 // x[b][s][c], s = (d, h, w) flattened, c fastest; groups of C / G consecutive channels.  C % 4 == 0 and
-// (C / G) % 4 == 0: a float4 of channels never straddles a group.  fp32 data, fp64 statistics; the partial sums
-// are combined in a fixed order, so the result is a deterministic function of the input.
+// (C / G) % 4 == 0: a thread's four channels never straddle a group.  fp32, fp16 or bf16 data (one template on
+// the storage type T; a thread moves four channels, 16 bytes of fp32 or 8 of a half type, so the launch geometry
+// is the same for all three); arithmetic in fp32, statistics in fp64, each output rounded once to T.  The
+// partial sums are combined in a fixed order, so the result is a deterministic function of the input.
 //
 // The statistics are formed around pivots, so that their rounding scales with the spread of a group and not
 // with its mean (a sum of squares formed around zero and a variance taken as E[x^2] - mean^2 lose (mean / std)^2
@@ -27,32 +29,60 @@ namespace exabm4d {
 
 constexpr int GN_THREADS = 256;
 
+// Four consecutive channels in storage type T: Pack<T>::type is what one thread loads or stores, unpack widens
+// it to fp32 exactly, pack rounds each element once, to nearest even (v_cvt_f16_f32 / v_cvt_pk_bf16_f32).
+typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+typedef float float4_t __attribute__((ext_vector_type(4)));
+template <typename T> struct Pack;
+template <> struct Pack<float> {
+    using type = float4;
+    static __device__ __forceinline__ float4 unpack(const float4 v) { return v; }
+    static __device__ __forceinline__ float4 pack(const float4 v) { return v; }
+};
+template <typename V> struct HalfPack {
+    using type = V;
+    static __device__ __forceinline__ float4 unpack(const V v) {
+        const float4_t f = __builtin_convertvector(v, float4_t);
+        return make_float4(f.x, f.y, f.z, f.w);
+    }
+    static __device__ __forceinline__ V pack(const float4 v) {
+        const float4_t f = {v.x, v.y, v.z, v.w};
+        return __builtin_convertvector(f, V);
+    }
+};
+template <> struct Pack<_Float16> : HalfPack<half4_t> {};
+template <> struct Pack<__bf16> : HalfPack<bf16x4_t> {};
+
 // Partial sums of one (sample, chunk of rows) about the group's reference p:
 // part[((b * nchunk + chunk) * G + g) * 2 + {0: sum of (x - p), 1: sum of (x - p)^2}]
-__device__ __forceinline__ float group_pivot(const float* x, size_t spatial, int C, int b, int c0, const float* cbias) {
-    return x[(size_t)b * spatial * C + c0] + (cbias ? cbias[c0] : 0.0f);
+template <typename T>
+__device__ __forceinline__ float group_pivot(const T* x, size_t spatial, int C, int b, int c0, const float* cbias) {
+    return (float)x[(size_t)b * spatial * C + c0] + (cbias ? cbias[c0] : 0.0f);
 }
 __device__ __forceinline__ void acc_shifted(float4& s, float4& q, const float4 v, const float4 k) {
     const float dx = v.x - k.x, dy = v.y - k.y, dz = v.z - k.z, dw = v.w - k.w;
     s.x += dx; s.y += dy; s.z += dz; s.w += dw;
     q.x += dx * dx; q.y += dy * dy; q.z += dz * dz; q.w += dw * dw;
 }
-__global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const float* __restrict__ x, size_t spatial, int C,
+template <typename T>
+__global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const T* __restrict__ x, size_t spatial, int C,
                                                              int G, int nchunk, size_t rows_per_chunk,
                                                              double* __restrict__ part,
                                                              const float* __restrict__ cbias) {
     // cbias (optional): the preceding convolution's bias, added here instead of in a pass of its own --
     // the statistics are those of x + cbias[c]
     const int b = blockIdx.y, chunk = blockIdx.x;
-    const int lanes = C / 4;                         // float4 lanes per row
+    const int lanes = C / 4;                         // four-channel lanes per row
     const int rows_per_iter = GN_THREADS / lanes;    // lanes divides GN_THREADS (C in {16 ... 1024}, power of two)
     const int lane = threadIdx.x % lanes, rsub = threadIdx.x / lanes;
     const size_t r0 = (size_t)chunk * rows_per_chunk;
     const size_t r1 = r0 + rows_per_chunk < spatial ? r0 + rows_per_chunk : spatial;
-    const float4* base = reinterpret_cast<const float4*>(x + (size_t)b * spatial * C) + lane;
+    using P = Pack<T>;
+    const typename P::type* base = reinterpret_cast<const typename P::type*>(x + (size_t)b * spatial * C) + lane;
     const float4 cb = cbias ? reinterpret_cast<const float4*>(cbias)[lane] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     auto ld = [&](size_t row) {
-        float4 v = base[row * lanes];
+        float4 v = P::unpack(base[row * lanes]);
         v.x += cb.x; v.y += cb.y; v.z += cb.z; v.w += cb.w;
         return v;
     };
@@ -104,10 +134,11 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const float* __res
 }
 
 // a[b][c] = rstd * gamma[c], sh[b][c] = beta[c] - mean * a[b][c]   (y = a x + sh, as PyTorch's fused parameters)
+template <typename T>
 __global__ void gn_params_kernel(const double* __restrict__ part, int batch, int C, int G, int nchunk,
                                  double count, const float* __restrict__ gamma, const float* __restrict__ beta,
                                  float eps, float* __restrict__ a, float* __restrict__ shift,
-                                 const float* __restrict__ cbias, const float* __restrict__ x, size_t spatial) {
+                                 const float* __restrict__ cbias, const T* __restrict__ x, size_t spatial) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= batch * C) return;
     const int b = i / C, c = i - b * C, cpg = C / G, g = c / cpg;
@@ -129,14 +160,16 @@ __global__ void gn_params_kernel(const double* __restrict__ part, int batch, int
     shift[i] = be + av * ((cbias ? cbias[c] : 0.0f) - (float)mean);
 }
 
-__global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const float* __restrict__ x, float* __restrict__ y,
+template <typename T>
+__global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const T* __restrict__ x, T* __restrict__ y,
                                                              size_t spatial, int C, const float* __restrict__ a,
                                                              const float* __restrict__ shift, float slope) {
     const int b = blockIdx.y;
     const int lanes = C / 4;
     const size_t n4 = spatial * (size_t)lanes;
-    const float4* xi = reinterpret_cast<const float4*>(x + (size_t)b * spatial * C);
-    float4* yo = reinterpret_cast<float4*>(y + (size_t)b * spatial * C);
+    using P = Pack<T>;
+    const typename P::type* xi = reinterpret_cast<const typename P::type*>(x + (size_t)b * spatial * C);
+    typename P::type* yo = reinterpret_cast<typename P::type*>(y + (size_t)b * spatial * C);
     const float4* a4 = reinterpret_cast<const float4*>(a + (size_t)b * C);
     const float4* s4 = reinterpret_cast<const float4*>(shift + (size_t)b * C);
     // a thread keeps its float4 lane over the rows it visits when the stride is a multiple of `lanes`
@@ -149,7 +182,7 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const float* __res
             av = a4[i % lanes];
             sv = s4[i % lanes];
         }
-        float4 v = xi[i];
+        float4 v = P::unpack(xi[i]);
         v.x = fmaf(v.x, av.x, sv.x);
         v.y = fmaf(v.y, av.y, sv.y);
         v.z = fmaf(v.z, av.z, sv.z);
@@ -158,18 +191,23 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const float* __res
         v.y = v.y > 0.0f ? v.y : v.y * slope;
         v.z = v.z > 0.0f ? v.z : v.z * slope;
         v.w = v.w > 0.0f ? v.w : v.w * slope;
-        yo[i] = v;
+        yo[i] = P::pack(v);
     }
 }
 
 // ---- MaxPool3d(2) and trilinear x2 up-sampling (align_corners = True) on NDHWC ---------------------------
 // The U-Net's four down- and four up-samplings (reference unet3d.py:211-342).  PyTorch's kernels for these walk
 // an NDHWC tensor through generic strides (3.8 ms per call here) or want an NCDHW copy; a float4 of channels per
-// thread makes both trivially coalesced on the layout the convolutions use.
+// thread makes both trivially coalesced on the layout the convolutions use.  Half types: four channels (8 bytes)
+// per thread as well, widened to fp32 exactly; the max-pool's output is then one of its inputs (a signalling NaN
+// comes back quiet), the up-sampling's is the fp32 interpolation rounded once.
 __device__ __forceinline__ float max_nan(float a, float b) { return (b > a || b != b) ? b : a; }   // NaN wins, as in torch
-__global__ __launch_bounds__(GN_THREADS) void maxpool2_ndhwc_kernel(const float4* __restrict__ x,
-                                                                   float4* __restrict__ y, size_t total, int OD,
-                                                                   int OH, int OW, int H, int W, int D, int lanes) {
+template <typename T>
+__global__ __launch_bounds__(GN_THREADS) void maxpool2_ndhwc_kernel(const typename Pack<T>::type* __restrict__ x,
+                                                                   typename Pack<T>::type* __restrict__ y,
+                                                                   size_t total, int OD, int OH, int OW, int H,
+                                                                   int W, int D, int lanes) {
+    using P = Pack<T>;
     for (size_t o = (size_t)blockIdx.x * GN_THREADS + threadIdx.x; o < total; o += (size_t)gridDim.x * GN_THREADS) {
         const int l = (int)(o % lanes);
         size_t t = o / lanes;
@@ -177,25 +215,26 @@ __global__ __launch_bounds__(GN_THREADS) void maxpool2_ndhwc_kernel(const float4
         const int oh = (int)(t % OH); t /= OH;
         const int od = (int)(t % OD);
         const size_t b = t / OD;
-        const float4* p = x + ((((b * D + 2 * od) * H + 2 * oh) * (size_t)W + 2 * ow) * lanes + l);
-        float4 m = p[0];
+        const typename P::type* p = x + ((((b * D + 2 * od) * H + 2 * oh) * (size_t)W + 2 * ow) * lanes + l);
+        float4 m = P::unpack(p[0]);
 #pragma unroll
         for (int k = 1; k < 8; k++) {
-            const float4 v = p[(((size_t)(k >> 2) * H + ((k >> 1) & 1)) * W + (k & 1)) * lanes];
+            const float4 v = P::unpack(p[(((size_t)(k >> 2) * H + ((k >> 1) & 1)) * W + (k & 1)) * lanes]);
             m.x = max_nan(m.x, v.x); m.y = max_nan(m.y, v.y); m.z = max_nan(m.z, v.z); m.w = max_nan(m.w, v.w);
         }
-        y[o] = m;
+        y[o] = P::pack(m);
     }
 }
-hipError_t launch_maxpool2_ndhwc(const float* x, float* y, int batch, int D, int H, int W, int C, hipStream_t s) {
+template <typename T>
+hipError_t launch_maxpool2_ndhwc(const T* x, T* y, int batch, int D, int H, int W, int C, hipStream_t s) {
     const int OD = D / 2, OH = H / 2, OW = W / 2, lanes = C / 4;
     const size_t total = (size_t)batch * OD * OH * OW * lanes;
     if (total == 0) return hipSuccess;
     size_t blocks = (total + GN_THREADS - 1) / GN_THREADS;
     if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(maxpool2_ndhwc_kernel, dim3((unsigned)blocks), dim3(GN_THREADS), 0, s,
-                       reinterpret_cast<const float4*>(x), reinterpret_cast<float4*>(y), total, OD, OH, OW, H, W, D,
-                       lanes);
+    hipLaunchKernelGGL(maxpool2_ndhwc_kernel<T>, dim3((unsigned)blocks), dim3(GN_THREADS), 0, s,
+                       reinterpret_cast<const typename Pack<T>::type*>(x), reinterpret_cast<typename Pack<T>::type*>(y),
+                       total, OD, OH, OW, H, W, D, lanes);
     return hipGetLastError();
 }
 
@@ -214,10 +253,12 @@ __device__ __forceinline__ UpAxis up_axis(int o, int in, float r) {
     a.w0 = 1.0f - a.w1;
     return a;
 }
-__global__ __launch_bounds__(GN_THREADS) void upsample2_ndhwc_kernel(const float4* __restrict__ x,
-                                                                    float4* __restrict__ y, size_t total, int D,
-                                                                    int H, int W, int lanes, float rd, float rh,
-                                                                    float rw) {
+template <typename T>
+__global__ __launch_bounds__(GN_THREADS) void upsample2_ndhwc_kernel(const typename Pack<T>::type* __restrict__ x,
+                                                                    typename Pack<T>::type* __restrict__ y,
+                                                                    size_t total, int D, int H, int W, int lanes,
+                                                                    float rd, float rh, float rw) {
+    using P = Pack<T>;
     const int OD = 2 * D, OH = 2 * H, OW = 2 * W;
     for (size_t o = (size_t)blockIdx.x * GN_THREADS + threadIdx.x; o < total; o += (size_t)gridDim.x * GN_THREADS) {
         const int l = (int)(o % lanes);
@@ -227,8 +268,8 @@ __global__ __launch_bounds__(GN_THREADS) void upsample2_ndhwc_kernel(const float
         const int od = (int)(t % OD);
         const size_t b = t / OD;
         const UpAxis ad = up_axis(od, D, rd), ah = up_axis(oh, H, rh), aw = up_axis(ow, W, rw);
-        const float4* base = x + (b * D * H * (size_t)W) * lanes + l;
-        auto at = [&](int d, int h, int w) { return base[(((size_t)d * H + h) * W + w) * lanes]; };
+        const typename P::type* base = x + (b * D * H * (size_t)W) * lanes + l;
+        auto at = [&](int d, int h, int w) { return P::unpack(base[(((size_t)d * H + h) * W + w) * lanes]); };
         auto lerp_w = [&](int d, int h) {
             const float4 a = at(d, h, aw.i0), c = at(d, h, aw.i1);
             return make_float4(aw.w0 * a.x + aw.w1 * c.x, aw.w0 * a.y + aw.w1 * c.y, aw.w0 * a.z + aw.w1 * c.z,
@@ -240,21 +281,21 @@ __global__ __launch_bounds__(GN_THREADS) void upsample2_ndhwc_kernel(const float
                                ah.w0 * a.w + ah.w1 * c.w);
         };
         const float4 a = lerp_h(ad.i0), c = lerp_h(ad.i1);
-        y[o] = make_float4(ad.w0 * a.x + ad.w1 * c.x, ad.w0 * a.y + ad.w1 * c.y, ad.w0 * a.z + ad.w1 * c.z,
-                           ad.w0 * a.w + ad.w1 * c.w);
+        y[o] = P::pack(make_float4(ad.w0 * a.x + ad.w1 * c.x, ad.w0 * a.y + ad.w1 * c.y, ad.w0 * a.z + ad.w1 * c.z,
+                                   ad.w0 * a.w + ad.w1 * c.w));
     }
 }
-hipError_t launch_upsample2_trilinear_ndhwc(const float* x, float* y, int batch, int D, int H, int W, int C,
-                                            hipStream_t s) {
+template <typename T>
+hipError_t launch_upsample2_trilinear_ndhwc(const T* x, T* y, int batch, int D, int H, int W, int C, hipStream_t s) {
     const int lanes = C / 4;
     const size_t total = (size_t)batch * (2 * (size_t)D) * (2 * (size_t)H) * (2 * (size_t)W) * lanes;
     if (total == 0) return hipSuccess;
     auto ratio = [](int in) { return 2 * in > 1 ? (float)(in - 1) / (float)(2 * in - 1) : 0.0f; };
     size_t blocks = (total + GN_THREADS - 1) / GN_THREADS;
     if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(upsample2_ndhwc_kernel, dim3((unsigned)blocks), dim3(GN_THREADS), 0, s,
-                       reinterpret_cast<const float4*>(x), reinterpret_cast<float4*>(y), total, D, H, W, lanes,
-                       ratio(D), ratio(H), ratio(W));
+    hipLaunchKernelGGL(upsample2_ndhwc_kernel<T>, dim3((unsigned)blocks), dim3(GN_THREADS), 0, s,
+                       reinterpret_cast<const typename Pack<T>::type*>(x), reinterpret_cast<typename Pack<T>::type*>(y),
+                       total, D, H, W, lanes, ratio(D), ratio(H), ratio(W));
     return hipGetLastError();
 }
 
@@ -263,7 +304,8 @@ size_t groupnorm_workspace_bytes(int batch, size_t spatial, int C, int G) {
     return (size_t)batch * 64 * (size_t)G * 2 * sizeof(double) + 2 * (size_t)batch * C * sizeof(float);
 }
 
-hipError_t launch_groupnorm_lrelu_ndhwc(const float* x, float* y, int batch, size_t spatial, int C, int G,
+template <typename T>
+hipError_t launch_groupnorm_lrelu_ndhwc(const T* x, T* y, int batch, size_t spatial, int C, int G,
                                         const float* gamma, const float* beta, float eps, float slope,
                                         void* workspace, hipStream_t s, const float* cbias) {
     const int lanes = C / 4;
@@ -280,10 +322,10 @@ hipError_t launch_groupnorm_lrelu_ndhwc(const float* x, float* y, int batch, siz
     double* part = static_cast<double*>(workspace);
     float* a = reinterpret_cast<float*>(part + (size_t)batch * 64 * G * 2);
     float* shift = a + (size_t)batch * C;
-    hipLaunchKernelGGL(gn_stats_kernel, dim3((unsigned)nchunk, (unsigned)batch), dim3(GN_THREADS), 0, s, x, spatial,
+    hipLaunchKernelGGL(gn_stats_kernel<T>, dim3((unsigned)nchunk, (unsigned)batch), dim3(GN_THREADS), 0, s, x, spatial,
                        C, G, (int)nchunk, rows_per_chunk, part, cbias);
     const int total = batch * C;
-    hipLaunchKernelGGL(gn_params_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, part, batch, C, G,
+    hipLaunchKernelGGL(gn_params_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, part, batch, C, G,
                        (int)nchunk, (double)spatial * (double)(C / G), gamma, beta, eps, a, shift, cbias, x,
                        spatial);
     const size_t n4 = spatial * (size_t)lanes;
@@ -293,9 +335,20 @@ hipError_t launch_groupnorm_lrelu_ndhwc(const float* x, float* y, int batch, siz
     // (GN_THREADS is a multiple of the row's lanes -- checked by the caller -- so is the grid stride: a thread
     // keeps its (scale, shift) in registers)
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(gn_apply_kernel, dim3((unsigned)blocks, (unsigned)batch), dim3(GN_THREADS), 0, s, x, y,
+    hipLaunchKernelGGL(gn_apply_kernel<T>, dim3((unsigned)blocks, (unsigned)batch), dim3(GN_THREADS), 0, s, x, y,
                        spatial, C, a, shift, slope);
     return hipGetLastError();
 }
+
+#define EXABM4D_NN_INSTANTIATE(T)                                                                                \
+    template hipError_t launch_groupnorm_lrelu_ndhwc<T>(const T*, T*, int, size_t, int, int, const float*,        \
+                                                        const float*, float, float, void*, hipStream_t,           \
+                                                        const float*);                                            \
+    template hipError_t launch_maxpool2_ndhwc<T>(const T*, T*, int, int, int, int, int, hipStream_t);             \
+    template hipError_t launch_upsample2_trilinear_ndhwc<T>(const T*, T*, int, int, int, int, int, hipStream_t);
+EXABM4D_NN_INSTANTIATE(float)
+EXABM4D_NN_INSTANTIATE(_Float16)
+EXABM4D_NN_INSTANTIATE(__bf16)
+#undef EXABM4D_NN_INSTANTIATE
 
 }  // namespace exabm4d

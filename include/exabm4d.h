@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define EXABM4D_VERSION 400 /* 0.4.0 (round 4): order-independent aggregation -- exabm4d_stage_dev takes data_exp and WRITES num / den, options "stage_pairs" / "stage_quads" / "fuse_den_z" are gone, the stage / block-matching options are per context; 0.3.2: + exabm4d_blockmatch_plan, option "stage_strip"; 0.3.1: + exabm4d_denoise_chunked_u16_host, options "bm_carry" / "bm_xcd_mode"; 0.3.0: EXAC v2 coder, exabm4d_codec_decode_dev takes in_bytes (round 3) */
+#define EXABM4D_VERSION 400 /* additive within 400: + exabm4d_groupnorm_lrelu_ndhwc_dt_dev, exabm4d_maxpool2_ndhwc_dt_dev, exabm4d_upsample2_trilinear_ndhwc_dt_dev (fp16 / bf16 BM4DNet kernels); 0.4.0 (round 4): order-independent aggregation -- exabm4d_stage_dev takes data_exp and WRITES num / den, options "stage_pairs" / "stage_quads" / "fuse_den_z" are gone, the stage / block-matching options are per context; 0.3.2: + exabm4d_blockmatch_plan, option "stage_strip"; 0.3.1: + exabm4d_denoise_chunked_u16_host, options "bm_carry" / "bm_xcd_mode"; 0.3.0: EXAC v2 coder, exabm4d_codec_decode_dev takes in_bytes (round 3) */
 
 typedef enum exabm4d_status {
     EXABM4D_OK = 0,
@@ -321,6 +321,27 @@ int exabm4d_maxpool2_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* 
                                int h, int w, int channels);
 int exabm4d_upsample2_trilinear_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, float* y, int batch,
                                           int d, int h, int w, int channels);
+
+/* The same three layers on fp32, fp16 or bf16 tensors, chosen by `dtype` (an exabm4d_dtype); the fp32 entries
+ * above are these with EXABM4D_DTYPE_F32.  Storage is `dtype`, arithmetic is not: a thread widens four channels
+ * to fp32, the GroupNorm statistics are the fp32 kernels' (pivot-shifted fp32 sums, fp64 partials, fixed-order
+ * combination), gamma, beta and conv_bias stay fp32, and every output is rounded once, to nearest even, to
+ * `dtype`.  The max-pool returns one of its inputs (bit for bit, a signalling NaN quieted).  Tensors must be
+ * 16-byte (fp32) or 8-byte (fp16, bf16) aligned; the shape rules, the workspace and EXABM4D_ERR_UNSUPPORTED are
+ * those of the fp32 entries.  An unknown dtype is EXABM4D_ERR_INVALID. */
+typedef enum exabm4d_dtype {
+    EXABM4D_DTYPE_F32 = 0,
+    EXABM4D_DTYPE_F16 = 1,        /* IEEE binary16 (_Float16, torch.float16)                     */
+    EXABM4D_DTYPE_BF16 = 2        /* bfloat16 (__hip_bfloat16, torch.bfloat16)                   */
+} exabm4d_dtype;
+int exabm4d_groupnorm_lrelu_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* x, void* y,
+                                         int batch, size_t spatial, int channels, int groups, const float* gamma,
+                                         const float* beta, float eps, float slope, void* workspace,
+                                         size_t workspace_bytes, const float* conv_bias);
+int exabm4d_maxpool2_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* x, void* y, int batch,
+                                  int d, int h, int w, int channels);
+int exabm4d_upsample2_trilinear_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* x, void* y,
+                                             int batch, int d, int h, int w, int channels);
 
 /* Page-lock `bytes` of caller memory at `ptr` that the host entry points will copy from / to repeatedly (the
  * broker registers every worker's shared-memory segment once): copies become DMA transfers instead of staged
