@@ -96,28 +96,39 @@ class FusedGroupNormLeakyReLU(torch.nn.Module):
     """``GroupNorm`` followed by ``LeakyReLU`` as ONE module for inference on NDHWC tensors: the pair of the
     reference's ``DoubleConv`` (unet3d.py:137-208) through ``exabm4d_groupnorm_lrelu_ndhwc_dev`` -- statistics,
     normalisation and activation in two passes over the layout MIOpen's convolutions produce, in place on the
-    convolution's output.  PyTorch's own GroupNorm wants NCDHW: per layer a layout copy in, statistics, apply,
-    the activation and a layout copy back (45 % of the forward's kernel time).  Falls back to the framework's
-    two modules for anything the kernels do not take (training, other dtypes / layouts / channel counts)."""
+    convolution's output (``inplace``) or into a new tensor.  PyTorch's own GroupNorm wants NCDHW: per layer a
+    layout copy in, statistics, apply, the activation and a layout copy back (45 % of the forward's kernel time).
+    Falls back to the framework's two modules for anything the kernels do not take (training, other dtypes /
+    layouts / channel counts); the fallback never writes into its input."""
 
-    def __init__(self, norm, act, conv_bias=None, half=False):
+    def __init__(self, norm, act, conv_bias=None, half=False, inplace=True):
         """``conv_bias``: the bias of the convolution in front, taken over from it (the caller sets that
         convolution's ``bias`` to None): added inside the kernels instead of in a pass of its own.
         ``half``: also take fp16 / bf16 tensors (the half-width kernels; gamma, beta and the bias stay fp32) --
-        for the shadow ``predict(precision="fp16" | "bf16")`` builds; otherwise those fall back as before."""
+        for the shadow ``predict(precision="fp16" | "bf16")`` builds; otherwise those fall back as before.
+        ``inplace`` (default, as for the U-Net's pairs): the kernels overwrite their input -- only for an input
+        nothing else reads afterwards, a convolution's fresh output; ``inplace=False``: the result goes to a new
+        ``channels_last_3d`` tensor and the input is left as it was (``_fuse_norm_act`` decides per pair)."""
         super().__init__()
         self.norm, self.act = norm, act
         self.conv_bias = conv_bias
         self.half = half
+        self.inplace = inplace
         self._ws = None
+
+    @property
+    def native_channels(self):
+        """Whether the kernels take this norm's channels: C % 4 == 0, (C / G) % 4 == 0, 256 % (C / 4) == 0 and
+        G <= 32 (see include/exabm4d.h)."""
+        c, g = self.norm.num_channels, self.norm.num_groups
+        return c % 4 == 0 and (c // g) % 4 == 0 and 256 % (c // 4) == 0 and g <= 32
 
     def forward(self, x):
         n = self.norm
         code = _native_dtype(x.dtype, self.half)
         fused = (not self.training and x.is_cuda and code is not None and x.dim() == 5
                  and x.is_contiguous(memory_format=torch.channels_last_3d) and not torch.is_grad_enabled()
-                 and n.num_channels % 4 == 0 and (n.num_channels // n.num_groups) % 4 == 0
-                 and 256 % (n.num_channels // 4) == 0 and n.num_groups <= 32 and x.shape[0] <= 65535)
+                 and self.native_channels and x.shape[0] <= 65535)
         if not fused:
             if self.conv_bias is not None:
                 x = x + self.conv_bias.view(1, -1, 1, 1, 1)
@@ -127,11 +138,12 @@ class FusedGroupNormLeakyReLU(torch.nn.Module):
         need = int(_native.lib().exabm4d_groupnorm_workspace_bytes(b, spatial, c, n.num_groups))
         if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
             self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        y = x if self.inplace else torch.empty_like(x, memory_format=torch.channels_last_3d)
         ctx = _native.context(x.device.index or 0)
-        ctx.groupnorm_lrelu_ndhwc(torch.cuda.current_stream(x.device).cuda_stream, x, x, b, spatial, c,
+        ctx.groupnorm_lrelu_ndhwc(torch.cuda.current_stream(x.device).cuda_stream, x, y, b, spatial, c,
                                   n.num_groups, n.weight, n.bias, n.eps, self.act.negative_slope,
                                   self._ws, need, self.conv_bias, dtype=code)
-        return x
+        return y
 
 
 def _all_equal(v, want):
@@ -186,22 +198,41 @@ def _fuse_norm_act(module, half=False):
     """Replace every (GroupNorm, LeakyReLU) neighbour pair inside ``nn.Sequential`` containers of ``module`` by
     a ``FusedGroupNormLeakyReLU`` + ``Identity`` (same positions: the copy's parameters are the pair's), and
     put every ``MaxPool3d`` / ``Upsample`` behind ``_ResampleNDHWC``.  For the private copy ``_ndhwc_shadow`` makes;
-    its ``state_dict`` keys are not the model's any more.  ``half``: the new modules take fp16 / bf16 too."""
-    for name, child in list(module.named_children()):
-        if isinstance(child, (torch.nn.MaxPool3d, torch.nn.Upsample)):
-            setattr(module, name, _ResampleNDHWC(child, half).train(module.training))
-        else:
-            _fuse_norm_act(child, half)
-    if isinstance(module, torch.nn.Sequential):
-        for i in range(len(module) - 1):
-            a, b = module[i], module[i + 1]
+    its ``state_dict`` keys are not the model's any more.  ``half``: the new modules take fp16 / bf16 too.
+
+    What the rewrite can see is the module tree, so it stays correct only where the tree tells the data flow:
+      * a pair runs in place only right behind a ``Conv3d`` in the same container (a fresh output nobody else
+        holds); at the head of a container, or behind a module that may return its input (``Identity``,
+        ``Dropout`` in eval mode, ...), it writes a new tensor;
+      * the convolution's bias moves into the fused kernels only when that ``Conv3d`` sits in ONE slot of the
+        tree (one container, one name); a convolution that also appears elsewhere keeps its bias;
+      * each module is rewritten once, however many slots share it.
+    Not visible, so not accounted for: a custom ``forward`` that calls an element of a ``Sequential`` outside
+    it (``self.block[0](x)``), forward hooks on the replaced modules, and functional ``F.group_norm`` /
+    ``F.max_pool3d`` / ``F.interpolate`` calls (those run as the framework's, unchanged)."""
+    slots = {}                                       # id(child) -> the (container, name) slots holding it
+    for parent in module.modules():
+        for name, child in parent._modules.items():
+            if child is not None:
+                slots.setdefault(id(child), set()).add((id(parent), name))
+    for parent in list(module.modules()):            # unique modules; the wrappers made below are not revisited
+        for name, child in list(parent._modules.items()):
+            if isinstance(child, (torch.nn.MaxPool3d, torch.nn.Upsample)):
+                setattr(parent, name, _ResampleNDHWC(child, half).train(parent.training))
+        if not isinstance(parent, torch.nn.Sequential):
+            continue
+        for i in range(len(parent) - 1):
+            a, b = parent[i], parent[i + 1]
             if isinstance(a, torch.nn.GroupNorm) and isinstance(b, torch.nn.LeakyReLU) and a.affine:
-                conv = module[i - 1] if i > 0 else None
+                conv = parent[i - 1] if i > 0 else None
+                after_conv = isinstance(conv, torch.nn.Conv3d)
                 bias = None
-                if isinstance(conv, torch.nn.Conv3d) and conv.bias is not None and conv.out_channels == a.num_channels:
+                if (after_conv and conv.bias is not None and conv.out_channels == a.num_channels
+                        and len(slots[id(conv)]) == 1):
                     bias, conv.bias = conv.bias, None             # added inside the fused kernels instead
-                module[i] = FusedGroupNormLeakyReLU(a, b, bias, half).train(module.training)   # (a new module starts in training mode)
-                module[i + 1] = torch.nn.Identity()
+                # (a new module starts in training mode)
+                parent[i] = FusedGroupNormLeakyReLU(a, b, bias, half, inplace=after_conv).train(parent.training)
+                parent[i + 1] = torch.nn.Identity().train(parent.training)
     return module
 
 
@@ -213,7 +244,9 @@ def _ndhwc_shadow(model, fuse=True, half=False):
     model is not touched (52 MB copied per call); same fp32 arithmetic, results differ by summation order
     (tests at 2e-3 against the golden patch).  ``half``: for forward passes under an fp16 / bf16 autocast
     (``predict(precision=...)``): the parameters stay fp32, the fused modules also take the half-width tensors
-    autocast's convolutions produce."""
+    autocast's convolutions produce.  Any module may come in, not only this package's U-Nets: the rewrite
+    writes in place and moves a convolution's bias only where the module tree shows that is safe, and what the
+    tree cannot show is listed at ``_fuse_norm_act`` (tests/nn_zoo.py holds the models it is checked on)."""
     import copy
     shadow = copy.deepcopy(model).to(memory_format=torch.channels_last_3d)
     return _fuse_norm_act(shadow, half) if fuse else shadow

@@ -185,6 +185,48 @@ def test_groupnorm_writes_only_its_view(name):
 
 
 @pytest.mark.parametrize("name", DTYPES)
+def test_groupnorm_out_of_place(name):
+    """y != x in the half types: into a view at an 8-byte offset inside a larger buffer, y is within 1 ulp + the
+    fp32 bound, x is bit-unchanged and the elements before and after y stay as they were; the module with
+    ``inplace=False`` returns a new NDHWC tensor holding the same bits, through the native entry."""
+    dtype = DTYPES[name]
+    code = inference._NATIVE_DTYPES[dtype]
+    shape = (2, 8, 8, 8, 32)
+    n = int(np.prod(shape))
+    pre, post = 4096 + 4, 4096
+    buf = torch.full((pre + n + post,), -7.25, dtype=dtype, device="cuda")
+    y = buf[pre:pre + n].view(shape).permute(0, 4, 1, 2, 3)
+    x_dev = to_dev(gn_inputs("mean10", shape, 8, 12), dtype)
+    xh = widen(x_dev)
+    x0 = x_dev.clone()
+    gamma, beta = params(32, 9)
+    cbias = (np.random.default_rng(13).standard_normal(32) * 3).astype(np.float32)
+    norm = torch.nn.GroupNorm(8, 32).cuda()
+    with torch.no_grad():
+        norm.weight.copy_(torch.from_numpy(gamma))
+        norm.bias.copy_(torch.from_numpy(beta))
+    cb = torch.nn.Parameter(torch.from_numpy(cbias).cuda())
+    need = int(_native.lib().exabm4d_groupnorm_workspace_bytes(2, 512, 32, 8))
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    _native.context(0).groupnorm_lrelu_ndhwc(torch.cuda.current_stream().cuda_stream, x_dev, y, 2, 512, 32, 8,
+                                             norm.weight, norm.bias, 1e-5, 0.01, ws, need, cb, dtype=code)
+    host = buf.float().cpu().numpy()
+    assert np.all(host[:pre] == -7.25) and np.all(host[pre + n:] == -7.25)
+    assert torch.equal(x_dev.view(torch.int16), x0.view(torch.int16))
+    want, e32 = gn_bound(xh, 8, gamma, beta, 1e-5, 0.01, cbias)
+    got = host[pre:pre + n].reshape(shape)
+    assert excess(got, want, ulp(want, dtype) + e32) <= 1.0
+    mod = inference.FusedGroupNormLeakyReLU(norm, torch.nn.LeakyReLU(0.01), cb, half=True, inplace=False).eval()
+    with torch.no_grad():
+        seen, out = _count_native(lambda: mod(x_dev))
+    assert seen["gn"] == [code]
+    assert out.dtype == dtype and out.data_ptr() != x_dev.data_ptr()
+    assert out.is_contiguous(memory_format=torch.channels_last_3d)
+    assert torch.equal(x_dev.view(torch.int16), x0.view(torch.int16))
+    np.testing.assert_array_equal(widen(out).view(np.int32), got.view(np.int32))
+
+
+@pytest.mark.parametrize("name", DTYPES)
 def test_unsupported_shapes_and_framework_fallback(name):
     """Channel counts the kernels do not take: the entries return EXABM4D_ERR_UNSUPPORTED, and the modules give
     the framework's result on the same half tensor."""

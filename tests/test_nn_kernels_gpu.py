@@ -17,7 +17,7 @@ import torch
 import nn_pyref as R
 from test_inference_gpu import TF_CFG
 
-from aind_exaspim_image_compression import inference
+from aind_exaspim_image_compression import _native, inference
 from aind_exaspim_image_compression.machine_learning import transforms as T
 from aind_exaspim_image_compression.machine_learning import unet3d
 
@@ -258,6 +258,50 @@ def test_groupnorm_writes_only_its_view():
     assert np.all(host[:pre] == -7.25) and np.all(host[pre + n:] == -7.25)
     want, bound = gn_bound(x, 8, gamma, beta, 1e-5, 0.01, None)
     assert _excess(host[pre:pre + n].reshape(shape), want, bound) <= 1.0
+
+
+def test_groupnorm_out_of_place():
+    """y != x (the header's "y may be x"; what the shadow runs for a pair that does not sit right behind a
+    convolution): into a view inside a larger buffer, y is within the bound, x is bit-unchanged and the bytes
+    before and after y stay as they were; the module with ``inplace=False`` returns a new NDHWC tensor holding
+    the same bytes, through the native entry, and leaves its input alone."""
+    shape = (2, 8, 8, 8, 32)
+    n = int(np.prod(shape))
+    pre, post = 4096 + 4, 4096
+    buf = torch.full((pre + n + post,), -7.25, dtype=torch.float32, device="cuda")
+    y = buf[pre:pre + n].view(shape).permute(0, 4, 1, 2, 3)
+    x = gn_inputs("mean10", shape, 8, 12)
+    gamma, beta = params(32, 9)
+    cbias = (np.random.default_rng(13).standard_normal(32) * 3).astype(np.float32)
+    x_dev = to_dev(x)
+    x0 = x_dev.clone()
+    norm = torch.nn.GroupNorm(8, 32).cuda()
+    with torch.no_grad():
+        norm.weight.copy_(torch.from_numpy(gamma))
+        norm.bias.copy_(torch.from_numpy(beta))
+    cb = torch.nn.Parameter(torch.from_numpy(cbias).cuda())
+    need = int(_native.lib().exabm4d_groupnorm_workspace_bytes(2, 512, 32, 8))
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    _native.context(0).groupnorm_lrelu_ndhwc(torch.cuda.current_stream().cuda_stream, x_dev, y, 2, 512, 32, 8,
+                                             norm.weight, norm.bias, 1e-5, 0.01, ws, need, cb)
+    host = buf.cpu().numpy()
+    assert np.all(host[:pre] == -7.25) and np.all(host[pre + n:] == -7.25)
+    assert torch.equal(x_dev.view(torch.int32), x0.view(torch.int32))
+    want, bound = gn_bound(x, 8, gamma, beta, 1e-5, 0.01, cbias)
+    got = host[pre:pre + n].reshape(shape)
+    assert _excess(got, want, bound) <= 1.0
+    calls = []
+    real = _native.Context.groupnorm_lrelu_ndhwc
+    _native.Context.groupnorm_lrelu_ndhwc = lambda self, *a, **k: (calls.append(a[1:3]), real(self, *a, **k))[1]
+    try:
+        with torch.no_grad():
+            out = inference.FusedGroupNormLeakyReLU(norm, torch.nn.LeakyReLU(0.01), cb, inplace=False).eval()(x_dev)
+    finally:
+        _native.Context.groupnorm_lrelu_ndhwc = real
+    assert len(calls) == 1 and calls[0][0] is x_dev and calls[0][1] is out
+    assert out.data_ptr() != x_dev.data_ptr() and out.is_contiguous(memory_format=torch.channels_last_3d)
+    assert torch.equal(x_dev.view(torch.int32), x0.view(torch.int32))
+    np.testing.assert_array_equal(to_host(out).view(np.int32), got.view(np.int32))
 
 
 # ---- MaxPool3d(2) ------------------------------------------------------------------------------------------
