@@ -184,10 +184,12 @@ static int ensure_scratch(exabm4d_ctx* ctx, size_t bytes) {
 }
 static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 // The kernels raise bits of the context's status word instead of hanging (block matching's carry: bm_kernels.hip
-// ORDER).  Looked at wherever the host has just synchronised with the context's stream.
-static int check_async_status(exabm4d_ctx* ctx) {
-    if (!ctx->status_host || *ctx->status_host == 0) return EXABM4D_OK;
-    const unsigned bits = *ctx->status_host;
+// ORDER).  Looked at, and cleared, wherever the host has just synchronised with the context's stream; `fired` gets
+// the bits.  With both set the carry's error is returned: host_batch repeats the run, and the repeat reports bit 1.
+static int check_async_status(exabm4d_ctx* ctx, unsigned* fired = nullptr) {
+    const unsigned bits = ctx->status_host ? *ctx->status_host : 0u;
+    if (fired) *fired = bits;
+    if (bits == 0) return EXABM4D_OK;
     *ctx->status_host = 0;
     if (bits & 1u) {
         ctx->bm.carry = 0;       // the assumption behind the carry failed on this device: do without it from now on
@@ -562,17 +564,84 @@ size_t exabm4d_scratch_bytes(int nz, int ny, int nx, int batch, int stages) {
     return pipe_bytes(BmOpts(), nz, ny, nx, batch, stages);     // default options; includes the carry (round 4)
 }
 
+// ---- argument checks of the BM4D entry points, in the order each entry has always reported them -----------
+static int arg_checks(exabm4d_ctx* ctx, bool ptrs_ok, const exabm4d_params* p) {   // first: NULL, params
+    if (!ctx || !ptrs_ok) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    return check_params(ctx, p);
+}
+static int geom_on_device(exabm4d_ctx* ctx, int nz, int ny, int nx, int batch, VolGeom& g) {   // last: geometry, device
+    int rc = make_geom(ctx, nz, ny, nx, batch, g);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return EXABM4D_OK;
+}
+// the whole-pipeline entries: NULL, params, sigma, stages, then the batch geometry (pipeline_checks) or the chunk
+// sizes (chunk_checks)
+static int bm4d_checks(exabm4d_ctx* ctx, const void* in, const void* out, float sigma, const exabm4d_params* p,
+                       int stages) {
+    int rc = arg_checks(ctx, in && out, p);
+    if (rc) return rc;
+    if (!(sigma > 0.0f)) return fail(ctx, EXABM4D_ERR_INVALID, "sigma must be > 0");
+    if (stages != 1 && stages != 2) return fail(ctx, EXABM4D_ERR_INVALID, "stages must be 1 or 2");
+    return EXABM4D_OK;
+}
+static int pipeline_checks(exabm4d_ctx* ctx, const void* in, const void* out, int nz, int ny, int nx,
+                           int batch, float sigma, const exabm4d_params* p, int stages, VolGeom& g) {
+    int rc = bm4d_checks(ctx, in, out, sigma, p, stages);
+    if (!rc) rc = geom_on_device(ctx, nz, ny, nx, batch, g);
+    return rc ? rc : ensure_window(ctx, (double)p->kaiser_beta);
+}
+static int chunk_checks(exabm4d_ctx* ctx, const void* in, const void* out, int nz, int ny, int nx, int chunk,
+                        int halo, float sigma, const exabm4d_params* p, int stages) {
+    int rc = bm4d_checks(ctx, in, out, sigma, p, stages);
+    if (!rc && (nz < 1 || ny < 1 || nx < 1 || chunk < 1 || halo < 0 || halo > 64))
+        rc = fail(ctx, EXABM4D_ERR_INVALID, "chunked: sizes >= 1, chunk >= 1, 0 <= halo <= 64");
+    return rc;
+}
+static int check_offset(exabm4d_ctx* ctx, float offset) {   // |v - offset| < 2^17: the uint16 pipelines' fixed unit
+    if (std::fabs(offset) <= 65536.0f) return EXABM4D_OK;
+    return fail(ctx, EXABM4D_ERR_INVALID, "offset must lie within [-65536, 65536]");
+}
+
+// (float)v - offset is exact in fp32 for every uint16 v iff the offset has at most 7 fractional bits
+// (17 integer bits of |v - offset| + 7 = 24) -- 0, 37, 100.5 ...; only then do two voxels of the
+// fp32 counts differ by an exact integer and the integer matching kernel reproduce the float
+// kernel's (and the oracle's) tables.  A percentile such as 36.73 takes the float kernel.
+static bool offset_exact_in_fp32(float offset) {
+    const float s = offset * 128.0f;
+    return std::fabs(offset) <= 65536.0f && s == std::rint(s);
+}
+// Integer block matching (bm_tile16_kernel) on `vol16`, the uint16 shadow of n voxels cast with `offset`, where its
+// tables equal the float kernel's: c sigma^2 512 < 2^24, even rows, counts exact in fp32, shadow
+// in guarded scratch.  exabm4d_blockmatch_u16_dev casts with offset 0, which is always exact.
+static bool int_match_ok(const exabm4d_ctx* ctx, float c_match, float sigma, const VolGeom& g,
+                         const uint16_t* vol16, size_t n, float offset) {
+    const double tau512 = (double)c_match * (double)sigma * (double)sigma * 512.0;
+    return vol16 && ctx->bm_int && tau512 < 16777216.0 && (g.nx % 2) == 0 && offset_exact_in_fp32(offset) &&
+           guarded_region_ok(ctx, vol16, n * sizeof(uint16_t));
+}
+
+// A uint16 pipeline run's scratch: pipe_bytes, fp32 counts, GUARD_BYTES, uint16 shadow (run_pipeline's guarded
+// regions rely on this layout).
+static int u16_pipe_scratch(exabm4d_ctx* ctx, const VolGeom& g, int batch, int stages, float*& f32, uint16_t*& u16) {
+    const size_t n = (size_t)g.nvox * (size_t)batch, pipe = pipe_bytes(ctx->bm, g.nz, g.ny, g.nx, batch, stages);
+    const size_t fbytes = align256(n * sizeof(float));
+    int rc = ensure_scratch(ctx, pipe + fbytes + GUARD_BYTES + align256(n * sizeof(uint16_t)));
+    if (rc) return rc;
+    f32 = reinterpret_cast<float*>(static_cast<char*>(ctx->scratch) + pipe);
+    u16 = reinterpret_cast<uint16_t*>(static_cast<char*>(ctx->scratch) + pipe + fbytes + GUARD_BYTES);
+    return EXABM4D_OK;
+}
+
 // ---- staged entry points ---------------------------------------------------------------------------------
 int exabm4d_blockmatch_dev(exabm4d_ctx* ctx, const float* vol, int nz, int ny, int nx, int batch,
                            float sigma, float c_match, const exabm4d_params* p, uint32_t* keys) {
-    if (!ctx || !vol || !keys) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
-    int rc = check_params(ctx, p);
+    int rc = arg_checks(ctx, vol && keys, p);
     if (rc) return rc;
     if (!(sigma > 0.0f) || !(c_match > 0.0f)) return fail(ctx, EXABM4D_ERR_INVALID, "sigma and c_match must be > 0");
     VolGeom g;
-    rc = make_geom(ctx, nz, ny, nx, batch, g);
+    rc = geom_on_device(ctx, nz, ny, nx, batch, g);
     if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     const BmPlan plan = bm_plan(g, batch, ctx->bm);
     if (ctx->bm_guarded_copy) {
         // parity hook for the pipeline's path: match on a copy inside the scratch allocation, with
@@ -603,14 +672,12 @@ int exabm4d_blockmatch_dev(exabm4d_ctx* ctx, const float* vol, int nz, int ny, i
 // kernel's (else the float kernel), one-wave kernel for clamped last grid positions.
 int exabm4d_blockmatch_u16_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, int ny, int nx, int batch,
                                float sigma, float c_match, const exabm4d_params* p, uint32_t* keys) {
-    if (!ctx || !vol || !keys) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
-    int rc = check_params(ctx, p);
+    int rc = arg_checks(ctx, vol && keys, p);
     if (rc) return rc;
     if (!(sigma > 0.0f) || !(c_match > 0.0f)) return fail(ctx, EXABM4D_ERR_INVALID, "sigma and c_match must be > 0");
     VolGeom g;
-    rc = make_geom(ctx, nz, ny, nx, batch, g);
+    rc = geom_on_device(ctx, nz, ny, nx, batch, g);
     if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)g.nvox * (size_t)batch;
     const size_t fbytes = align256(n * sizeof(float));
     const BmPlan plan = bm_plan(g, batch, ctx->bm);
@@ -621,9 +688,7 @@ int exabm4d_blockmatch_u16_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, in
     float* f32 = reinterpret_cast<float*>(base + GUARD_BYTES);
     uint16_t* u16 = reinterpret_cast<uint16_t*>(base + 2 * GUARD_BYTES + fbytes);
     HIP_TRY(ctx, launch_counts_from_u16(vol, f32, n, 0.0f, ctx->stream, u16));
-    const double tau512 = (double)c_match * (double)sigma * (double)sigma * 512.0;
-    const bool use16 = ctx->bm_int && tau512 < 16777216.0 && (nx % 2) == 0 &&
-                       guarded_region_ok(ctx, u16, n * sizeof(uint16_t));
+    const bool use16 = int_match_ok(ctx, c_match, sigma, g, u16, n, 0.0f);
     if (!guarded_region_ok(ctx, f32, n * sizeof(float)))
         return fail(ctx, EXABM4D_ERR_INVALID, "internal: guarded volume without mapped slack around it");
     HIP_TRY(ctx, launch_blockmatch(f32, g, batch, keymax_of(sigma, c_match), keys, ctx->stream,
@@ -658,16 +723,14 @@ int exabm4d_match_decode(const uint32_t* keys16, int rz, int ry, int rx, int ny,
 int exabm4d_stage_dev(exabm4d_ctx* ctx, const float* noisy, const float* basic,
                       const uint32_t* keys, int nz, int ny, int nx, int batch, float sigma,
                       const exabm4d_params* p, int data_exp, float* num, float* den) {
-    if (!ctx || !noisy || !keys || !num || !den) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
-    int rc = check_params(ctx, p);
+    int rc = arg_checks(ctx, noisy && keys && num && den, p);
     if (rc) return rc;
     if (!(sigma > 0.0f)) return fail(ctx, EXABM4D_ERR_INVALID, "sigma must be > 0");
     if (data_exp != EXABM4D_DATA_EXP_AUTO && (data_exp < -200 || data_exp > 200))
         return fail(ctx, EXABM4D_ERR_INVALID, "data_exp must be EXABM4D_DATA_EXP_AUTO or within [-200, 200]");
     VolGeom g;
-    rc = make_geom(ctx, nz, ny, nx, batch, g);
+    rc = geom_on_device(ctx, nz, ny, nx, batch, g);
     if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     rc = ensure_window(ctx, (double)p->kaiser_beta);
     if (rc) return rc;
     const float thr = (float)((double)p->lambda_ht * (double)sigma);
@@ -724,15 +787,6 @@ int exabm4d_normalize_u16_dev(exabm4d_ctx* ctx, const float* num, const float* d
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_normalize_u16(num, den, out, n, offset, ctx->stream));
     return EXABM4D_OK;
-}
-
-// (float)v - offset is exact in fp32 for every uint16 v iff the offset has at most 7 fractional bits
-// (17 integer bits of |v - offset| + 7 = 24) -- 0, 37, 100.5 ...; only then do two voxels of the
-// fp32 counts differ by an exact integer and the integer matching kernel reproduce the float
-// kernel's (and the oracle's) tables.  A percentile such as 36.73 takes the float kernel.
-static bool offset_exact_in_fp32(float offset) {
-    const float s = offset * 128.0f;
-    return std::fabs(offset) <= 65536.0f && s == std::rint(s);
 }
 
 // Bracket one phase of a pipeline call with events when profiling is on.
@@ -811,10 +865,8 @@ static int run_pipeline(exabm4d_ctx* ctx, const float* noisy, float* out_f32, ui
     int pair_ready = 0;      // the first normalisation wrote the Wiener stage's (noisy, basic) volume
     // stage 2 of a uint16 pipeline in the integer kernel?  Decided here because the first
     // normalisation then also writes the rounded estimate (into noisy16's memory: stage 1 is done with it)
-    const bool match_use16 = match_counts && stages >= 2 && noisy16 && ctx->bm_int &&
-                             (double)p->c_match_wie * (double)sigma * (double)sigma * 512.0 < 16777216.0 &&
-                             (g.nx % 2) == 0 && offset_exact_in_fp32(match_offset) &&
-                             guarded_region_ok(ctx, noisy16, n * sizeof(uint16_t));
+    const bool match_use16 = match_counts && stages >= 2 &&
+                             int_match_ok(ctx, p->c_match_wie, sigma, g, noisy16, n, match_offset);
     int match16_ready = 0;
     if (ctx->profile)
         for (int i = 1; i < EXABM4D_PHASE_COUNT; i++) ctx->ev_used[i] = false;
@@ -831,10 +883,7 @@ static int run_pipeline(exabm4d_ctx* ctx, const float* noisy, float* out_f32, ui
     }
     {
         PhaseTimer t(ctx, EXABM4D_PHASE_BLOCKMATCH_HT);
-        const double tau512 = (double)p->c_match_ht * (double)sigma * (double)sigma * 512.0;
-        const bool use16 = noisy16 && ctx->bm_int && tau512 < 16777216.0 && (g.nx % 2) == 0 &&
-                           offset_exact_in_fp32(u16_offset) &&
-                           guarded_region_ok(ctx, noisy16, n * sizeof(uint16_t));
+        const bool use16 = int_match_ok(ctx, p->c_match_ht, sigma, g, noisy16, n, u16_offset);
         HIP_TRY(ctx, launch_blockmatch(noisy, g, batch, keymax_of(sigma, p->c_match_ht), keys, s,
                                        ctx->force_generic_bm, noisy_guarded, use16 ? noisy16 : nullptr, plan,
                                        scratch + L.carry, ctx->status_dev));
@@ -867,8 +916,7 @@ static int run_pipeline(exabm4d_ctx* ctx, const float* noisy, float* out_f32, ui
             const uint16_t* match16 = nullptr;
             int match_guarded = 1;
             if (match_counts) {
-                const bool use16 = match_use16;
-                if (use16) {
+                if (match_use16) {
                     uint16_t* m16 = const_cast<uint16_t*>(noisy16);      // our own scratch; stage 1 is done with it
                     if (!match16_ready)                                  // (normally written by the normalisation)
                         HIP_TRY(ctx, launch_round_counts(basic, nullptr, m16, n, match_offset, s));
@@ -877,7 +925,7 @@ static int run_pipeline(exabm4d_ctx* ctx, const float* noisy, float* out_f32, ui
                 // reference blocks at clamped grid positions (an extent - 8 that is no multiple of 4) go through
                 // the one-wave kernel, which reads fp32: it needs the same counts as fp32
                 const bool generic_too = ctx->force_generic_bm || g.gz != g.az || g.gy != g.ay || g.gx != g.ax;
-                if (!use16 || generic_too) {
+                if (!match_use16 || generic_too) {
                     HIP_TRY(ctx, launch_round_counts(basic, tmp, nullptr, n, match_offset, s));
                     match_on = tmp;
                     match_guarded = guarded_region_ok(ctx, tmp, n * sizeof(float)) ? 1 : 0;
@@ -904,19 +952,6 @@ static int run_pipeline(exabm4d_ctx* ctx, const float* noisy, float* out_f32, ui
     return EXABM4D_OK;
 }
 
-static int pipeline_checks(exabm4d_ctx* ctx, const void* in, const void* out, int nz, int ny, int nx,
-                           int batch, float sigma, const exabm4d_params* p, int stages, VolGeom& g) {
-    if (!ctx || !in || !out) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
-    int rc = check_params(ctx, p);
-    if (rc) return rc;
-    if (!(sigma > 0.0f)) return fail(ctx, EXABM4D_ERR_INVALID, "sigma must be > 0");
-    if (stages != 1 && stages != 2) return fail(ctx, EXABM4D_ERR_INVALID, "stages must be 1 or 2");
-    rc = make_geom(ctx, nz, ny, nx, batch, g);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return ensure_window(ctx, (double)p->kaiser_beta);
-}
-
 int exabm4d_denoise_f32_dev(exabm4d_ctx* ctx, const float* in, float* out, int nz, int ny, int nx,
                             int batch, float sigma, const exabm4d_params* p, int stages,
                             float clip_lo, float clip_hi) {
@@ -935,23 +970,19 @@ int exabm4d_denoise_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out,
     VolGeom g;
     int rc = pipeline_checks(ctx, in, out, nz, ny, nx, batch, sigma, p, stages, g);
     if (rc) return rc;
-    const size_t n = (size_t)g.nvox * (size_t)batch;
-    if (!(std::fabs(offset) <= 65536.0f))     // |v - offset| < 2^17: the fixed unit of the uint16 pipelines
-        return fail(ctx, EXABM4D_ERR_INVALID, "offset must lie within [-65536, 65536]");
-    const size_t base = pipe_bytes(ctx->bm, nz, ny, nx, batch, stages);
-    const size_t fbytes = align256(n * sizeof(float));
-    rc = ensure_scratch(ctx, base + fbytes + GUARD_BYTES + align256(n * sizeof(uint16_t)));
+    rc = check_offset(ctx, offset);
     if (rc) return rc;
-    char* scratch = static_cast<char*>(ctx->scratch);
-    float* noisy = reinterpret_cast<float*>(scratch + base);
-    uint16_t* noisy16 = reinterpret_cast<uint16_t*>(scratch + base + fbytes + GUARD_BYTES);
+    float* noisy;
+    uint16_t* noisy16;
+    rc = u16_pipe_scratch(ctx, g, batch, stages, noisy, noisy16);
+    if (rc) return rc;
     ctx->ev_used[EXABM4D_PHASE_COUNTS_FROM_U16] = false;
     {
         PhaseTimer t(ctx, EXABM4D_PHASE_COUNTS_FROM_U16);
-        HIP_TRY(ctx, launch_counts_from_u16(in, noisy, n, offset, ctx->stream, noisy16));
+        HIP_TRY(ctx, launch_counts_from_u16(in, noisy, (size_t)g.nvox * (size_t)batch, offset, ctx->stream, noisy16));
     }
     return run_pipeline(ctx, noisy, nullptr, out, g, batch, sigma, p, stages, 0.0f, 0.0f, offset,
-                        scratch, 1, EXABM4D_DATA_EXP_U16, noisy16, 1, offset);
+                        static_cast<char*>(ctx->scratch), 1, EXABM4D_DATA_EXP_U16, noisy16, 1, offset);
 }
 
 // Chunk-local mode: every chunk (core + halo, the halo cut off where the buffer ends) is denoised
@@ -960,15 +991,11 @@ int exabm4d_denoise_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out,
 int exabm4d_denoise_chunked_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out, int nz, int ny,
                                     int nx, int zc0, int zc1, int chunk, int halo, float sigma,
                                     float offset, const exabm4d_params* p, int stages) {
-    if (!ctx || !in || !out) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
-    int rc = check_params(ctx, p);
+    int rc = chunk_checks(ctx, in, out, nz, ny, nx, chunk, halo, sigma, p, stages);
     if (rc) return rc;
-    if (!(sigma > 0.0f)) return fail(ctx, EXABM4D_ERR_INVALID, "sigma must be > 0");
-    if (stages != 1 && stages != 2) return fail(ctx, EXABM4D_ERR_INVALID, "stages must be 1 or 2");
-    if (nz < 1 || ny < 1 || nx < 1 || chunk < 1 || halo < 0 || halo > 64)
-        return fail(ctx, EXABM4D_ERR_INVALID, "chunked: sizes >= 1, chunk >= 1, 0 <= halo <= 64");
     if (zc0 < 0 || zc1 > nz || zc0 >= zc1) return fail(ctx, EXABM4D_ERR_INVALID, "chunked: bad core plane range");
-    if (!(std::fabs(offset) <= 65536.0f)) return fail(ctx, EXABM4D_ERR_INVALID, "offset must lie within [-65536, 65536]");
+    rc = check_offset(ctx, offset);
+    if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     rc = ensure_window(ctx, (double)p->kaiser_beta);
     if (rc) return rc;
@@ -1005,18 +1032,14 @@ int exabm4d_denoise_chunked_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, uint16
                     VolGeom g;
                     rc = make_geom(ctx, cb.pz, cb.py, cb.px, count, g);
                     if (rc) return rc;
-                    const size_t n = (size_t)g.nvox * (size_t)count;
-                    const size_t base = pipe_bytes(ctx->bm, cb.pz, cb.py, cb.px, count, stages);
-                    const size_t fbytes = align256(n * sizeof(float));
-                    rc = ensure_scratch(ctx, base + fbytes + GUARD_BYTES + align256(n * sizeof(uint16_t)));
+                    float* vol;
+                    uint16_t* vol16;
+                    rc = u16_pipe_scratch(ctx, g, count, stages, vol, vol16);
                     if (rc) return rc;
-                    char* scratch = static_cast<char*>(ctx->scratch);
-                    float* vol = reinterpret_cast<float*>(scratch + base);
-                    uint16_t* vol16 = reinterpret_cast<uint16_t*>(scratch + base + fbytes + GUARD_BYTES);
                     HIP_TRY(ctx, launch_chunk_gather(in, cb, offset, vol, ctx->stream, vol16));
                     rc = run_pipeline(ctx, vol, vol, nullptr, g, count, sigma, p, stages, 1.0f, 0.0f, 0.0f,
-                                      scratch, 1, EXABM4D_DATA_EXP_U16, offset_exact_in_fp32(offset) ? vol16 : nullptr,
-                                      1, offset);
+                                      static_cast<char*>(ctx->scratch), 1, EXABM4D_DATA_EXP_U16,
+                                      offset_exact_in_fp32(offset) ? vol16 : nullptr, 1, offset);
                     if (rc) return rc;
                     HIP_TRY(ctx, launch_chunk_scatter(vol, cb, offset, out, ctx->stream));
                 }
@@ -1060,13 +1083,8 @@ struct StreamedLayers {
 int exabm4d_denoise_chunked_u16_host(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out, int nz, int ny,
                                      int nx, int chunk, int halo, float sigma, float offset,
                                      const exabm4d_params* p, int stages) {
-    if (!ctx || !in || !out) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
-    int rc = check_params(ctx, p);
+    int rc = chunk_checks(ctx, in, out, nz, ny, nx, chunk, halo, sigma, p, stages);
     if (rc) return rc;
-    if (!(sigma > 0.0f)) return fail(ctx, EXABM4D_ERR_INVALID, "sigma must be > 0");
-    if (stages != 1 && stages != 2) return fail(ctx, EXABM4D_ERR_INVALID, "stages must be 1 or 2");
-    if (nz < 1 || ny < 1 || nx < 1 || chunk < 1 || halo < 0 || halo > 64)
-        return fail(ctx, EXABM4D_ERR_INVALID, "chunked: sizes >= 1, chunk >= 1, 0 <= halo <= 64");
     {   // the downloads of early layers would overwrite planes that later layers still have to upload
         const size_t bytes = (size_t)nz * (size_t)ny * (size_t)nx * sizeof(uint16_t);
         const char *a = reinterpret_cast<const char*>(in), *b = reinterpret_cast<const char*>(out);
@@ -1189,7 +1207,7 @@ int exabm4d_denoise_chunked_u16_host(exabm4d_ctx* ctx, const uint16_t* in, uint1
 static constexpr size_t HOST_SUB_VOXELS = (size_t)1 << 26;
 static int denoise_f32_host_pipelined(exabm4d_ctx* ctx, const float* in, float* out, int nz, int ny, int nx,
                                       int batch, int sub, float sigma, const exabm4d_params* p, int stages,
-                                      float clip_lo, float clip_hi) {
+                                      float clip_lo, float clip_hi, unsigned* fired) {
     VolGeom g;
     int rc = make_geom(ctx, nz, ny, nx, sub, g);
     if (rc) return rc;
@@ -1238,7 +1256,46 @@ static int denoise_f32_host_pipelined(exabm4d_ctx* ctx, const float* in, float* 
                                 nv * count_of(nsub - 1) * sizeof(float), hipMemcpyDeviceToHost, cs));
     HIP_TRY(ctx, hipStreamSynchronize(cs));
     HIP_TRY(ctx, hipStreamSynchronize(s));
-    return check_async_status(ctx);
+    return check_async_status(ctx, fired);
+}
+
+// A host run is repeated, once and in one piece, only when the carry's wait ran out (bit 0) in a run that had the
+// carry on (check_async_status has now switched it off); any other error, bit 1 included, is returned as is.
+static bool repeat_without_carry(unsigned fired, bool carry_was_on) { return (fired & 1u) && carry_was_on; }
+
+// The host batch entries' body: the batch lies in `pieces` host arrays of `per_piece` voxels.  `out[i]` may be
+// `in[i]`: the results go to the host only once the run is known to be good, and a repeat reads `in` again.
+static int host_batch(exabm4d_ctx* ctx, const float* const* in, float* const* out, int pieces, size_t per_piece,
+                      const VolGeom& g, int batch, float sigma, const exabm4d_params* p, int stages, float clip_lo,
+                      float clip_hi) {
+    const size_t n = (size_t)g.nvox * (size_t)batch;
+    int rc = EXABM4D_OK;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        const bool carry_was_on = ctx->bm.carry != 0;
+        const size_t base = pipe_bytes(ctx->bm, g.nz, g.ny, g.nx, batch, stages);
+        rc = ensure_scratch(ctx, base + align256(n * sizeof(float)));
+        if (rc) return rc;
+        char* scratch = static_cast<char*>(ctx->scratch);
+        float* vol = reinterpret_cast<float*>(scratch + base);
+        for (int i = 0; i < pieces; i++)
+            HIP_TRY(ctx, hipMemcpyAsync(vol + (size_t)i * per_piece, in[i], per_piece * sizeof(float),
+                                        hipMemcpyHostToDevice, ctx->stream));
+        rc = run_pipeline(ctx, vol, vol, nullptr, g, batch, sigma, p, stages, clip_lo, clip_hi, 0.0f,
+                          scratch, 1, EXABM4D_DATA_EXP_AUTO);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        unsigned fired = 0;
+        rc = check_async_status(ctx, &fired);
+        if (rc == EXABM4D_OK) {
+            for (int i = 0; i < pieces; i++)
+                HIP_TRY(ctx, hipMemcpyAsync(out[i], vol + (size_t)i * per_piece, per_piece * sizeof(float),
+                                            hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            return EXABM4D_OK;
+        }
+        if (!repeat_without_carry(fired, carry_was_on)) return rc;
+    }
+    return rc;
 }
 
 int exabm4d_denoise_f32_host(exabm4d_ctx* ctx, const float* in, float* out, int nz, int ny, int nx,
@@ -1247,40 +1304,20 @@ int exabm4d_denoise_f32_host(exabm4d_ctx* ctx, const float* in, float* out, int 
     VolGeom g;
     int rc = pipeline_checks(ctx, in, out, nz, ny, nx, batch, sigma, p, stages, g);
     if (rc) return rc;
-    const size_t n = (size_t)g.nvox * (size_t)batch;
     // Large batches of volumes: sub-batches with the copies under the kernels.  Not in place (a repeated run
     // must find its input), not while a debug option wants to see one launch.
     const size_t per = std::max<size_t>(1, HOST_SUB_VOXELS / (size_t)g.nvox);
     if (ctx->host_pipeline && in != out && batch >= 2 && (size_t)batch >= 2 * per && per <= 65535) {
+        const bool carry_was_on = ctx->bm.carry != 0;
+        unsigned fired = 0;
         rc = denoise_f32_host_pipelined(ctx, in, out, nz, ny, nx, batch, (int)per, sigma, p, stages, clip_lo,
-                                        clip_hi);
+                                        clip_hi, &fired);
         if (rc != EXABM4D_OK && ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);   // nothing of it left in flight
-        if (rc == EXABM4D_OK || ctx->bm.carry != 0) return rc;
-        // the carry's wait ran out somewhere (it is off now): once more below, in one piece
+        if (rc == EXABM4D_OK || !repeat_without_carry(fired, carry_was_on)) return rc;
+        // the carry's wait ran out somewhere (it is off now): once more, in one piece
     }
-    // This call owns its input and synchronises, so a run whose carry wait ran out (check_async_status) is
-    // simply repeated without the carry: the caller of bm4d(raw, sigma) sees a result, never a hang or a retry.
-    for (int attempt = 0;; attempt++) {
-        const size_t base = pipe_bytes(ctx->bm, nz, ny, nx, batch, stages);
-        rc = ensure_scratch(ctx, base + align256(n * sizeof(float)));
-        if (rc) return rc;
-        char* scratch = static_cast<char*>(ctx->scratch);
-        float* vol = reinterpret_cast<float*>(scratch + base);
-        HIP_TRY(ctx, hipMemcpyAsync(vol, in, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        rc = run_pipeline(ctx, vol, vol, nullptr, g, batch, sigma, p, stages, clip_lo, clip_hi, 0.0f,
-                          scratch, 1, EXABM4D_DATA_EXP_AUTO);
-        if (rc) return rc;
-        // (out may be in: the result goes to the host only once the run is known to be good)
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        rc = check_async_status(ctx);
-        if (rc != EXABM4D_OK) {
-            if (attempt == 1 || ctx->bm.carry != 0) return rc;
-            continue;
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(out, vol, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        return EXABM4D_OK;
-    }
+    return host_batch(ctx, &in, &out, 1, (size_t)g.nvox * (size_t)batch, g, batch, sigma, p, stages, clip_lo,
+                      clip_hi);
 }
 
 // The same for a batch whose volumes lie anywhere in host memory (the broker's shape: every caller's patch in
@@ -1293,32 +1330,7 @@ int exabm4d_denoise_f32_host_v(exabm4d_ctx* ctx, const float* const* in, float* 
     if (rc) return rc;
     for (int b = 0; b < batch; b++)
         if (!in[b] || !out[b]) return fail(ctx, EXABM4D_ERR_INVALID, "NULL volume pointer");
-    const size_t nv = (size_t)g.nvox, n = nv * (size_t)batch;
-    for (int attempt = 0;; attempt++) {
-        const size_t base = pipe_bytes(ctx->bm, nz, ny, nx, batch, stages);
-        rc = ensure_scratch(ctx, base + align256(n * sizeof(float)));
-        if (rc) return rc;
-        char* scratch = static_cast<char*>(ctx->scratch);
-        float* vol = reinterpret_cast<float*>(scratch + base);
-        for (int b = 0; b < batch; b++)
-            HIP_TRY(ctx, hipMemcpyAsync(vol + (size_t)b * nv, in[b], nv * sizeof(float), hipMemcpyHostToDevice,
-                                        ctx->stream));
-        rc = run_pipeline(ctx, vol, vol, nullptr, g, batch, sigma, p, stages, clip_lo, clip_hi, 0.0f,
-                          scratch, 1, EXABM4D_DATA_EXP_AUTO);
-        if (rc) return rc;
-        // (a repeated run reads in[] again: the results go to the host only once the run is known to be good)
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        rc = check_async_status(ctx);
-        if (rc != EXABM4D_OK) {
-            if (attempt == 1 || ctx->bm.carry != 0) return rc;
-            continue;
-        }
-        for (int b = 0; b < batch; b++)
-            HIP_TRY(ctx, hipMemcpyAsync(out[b], vol + (size_t)b * nv, nv * sizeof(float), hipMemcpyDeviceToHost,
-                                        ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        return EXABM4D_OK;
-    }
+    return host_batch(ctx, in, out, batch, (size_t)g.nvox, g, batch, sigma, p, stages, clip_lo, clip_hi);
 }
 
 // ---- BM4DNet stage: fused GroupNorm + LeakyReLU on NDHWC tensors (nn_kernels.hip) ------------------------

@@ -131,7 +131,8 @@ def test_a_carry_wait_that_runs_out_is_an_error_not_a_hang(ctx, oracle, carry):
     and the wait ends; it is bounded all the same.  The debug option "bm_carry_fault" makes every wait count
     as run out: the launch finishes (void tables), the next synchronising call reports EXABM4D_ERR_HIP and
     names the carry, the context switches the carry off and works -- and the bm4d() path
-    (exabm4d_denoise_f32_host) repeats its run without the carry by itself."""
+    (exabm4d_denoise_f32_host) and the broker's (exabm4d_denoise_f32_host_v) repeat their run without the
+    carry by themselves."""
     vol = synth_volume((100, 40, 44), seed=5, as_u16=True)[0]
     f = vol.astype(np.float32) - np.float32(37.0)
     want = oracle.blockmatch(f, SIGMA, 3.0)
@@ -144,13 +145,60 @@ def test_a_carry_wait_that_runs_out_is_an_error_not_a_hang(ctx, oracle, carry):
         assert not _native.blockmatch_plan(vol.shape, ctx=ctx)["carry"]          # off for this context now
         np.testing.assert_array_equal(_keys(ctx, vol, 3.0, False), want)         # and the context works
         carry(2)                                              # forced again, fault still armed: the host entry recovers
+        want_f = oracle.bm4d(f, SIGMA, stages=1)
         got = ctx.denoise_f32_host(f, SIGMA, stages=1)
-        np.testing.assert_array_equal(got, oracle.bm4d(f, SIGMA, stages=1))
+        np.testing.assert_array_equal(got, want_f)
+        assert not _native.blockmatch_plan(vol.shape, ctx=ctx)["carry"]
+        carry(2)                                              # the same through the per-volume host entry
+        got = np.empty_like(f)
+        ctx.denoise_f32_host_v([f.ctypes.data], [got.ctypes.data], f.shape, SIGMA, stages=1)
+        np.testing.assert_array_equal(got, want_f)
         assert not _native.blockmatch_plan(vol.shape, ctx=ctx)["carry"]
     finally:
         ctx.set_option("bm_carry_fault", 0)
     carry(2)
     np.testing.assert_array_equal(_keys(ctx, vol, 3.0, False), want)             # the carry itself is intact
+
+
+def test_a_host_call_repeats_only_a_run_that_had_the_carry(ctx, oracle, carry):
+    """The host entries repeat a run by themselves only when the carry's wait ran out in a run that had the carry
+    on.  A carry fault left pending by an earlier launch that nobody synchronised with, found by a host call that
+    runs without the carry, is reported (that launch's tables are void), not absorbed by a repeat; the next call
+    works.  With the carry off, fp32 input outside the working range is refused as with it on."""
+    vol = synth_volume((100, 40, 44), seed=5, as_u16=True)[0]
+    f = vol.astype(np.float32) - np.float32(37.0)
+    want = oracle.bm4d(f, SIGMA, stages=1)
+    g = [len(_native.grid_positions(n)) for n in vol.shape]
+
+    def host(x):
+        return ctx.denoise_f32_host(x, SIGMA, stages=1)
+
+    def host_v(x):
+        out = np.empty_like(x)
+        ctx.denoise_f32_host_v([x.ctypes.data], [out.ctypes.data], x.shape, SIGMA, stages=1)
+        return out
+
+    d_vol = ctx.to_device(f)
+    d_keys = ctx.alloc(g[0] * g[1] * g[2] * 16 * 4)
+    ctx.set_option("bm_carry_fault", 1)
+    try:
+        for run in (host, host_v):
+            carry(2)
+            ctx.blockmatch(d_vol, vol.shape, SIGMA, 3.0, d_keys)      # its carry waits run out; no sync yet
+            carry(0)
+            with pytest.raises(_native.NativeError, match="carry"):
+                run(f)
+            np.testing.assert_array_equal(run(f), want)
+        nan = f.copy()
+        nan[3, 4, 5] = np.nan
+        for run in (host, host_v):
+            with pytest.raises(ValueError, match="working range"):
+                run(nan)
+        np.testing.assert_array_equal(host(f), want)
+    finally:
+        ctx.set_option("bm_carry_fault", 0)
+        d_vol.free()
+        d_keys.free()
 
 
 def test_options_belong_to_their_context(ctx):
