@@ -27,6 +27,12 @@ c_i64p = ctypes.POINTER(ctypes.c_int64)
 c_vp = ctypes.c_void_p
 
 KEY_EMPTY = 0xFFFFFFFF
+LABEL_SET_MAX = 1024        # exabm4d.h EXABM4D_LABEL_SET_MAX: distinct labels one patch's device set holds
+SEG_STATS_K = 23            # exabm4d.h EXABM4D_SEG_STATS_K
+GAUSS_MAX_RADIUS = 64       # exabm4d.h EXABM4D_GAUSS_MAX_RADIUS
+# exabm4d.h label element types
+LABEL_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.uint32): 1, np.dtype(np.uint64): 2,
+                np.dtype(np.int32): 3, np.dtype(np.int64): 4}
 DATA_EXP_AUTO = -2 ** 31    # exabm4d.h EXABM4D_DATA_EXP_AUTO: E per volume from the data (fp32 entry points)
 DATA_EXP_U16 = 17           # exabm4d.h EXABM4D_DATA_EXP_U16: the uint16 pipelines' fixed E
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2   # exabm4d.h exabm4d_dtype: element types of the *_dt_dev entries
@@ -157,6 +163,12 @@ SIGNATURES = {
                                             ctypes.c_double, c_vp]),
     "exabm4d_ssim3d_dev": (_I, [_CTX, c_vp, c_vp, _I, _I, _I, _I, _I, ctypes.c_double,
                                 ctypes.c_double, c_vp]),
+    "exabm4d_foreground_masks_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, _F, _I, c_vp, c_vp]),
+    "exabm4d_binary_dilate_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp]),
+    "exabm4d_gaussian_filter3d_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp, _I, c_vp]),
+    "exabm4d_label_set_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp]),
+    "exabm4d_segment_stats_dev": (_I, [_CTX, c_vp, _I, c_vp, _I, c_vp, _I, _I, _I, _I, _I, c_vp, c_vp, _I,
+                                       c_vp]),
 }
 
 _lib = None
@@ -299,6 +311,12 @@ class DeviceBuffer:
         if self.ptr:
             lib().exabm4d_free(self.ctx.handle, self.ptr)
             self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
 
     def __del__(self):
         try:
@@ -632,6 +650,55 @@ class Context:
                                              self.DTYPES[np.dtype(dtype)], nz, ny, nx, int(window),
                                              float(c1), float(c2), out.ctypes.data_as(c_vp)))
         return float(out[0])
+
+    # -- patch-cache masks and coherence gate; batches of (nz, ny, nx) patches --
+    def foreground_masks(self, raw, dtype, batch, shape, k, dilate, mask):
+        """Masks into the device bytes ``mask``; returns the per-patch fp32 thresholds."""
+        thr = np.empty(batch, dtype=np.float32)
+        nz, ny, nx = shape
+        self._check(lib().exabm4d_foreground_masks_dev(
+            self.handle, _ptr(raw), self.DTYPES[np.dtype(dtype)], int(batch), nz, ny, nx, float(k),
+            int(dilate), _ptr(mask), thr.ctypes.data_as(c_vp)))
+        return thr
+
+    def binary_dilate(self, src, batch, shape, iterations, out):
+        nz, ny, nx = shape
+        self._check(lib().exabm4d_binary_dilate_dev(self.handle, _ptr(src), int(batch), nz, ny, nx,
+                                                    int(iterations), _ptr(out)))
+
+    def gaussian_filter3d(self, src, dtype, batch, shape, weights, out):
+        """``weights``: the centre-and-right half (radius + 1 doubles) of the normalised kernel."""
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        nz, ny, nx = shape
+        self._check(lib().exabm4d_gaussian_filter3d_dev(
+            self.handle, _ptr(src), self.DTYPES[np.dtype(dtype)], int(batch), nz, ny, nx,
+            w.ctypes.data_as(c_vp), len(w) - 1, _ptr(out)))
+
+    def label_set(self, labels, dtype, batch, shape):
+        """(keys, counts, held, status): keys / counts (batch, LABEL_SET_MAX), unordered."""
+        keys = np.empty((batch, LABEL_SET_MAX), dtype=np.uint64)
+        counts = np.empty((batch, LABEL_SET_MAX), dtype=np.uint32)
+        held = np.empty(batch, dtype=np.uint32)
+        status = np.empty(batch, dtype=np.uint32)
+        nz, ny, nx = shape
+        self._check(lib().exabm4d_label_set_dev(
+            self.handle, _ptr(labels), LABEL_DTYPES[np.dtype(dtype)], int(batch), nz, ny, nx,
+            keys.ctypes.data_as(c_vp), counts.ctypes.data_as(c_vp), held.ctypes.data_as(c_vp),
+            status.ctypes.data_as(c_vp)))
+        return keys, counts, held, status
+
+    def segment_stats(self, labels, label_dtype, raw, raw_dtype, smooth, batch, shape, lag,
+                      item_patch, item_key):
+        """(n_items, SEG_STATS_K) float64 statistics of each (patch, label) item."""
+        ip = np.ascontiguousarray(item_patch, dtype=np.int32)
+        ik = np.ascontiguousarray(item_key, dtype=np.uint64)
+        out = np.empty((len(ip), SEG_STATS_K), dtype=np.float64)
+        nz, ny, nx = shape
+        self._check(lib().exabm4d_segment_stats_dev(
+            self.handle, _ptr(labels), LABEL_DTYPES[np.dtype(label_dtype)], _ptr(raw),
+            self.DTYPES[np.dtype(raw_dtype)], _ptr(smooth), int(batch), nz, ny, nx, int(lag),
+            ip.ctypes.data_as(c_vp), ik.ctypes.data_as(c_vp), len(ip), out.ctypes.data_as(c_vp)))
+        return out
 
     def close(self):
         if self.handle and os.getpid() == self.pid:

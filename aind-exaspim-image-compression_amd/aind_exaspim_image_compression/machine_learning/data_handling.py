@@ -17,8 +17,13 @@ Provided with the reference's names and behaviour: ``build_training_example`` (:
 ``CachedPatchDataset`` (:1015-1187), ``CachedValidateDataset`` (:1190-1217); plus
 ``PatchCacheWriter`` / ``write_patch_cache`` (the file-writing half of ``precompute()``) and
 ``load_cached_transform`` (``scripts/train_bm4dnet.py:42-79``).  The cloud datasets, samplers and
-mask builders of the reference module are out of scope: the writer takes the
-patches and masks from the caller.
+the resample loop of the reference module are out of scope: the writer takes
+the patches from the caller.  The masks it may take too; without them it builds the reference's
+``sample_counts`` fallback (``data_handling.py:929-930``), ``make_foreground_mask`` of each raw
+patch, on the device (``metrics.foreground_masks``).  The mask builders and the coherence gate the
+reference's samplers call (``data_handling.py:398-405, 444, 477, 500``) are in ``metrics``:
+callers that resample like ``sample_clean`` gate their draws with ``metrics.incoherent_segments``
+(one device pass per batch of draws) before writing them.
 """
 import json
 import os
@@ -224,15 +229,22 @@ class PatchCacheWriter:
                               shape=shape)
         self.written = 0
 
-    def write(self, raw, fg_mask):
+    def write(self, raw, fg_mask=None):
         """Append a batch: ``raw`` (B, *patch_shape) offset-subtracted counts, ``fg_mask`` the
-        matching boolean masks.  The teacher is ``clip(bm4d(raw, sigma), 0, max_count)``
-        (``data_handling.py:332-333``) from the HIP path."""
+        matching boolean masks, or None for ``make_foreground_mask(raw)`` of each patch, built on
+        the device (the reference's fallback, ``data_handling.py:929-930``).  Draws are not
+        resampled here: gate them with ``metrics.incoherent_segments`` first.  The teacher is
+        ``clip(bm4d(raw, sigma), 0, max_count)`` (``data_handling.py:332-333``) from the HIP path."""
         from aind_exaspim_image_compression.bm4d import denoise_patches
         raw = np.asarray(raw, dtype=COUNT_DTYPE)
-        fg_mask = np.asarray(fg_mask)
         if raw.ndim == len(self.patch_shape):
-            raw, fg_mask = raw[None], fg_mask[None]
+            raw = raw[None]
+            if fg_mask is not None:
+                fg_mask = np.asarray(fg_mask)[None]
+        if fg_mask is None and raw.ndim == 4 and raw.shape[1:] == self.patch_shape:
+            from aind_exaspim_image_compression.machine_learning.metrics import foreground_masks
+            fg_mask = foreground_masks(raw)
+        fg_mask = np.asarray(fg_mask)
         if raw.shape[1:] != self.patch_shape or fg_mask.shape != raw.shape:
             raise ValueError("patch / mask shape does not match the cache's patch_shape")
         if self.written + len(raw) > self.n_patches:

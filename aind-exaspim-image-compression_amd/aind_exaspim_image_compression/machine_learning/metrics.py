@@ -9,8 +9,16 @@ and the bright-voxel count (``exabm4d_masked_error_stats_dev``), and the percent
 MAD come from device histograms (``utils/order_stats.py``).  Integer-valued inputs give the
 reference's numbers exactly; float inputs differ only by fp64 summation order.
 
-The mask builders of the reference module (segmentation / skeleton / coherence masks, lines
-32-303) belong to the training data pipeline and are out of scope.
+The mask builders and the coherence gate of the reference module (lines 32-303) are here too,
+with the reference's names, signatures, defaults and return types: ``make_foreground_mask``,
+``local_autocorr``, ``highfreq_energy_fraction``, ``make_segmentation_mask``,
+``patch_has_incoherent_segment`` and ``make_skeleton_mask``; plus the batched forms
+``foreground_masks`` and ``incoherent_segments`` that take (B, z, y, x) arrays and make one device
+pass each.  The per-patch median / MAD threshold, the binary dilation, the Gaussian
+smoothing (scipy's ``gaussian_filter`` bit for bit), the distinct-label set and the per-segment
+two-pass statistics are HIP kernels (``csrc/mask_kernels.hip``); the host only rasterises skeleton
+points, sorts the short label lists and applies the reference's finishing rules to the sums.
+There is no CPU fallback: without a GPU they raise ``NativeError``.
 """
 import numpy as np
 
@@ -192,3 +200,254 @@ def checkpoint_score(metrics, cratio, weights=None):
         + w.get("top_pct_error", 0.0) * metrics["top_pct_error"]
         - w.get("cratio", 0.0) * cratio
     )
+
+
+# ---- patch-cache mask builders and coherence gate (reference metrics.py:32-303) -----------------
+GAUSS_TRUNCATE = 4.0        # scipy.ndimage.gaussian_filter's default truncate
+_SEG = {"n": 0, "mean_raw": 1, "mean_hf": 2, "ss_raw": 3, "ss_hf": 4, "axes": 5}   # segment_stats columns
+
+
+def gaussian_weights(sigma):
+    """The centre-and-right half of scipy's ``_gaussian_kernel1d(sigma, 0, int(4 * sigma + 0.5))``,
+    computed the way scipy computes it (the kernel is symmetric bit for bit).  A sigma scipy skips
+    (<= 1e-15) gives the identity kernel."""
+    if float(sigma) <= 1e-15:
+        return np.ones(1, dtype=np.float64)
+    radius = int(GAUSS_TRUNCATE * float(sigma) + 0.5)
+    if radius > _native.GAUSS_MAX_RADIUS:
+        raise ValueError(f"smooth_sigma {sigma} needs a radius above {_native.GAUSS_MAX_RADIUS}")
+    sigma2 = sigma * sigma
+    x = np.arange(-radius, radius + 1)
+    phi_x = np.exp(-0.5 / sigma2 * x ** 2)
+    phi_x = phi_x / phi_x.sum()
+    return np.ascontiguousarray(phi_x[radius:])
+
+
+def autocorr_from_stats(st):
+    """``local_autocorr`` from one row of segment statistics (``SEG_STATS_K`` columns): the
+    reference's rules (metrics.py:100-113) on centred pair sums."""
+    vals = []
+    for ax in range(3):
+        n, _, _, sxx, syy, sxy = (float(v) for v in st[_SEG["axes"] + 6 * ax:_SEG["axes"] + 6 * ax + 6])
+        if n < 2:
+            continue
+        if np.sqrt(sxx / n) < 1e-6 or np.sqrt(syy / n) < 1e-6:
+            continue
+        # np.corrcoef: cov / stddev / stddev, clipped to [-1, 1]
+        c = (sxy / (n - 1)) / np.sqrt(sxx / (n - 1)) / np.sqrt(syy / (n - 1))
+        vals.append(float(np.clip(c, -1.0, 1.0)))
+    return float(np.mean(vals)) if vals else 1.0
+
+
+def highfreq_from_stats(st):
+    """``highfreq_energy_fraction`` from one row of segment statistics (metrics.py:150-155):
+    0.0 when the masked variance is below 1e-12, NaN for an empty mask (numpy's var of nothing)."""
+    n = float(st[_SEG["n"]])
+    if n == 0:
+        return float("nan")
+    var_v = float(st[_SEG["ss_raw"]]) / n
+    if var_v < 1e-12:
+        return 0.0
+    return float((float(st[_SEG["ss_hf"]]) / n) / var_v)
+
+
+def _patches(arr, ndim, name):
+    arr = np.asarray(arr)
+    if arr.ndim != ndim:
+        raise ValueError(f"{name} must be {ndim}-D, got shape {arr.shape}")
+    if 0 in arr.shape[-3:]:
+        raise ValueError(f"{name} has an empty axis: {arr.shape}")
+    return arr
+
+
+def _raw_f32(raw):
+    """uint16 converts to float32 exactly on the device; everything else is cast on the host, as
+    the reference casts it (``np.asarray(raw, dtype=np.float32)``)."""
+    return np.ascontiguousarray(raw if raw.dtype == np.uint16 else raw.astype(np.float32, copy=False))
+
+
+def _raw_f64(raw):
+    """The reference widens raw to float64; uint16 and float32 widen exactly on the device."""
+    if raw.dtype in (np.uint16, np.float32):
+        return np.ascontiguousarray(raw.astype(np.float32, copy=False))
+    return np.ascontiguousarray(raw.astype(np.float64, copy=False))
+
+
+def _labels_dev(labels):
+    """Labels as an element type the device reads: uint8 / uint32 / uint64 / int32 / int64."""
+    if labels.dtype == np.bool_:
+        return np.ascontiguousarray(labels.view(np.uint8))
+    if labels.dtype.kind not in "iu":
+        raise ValueError(f"labels must be integers, got {labels.dtype}")
+    if labels.dtype in (np.uint8, np.uint32, np.uint64, np.int32, np.int64):
+        return np.ascontiguousarray(labels)
+    return np.ascontiguousarray(labels.astype(np.uint32 if labels.dtype.kind == "u" else np.int32))
+
+
+def foreground_masks(raw, k=6.0, dilate=1):
+    """``make_foreground_mask`` of every patch of ``raw`` (B, z, y, x) in one device pass:
+    a (B, z, y, x) bool array."""
+    raw = _patches(raw, 4, "raw")
+    if raw.shape[0] == 0:
+        return np.zeros(raw.shape, dtype=bool)
+    src = _raw_f32(raw)
+    ctx = _native.context()
+    with ctx.to_device(src) as d_raw, ctx.alloc(src.size) as d_mask:
+        ctx.foreground_masks(d_raw, src.dtype, src.shape[0], src.shape[1:], k, max(int(dilate), 0), d_mask)
+        return d_mask.download(src.shape, np.uint8).view(bool)
+
+
+def _dilate(masks, iterations):
+    """scipy.ndimage.binary_dilation(m, iterations) of every (z, y, x) mask of ``masks`` (B, ...)."""
+    m = np.ascontiguousarray(masks, dtype=bool).view(np.uint8)
+    ctx = _native.context()
+    with ctx.to_device(m) as d_in, ctx.alloc(m.size) as d_out:
+        ctx.binary_dilate(d_in, m.shape[0], m.shape[1:], max(int(iterations), 0), d_out)
+        return d_out.download(m.shape, np.uint8).view(bool)
+
+
+def make_foreground_mask(raw, k=6.0, dilate=1):
+    """Robust intensity foreground mask, raw > median + k * 1.4826 * MAD, then ``dilate`` binary
+    dilations (reference metrics.py:32-62): ``foreground_masks`` with B = 1."""
+    return foreground_masks(_patches(raw, 3, "raw")[None], k, dilate)[0]
+
+
+def make_segmentation_mask(labels, dilate=0):
+    """``labels > 0``, dilated ``dilate`` times on the device (reference metrics.py:161-199)."""
+    labels = _patches(labels, 3, "labels")
+    return _dilate((labels > 0)[None], dilate if dilate > 0 else 0)[0]
+
+
+def make_skeleton_mask(points, start, patch_shape, dilate=2):
+    """Skeleton points inside the patch rasterised as the reference does, then ``dilate`` binary
+    dilations on the device (reference metrics.py:263-303)."""
+    start = np.asarray(start)
+    stop = start + np.asarray(patch_shape)
+    pts = np.asarray(points)
+    inside = np.all((pts >= start) & (pts < stop), axis=1)
+    mask = np.zeros(tuple(patch_shape), dtype=bool)
+    local = (pts[inside] - start).astype(int)
+    if local.size:
+        mask[local[:, 0], local[:, 1], local[:, 2]] = True
+    mask = _patches(mask, 3, "patch")
+    return _dilate(mask[None], dilate if dilate > 0 else 0)[0]
+
+
+def _segment_stats(ctx, d_labels, label_dtype, d_raw, raw_dtype, d_smooth, batch, shape, lag,
+                   item_patch, item_key):
+    lag = int(lag)
+    if lag < 1:
+        raise ValueError("lag must be >= 1")
+    return ctx.segment_stats(d_labels, label_dtype, d_raw, raw_dtype, d_smooth, batch, shape, lag,
+                             item_patch, item_key)
+
+
+def _single_mask_stats(raw, mask, lag, smooth, smooth_sigma):
+    """Segment statistics of one boolean mask over one patch (the mask is label 1)."""
+    raw = _patches(raw, 3, "raw")
+    mask = np.asarray(mask, dtype=bool)
+    if mask.shape != raw.shape:
+        raise ValueError("raw and mask shapes differ")
+    src = _raw_f64(raw)
+    m = np.ascontiguousarray(mask).view(np.uint8)
+    ctx = _native.context()
+    with ctx.to_device(src) as d_raw, ctx.to_device(m) as d_mask:
+        d_smooth = None
+        try:
+            if smooth is not None:
+                sm = np.asarray(smooth, dtype=np.float64)
+                if sm.shape != raw.shape:
+                    raise ValueError("raw and smooth shapes differ")
+                d_smooth = ctx.to_device(sm)
+            elif smooth_sigma is not None:
+                d_smooth = ctx.alloc(src.size * 8)
+                ctx.gaussian_filter3d(d_raw, src.dtype, 1, src.shape, gaussian_weights(smooth_sigma), d_smooth)
+            return _segment_stats(ctx, d_mask, np.uint8, d_raw, src.dtype, d_smooth, 1, src.shape, lag,
+                                  [0], [1])[0]
+        finally:
+            if d_smooth is not None:
+                d_smooth.free()
+
+
+def local_autocorr(raw, mask, lag=2):
+    """Mean over the axes of the Pearson correlation of masked voxel pairs ``lag`` apart; 1.0 when
+    no axis can be measured (reference metrics.py:65-113)."""
+    return autocorr_from_stats(_single_mask_stats(raw, mask, lag, None, None))
+
+
+def highfreq_energy_fraction(raw, mask, smooth=None, smooth_sigma=1.0):
+    """``var(raw - smooth) / var(raw)`` over the mask, ``smooth`` the Gaussian-smoothed raw
+    (computed on the device when not given); 0.0 when the masked variance is below 1e-12
+    (reference metrics.py:116-158)."""
+    return highfreq_from_stats(_single_mask_stats(raw, mask, 1, smooth, smooth_sigma))
+
+
+def _label_lists(ctx, d_labels, labels, batch, shape):
+    """Per patch, np.unique(labels[labels > 0], return_counts=True): the device set, sorted here;
+    a patch the set cannot hold is counted on the host."""
+    keys, counts, held, status = ctx.label_set(d_labels, labels.dtype, batch, shape)
+    out = []
+    for b in range(batch):
+        if status[b]:
+            lb = labels[b]
+            u, c = np.unique(lb[lb > 0], return_counts=True)
+            out.append((u.astype(np.uint64), c.astype(np.int64)))
+        else:
+            k = keys[b, :held[b]]
+            order = np.argsort(k, kind="stable")
+            out.append((k[order], counts[b, :held[b]][order].astype(np.int64)))
+    return out
+
+
+def segment_scores(labels, raw, min_segment_voxels=50, smooth_sigma=1.0, coherence_lag=2):
+    """For every patch of (B, z, y, x) ``labels`` / ``raw``, the list of
+    ``(label, voxels, autocorr, highfreq)`` of its segments with at least ``min_segment_voxels``
+    voxels, in ``np.unique`` order: what ``patch_has_incoherent_segment`` decides on."""
+    labels = _patches(labels, 4, "labels")
+    raw = _patches(raw, 4, "raw")
+    if labels.shape != raw.shape:
+        raise ValueError("labels and raw shapes differ")
+    batch, shape = labels.shape[0], labels.shape[1:]
+    scores = [[] for _ in range(batch)]
+    if batch == 0:
+        return scores
+    lab = _labels_dev(labels)
+    ctx = _native.context()
+    with ctx.to_device(lab) as d_labels:
+        lists = _label_lists(ctx, d_labels, lab, batch, shape)
+        item_patch, item_key, item_count = [], [], []
+        for b, (keys, counts) in enumerate(lists):
+            keep = counts >= min_segment_voxels
+            item_patch += [b] * int(keep.sum())
+            item_key += [int(x) for x in keys[keep]]
+            item_count += [int(x) for x in counts[keep]]
+        if not item_patch:
+            return scores
+        src = _raw_f64(raw)
+        with ctx.to_device(src) as d_raw, ctx.alloc(src.size * 8) as d_smooth:
+            ctx.gaussian_filter3d(d_raw, src.dtype, batch, shape, gaussian_weights(smooth_sigma), d_smooth)
+            st = _segment_stats(ctx, d_labels, lab.dtype, d_raw, src.dtype, d_smooth, batch, shape,
+                                coherence_lag, item_patch, np.array(item_key, dtype=np.uint64))
+    for b, key, cnt, row in zip(item_patch, item_key, item_count, st):
+        scores[b].append((key, cnt, autocorr_from_stats(row), highfreq_from_stats(row)))
+    return scores
+
+
+def incoherent_segments(labels, raw, min_autocorr=0.4, max_highfreq_frac=0.35, min_segment_voxels=50,
+                        smooth_sigma=1.0, coherence_lag=2):
+    """``patch_has_incoherent_segment`` of every patch of (B, z, y, x) ``labels`` / ``raw`` in one
+    device pass: a (B,) bool array."""
+    scores = segment_scores(labels, raw, min_segment_voxels, smooth_sigma, coherence_lag)
+    return np.array([any(not (ac >= min_autocorr) and hf > max_highfreq_frac for _, _, ac, hf in seg)
+                     for seg in scores], dtype=bool)
+
+
+def patch_has_incoherent_segment(labels, raw, min_autocorr=0.4, max_highfreq_frac=0.35,
+                                 min_segment_voxels=50, smooth_sigma=1.0, coherence_lag=2):
+    """True when a segment of at least ``min_segment_voxels`` voxels fails both coherence tests:
+    lag-``coherence_lag`` autocorrelation below ``min_autocorr`` and high-frequency energy fraction
+    above ``max_highfreq_frac`` (reference metrics.py:202-260): ``incoherent_segments`` with B = 1."""
+    labels = _patches(labels, 3, "labels")
+    raw = _patches(raw, 3, "raw")
+    return bool(incoherent_segments(labels[None], raw[None], min_autocorr, max_highfreq_frac,
+                                    min_segment_voxels, smooth_sigma, coherence_lag)[0])

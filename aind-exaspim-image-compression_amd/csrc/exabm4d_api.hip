@@ -1785,4 +1785,125 @@ int exabm4d_ssim3d_dev(exabm4d_ctx* ctx, const void* a, const void* b, int dtype
     return metric_fetch(ctx, sum_host, d, sizeof(double));
 }
 
+// ---- patch-cache foreground masks and coherence gate ---------------------------------
+static int check_patches(exabm4d_ctx* ctx, int batch, int nz, int ny, int nx) {
+    if (batch < 1 || nz < 1 || ny < 1 || nx < 1) return fail(ctx, EXABM4D_ERR_INVALID, "bad batch / sizes");
+    if ((long long)nz * ny * nx >= (1ll << 32) || (long long)nz * ny * nx * batch > (1ll << 40))
+        return fail(ctx, EXABM4D_ERR_INVALID, "patch or batch too large");
+    return EXABM4D_OK;
+}
+
+static_assert(LS_MAX == EXABM4D_LABEL_SET_MAX && SEG_STATS_K == EXABM4D_SEG_STATS_K &&
+              GF_MAXR == EXABM4D_GAUSS_MAX_RADIUS && LBL_I64 == EXABM4D_LBL_I64, "exabm4d.h and exabm4d_kernels.h differ");
+
+int exabm4d_foreground_masks_dev(exabm4d_ctx* ctx, const void* raw, int dtype, int batch, int nz, int ny,
+                                 int nx, float k, int dilate, uint8_t* mask, float* thr_host) {
+    if (!ctx || !raw || !mask) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (dtype != EXABM4D_DT_U16 && dtype != EXABM4D_DT_F32)
+        return fail(ctx, EXABM4D_ERR_INVALID, "raw must be uint16 or float32");
+    if (dilate < 0) return fail(ctx, EXABM4D_ERR_INVALID, "dilate must be >= 0");
+    if (int rc = check_patches(ctx, batch, nz, ny, nx)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t total = (size_t)nz * ny * nx * batch, thr_bytes = align256((size_t)batch * sizeof(float));
+    if (int rc = metric_scratch(ctx, thr_bytes + (dilate > 1 ? total : 0))) return rc;
+    float* thr = (float*)ctx->red;
+    uint8_t* tmp = (uint8_t*)ctx->red + thr_bytes;
+    HIP_TRY(ctx, launch_fg_threshold(raw, dtype, batch, (size_t)nz * ny * nx, k, thr, ctx->stream));
+    HIP_TRY(ctx, launch_dilate(nullptr, raw, dtype, thr, batch, nz, ny, nx, dilate, tmp, mask, ctx->stream));
+    if (thr_host) return metric_fetch(ctx, thr_host, thr, (size_t)batch * sizeof(float));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return EXABM4D_OK;
+}
+
+int exabm4d_binary_dilate_dev(exabm4d_ctx* ctx, const uint8_t* in, int batch, int nz, int ny, int nx,
+                              int iterations, uint8_t* out) {
+    if (!ctx || !in || !out) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (in == out) return fail(ctx, EXABM4D_ERR_INVALID, "in and out must be distinct");
+    if (iterations < 0) return fail(ctx, EXABM4D_ERR_INVALID, "iterations must be >= 0");
+    if (int rc = check_patches(ctx, batch, nz, ny, nx)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t total = (size_t)nz * ny * nx * batch;
+    if (iterations > 1)
+        if (int rc = metric_scratch(ctx, total)) return rc;
+    HIP_TRY(ctx, launch_dilate(in, nullptr, 0, nullptr, batch, nz, ny, nx, iterations, (uint8_t*)ctx->red, out,
+                               ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return EXABM4D_OK;
+}
+
+int exabm4d_gaussian_filter3d_dev(exabm4d_ctx* ctx, const void* src, int dtype, int batch, int nz, int ny,
+                                  int nx, const double* weights_host, int radius, double* out) {
+    if (!ctx || !src || !weights_host || !out) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (dtype != EXABM4D_DT_F32 && dtype != EXABM4D_DT_F64)
+        return fail(ctx, EXABM4D_ERR_INVALID, "src must be float32 or float64");
+    if (src == out) return fail(ctx, EXABM4D_ERR_INVALID, "src and out must be distinct");
+    if (radius < 0 || radius > EXABM4D_GAUSS_MAX_RADIUS)
+        return fail(ctx, EXABM4D_ERR_UNSUPPORTED, "gaussian radius must be 0..EXABM4D_GAUSS_MAX_RADIUS");
+    if (int rc = check_patches(ctx, batch, nz, ny, nx)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    GaussWeights w{};
+    w.radius = radius;
+    for (int j = 0; j <= radius; j++) w.w[j] = weights_host[j];
+    const size_t total = (size_t)nz * ny * nx * batch;
+    if (int rc = metric_scratch(ctx, total * sizeof(double))) return rc;
+    HIP_TRY(ctx, launch_gaussian3d(src, dtype, batch, nz, ny, nx, w, (double*)ctx->red, out, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return EXABM4D_OK;
+}
+
+static bool bad_label_dtype(int d) { return d < EXABM4D_LBL_U8 || d > EXABM4D_LBL_I64; }
+
+int exabm4d_label_set_dev(exabm4d_ctx* ctx, const void* labels, int label_dtype, int batch, int nz, int ny,
+                          int nx, uint64_t* keys_host, uint32_t* counts_host, uint32_t* n_host,
+                          uint32_t* status_host) {
+    if (!ctx || !labels || !keys_host || !counts_host || !n_host || !status_host)
+        return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (bad_label_dtype(label_dtype)) return fail(ctx, EXABM4D_ERR_INVALID, "bad label dtype");
+    if (int rc = check_patches(ctx, batch, nz, ny, nx)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t nk = (size_t)batch * LS_MAX;
+    const size_t kb = align256(nk * 8), cb = align256(nk * 4), nb = align256((size_t)batch * 4);
+    if (int rc = metric_scratch(ctx, kb + cb + 2 * nb)) return rc;
+    uint8_t* d = (uint8_t*)ctx->red;
+    unsigned long long* keys = (unsigned long long*)d;
+    uint32_t* counts = (uint32_t*)(d + kb);
+    uint32_t* n_out = (uint32_t*)(d + kb + cb);
+    uint32_t* status = (uint32_t*)(d + kb + cb + nb);
+    HIP_TRY(ctx, launch_label_set(labels, label_dtype, batch, (size_t)nz * ny * nx, keys, counts, n_out, status,
+                                  ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(keys_host, keys, nk * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(counts_host, counts, nk * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(n_host, n_out, (size_t)batch * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return metric_fetch(ctx, status_host, status, (size_t)batch * 4);
+}
+
+int exabm4d_segment_stats_dev(exabm4d_ctx* ctx, const void* labels, int label_dtype, const void* raw,
+                              int raw_dtype, const double* smooth, int batch, int nz, int ny, int nx, int lag,
+                              const int32_t* item_patch_host, const uint64_t* item_key_host, int n_items,
+                              double* out_host) {
+    if (!ctx || !labels || !raw || (n_items > 0 && (!item_patch_host || !item_key_host || !out_host)))
+        return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (bad_label_dtype(label_dtype) || (raw_dtype != EXABM4D_DT_F32 && raw_dtype != EXABM4D_DT_F64))
+        return fail(ctx, EXABM4D_ERR_INVALID, "bad label / raw dtype");
+    if (lag < 1 || n_items < 0) return fail(ctx, EXABM4D_ERR_INVALID, "lag must be >= 1, n_items >= 0");
+    if (int rc = check_patches(ctx, batch, nz, ny, nx)) return rc;
+    for (int i = 0; i < n_items; i++)
+        if (item_patch_host[i] < 0 || item_patch_host[i] >= batch)
+            return fail(ctx, EXABM4D_ERR_INVALID, "item patch index out of range");
+    if (n_items == 0) return EXABM4D_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t pb = align256((size_t)n_items * 4), kb = align256((size_t)n_items * 8);
+    const size_t ob = (size_t)n_items * SEG_STATS_K * sizeof(double);
+    if (int rc = metric_scratch(ctx, pb + kb + ob)) return rc;
+    uint8_t* d = (uint8_t*)ctx->red;
+    int32_t* ip = (int32_t*)d;
+    unsigned long long* ik = (unsigned long long*)(d + pb);
+    double* o = (double*)(d + pb + kb);
+    HIP_TRY(ctx, hipMemcpyAsync(ip, item_patch_host, (size_t)n_items * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ik, item_key_host, (size_t)n_items * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, launch_segment_stats(labels, label_dtype, raw, raw_dtype, smooth, nz, ny, nx, lag, ip, ik,
+                                      n_items, o, ctx->stream));
+    return metric_fetch(ctx, out_host, o, ob);
+}
+
 }  // extern "C"

@@ -185,4 +185,30 @@ hipError_t launch_rans2_encode(const void* vol, const CodecGeom& g, const uint32
 hipError_t launch_rans2_decode(const uint8_t* in, size_t in_bytes, const unsigned long long* offsets,
                                const CodecGeom& g, void* vol, uint32_t* status, hipStream_t s);
 
+// ---- patch-cache masks and coherence gate (mask_kernels.hip) ---------------------------------------------
+constexpr int LS_MAX = 1024;        // distinct labels a patch's LDS hash set holds (exabm4d.h EXABM4D_LABEL_SET_MAX)
+constexpr int SEG_STATS_K = 23;     // doubles per (patch, label) of launch_segment_stats (EXABM4D_SEG_STATS_K)
+constexpr int GF_MAXR = 64;         // largest Gaussian radius (exabm4d.h EXABM4D_GAUSS_MAX_RADIUS)
+enum { LBL_U8 = 0, LBL_U32 = 1, LBL_U64 = 2, LBL_I32 = 3, LBL_I64 = 4 };
+struct GaussWeights {
+    int radius;
+    double w[GF_MAXR + 1];          // w[0] centre, w[j] = w[-j]
+};
+// raw: dtype 0 uint16, 1 float32; thr[batch] fp32
+hipError_t launch_fg_threshold(const void* raw, int dtype, int batch, size_t n, float k, float* thr,
+                               hipStream_t s);
+// thr != NULL: the source is raw > thr[b] (raw_dtype as above), else the masks `in` (!= out)
+hipError_t launch_dilate(const uint8_t* in, const void* raw, int raw_dtype, const float* thr, int batch,
+                         int nz, int ny, int nx, int iterations, uint8_t* tmp, uint8_t* out,
+                         hipStream_t s);
+// src: dtype 1 float32, 2 float64
+hipError_t launch_gaussian3d(const void* src, int dtype, int batch, int nz, int ny, int nx,
+                             const GaussWeights& w, double* tmp, double* out, hipStream_t s);
+hipError_t launch_label_set(const void* labels, int ldtype, int batch, size_t n, unsigned long long* keys,
+                            uint32_t* counts, uint32_t* n_out, uint32_t* status, hipStream_t s);
+// raw: rdtype 1 float32, 2 float64; smooth may be NULL (then the raw - smooth columns are 0)
+hipError_t launch_segment_stats(const void* labels, int ldtype, const void* raw, int rdtype, const double* smooth,
+                                int nz, int ny, int nx, int lag, const int32_t* item_patch,
+                                const unsigned long long* item_key, int items, double* out, hipStream_t s);
+
 }  // namespace exabm4d

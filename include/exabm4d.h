@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define EXABM4D_VERSION 400 /* additive within 400: + exabm4d_groupnorm_lrelu_ndhwc_dt_dev, exabm4d_maxpool2_ndhwc_dt_dev, exabm4d_upsample2_trilinear_ndhwc_dt_dev (fp16 / bf16 BM4DNet kernels); 0.4.0 (round 4): order-independent aggregation -- exabm4d_stage_dev takes data_exp and WRITES num / den, options "stage_pairs" / "stage_quads" / "fuse_den_z" are gone, the stage / block-matching options are per context; 0.3.2: + exabm4d_blockmatch_plan, option "stage_strip"; 0.3.1: + exabm4d_denoise_chunked_u16_host, options "bm_carry" / "bm_xcd_mode"; 0.3.0: EXAC v2 coder, exabm4d_codec_decode_dev takes in_bytes (round 3) */
+#define EXABM4D_VERSION 400 /* additive within 400: + exabm4d_foreground_masks_dev, exabm4d_binary_dilate_dev, exabm4d_gaussian_filter3d_dev, exabm4d_label_set_dev, exabm4d_segment_stats_dev (patch-cache masks and coherence gate); + exabm4d_groupnorm_lrelu_ndhwc_dt_dev, exabm4d_maxpool2_ndhwc_dt_dev, exabm4d_upsample2_trilinear_ndhwc_dt_dev (fp16 / bf16 BM4DNet kernels); 0.4.0 (round 4): order-independent aggregation -- exabm4d_stage_dev takes data_exp and WRITES num / den, options "stage_pairs" / "stage_quads" / "fuse_den_z" are gone, the stage / block-matching options are per context; 0.3.2: + exabm4d_blockmatch_plan, option "stage_strip"; 0.3.1: + exabm4d_denoise_chunked_u16_host, options "bm_carry" / "bm_xcd_mode"; 0.3.0: EXAC v2 coder, exabm4d_codec_decode_dev takes in_bytes (round 3) */
 
 typedef enum exabm4d_status {
     EXABM4D_OK = 0,
@@ -509,6 +509,61 @@ int exabm4d_masked_error_stats_dev(exabm4d_ctx* ctx, const void* pred, int pred_
  * supplied by the caller: ssim3D of utils/img_util.py:953-1003 is *sum_host / (nz ny nx). */
 int exabm4d_ssim3d_dev(exabm4d_ctx* ctx, const void* a, const void* b, int dtype, int nz, int ny,
                        int nx, int window, double c1, double c2, double* sum_host);
+
+/* ---- patch-cache foreground masks and coherence gate --
+ * Batches of `batch` patches of nz x ny x nx voxels, contiguous in HBM.  Every entry point
+ * synchronises the context's stream; floating-point results are deterministic (fixed mappings and
+ * fixed-order reductions) and independent of the batch size. */
+#define EXABM4D_LABEL_SET_MAX 1024    /* distinct positive labels one patch's device hash set holds */
+#define EXABM4D_SEG_STATS_K 23        /* doubles per item of exabm4d_segment_stats_dev */
+#define EXABM4D_GAUSS_MAX_RADIUS 64   /* largest radius of exabm4d_gaussian_filter3d_dev */
+/* Label element types (signed types: ids <= 0 are background; unsigned: 0 is). */
+enum { EXABM4D_LBL_U8 = 0, EXABM4D_LBL_U32 = 1, EXABM4D_LBL_U64 = 2, EXABM4D_LBL_I32 = 3, EXABM4D_LBL_I64 = 4 };
+
+/* make_foreground_mask of every patch (machine_learning/metrics.py:32-62): per patch, med =
+ * median(raw) and mad = median(|raw - med|) + 1e-6 by an exact radix selection, thr = med +
+ * k * (1.4826 * mad), every step rounded to fp32 as numpy does; mask = raw > thr, then `dilate`
+ * iterations of scipy.ndimage.binary_dilation (6-neighbour cross, border 0).  raw: dtype
+ * EXABM4D_DT_U16 or EXABM4D_DT_F32; mask: batch * nz * ny * nx bytes (0 / 1) on the device;
+ * thr_host: NULL or `batch` floats. */
+int exabm4d_foreground_masks_dev(exabm4d_ctx* ctx, const void* raw, int dtype, int batch, int nz, int ny,
+                                 int nx, float k, int dilate, uint8_t* mask, float* thr_host);
+
+/* scipy.ndimage.binary_dilation(m, iterations) of every patch -- the dilation of
+ * make_segmentation_mask and make_skeleton_mask (metrics.py:196-198, 296-302).  in and out are
+ * distinct device arrays of 0 / non-0 bytes; iterations >= 0 (0 copies). */
+int exabm4d_binary_dilate_dev(exabm4d_ctx* ctx, const uint8_t* in, int batch, int nz, int ny, int nx,
+                              int iterations, uint8_t* out);
+
+/* scipy.ndimage.gaussian_filter(src.astype(float64), sigma) of every patch, bit for bit
+ * (metrics.py:145, 278): axes 0, 1, 2 in turn with fp64 intermediates, mode "reflect" (repeated
+ * on axes shorter than the radius), per output acc = x[0] w[0], then acc += (x[-j] + x[+j]) w[j]
+ * for j = radius .. 1.  weights_host[radius + 1] is the centre-and-right half of scipy's
+ * normalised kernel; radius <= EXABM4D_GAUSS_MAX_RADIUS.  src: EXABM4D_DT_F32 or EXABM4D_DT_F64;
+ * out: batch * nz * ny * nx doubles on the device. */
+int exabm4d_gaussian_filter3d_dev(exabm4d_ctx* ctx, const void* src, int dtype, int batch, int nz, int ny,
+                                  int nx, const double* weights_host, int radius, double* out);
+
+/* The distinct positive labels of every patch and their voxel counts (np.unique(labels[labels > 0])
+ * of metrics.py:280, unordered): keys_host / counts_host [batch][EXABM4D_LABEL_SET_MAX],
+ * n_host[batch] the number held, status_host[batch] 1 when the patch has more distinct labels than
+ * the set holds (its keys are then incomplete and the caller must count it another way). */
+int exabm4d_label_set_dev(exabm4d_ctx* ctx, const void* labels, int label_dtype, int batch, int nz, int ny,
+                          int nx, uint64_t* keys_host, uint32_t* counts_host, uint32_t* n_host,
+                          uint32_t* status_host);
+
+/* Segment statistics for local_autocorr / highfreq_energy_fraction (metrics.py:65-158), one item
+ * per (patch item_patch_host[i], label item_key_host[i]); a voxel belongs to the segment when its
+ * label equals the key (signed labels <= 0 never do).  Two passes, the second centred on the means
+ * of the first; out_host[i * EXABM4D_SEG_STATS_K + .] = { n, mean raw, mean (raw - smooth), sum
+ * (raw - mean)^2, sum (raw - smooth - mean)^2, then for axes 0, 1, 2: pairs (v, v + lag along the
+ * axis) with both voxels in the segment, mean x = raw[v], mean y = raw[v + lag], Sxx, Syy, Sxy
+ * centred }.  raw: EXABM4D_DT_F32 or EXABM4D_DT_F64; smooth: NULL (raw - smooth columns 0) or
+ * batch * nz * ny * nx doubles; lag >= 1. */
+int exabm4d_segment_stats_dev(exabm4d_ctx* ctx, const void* labels, int label_dtype, const void* raw,
+                              int raw_dtype, const double* smooth, int batch, int nz, int ny, int nx, int lag,
+                              const int32_t* item_patch_host, const uint64_t* item_key_host, int n_items,
+                              double* out_host);
 
 #ifdef __cplusplus
 }
