@@ -29,23 +29,29 @@ constexpr int NE = 6;        // dy values per pass (two passes: dy = -5..0 and 1
 constexpr int NSTEP = SWIN * 2 * 4;             // (dz, pass, z) steps
 // A wave is one z-layer of TCY x TCX cells (64 lanes).  8 x 8 is the shape for volumes; 4 x 16
 // tiles a 64^3 patch (15 reference positions per axis) exactly in x (15) and y (5 x 3), where the
-// cube needs 3 x 3 tiles of 7 x 7 positions for the same 15 x 15.
+// cube needs 3 x 3 tiles of 7 x 7 positions for the same 15 x 15.  The tile plan is common to the
+// float and the integer kernel (bm_plan); their shapes add how a plane is staged.
 template <int TCY_, int TCX_>
-struct TileShape {
+struct TilePlan {
     static constexpr int TCY = TCY_, TCX = TCX_;
     static constexpr int TRY = TCY - 1, TRX = TCX - 1;      // reference blocks per tile edge
     static constexpr int PROWS = 4 * (TCY - 1) + 3 + NE;    // staged rows: 4*cy + y + e (37 / 21)
-    static constexpr int PCOLS = 4 * (TCX - 1) + 16;        // staged columns: 4*cx + 0..15 (44 / 76)
+    static_assert(TCY * TCX == 64, "one wave per cell layer");
+};
+template <int TCY_, int TCX_>
+struct TileShape : TilePlan<TCY_, TCX_> {
+    using Plan = TilePlan<TCY_, TCX_>;
+    static constexpr int PCOLS = 4 * (TCX_ - 1) + 16;       // staged columns: 4*cx + 0..15 (44 / 76)
     // row stride in floats.  8 x 8: 56 = 8 (mod 16) makes the b128 window reads of the two cell
     // rows that share 16 lanes conflict-free; 4 x 16: 16 lanes are one cell row, any stride does.
-    static constexpr int PSTR = TCX == 8 ? 56 : PCOLS;
+    static constexpr int PSTR = TCX_ == 8 ? 56 : PCOLS;
     static constexpr int PCH = PSTR / 4;                    // 16-byte chunks per staged row
-    static constexpr int NDMA = (PROWS * PCH + 63) / 64;    // LDS-DMA instructions per plane
+    static constexpr int NDMA = (Plan::PROWS * PCH + 63) / 64;    // LDS-DMA instructions per plane
     // floats per plane buffer: the staged rows (the tail of the last LDS-DMA instruction is masked off)
     // or the cell-sum exchange, 33 sums x 64 cells + the y-neighbour overhang of the last row
-    static constexpr int PLANE = (PROWS * PSTR + 3) / 4 * 4;
+    static constexpr int PLANE = (Plan::PROWS * PSTR + 3) / 4 * 4;
     static constexpr int PBUF = PLANE > 2144 ? PLANE : 2144;
-    static_assert(TCY * TCX == 64 && PCOLS % 4 == 0 && PSTR % 4 == 0, "one wave per cell layer");
+    static_assert(PCOLS % 4 == 0 && PSTR % 4 == 0, "whole 16-byte chunks");
 };
 
 // CARRY (round 3).  A reference block is two cell layers, so a tile of eight cell layers gives seven
@@ -135,6 +141,75 @@ __device__ __forceinline__ int launch_position(const Carry& carry, int quota) {
     return s_pos;
 }
 
+// ------------------------------------------------------------------------------------------------
+// What both tile kernels share: which tile a workgroup computes, how a reference lane admits a candidate
+// to its top-16 list and how it writes the list to the table.
+// ------------------------------------------------------------------------------------------------
+// Tile order.  Slab order (xcd_q != 0): one slab = the tiles of ONE tz of all batch elements, all XCDs
+// inside it (xcd_slab_sync); a column is (batch element, ty, tx).  Otherwise every XCD walks its own
+// contiguous range of a batch element's tiles (blockIdx.y = batch element).
+struct TileId {
+    int tz, col, cols;       // z tile, its column and the launch's columns
+    int bi, ty, tx;          // the column's batch element and (y, x) tile
+};
+// false: the workgroup is padding of the slab order and returns
+__device__ __forceinline__ bool tile_id(TileId& t, int tiles_y, int tiles_x, int xcd_q, int nbatch,
+                                        const Carry& carry) {
+    const int per = tiles_y * tiles_x;
+    t.cols = per * nbatch;
+    if (xcd_q) {
+        const int lp = launch_position(carry, (int)(gridDim.x >> 3));
+        const int s = lp < 0 ? -1 : xcd_slab_sync(lp, t.cols, xcd_q);
+        if (s < 0) return false;
+        t.tz = s / t.cols;
+        t.col = s - t.tz * t.cols;
+    } else {
+        const int s = xcd_contiguous(blockIdx.x, gridDim.x);
+        t.tz = s / per;
+        t.col = (int)blockIdx.y * per + (s - t.tz * per);
+    }
+    t.bi = t.col / per;
+    const int pos = t.col - t.bi * per;
+    int ty, tx;             // (locals: fields the two branches write in different orders end up in scratch)
+    if (carry.strip) {      // strips of `strip` tile rows, column-major inside a strip: concurrent tiles form a compact patch
+        const int sidx = pos / (carry.strip * tiles_x), r = pos - sidx * (carry.strip * tiles_x);
+        const int h = min(carry.strip, tiles_y - sidx * carry.strip);
+        tx = r / h;
+        ty = sidx * carry.strip + (r - tx * h);
+    } else {
+        ty = pos / tiles_x;
+        tx = pos - ty * tiles_x;
+    }
+    t.ty = ty;
+    t.tx = tx;
+    return true;
+}
+
+// A reference lane's running top-16 list `list`, `thr` = min(list[15], keymax): a key below it enters the list.
+// Admits candidate `code` at the distance whose fp32 bits are `sbits`.
+__device__ __forceinline__ void list_admit(uint32_t (&list)[MAXG], uint32_t& thr, uint32_t keymax, uint32_t sbits,
+                                           uint32_t code, bool valid) {
+    uint32_t key = (sbits & KEY_DMASK) | code;
+    key = valid ? key : KEY_EMPTY;
+    // thr = min(16th best so far, admission bound): one compare decides
+    if (__any(key < thr)) {
+        const uint32_t kins = key < thr ? key : KEY_EMPTY;
+        list_insert_inplace(list, kins);
+        thr = min(list[MAXG - 1], keymax);
+    }
+}
+// The reference block's 16 keys of the table.
+__device__ __forceinline__ void list_store(uint32_t* out, uint32_t (&list)[MAXG]) {
+    // never empty: a block with an infinity or a NaN in it has no admissible distance, not
+    // even to itself; it forms the one-block group of key 0, so that every key downstream names a block
+    list[0] = list[0] == KEY_EMPTY ? 0u : list[0];
+#pragma unroll
+    for (int k = 0; k < MAXG; k += 4) {
+        uint4 v = make_uint4(list[k], list[k + 1], list[k + 2], list[k + 3]);
+        *reinterpret_cast<uint4*>(out + k) = v;
+    }
+}
+
 // Each WAVE (= one z-layer of 8x8 cells) streams the candidate planes it needs through its own
 // pair of LDS buffers: for a fixed dz and a pass of NE dy values, plane z+dz of the volume
 // (37 rows x 44 columns around the tile) is staged once and serves all 4 x NE x 11 (row, dy, dx)
@@ -155,33 +230,9 @@ __global__ __launch_bounds__(512) void bm_tile_kernel(const float* __restrict__ 
     __shared__ __align__(16) float pbuf_all[TCZ][2][PBUF];
     __shared__ __align__(16) float lower0[2 * CARRY_ROUND + 64];   // wave 0's lower cell layer (from the carry), both rounds
 
-    // Tile order.  Slab order (xcd_q != 0): one slab = the tiles of ONE tz of all batch elements, all XCDs
-    // inside it (xcd_slab_sync); a column is (batch element, ty, tx).  Otherwise every XCD walks its own
-    // contiguous range of a batch element's tiles (blockIdx.y = batch element).
-    const int per = tiles_y * tiles_x, cols = per * nbatch;
-    int tz, col;
-    if (xcd_q) {
-        const int lp = launch_position(carry, (int)(gridDim.x >> 3));
-        const int t = lp < 0 ? -1 : xcd_slab_sync(lp, cols, xcd_q);
-        if (t < 0) return;                         // padding of the slab order
-        tz = t / cols;
-        col = t - tz * cols;
-    } else {
-        const int t = xcd_contiguous(blockIdx.x, gridDim.x);
-        tz = t / per;
-        col = (int)blockIdx.y * per + (t - tz * per);
-    }
-    const int bi = col / per, pos = col - bi * per;
-    int ty, tx;
-    if (carry.strip) {      // strips of `strip` tile rows, column-major inside a strip: concurrent tiles form a compact patch
-        const int sidx = pos / (carry.strip * tiles_x), r = pos - sidx * (carry.strip * tiles_x);
-        const int h = min(carry.strip, tiles_y - sidx * carry.strip);
-        tx = r / h;
-        ty = sidx * carry.strip + (r - tx * h);
-    } else {
-        ty = pos / tiles_x;
-        tx = pos - ty * tiles_x;
-    }
+    TileId id;
+    if (!tile_id(id, tiles_y, tiles_x, xcd_q, nbatch, carry)) return;
+    const int tz = id.tz, col = id.col, cols = id.cols, bi = id.bi, ty = id.ty, tx = id.tx;
     const float* __restrict__ vol = vol_all + (size_t)bi * (size_t)g.nvox;
     uint32_t* __restrict__ keys = keys_all + (size_t)bi * (size_t)g.nref * MAXG;
     const int tid = threadIdx.x;
@@ -425,14 +476,7 @@ __global__ __launch_bounds__(512) void bm_tile_kernel(const float* __restrict__ 
                                 const float S = s0 + s1;
                                 const uint32_t code = (d == RAD && self_row) ? 0u : cbase + d;
                                 const bool valid = vzy && ((xmask >> d) & 1u);
-                                uint32_t key = (__float_as_uint(S) & KEY_DMASK) | code;
-                                key = valid ? key : KEY_EMPTY;
-                                // thr = min(16th best so far, admission bound): one compare decides
-                                if (__any(key < thr)) {
-                                    const uint32_t kins = key < thr ? key : KEY_EMPTY;
-                                    list_insert_inplace(list, kins);
-                                    thr = min(list[MAXG - 1], keymax);
-                                }
+                                list_admit(list, thr, keymax, __float_as_uint(S), code, valid);
                             }
                         }
                     }
@@ -462,17 +506,7 @@ __global__ __launch_bounds__(512) void bm_tile_kernel(const float* __restrict__ 
         if (!xin && step + 1 < NSTEP) stage_edge(step + 1, nxt);
     }
 
-    if (ref_ok) {
-        uint32_t* out = keys + ((size_t)((size_t)iz * g.gy + iy) * g.gx + ix) * MAXG;
-        // never empty: a block with an infinity or a NaN in it has no admissible distance, not
-        // even to itself; it forms the one-block group of key 0, so that every key downstream names a block
-        list[0] = list[0] == KEY_EMPTY ? 0u : list[0];
-#pragma unroll
-        for (int k = 0; k < MAXG; k += 4) {
-            uint4 v = make_uint4(list[k], list[k + 1], list[k + 2], list[k + 3]);
-            *reinterpret_cast<uint4*>(out + k) = v;
-        }
-    }
+    if (ref_ok) list_store(keys + ((size_t)((size_t)iz * g.gy + iy) * g.gx + ix) * MAXG, list);
     } while (false);
 
     if (carry.on) {
@@ -505,20 +539,18 @@ __global__ __launch_bounds__(512) void bm_tile_kernel(const float* __restrict__ 
 // ------------------------------------------------------------------------------------------------
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 template <int TCY_, int TCX_>
-struct TileShape16 {
-    static constexpr int TCY = TCY_, TCX = TCX_;
-    static constexpr int TRY = TCY - 1, TRX = TCX - 1;
-    static constexpr int PROWS = 4 * (TCY - 1) + 3 + NE;          // staged rows (37 / 21)
-    static constexpr int PCOLS = ((4 * TCX + 10 + 7) / 8) * 8;    // staged uint16 columns (48 / 80)
+struct TileShape16 : TilePlan<TCY_, TCX_> {
+    using Plan = TilePlan<TCY_, TCX_>;
+    static constexpr int PCOLS = ((4 * TCX_ + 10 + 7) / 8) * 8;   // staged uint16 columns (48 / 80)
     // row stride in uint16: two cell rows of a 32-lane ds_read_b64 group must fall into different
     // 16-bank windows (8 x 8: 56 = 24 mod 32), one 16-lane cell row is 32 banks (4 x 16: 80 = 16 mod 32)
-    static constexpr int PSTR = TCX == 8 ? 56 : 80;
+    static constexpr int PSTR = TCX_ == 8 ? 56 : 80;
     static constexpr int PCH = PSTR / 8;                          // 16-byte chunks per staged row
-    static constexpr int NDMA = (PROWS * PCH + 63) / 64;
+    static constexpr int NDMA = (Plan::PROWS * PCH + 63) / 64;
     static constexpr int PLANE_DW = NDMA * 256;                   // dwords of one plane buffer
     static constexpr int XCH_DW = (NE / 2) * SWIN * 64;           // cell-sum exchange: 33 sums x 64 cells
     static constexpr int PBUF = PLANE_DW > XCH_DW ? PLANE_DW : XCH_DW;
-    static_assert(TCY * TCX == 64 && PCOLS <= PSTR, "one wave per cell layer");
+    static_assert(PCOLS <= PSTR, "staged columns fit the row");
 };
 
 template <class TS>
@@ -531,31 +563,9 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     __shared__ __align__(16) uint32_t pbuf_all[TCZ][2][PBUF];
     __shared__ __align__(16) uint32_t lower0[2 * CARRY_ROUND + 64];   // wave 0's lower cell layer (from the carry), both rounds
 
-    // tile order: see bm_tile_kernel
-    const int per = tiles_y * tiles_x, cols = per * nbatch;
-    int tz, col;
-    if (xcd_q) {
-        const int lp = launch_position(carry, (int)(gridDim.x >> 3));
-        const int t = lp < 0 ? -1 : xcd_slab_sync(lp, cols, xcd_q);
-        if (t < 0) return;                         // padding of the slab order
-        tz = t / cols;
-        col = t - tz * cols;
-    } else {
-        const int t = xcd_contiguous(blockIdx.x, gridDim.x);
-        tz = t / per;
-        col = (int)blockIdx.y * per + (t - tz * per);
-    }
-    const int bi = col / per, pos = col - bi * per;
-    int ty, tx;
-    if (carry.strip) {      // strips of `strip` tile rows, column-major inside a strip: concurrent tiles form a compact patch
-        const int sidx = pos / (carry.strip * tiles_x), r = pos - sidx * (carry.strip * tiles_x);
-        const int h = min(carry.strip, tiles_y - sidx * carry.strip);
-        tx = r / h;
-        ty = sidx * carry.strip + (r - tx * h);
-    } else {
-        ty = pos / tiles_x;
-        tx = pos - ty * tiles_x;
-    }
+    TileId id;
+    if (!tile_id(id, tiles_y, tiles_x, xcd_q, nbatch, carry)) return;
+    const int tz = id.tz, col = id.col, cols = id.cols, bi = id.bi, ty = id.ty, tx = id.tx;
     const uint16_t* __restrict__ vol = vol_all + (size_t)bi * (size_t)g.nvox;
     uint32_t* __restrict__ keys = keys_all + (size_t)bi * (size_t)g.nref * MAXG;
     const int tid = threadIdx.x;
@@ -751,13 +761,7 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
                                 const uint32_t S = Sv[0][d];
                                 const uint32_t code = (d == RAD && self_row) ? 0u : cbase + d;
                                 const bool valid = vzy && ((xmask >> d) & 1u);
-                                uint32_t key = (__float_as_uint((float)S) & KEY_DMASK) | code;
-                                key = valid ? key : KEY_EMPTY;
-                                if (__any(key < thr)) {
-                                    const uint32_t kins = key < thr ? key : KEY_EMPTY;
-                                    list_insert_inplace(list, kins);
-                                    thr = min(list[MAXG - 1], keymax);
-                                }
+                                list_admit(list, thr, keymax, __float_as_uint((float)S), code, valid);
                             }
                         }
                     }
@@ -789,17 +793,7 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
             step_body(std::integral_constant<int, NE - 1>{}, step);
     }
 
-    if (ref_ok) {
-        uint32_t* out = keys + ((size_t)((size_t)iz * g.gy + iy) * g.gx + ix) * MAXG;
-        // never empty: a block with an infinity or a NaN in it has no admissible distance, not
-        // even to itself; it forms the one-block group of key 0, so that every key downstream names a block
-        list[0] = list[0] == KEY_EMPTY ? 0u : list[0];
-#pragma unroll
-        for (int k = 0; k < MAXG; k += 4) {
-            uint4 v = make_uint4(list[k], list[k + 1], list[k + 2], list[k + 3]);
-            *reinterpret_cast<uint4*>(out + k) = v;
-        }
-    }
+    if (ref_ok) list_store(keys + ((size_t)((size_t)iz * g.gy + iy) * g.gx + ix) * MAXG, list);
     } while (false);
 
     if (carry.on) {
@@ -908,7 +902,8 @@ __global__ __launch_bounds__(64) void bm_generic_kernel(const float* __restrict_
 // saves a tile per column, 2 = on whenever a column has two tiles (tests).  Per context since round 4.)
 
 // Tile shape: fewer (y, x) tiles = fewer idle cell lanes (64^3 patches: 5 flat tiles against 9 cubes)
-template <class Cube, class Flat>
+using Cube = TilePlan<8, 8>;
+using Flat = TilePlan<4, 16>;
 static bool flat_tiles(const VolGeom& g) {
     auto tiles = [&](int try_, int trx) {
         return (long long)((g.ay + try_ - 1) / try_) * ((g.ax + trx - 1) / trx);
@@ -916,14 +911,12 @@ static bool flat_tiles(const VolGeom& g) {
     return tiles(Flat::TRY, Flat::TRX) < tiles(Cube::TRY, Cube::TRX);
 }
 // The launch block matching chooses for a geometry (host logic only; the float and the integer kernel share
-// tile shapes).  Evaluated ONCE per launch by the API layer, which also provides plan.carry_bytes of device
+// the tile plan).  Evaluated ONCE per launch by the API layer, which also provides plan.carry_bytes of device
 // memory when plan.carry is set.
 BmPlan bm_plan(const VolGeom& g, int batch, const BmOpts& opt) {
-    using Cube = TileShape<8, 8>;
-    using Flat = TileShape<4, 16>;
     BmPlan p = {};
     if (g.az <= 0 || g.ay <= 0 || g.ax <= 0) return p;
-    p.flat = flat_tiles<Cube, Flat>(g) ? 1 : 0;
+    p.flat = flat_tiles(g) ? 1 : 0;
     const int try_ = p.flat ? Flat::TRY : Cube::TRY, trx = p.flat ? Flat::TRX : Cube::TRX;
     p.ty = (g.ay + try_ - 1) / try_;
     p.tx = (g.ax + trx - 1) / trx;
@@ -953,13 +946,6 @@ hipError_t launch_blockmatch(const float* vol, const VolGeom& g, int batch, uint
     // carry_mem: p.carry_bytes of device memory when p.carry; status: the context's host-visible status word
     if (p.carry && (!carry_mem || !status)) return hipErrorInvalidValue;
     if (!force_generic && g.az > 0 && g.ay > 0 && g.ax > 0) {
-        using Cube16 = TileShape16<8, 8>;
-        using Flat16 = TileShape16<4, 16>;
-        using Cube = TileShape<8, 8>;
-        using Flat = TileShape<4, 16>;
-        static_assert(Cube::TRY == Cube16::TRY && Cube::TRX == Cube16::TRX && Flat::TRY == Flat16::TRY &&
-                      Flat::TRX == Flat16::TRX, "one tile plan for both kernels");
-        const bool flat = p.flat != 0;
         Carry carry;
         carry.strip = p.strip;
         carry.on = p.carry;
@@ -973,22 +959,21 @@ hipError_t launch_blockmatch(const float* vol, const VolGeom& g, int batch, uint
             hipError_t e = hipMemsetAsync(carry.done, 0, (cols + 8) * sizeof(int), stream);
             if (e != hipSuccess) return e;
         }
-        dim3 grid((unsigned)(p.xq ? 8 * p.xq * p.tz : p.tz * p.ty * p.tx), (unsigned)(p.xq ? 1 : batch));
-        if (vol16) {
-            if (flat)
-                hipLaunchKernelGGL(bm_tile16_kernel<Flat16>, grid, dim3(512), 0, stream, vol16, g, keymax,
-                                   keys, p.ty, p.tx, p.xq, batch, carry);
+        const dim3 grid((unsigned)(p.xq ? 8 * p.xq * p.tz : p.tz * p.ty * p.tx), (unsigned)(p.xq ? 1 : batch));
+        auto launch = [&](auto plan) {          // the kernel for the volume's type, in the plan's tile shape
+            using Shape16 = TileShape16<decltype(plan)::TCY, decltype(plan)::TCX>;
+            using Shape = TileShape<decltype(plan)::TCY, decltype(plan)::TCX>;
+            if (vol16)
+                hipLaunchKernelGGL(bm_tile16_kernel<Shape16>, grid, dim3(512), 0, stream, vol16, g, keymax, keys,
+                                   p.ty, p.tx, p.xq, batch, carry);
             else
-                hipLaunchKernelGGL(bm_tile16_kernel<Cube16>, grid, dim3(512), 0, stream, vol16, g, keymax,
-                                   keys, p.ty, p.tx, p.xq, batch, carry);
-        } else {
-            if (flat)
-                hipLaunchKernelGGL(bm_tile_kernel<Flat>, grid, dim3(512), 0, stream, vol, g, keymax, keys,
-                                   p.ty, p.tx, guarded, p.xq, batch, carry);
-            else
-                hipLaunchKernelGGL(bm_tile_kernel<Cube>, grid, dim3(512), 0, stream, vol, g, keymax, keys,
-                                   p.ty, p.tx, guarded, p.xq, batch, carry);
-        }
+                hipLaunchKernelGGL(bm_tile_kernel<Shape>, grid, dim3(512), 0, stream, vol, g, keymax, keys, p.ty,
+                                   p.tx, guarded, p.xq, batch, carry);
+        };
+        if (p.flat)
+            launch(Flat{});
+        else
+            launch(Cube{});
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
