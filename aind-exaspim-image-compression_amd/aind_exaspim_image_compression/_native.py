@@ -155,6 +155,10 @@ SIGNATURES = {
     "exabm4d_codec_encode_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, _I, _I, _I, c_vp, _SZ, c_vp, c_vp,
                                       c_vp]),
     "exabm4d_codec_decode_dev": (_I, [_CTX, c_vp, _SZ, c_vp, _I, _I, _I, _I, _I, _I, _I, c_vp]),
+    "exabm4d_dctq_ladder_errors_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, _I, c_vp]),
+    "exabm4d_bounded_volume_bound": (_SZ, [_I, _I, _I, _I, _I, _I]),
+    "exabm4d_bounded_encode_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, _I, _I, c_vp, _SZ, c_vp, c_vp, c_vp]),
+    "exabm4d_bounded_decode_dev": (_I, [_CTX, c_vp, _SZ, c_vp, _I, _I, _I, _I, _I, _I, c_vp]),
     "exabm4d_u16_histogram_dev": (_I, [_CTX, c_vp, _SZ, c_vp]),
     "exabm4d_key_histogram_dev": (_I, [_CTX, c_vp, _I, _SZ, _I, ctypes.c_double, _I,
                                        ctypes.c_uint64, c_vp]),
@@ -606,6 +610,33 @@ class Context:
             self.handle, _ptr(data), int(nbytes), _ptr(offsets), int(typesize), nz, ny, nx,
             int(chunk[0]), int(chunk[1]), int(chunk[2]), _ptr(vol)))
 
+    # -- error-bounded lossy chunk codec ----------------------------------------
+    def dctq_ladder_errors(self, vol, shape, chunk, err):
+        """err (device, uint32 [nchunks][29]) <- the largest reconstruction error of every chunk at every
+        ladder step.  Asynchronous."""
+        nz, ny, nx = shape
+        self._check(lib().exabm4d_dctq_ladder_errors_dev(self.handle, _ptr(vol), nz, ny, nx, int(chunk[0]),
+                                                         int(chunk[1]), int(chunk[2]), _ptr(err)))
+
+    def bounded_encode(self, vol, shape, chunk, max_error, out=None, out_capacity=0, offsets=None, sizes=None,
+                       totals=True):
+        """Code every chunk of a device uint16 volume under the bound.  -> (sum of stream lengths, container
+        bytes) when `totals` (synchronises), else None."""
+        nz, ny, nx = shape
+        tot = np.zeros(2, dtype=np.uint64)
+        self._check(lib().exabm4d_bounded_encode_dev(
+            self.handle, _ptr(vol), nz, ny, nx, int(chunk[0]), int(chunk[1]), int(chunk[2]), int(max_error),
+            _ptr(out), int(out_capacity), _ptr(offsets), _ptr(sizes), tot.ctypes.data_as(c_vp) if totals else None))
+        return (int(tot[0]), int(tot[1])) if totals else None
+
+    def bounded_decode(self, data, nbytes, offsets, shape, chunk, vol):
+        """``data``: ``nbytes`` bytes of bounded chunk streams on the device -> uint16 ``vol``; malformed
+        containers raise ValueError without a read outside them."""
+        nz, ny, nx = shape
+        self._check(lib().exabm4d_bounded_decode_dev(
+            self.handle, _ptr(data), int(nbytes), _ptr(offsets), nz, ny, nx, int(chunk[0]), int(chunk[1]),
+            int(chunk[2]), _ptr(vol)))
+
     # -- background offset + quality metrics (row f-4); inputs on device, scalars to the host ----
     DTYPES = {np.dtype(np.uint16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}
 
@@ -923,6 +954,13 @@ def codec_volume_bound(typesize, shape, chunk):
         raise ValueError("codec: typesize must be 2 or 4 and every size >= 1")
     return b
 
+
+
+def bounded_volume_bound(shape, chunk):
+    b = int(lib().exabm4d_bounded_volume_bound(*(int(s) for s in shape), *(int(c) for c in chunk)))
+    if b == 0:
+        raise ValueError("bounded codec: sizes >= 1, chunk axes multiples of 8 in [8, 65528], chunk <= 2^28 voxels")
+    return b
 
 
 def grid_positions(n):

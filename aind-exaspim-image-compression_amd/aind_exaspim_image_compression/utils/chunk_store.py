@@ -10,6 +10,10 @@ the MI355X in one batched call, and they go to disk in the same directory layout
                                 fill_value, codecs = [{"name": "exac", "configuration": {...}}])
     <path>/c/0/0/<z>/<y>/<x>    the EXAC stream of chunk (z, y, x): exactly ``codec.encode(chunk)``
 
+With ``codec=BoundedDctCodec(max_error)`` (``utils/bounded_codec.py``) the chunk streams are the
+error-bounded lossy ones, and the codec entry reads ``{"name": "exac-dctq", "configuration": {"version": 1,
+"max_error": ..., "edge_chunks": "truncated"}}``; the readers pick the decoder from ``zarr.json``.
+
 so that a chunk is addressable by its key like any Zarr chunk and ``sum(file sizes)`` is the denominator of
 ``compute_cratio`` (utils/img_util.py:401-441).  Differences from a stock Zarr array, stated in the metadata:
 the codec is this repo's (a generic Zarr reader needs an ``exac`` codec plug-in: ``ExacCodec.decode``), and
@@ -22,6 +26,7 @@ import os
 
 import numpy as np
 
+from aind_exaspim_image_compression.utils.bounded_codec import BoundedDctCodec
 from aind_exaspim_image_compression.utils.chunk_codec import EncodedVolume, ExacCodec
 
 FORMAT_NOTE = ("EXAC chunk streams (aind-exaspim-image-compression_amd, DESIGN.md 3.11b); edge chunks truncated to "
@@ -37,9 +42,15 @@ def chunk_key(iz, iy, ix):
     return os.path.join("c", "0", "0", str(int(iz)), str(int(iy)), str(int(ix)))
 
 
-def metadata(shape3, chunk3, typesize=2, version=2, attributes=None):
-    """The ``zarr.json`` document of a stored volume."""
+def metadata(shape3, chunk3, typesize=2, version=2, attributes=None, codec=None):
+    """The ``zarr.json`` document of a stored volume (``codec``: a ``BoundedDctCodec`` stores its own entry)."""
     dtype = {2: "uint16", 4: "int32"}[int(typesize)]
+    if isinstance(codec, BoundedDctCodec):
+        meta = metadata(shape3, chunk3, 2, attributes=attributes)
+        meta["codecs"] = [{"name": BoundedDctCodec.codec_id,
+                           "configuration": {"version": BoundedDctCodec.version, "max_error": codec.max_error,
+                                             "edge_chunks": "truncated"}}]
+        return meta
     return {
         "zarr_format": 3,
         "node_type": "array",
@@ -55,9 +66,10 @@ def metadata(shape3, chunk3, typesize=2, version=2, attributes=None):
     }
 
 
-def write_encoded(enc, output_path, version=2, attributes=None, overwrite=True):
+def write_encoded(enc, output_path, version=2, attributes=None, overwrite=True, codec=None):
     """``EncodedVolume`` (host container: data, offsets, sizes) -> chunk store at ``output_path``.  Host work
-    only.  Returns the number of bytes written as chunk streams."""
+    only.  Returns the number of bytes written as chunk streams.  ``codec``: the ``BoundedDctCodec`` that made
+    ``enc``, if one did (its entry goes into the metadata)."""
     if enc.data is None:
         raise ValueError("the EncodedVolume carries sizes only (encode with want_bytes=True)")
     gz, gy, gx = _grid(enc.shape, enc.chunk)
@@ -79,7 +91,7 @@ def write_encoded(enc, output_path, version=2, attributes=None, overwrite=True):
                 total += len(blob)
                 k += 1
     with open(os.path.join(output_path, "zarr.json"), "w") as f:      # last: a store without it is incomplete
-        json.dump(metadata(enc.shape, enc.chunk, enc.typesize, version, attributes), f, indent=1)
+        json.dump(metadata(enc.shape, enc.chunk, enc.typesize, version, attributes, codec), f, indent=1)
     return total
 
 
@@ -93,10 +105,16 @@ def read_encoded(path):
         if meta["zarr_format"] != 3 or meta["node_type"] != "array":
             raise ValueError("not a Zarr v3 array")
         codecs = meta["codecs"]
-        if len(codecs) != 1 or codecs[0]["name"] != "exac":
-            raise ValueError("the array's codec chain is not [exac]")
+        if len(codecs) != 1 or codecs[0]["name"] not in ("exac", BoundedDctCodec.codec_id):
+            raise ValueError("the array's codec chain is not [exac] or [exac-dctq]")
+        bounded = codecs[0]["name"] == BoundedDctCodec.codec_id
         cfg = codecs[0]["configuration"]
-        typesize = int(cfg["typesize"])
+        if bounded:
+            if int(cfg["version"]) != BoundedDctCodec.version or not 0 <= int(cfg["max_error"]) <= 65535:
+                raise ValueError("unsupported exac-dctq configuration")
+            typesize = 2
+        else:
+            typesize = int(cfg["typesize"])
         shape5, chunk5 = meta["shape"], meta["chunk_grid"]["configuration"]["chunk_shape"]
         if len(shape5) != 5 or shape5[:2] != [1, 1] or len(chunk5) != 5 or chunk5[:2] != [1, 1]:
             raise ValueError("only (1, 1, z, y, x) arrays with (1, 1, cz, cy, cx) chunks are stored this way")
@@ -123,7 +141,8 @@ def read_encoded(path):
     data = np.zeros(int(offsets[-1]), dtype=np.uint8)
     for b, o in zip(blobs, offsets[:-1]):
         data[int(o):int(o) + len(b)] = np.frombuffer(b, dtype=np.uint8)
-    chunk_eff = tuple(min(c, s) for c, s in zip(chunk3, shape3))
+    # the bounded format keeps the nominal chunk shape (its index chunks are sized by it)
+    chunk_eff = chunk3 if bounded else tuple(min(c, s) for c, s in zip(chunk3, shape3))
     return EncodedVolume(data, offsets, sizes, shape3, chunk_eff, typesize), meta
 
 
@@ -143,14 +162,17 @@ def write_zarr(img, output_path, chunks=(1, 1, 64, 64, 64), codec=None, attribut
     codec = codec or ExacCodec(2)
     vol = np.ascontiguousarray(img[0, 0])
     enc = codec.encode_volume(vol, chunk=tuple(int(c) for c in chunks[2:]))
-    stored = write_encoded(enc, output_path, version=codec.version, attributes=attributes)
+    if isinstance(codec, BoundedDctCodec):
+        stored = write_encoded(enc, output_path, attributes=attributes, codec=codec)
+    else:
+        stored = write_encoded(enc, output_path, version=codec.version, attributes=attributes)
     return vol.nbytes / stored
 
 
 def read_zarr(path, codec=None):
     """Chunk store -> the (1, 1, z, y, x) array, decoded on the device in one call."""
     enc, meta = read_encoded(path)
-    codec = codec or ExacCodec(enc.typesize)
+    codec = codec or _codec_of(meta)
     return codec.decode_volume(enc)[np.newaxis, np.newaxis]
 
 
@@ -158,7 +180,6 @@ def read_chunk(path, iz, iy, ix, codec=None):
     """One chunk by its key, decoded alone (random access: what a viewer does)."""
     with open(os.path.join(path, "zarr.json")) as f:
         meta = json.load(f)
-    cfg = meta["codecs"][0]["configuration"]
     shape3 = meta["shape"][2:]
     chunk3 = meta["chunk_grid"]["configuration"]["chunk_shape"][2:]
     ext = tuple(min(c, s - i * c) for i, c, s in zip((iz, iy, ix), chunk3, shape3))
@@ -166,5 +187,13 @@ def read_chunk(path, iz, iy, ix, codec=None):
         raise IndexError("chunk index outside the array")
     with open(os.path.join(path, chunk_key(iz, iy, ix)), "rb") as f:
         blob = f.read()
-    codec = codec or ExacCodec(int(cfg["typesize"]))
+    codec = codec or _codec_of(meta)
     return codec.decode(blob).reshape(ext)
+
+
+def _codec_of(meta):
+    """The decoder a store's ``zarr.json`` names."""
+    entry = meta["codecs"][0]
+    if entry["name"] == BoundedDctCodec.codec_id:
+        return BoundedDctCodec(int(entry["configuration"]["max_error"]))
+    return ExacCodec(int(entry["configuration"]["typesize"]))

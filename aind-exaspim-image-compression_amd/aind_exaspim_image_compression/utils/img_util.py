@@ -45,6 +45,36 @@ def compute_cratio(img, codec, patch_shape=(64, 64, 64)):
     return round(raw / packed, 2)
 
 
+def compress_and_decompress(img, codec, patch_shape=(64, 64, 64)):
+    """-> ``(decoded, cratio)``: the image after a round trip through ``codec`` chunk by chunk, and the chunked
+    compression ratio rounded like ``compute_cratio`` (the counterpart of the reference's
+    ``compress_and_decompress_jpeg``, ``utils/img_util.py:474-514``).  ``decoded`` has the input's shape; 5-D
+    input is accepted like ``compute_cratio``.  A device codec (``ExacCodec``, ``BoundedDctCodec``) takes one
+    batched encode and one batched decode."""
+    img = np.asarray(img)
+    vol = img[0, 0] if img.ndim == 5 else img
+    vol = np.ascontiguousarray(vol, dtype=np.uint16)
+    if vol.ndim == 3 and hasattr(codec, "encode_volume") and hasattr(codec, "decode_volume"):
+        enc = codec.encode_volume(vol, patch_shape)
+        decoded = codec.decode_volume(enc).reshape(vol.shape)
+        packed = enc.nbytes
+    else:
+        decoded = np.empty_like(vol)
+        packed = 0
+        grids = [range(0, s, c) for s, c in zip(vol.shape, patch_shape)]
+        for z0 in grids[0]:
+            for y0 in grids[1]:
+                for x0 in (grids[2] if len(grids) > 2 else [0]):
+                    sl = (slice(z0, z0 + patch_shape[0]), slice(y0, y0 + patch_shape[1]),
+                          slice(x0, x0 + patch_shape[2]))[:vol.ndim]
+                    chunk = np.ascontiguousarray(vol[sl])
+                    blob = codec.encode(chunk)
+                    packed += len(blob)
+                    decoded[sl] = np.asarray(codec.decode(blob)).reshape(chunk.shape)
+    out = decoded.reshape(img.shape) if img.ndim == 5 else decoded
+    return out, round(vol.nbytes / packed, 2)
+
+
 def chunk_byte_histograms(img, patch_shape=(64, 64, 64), device=None):
     """[nchunks, 2, 256] uint32 histograms of the low / high byte planes of every chunk (GPU)."""
     vol = np.ascontiguousarray(img, dtype=np.uint16)

@@ -1621,6 +1621,16 @@ static int codec_aux(exabm4d_ctx* ctx, int nchunks, uint32_t*& sizes, unsigned l
     status = reinterpret_cast<uint32_t*>(base + a + b + 256);
     return EXABM4D_OK;
 }
+// the rANS coders' reciprocal table, uploaded once per context
+static int codec_rcp(exabm4d_ctx* ctx) {
+    if (!ctx->rcp_dev) {
+        static uint32_t tab[4097 * 2];
+        codec_fill_rcp_table(tab);
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->rcp_dev, sizeof tab));
+        HIP_TRY(ctx, hipMemcpy(ctx->rcp_dev, tab, sizeof tab, hipMemcpyHostToDevice));
+    }
+    return EXABM4D_OK;
+}
 int exabm4d_codec_encode_dev(exabm4d_ctx* ctx, const void* vol, int typesize, int version, int nz, int ny, int nx,
                              int cz, int cy, int cx, uint8_t* out, size_t out_capacity,
                              uint64_t* offsets_dev, uint32_t* sizes_dev, uint64_t* totals_host) {
@@ -1634,15 +1644,11 @@ int exabm4d_codec_encode_dev(exabm4d_ctx* ctx, const void* vol, int typesize, in
         return fail(ctx, EXABM4D_ERR_INVALID, "codec: out_capacity is below exabm4d_codec_volume_bound()");
     if (out && ((uintptr_t)out & 15)) return fail(ctx, EXABM4D_ERR_INVALID, "codec: out must be 16-byte aligned");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!ctx->rcp_dev) {
-        static uint32_t tab[4097 * 2];
-        codec_fill_rcp_table(tab);
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->rcp_dev, sizeof tab));
-        HIP_TRY(ctx, hipMemcpy(ctx->rcp_dev, tab, sizeof tab, hipMemcpyHostToDevice));
-    }
+    int rc = codec_rcp(ctx);
+    if (rc) return rc;
     uint32_t *sizes, *status;
     unsigned long long *offsets, *totals;
-    int rc = codec_aux(ctx, g.nchunks, sizes, offsets, totals, status);
+    rc = codec_aux(ctx, g.nchunks, sizes, offsets, totals, status);
     if (rc) return rc;
     rc = ensure_scratch(ctx, (((size_t)g.nchunks * g.slot_bytes + 255) & ~(size_t)255) +
                                  (g.version == 2 ? codec2_work_bytes(g) : 0));
@@ -1690,6 +1696,196 @@ int exabm4d_codec_decode_dev(exabm4d_ctx* ctx, const uint8_t* in, size_t in_byte
     if (st) {
         char msg[96];
         std::snprintf(msg, sizeof msg, "codec: malformed chunk stream (status 0x%x)", st);
+        return fail(ctx, EXABM4D_ERR_INVALID, msg);
+    }
+    return EXABM4D_OK;
+}
+
+// ---- error-bounded lossy chunk codec -----------------------------------------------------------
+// The step ladder Q[j] = (float) 2^((j - 4) / 4): the kernels take it as a table, none of them computes it.
+struct BqLadder {
+    float q[BQ_STEPS];
+    BqLadder() {
+        for (int j = 0; j < BQ_STEPS; j++) q[j] = (float)std::pow(2.0, (j - 4) / 4.0);
+    }
+};
+static const BqLadder& bq_ladder() {
+    static const BqLadder t;
+    return t;
+}
+
+static int bq_geom(exabm4d_ctx* ctx, int nz, int ny, int nx, int cz, int cy, int cx, BoundedGeom& g, CodecGeom& lossy,
+                   CodecGeom& lossless) {
+    if (make_bounded_geom(nz, ny, nx, cz, cy, cx, g) ||
+        make_codec_geom(4, g.nchunks * g.nb, 8, 64, g.nb, 8, 64, lossy, 2) ||
+        make_codec_geom(2, nz, ny, nx, cz, cy, cx, lossless, 2))
+        return fail(ctx, EXABM4D_ERR_INVALID,
+                    "bounded codec: sizes >= 1, chunk axes multiples of 8 in [8, 65528], chunk <= 2^28 voxels");
+    return EXABM4D_OK;
+}
+
+static size_t bq_volume_bound(const BoundedGeom& g) {
+    const size_t a = codec_chunk_bound((size_t)g.nb * BVOX, 4), b = codec_chunk_bound((size_t)g.cz * g.cy * g.cx, 2);
+    return (size_t)g.nchunks * (BQ_HEADER + ((std::max(a, b) + 15) & ~(size_t)15));
+}
+
+// Carves the context's scratch: a first pass with base == nullptr only adds up the bytes.
+extern "C++" struct ScratchCarver {
+    char* base;
+    size_t at = 0;
+    template <typename T>
+    T* take(size_t bytes) {
+        T* p = base ? reinterpret_cast<T*>(base + at) : nullptr;
+        at += align256(bytes);
+        return p;
+    }
+};
+
+size_t exabm4d_bounded_volume_bound(int nz, int ny, int nx, int cz, int cy, int cx) {
+    BoundedGeom g;
+    if (make_bounded_geom(nz, ny, nx, cz, cy, cx, g)) return 0;
+    return bq_volume_bound(g);
+}
+
+int exabm4d_dctq_ladder_errors_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, int ny, int nx, int cz, int cy,
+                                   int cx, uint32_t* err) {
+    if (!ctx || !vol || !err) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    BoundedGeom g;
+    CodecGeom gl, gu;
+    int rc = bq_geom(ctx, nz, ny, nx, cz, cy, cx, g, gl, gu);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = ensure_scratch(ctx, align256(sizeof(BqLadder)));
+    if (rc) return rc;
+    float* qtab = static_cast<float*>(ctx->scratch);
+    float dct[64], win[512];
+    make_tables(0.0, dct, win);
+    HIP_TRY(ctx, hipMemcpyAsync(qtab, bq_ladder().q, sizeof(BqLadder), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(err, 0, (size_t)g.nchunks * BQ_STEPS * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, launch_bq_ladder(vol, g, dct, qtab, err, ctx->stream));
+    return EXABM4D_OK;
+}
+
+int exabm4d_bounded_encode_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, int ny, int nx, int cz, int cy, int cx,
+                               int max_error, uint8_t* out, size_t out_capacity, uint64_t* offsets_dev,
+                               uint32_t* sizes_dev, uint64_t* totals_host) {
+    if (!ctx || !vol) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (max_error < 0 || max_error > 65535) return fail(ctx, EXABM4D_ERR_INVALID, "bounded codec: max_error must be in [0, 65535]");
+    BoundedGeom g;
+    CodecGeom gl, gu;
+    int rc = bq_geom(ctx, nz, ny, nx, cz, cy, cx, g, gl, gu);
+    if (rc) return rc;
+    if (out && !offsets_dev) return fail(ctx, EXABM4D_ERR_INVALID, "bounded codec: offsets_dev is required with out");
+    if (out && out_capacity < bq_volume_bound(g))
+        return fail(ctx, EXABM4D_ERR_INVALID, "bounded codec: out_capacity is below exabm4d_bounded_volume_bound()");
+    if (out && ((uintptr_t)out & 15)) return fail(ctx, EXABM4D_ERR_INVALID, "bounded codec: out must be 16-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = codec_rcp(ctx);
+    if (rc) return rc;
+    const size_t nc = (size_t)g.nchunks;
+    const size_t slots = std::max(align256((size_t)gl.nchunks * gl.slot_bytes) + codec2_work_bytes(gl),
+                                  align256((size_t)gu.nchunks * gu.slot_bytes) + codec2_work_bytes(gu));
+    auto carve = [&](ScratchCarver& sc, float*& qtab, uint32_t*& err, int32_t*& jsel, float*& qsel, int32_t*& idx,
+                     uint32_t*& lsz, unsigned long long*& loff, uint8_t*& lbuf, uint32_t*& usz,
+                     unsigned long long*& uoff, uint8_t*& ubuf, unsigned long long*& tot, uint32_t*& sizes,
+                     unsigned long long*& offsets, uint8_t*& slot) {
+        qtab = sc.take<float>(sizeof(BqLadder));
+        err = sc.take<uint32_t>(nc * BQ_STEPS * sizeof(uint32_t));
+        jsel = sc.take<int32_t>(nc * sizeof(int32_t));
+        qsel = sc.take<float>(nc * sizeof(float));
+        idx = sc.take<int32_t>(nc * g.nb * BVOX * sizeof(int32_t));
+        lsz = sc.take<uint32_t>(nc * sizeof(uint32_t));
+        loff = sc.take<unsigned long long>((nc + 1) * 8);
+        lbuf = out ? sc.take<uint8_t>(codec_volume_bound(gl)) : nullptr;
+        usz = sc.take<uint32_t>(nc * sizeof(uint32_t));
+        uoff = sc.take<unsigned long long>((nc + 1) * 8);
+        ubuf = out ? sc.take<uint8_t>(codec_volume_bound(gu)) : nullptr;
+        tot = sc.take<unsigned long long>(6 * 8);          // lossy, lossless, bounded {exact, container}
+        sizes = sc.take<uint32_t>(nc * sizeof(uint32_t));
+        offsets = sc.take<unsigned long long>((nc + 1) * 8);
+        slot = sc.take<uint8_t>(slots);
+    };
+    float *qtab, *qsel;
+    uint32_t *err, *lsz, *usz, *sizes;
+    int32_t *jsel, *idx;
+    unsigned long long *loff, *uoff, *tot, *offsets;
+    uint8_t *lbuf, *ubuf, *slot;
+    ScratchCarver count{nullptr};
+    carve(count, qtab, err, jsel, qsel, idx, lsz, loff, lbuf, usz, uoff, ubuf, tot, sizes, offsets, slot);
+    rc = ensure_scratch(ctx, count.at);
+    if (rc) return rc;
+    ScratchCarver sc{static_cast<char*>(ctx->scratch)};
+    carve(sc, qtab, err, jsel, qsel, idx, lsz, loff, lbuf, usz, uoff, ubuf, tot, sizes, offsets, slot);
+    if (sizes_dev) sizes = sizes_dev;
+    if (offsets_dev) offsets = reinterpret_cast<unsigned long long*>(offsets_dev);
+    float dct[64], win[512];
+    make_tables(0.0, dct, win);
+    hipStream_t s = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(qtab, bq_ladder().q, sizeof(BqLadder), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(err, 0, nc * BQ_STEPS * sizeof(uint32_t), s));
+    HIP_TRY(ctx, launch_bq_ladder(vol, g, dct, qtab, err, s));
+    HIP_TRY(ctx, launch_bq_select(err, g.nchunks, (uint32_t)max_error, qtab, jsel, qsel, s));
+    HIP_TRY(ctx, launch_bq_forward(vol, g, dct, qsel, idx, s));
+    // the two candidates of every chunk through the existing chunk coder: the index chunks, then the voxels
+    HIP_TRY(ctx, launch_rans_encode(idx, gl, ctx->rcp_dev, slot, lsz, loff, tot, lbuf, s));
+    HIP_TRY(ctx, launch_rans_encode(vol, gu, ctx->rcp_dev, slot, usz, uoff, tot + 2, ubuf, s));
+    HIP_TRY(ctx, launch_bq_assemble(g, jsel, qsel, lbuf, loff, lsz, ubuf, uoff, usz, sizes, offsets, tot + 4, out, s));
+    if (totals_host) {
+        HIP_TRY(ctx, hipMemcpyAsync(totals_host, tot + 4, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+    }
+    return EXABM4D_OK;
+}
+
+int exabm4d_bounded_decode_dev(exabm4d_ctx* ctx, const uint8_t* in, size_t in_bytes, const uint64_t* offsets_dev,
+                               int nz, int ny, int nx, int cz, int cy, int cx, uint16_t* vol) {
+    if (!ctx || !in || !offsets_dev || !vol) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if ((uintptr_t)in & 15) return fail(ctx, EXABM4D_ERR_INVALID, "bounded codec: in must be 16-byte aligned");
+    BoundedGeom g;
+    CodecGeom gl, gu;
+    int rc = bq_geom(ctx, nz, ny, nx, cz, cy, cx, g, gl, gu);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t nc = (size_t)g.nchunks;
+    auto carve = [&](ScratchCarver& sc, float*& qtab, uint32_t*& mode, float*& qv, uint32_t*& lchunk,
+                     unsigned long long*& lrange, uint32_t*& lstat, int32_t*& idx) {
+        qtab = sc.take<float>(sizeof(BqLadder));
+        mode = sc.take<uint32_t>(nc * sizeof(uint32_t));
+        qv = sc.take<float>(nc * sizeof(float));
+        lchunk = sc.take<uint32_t>(2 * nc * sizeof(uint32_t));
+        lrange = sc.take<unsigned long long>(4 * nc * 8);
+        lstat = sc.take<uint32_t>(4 * sizeof(uint32_t));    // list counts [2], status
+        idx = sc.take<int32_t>(nc * g.nb * BVOX * sizeof(int32_t));
+    };
+    float *qtab, *qv;
+    uint32_t *mode, *lchunk, *lstat;
+    unsigned long long* lrange;
+    int32_t* idx;
+    ScratchCarver count{nullptr};
+    carve(count, qtab, mode, qv, lchunk, lrange, lstat, idx);
+    rc = ensure_scratch(ctx, count.at);
+    if (rc) return rc;
+    ScratchCarver sc{static_cast<char*>(ctx->scratch)};
+    carve(sc, qtab, mode, qv, lchunk, lrange, lstat, idx);
+    float dct[64], win[512];
+    make_tables(0.0, dct, win);
+    hipStream_t s = ctx->stream;
+    uint32_t* status = lstat + 2;
+    HIP_TRY(ctx, hipMemcpyAsync(qtab, bq_ladder().q, sizeof(BqLadder), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(lstat, 0, 4 * sizeof(uint32_t), s));
+    HIP_TRY(ctx, launch_bq_parse(in, in_bytes, reinterpret_cast<const unsigned long long*>(offsets_dev), g, qtab, mode,
+                                 qv, lchunk, lrange, lstat, status, s));
+    // lossless chunks straight into the volume, lossy chunks' indices into the chunk-major scratch, then their inverse
+    HIP_TRY(ctx, launch_rans2_decode_list(in, in_bytes, DecodeList{lchunk, lrange, lstat}, (unsigned)nc, gu, vol, status, s));
+    HIP_TRY(ctx, launch_rans2_decode_list(in, in_bytes, DecodeList{lchunk + nc, lrange + 2 * nc, lstat + 1}, (unsigned)nc,
+                                          gl, idx, status, s));
+    HIP_TRY(ctx, launch_bq_inverse(idx, g, dct, mode, qv, vol, s));
+    uint32_t st = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&st, status, sizeof st, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    if (st) {
+        char msg[96];
+        std::snprintf(msg, sizeof msg, "bounded codec: malformed chunk stream (status 0x%x)", st);
         return fail(ctx, EXABM4D_ERR_INVALID, msg);
     }
     return EXABM4D_OK;

@@ -184,6 +184,56 @@ hipError_t launch_rans2_encode(const void* vol, const CodecGeom& g, const uint32
                                int stage, hipStream_t s);
 hipError_t launch_rans2_decode(const uint8_t* in, size_t in_bytes, const unsigned long long* offsets,
                                const CodecGeom& g, void* vol, uint32_t* status, hipStream_t s);
+// The same decoder over a device-side list of chunks: workgroup k (< grid, which must be >= *count) decodes chunk
+// chunk[k] of g from bytes [range[2k], range[2k + 1]) of `in`; workgroups k >= *count return at once.
+struct DecodeList {
+    const uint32_t* chunk;
+    const unsigned long long* range;
+    const uint32_t* count;
+};
+hipError_t launch_rans2_decode_list(const uint8_t* in, size_t in_bytes, const DecodeList& lst, unsigned grid,
+                                    const CodecGeom& g, void* vol, uint32_t* status, hipStream_t s);
+// offsets[c] = sum of the 16-byte-aligned sizes before c, offsets[n] and totals = {sum of sizes, container bytes}
+hipError_t launch_codec_scan(const uint32_t* sizes, int nchunks, unsigned long long* offsets,
+                             unsigned long long* totals, hipStream_t s);
+
+// ---- error-bounded lossy chunk codec (bounded_kernels.hip) ---------------------------------
+constexpr int BQ_STEPS = 29;        // the step ladder Q[j] = 2^((j - 4) / 4), j = 0..28 (host table)
+constexpr int BQ_HEADER = 32;       // bytes of a chunk stream's header in front of its EXAC payload
+struct BoundedGeom {
+    int nz, ny, nx;          // volume
+    int cz, cy, cx;          // nominal chunk shape, every axis a multiple of 8 (not clamped to the volume)
+    int gz, gy, gx;          // chunks per axis
+    int nchunks;
+    int cbz, cby, cbx;       // 8^3 blocks per chunk axis (nominal)
+    int nb;                  // blocks per chunk: the index chunk is (nb, 8, 64) int32
+};
+int make_bounded_geom(int nz, int ny, int nx, int cz, int cy, int cx, BoundedGeom& g);
+// err[nchunks][BQ_STEPS] (zeroed by the caller) <- max over the chunk's voxels of |dctq round trip at Q[j] - v|
+hipError_t launch_bq_ladder(const uint16_t* vol, const BoundedGeom& g, const float* dct64, const float* qtab,
+                            uint32_t* err, hipStream_t s);
+// jsel[c] = max{j : err[c][j] <= delta} or -1, qsel[c] = Q[jsel] or 0
+hipError_t launch_bq_select(const uint32_t* err, int nchunks, uint32_t delta, const float* qtab, int32_t* jsel,
+                            float* qsel, hipStream_t s);
+// chunk-major indices at q = qsel[c]: idx[c][nb][512]; blocks outside the volume and chunks with qsel 0 are zero
+hipError_t launch_bq_forward(const uint16_t* vol, const BoundedGeom& g, const float* dct64, const float* qsel,
+                             int32_t* idx, hipStream_t s);
+// mode per chunk from the two candidates' exact sizes, stream sizes = header + payload, offsets by scan, then
+// (out != NULL) headers + the chosen payloads
+hipError_t launch_bq_assemble(const BoundedGeom& g, const int32_t* jsel, const float* qsel,
+                              const uint8_t* lossy, const unsigned long long* lossy_off, const uint32_t* lossy_sz,
+                              const uint8_t* lossless, const unsigned long long* lossless_off,
+                              const uint32_t* lossless_sz, uint32_t* sizes, unsigned long long* offsets,
+                              unsigned long long* totals, uint8_t* out, hipStream_t s);
+// decode, step 1: validate every chunk's offsets and header, record mode / q, and list the chunks of either mode
+// (lists: chunk[2][nchunks], range[2][2 nchunks], count[2], zeroed by the caller); status |= 32 / 64 on a bad
+// header / offsets
+hipError_t launch_bq_parse(const uint8_t* in, size_t in_bytes, const unsigned long long* offsets,
+                           const BoundedGeom& g, const float* qtab, uint32_t* mode, float* qv, uint32_t* lchunk,
+                           unsigned long long* lrange, uint32_t* lcount, uint32_t* status, hipStream_t s);
+// decode, last step: inverse DCT of the mode-1 chunks' indices at their own q into the volume
+hipError_t launch_bq_inverse(const int32_t* idx, const BoundedGeom& g, const float* dct64, const uint32_t* mode,
+                             const float* qv, uint16_t* vol, hipStream_t s);
 
 // ---- patch-cache masks and coherence gate (mask_kernels.hip) ---------------------------------------------
 constexpr int LS_MAX = 1024;        // distinct labels a patch's LDS hash set holds (exabm4d.h EXABM4D_LABEL_SET_MAX)

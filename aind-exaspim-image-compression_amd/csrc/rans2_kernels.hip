@@ -620,7 +620,8 @@ template <int TS>
 __global__ __launch_bounds__(64) void rans2_decode_kernel(const uint8_t* __restrict__ in, size_t in_bytes,
                                                           const unsigned long long* __restrict__ offsets,
                                                           CodecGeom g, void* __restrict__ vol,
-                                                          uint32_t* __restrict__ status, uint32_t ring) {
+                                                          uint32_t* __restrict__ status, uint32_t ring,
+                                                          DecodeList lst) {
     // History ring of `ring` elements (a multiple of 64 that covers the farthest tap of any chunk of
     // this volume plus the row being written: decode_ring_elems): magnitudes, and for uint16 the
     // values.  Sized per launch -- 4224 elements for 64^3 chunks instead of a fixed 8192 -- because
@@ -629,13 +630,23 @@ __global__ __launch_bounds__(64) void rans2_decode_kernel(const uint8_t* __restr
     uint16_t* cum = reinterpret_cast<uint16_t*>(dyn_lds);
     uint16_t* vring = cum + ((NCTX * (NSYM + 1) + 7) & ~7);
     uint8_t* mring = reinterpret_cast<uint8_t*>(vring + (TS == 2 ? ring : 0));
-    const int c = blockIdx.x;
+    // chunk and byte range: the container's own (offsets) or, for a chunk list, the list's (DecodeList)
+    int c = blockIdx.x;
+    unsigned long long o0, o1;
+    if (lst.chunk) {
+        if ((uint32_t)blockIdx.x >= *lst.count) return;
+        c = (int)lst.chunk[blockIdx.x];
+        o0 = lst.range[2 * (size_t)blockIdx.x];
+        o1 = lst.range[2 * (size_t)blockIdx.x + 1];
+    } else {
+        o0 = offsets[c];
+        o1 = offsets[c + 1];
+    }
     const uint32_t lane = lane_id();
     const ChunkBox b = chunk_box(g, c);
     const uint32_t n = b.n;
     const uint32_t rows = (n + 63u) >> 6;
     const bool fast = (b.ex & 63) == 0;
-    const unsigned long long o0 = offsets[c], o1 = offsets[c + 1];
     if (o0 > o1 || o1 > in_bytes || (o0 & 1ull)) {
         if (lane == 0) atomicOr(status, 8u);
         return;
@@ -910,17 +921,30 @@ static uint32_t decode_ring_elems(const CodecGeom& g) {
     return (uint32_t)ring;
 }
 
-hipError_t launch_rans2_decode(const uint8_t* in, size_t in_bytes, const unsigned long long* offsets,
-                               const CodecGeom& g, void* vol, uint32_t* status, hipStream_t s) {
+static hipError_t rans2_decode_grid(const uint8_t* in, size_t in_bytes, const unsigned long long* offsets,
+                                    const DecodeList& lst, unsigned grid, const CodecGeom& g, void* vol,
+                                    uint32_t* status, hipStream_t s) {
     const uint32_t ring = decode_ring_elems(g);
     const size_t lds = 2 * (size_t)((NCTX * (NSYM + 1) + 7) & ~7) + (g.ts == 2 ? 2 * (size_t)ring : 0) + ring;
     if (g.ts == 2)
-        hipLaunchKernelGGL(rans2_decode_kernel<2>, dim3((unsigned)g.nchunks), dim3(64), lds, s, in, in_bytes, offsets,
-                           g, vol, status, ring);
+        hipLaunchKernelGGL(rans2_decode_kernel<2>, dim3(grid), dim3(64), lds, s, in, in_bytes, offsets,
+                           g, vol, status, ring, lst);
     else
-        hipLaunchKernelGGL(rans2_decode_kernel<4>, dim3((unsigned)g.nchunks), dim3(64), lds, s, in, in_bytes, offsets,
-                           g, vol, status, ring);
+        hipLaunchKernelGGL(rans2_decode_kernel<4>, dim3(grid), dim3(64), lds, s, in, in_bytes, offsets,
+                           g, vol, status, ring, lst);
     return hipGetLastError();
+}
+
+hipError_t launch_rans2_decode(const uint8_t* in, size_t in_bytes, const unsigned long long* offsets,
+                               const CodecGeom& g, void* vol, uint32_t* status, hipStream_t s) {
+    return rans2_decode_grid(in, in_bytes, offsets, DecodeList{nullptr, nullptr, nullptr}, (unsigned)g.nchunks, g,
+                             vol, status, s);
+}
+
+hipError_t launch_rans2_decode_list(const uint8_t* in, size_t in_bytes, const DecodeList& lst, unsigned grid,
+                                    const CodecGeom& g, void* vol, uint32_t* status, hipStream_t s) {
+    if (!lst.chunk || !lst.range || !lst.count || g.version != 2) return hipErrorInvalidValue;
+    return rans2_decode_grid(in, in_bytes, nullptr, lst, grid, g, vol, status, s);
 }
 
 }  // namespace exabm4d

@@ -637,6 +637,12 @@ hipError_t launch_rans_encode(const void* vol, const CodecGeom& g, const uint32_
     return hipGetLastError();
 }
 
+hipError_t launch_codec_scan(const uint32_t* sizes, int nchunks, unsigned long long* offsets,
+                             unsigned long long* totals, hipStream_t s) {
+    hipLaunchKernelGGL(rans_scan_kernel, dim3(1), dim3(1024), 0, s, sizes, nchunks, offsets, totals);
+    return hipGetLastError();
+}
+
 hipError_t launch_rans_decode(const uint8_t* in, size_t in_bytes, const unsigned long long* offsets,
                               const CodecGeom& g, void* vol, uint32_t* status, hipStream_t s) {
     if (g.version == 2) return launch_rans2_decode(in, in_bytes, offsets, g, vol, status, s);

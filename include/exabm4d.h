@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define EXABM4D_VERSION 400 /* additive within 400: + exabm4d_foreground_masks_dev, exabm4d_binary_dilate_dev, exabm4d_gaussian_filter3d_dev, exabm4d_label_set_dev, exabm4d_segment_stats_dev (patch-cache masks and coherence gate); + exabm4d_groupnorm_lrelu_ndhwc_dt_dev, exabm4d_maxpool2_ndhwc_dt_dev, exabm4d_upsample2_trilinear_ndhwc_dt_dev (fp16 / bf16 BM4DNet kernels); 0.4.0 (round 4): order-independent aggregation -- exabm4d_stage_dev takes data_exp and WRITES num / den, options "stage_pairs" / "stage_quads" / "fuse_den_z" are gone, the stage / block-matching options are per context; 0.3.2: + exabm4d_blockmatch_plan, option "stage_strip"; 0.3.1: + exabm4d_denoise_chunked_u16_host, options "bm_carry" / "bm_xcd_mode"; 0.3.0: EXAC v2 coder, exabm4d_codec_decode_dev takes in_bytes (round 3) */
+#define EXABM4D_VERSION 400 /* additive within 400: + exabm4d_dctq_ladder_errors_dev, exabm4d_bounded_volume_bound, exabm4d_bounded_encode_dev, exabm4d_bounded_decode_dev (error-bounded lossy chunk codec); + exabm4d_foreground_masks_dev, exabm4d_binary_dilate_dev, exabm4d_gaussian_filter3d_dev, exabm4d_label_set_dev, exabm4d_segment_stats_dev (patch-cache masks and coherence gate); + exabm4d_groupnorm_lrelu_ndhwc_dt_dev, exabm4d_maxpool2_ndhwc_dt_dev, exabm4d_upsample2_trilinear_ndhwc_dt_dev (fp16 / bf16 BM4DNet kernels); 0.4.0 (round 4): order-independent aggregation -- exabm4d_stage_dev takes data_exp and WRITES num / den, options "stage_pairs" / "stage_quads" / "fuse_den_z" are gone, the stage / block-matching options are per context; 0.3.2: + exabm4d_blockmatch_plan, option "stage_strip"; 0.3.1: + exabm4d_denoise_chunked_u16_host, options "bm_carry" / "bm_xcd_mode"; 0.3.0: EXAC v2 coder, exabm4d_codec_decode_dev takes in_bytes (round 3) */
 
 typedef enum exabm4d_status {
     EXABM4D_OK = 0,
@@ -467,6 +467,40 @@ int exabm4d_codec_encode_dev(exabm4d_ctx* ctx, const void* vol, int typesize, in
  * reads outside [in, in + in_bytes). */
 int exabm4d_codec_decode_dev(exabm4d_ctx* ctx, const uint8_t* in, size_t in_bytes, const uint64_t* offsets_dev,
                              int typesize, int nz, int ny, int nx, int cz, int cy, int cx, void* vol);
+
+/* Error-bounded lossy chunk codec ("denoise, then quantise, then entropy-code" as a stored
+ * format).  Chunks as in exabm4d_codec_encode_dev -- (z, y, x) raster order, edge chunks truncated to their extent
+ * E -- but the chunk shape (cz, cy, cx) is NOMINAL: every axis a multiple of 8 in [8, 65528], cz * cy * cx <= 2^28,
+ * not clamped to the volume.  A chunk's lossy candidate at step j is the DESIGN.md 3.10 quantisation at the step
+ * Q[j] = (float) 2^((j - 4) / 4), j = 0..28 (0.5 .. 64), of its blocks (global block grid, edge voxels replicated),
+ * zero-filled to the nominal (cz/8)(cy/8)(cx/8) = nb blocks; err_j = max |dctq_inverse - v| over its voxels.
+ * Among the steps with err_j <= max_error the largest is taken, and the chunk stores the EXAC v2 int32 stream of
+ * those indices shaped (nb, 8, 64) (mode 1) when that is shorter than the EXAC v2 uint16 stream of its voxels,
+ * else the latter (mode 0; a tie too).  Every decoded voxel is within max_error of the encoder's input; with
+ * max_error = 0 the decode is exact.  Chunk stream: 32-byte header ('E' 'Q' 1 mode | j* (0xFF for mode 0) 0 0 0 |
+ * q as float32 bits (0 for mode 0) | Ez Ey Ex Cz Cy Cx as u16 | 8 zero bytes), then the unmodified EXAC payload.
+ *
+ * exabm4d_dctq_ladder_errors_dev: err[nchunks][29] (device, uint32) <- err_j of every chunk; no bound involved,
+ * the per-chunk rate-distortion picture.  Does not synchronise.
+ * exabm4d_bounded_volume_bound: capacity `out` needs (0 for bad sizes).
+ * exabm4d_bounded_encode_dev: the contract of exabm4d_codec_encode_dev -- out (device, 16-byte aligned, may be
+ * NULL: sizes only), offsets_dev[nchunks + 1], sizes_dev[nchunks] (exact stream lengths, header included),
+ * totals_host[2] = { sum of the exact lengths, container bytes } (non-NULL synchronises); every stream starts at a
+ * multiple of 16 bytes, padding zeroed.  0 <= max_error <= 65535.
+ * exabm4d_bounded_decode_dev: container (in_bytes bytes on the device, 16-byte aligned; offsets_dev[nchunks + 1],
+ * every stream at a multiple of 16 bytes) -> vol[nz][ny][nx].  Mixed containers decode in a fixed number of
+ * launches.  Synchronises.  A malformed container -- offsets not ascending, unaligned or beyond in_bytes, a bad
+ * header (magic, version, mode, q != Q[j*], E or C not those of the chunk), an EXAC payload that does not match
+ * the header's mode and shapes, or any error the EXAC decoder finds -- gives EXABM4D_ERR_INVALID and never reads
+ * outside [in, in + in_bytes).  Scratch comes from the context. */
+int exabm4d_dctq_ladder_errors_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, int ny, int nx, int cz, int cy,
+                                   int cx, uint32_t* err);
+size_t exabm4d_bounded_volume_bound(int nz, int ny, int nx, int cz, int cy, int cx);
+int exabm4d_bounded_encode_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, int ny, int nx, int cz, int cy, int cx,
+                               int max_error, uint8_t* out, size_t out_capacity, uint64_t* offsets_dev,
+                               uint32_t* sizes_dev, uint64_t* totals_host);
+int exabm4d_bounded_decode_dev(exabm4d_ctx* ctx, const uint8_t* in, size_t in_bytes, const uint64_t* offsets_dev,
+                               int nz, int ny, int nx, int cz, int cy, int cx, uint16_t* vol);
 
 /* ---- background offset + quality metrics on device (SURVEY.md section 8 "next" row f-4) --------- */
 /* Element types of the metric entry points. */
