@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the BM4D denoise hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 Step  = one pass of the hot path over one synthetic uint16 volume that is already resident in
         HBM, all through the C-ABI (include/exabm4d.h):
@@ -23,7 +23,9 @@ One JSON line is printed by rank 0.  `roofline` is for the dominant kernel, time
 events recorded on the stream the kernels run on (exabm4d "profile" option) inside the timed
 region; its `traffic` and `valu` entries come from the committed rocprofv3 passes
 (profiles/latest_counters.json names the profile and the commit) and are flagged stale when the
-live kernel time has moved.  `cpu_baseline` times the CPU port (oracle/exabm4d_cpu_port.c; the
+live kernel time has moved.  A plain run stops there: it sets up, warms up, times the steps, dumps
+(--dump-outputs) and prints.  `--full` adds the legs below and `end_to_end`, after the timed region
+and outside `value`.  `cpu_baseline` times the CPU port (oracle/exabm4d_cpu_port.c; the
 reference's BM4D is a closed wheel that cannot travel) on this box's host cores: BASELINE configs
 C1 and C2 fully, all usable cores and one thread, plus the host side of the encode half (the
 reference's codec family: byte shuffle + zstd-5 per 64^3 chunk through libzstd).  `psnr` compares
@@ -98,7 +100,10 @@ def _brick(seed):
 def synth_u16(shape, seed, z_range=None):
     """Pedestal 37 + the mirror-tiled structure brick + N(0, 24) noise, rint, clip, uint16
     (SURVEY.md section 8d).  Deterministic and random-access in z: the noise of every 32-plane
-    slab has its own seed, so a rank can regenerate exactly the planes [z0, z1) it holds."""
+    slab has its own seed, so a rank can regenerate exactly the planes [z0, z1) it holds.
+    Slabs are made on host threads (numpy's generators and ufuncs release the GIL), a few planes
+    at a time in reused buffers; a slab's generator is drawn from in plane order, so every voxel
+    gets the value one whole-slab draw would give it."""
     brick = _brick(seed)
     b = brick.shape[0]
     nz, ny, nx = shape
@@ -111,14 +116,37 @@ def synth_u16(shape, seed, z_range=None):
     iy, ix = tile_axis(np.arange(ny)), tile_axis(np.arange(nx))
     out = np.empty((z1 - z0, ny, nx), dtype=np.uint16)
     slab = 32
-    for s0 in range((z0 // slab) * slab, z1, slab):
+    part = max(1, min(slab, (1 << 22) // max(1, ny * nx)))     # planes per piece: about 4 M voxels
+
+    def fill(s0):
         rng = np.random.default_rng([seed, s0 // slab])
-        zs = np.arange(s0, min(s0 + slab, nz))
-        clean = brick[tile_axis(zs)][:, iy][:, :, ix] + np.float32(OFFSET)
-        noise = rng.standard_normal((slab, ny, nx), dtype=np.float32)[:len(zs)] * np.float32(SIGMA)
-        vals = np.rint(np.clip(clean + noise, 0, 65535)).astype(np.uint16)
-        a, e = max(z0, s0), min(z1, s0 + len(zs))
-        out[a - z0:e - z0] = vals[a - s0:e - s0]
+        a, e = max(z0, s0), min(z1, s0 + slab, nz)
+        noise = np.empty((part, ny, nx), dtype=np.float32)
+        clean = np.empty_like(noise)
+        for p0 in range(s0, e, part):
+            p1 = min(p0 + part, e)
+            nb, cb = noise[:p1 - p0], clean[:p1 - p0]
+            rng.standard_normal(dtype=np.float32, out=nb)      # planes below `a` are drawn and dropped
+            if p1 <= a:
+                continue
+            np.take(brick[tile_axis(np.arange(p0, p1))][:, iy], ix, axis=2, out=cb)
+            cb += np.float32(OFFSET)
+            nb *= np.float32(SIGMA)
+            nb += cb
+            np.clip(nb, 0, 65535, out=nb)
+            np.rint(nb, out=nb)
+            lo = max(a, p0)
+            out[lo - z0:p1 - z0] = nb[lo - p0:]
+
+    starts = range((z0 // slab) * slab, z1, slab)
+    threads = min(16, host_cpu()[1], len(starts))
+    if threads <= 1:
+        for s0 in starts:
+            fill(s0)
+    else:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(threads) as ex:
+            list(ex.map(fill, starts))
     return out
 
 
@@ -858,17 +886,23 @@ def main():
                          "backend); 'native' = exabm4d_halo_exchange_dev, rendezvous and barrier without importing torch")
     ap.add_argument("--no-encode", action="store_true",
                     help="time the denoiser alone (the metric's step includes the encode legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="--mode volumes: after the timed steps, also run the legs outside `value` -- `encoded` "
+                         "(the coder on the noisy input, shuffle + zstd-5 on sampled chunks), and at N = 1 "
+                         "`end_to_end`, `cpu_baseline` + `psnr` and `bm4dnet` (each can be switched off below); "
+                         "without it the run does the timed steps and the result line only")
     ap.add_argument("--end-to-end", type=int, default=1,
-                    help="0: skip the host-to-host legs (H2D + denoise + D2H, and the streamed chunk-local call) "
-                         "reported next to `value` at N = 1")
+                    help="with --full, 0: skip the host-to-host legs (H2D + denoise + D2H, and the streamed "
+                         "chunk-local call) reported next to `value` at N = 1")
     ap.add_argument("--cpu-sample", type=int, default=1,
-                    help="0 disables the CPU-baseline leg (C1 64^3 and C2 256^3 timed fully on the host)")
+                    help="with --full, 0 disables the CPU-baseline leg (C1 64^3 and C2 256^3 timed fully on the "
+                         "host) and the PSNR comparison")
     ap.add_argument("--bm4dnet", type=int, default=1,
-                    help="BASELINE config 3's learned stage: predict() of the BM4DNet U-Net on the bench volume "
-                         "itself (1024^3 by default: ~18 s), reported as extra keys; 0 disables")
+                    help="with --full: BASELINE config 3's learned stage, predict() of the BM4DNet U-Net on the "
+                         "bench volume itself (1024^3 by default: ~18 s), reported as extra keys; 0 disables")
     ap.add_argument("--bm4dnet-tune", type=int, default=256,
-                    help="edge of the volume the reference-like path (fast=False, MIOpen's own defaults, a fresh "
-                         "child process: ~20 s of solver selection) is measured on; 0 disables")
+                    help="with --full: edge of the volume the reference-like path (fast=False, MIOpen's own "
+                         "defaults, a fresh child process: ~20 s of solver selection) is measured on; 0 disables")
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
                     help="--mode volumes: write what rank 0's last timed step computed to DIR/<name>.npy "
                          "(float32 / float64, seeded samples of the large arrays, under 64 MB in all)")
@@ -1015,7 +1049,9 @@ def main():
         elapsed = float(t.item())
 
     # size-independent sanity property at full size: output is a denoised version of the input
-    out = d_out.download(shape, np.uint16)
+    # (the first 64 planes, or the whole volume when a dump or the --full legs need it)
+    whole = args.full or (args.dump_outputs and rank == 0)
+    out = d_out.download(shape if whole else (min(64, shape[0]),) + shape[1:], np.uint16)
     sl = (slice(0, min(64, shape[0])),)
     resid = out[sl].astype(np.float32) - vol[sl].astype(np.float32)
     resid_std = float(resid.std())
@@ -1025,7 +1061,7 @@ def main():
                                           ("encode_idx", nchunks_i, d_enc32, d_off32, d_sz32))
         write_outputs(args.dump_outputs, timed_outputs(out, *legs))
     encoded = None
-    if not args.no_encode:
+    if args.full and not args.no_encode:
         sz16 = d_sz16.download((nchunks,), np.uint32).astype(np.uint64)
         sz32 = d_sz32.download((nchunks_i,), np.uint32).astype(np.uint64)
         # the same coder on the noisy input, outside the timed region: the reference reports
@@ -1122,9 +1158,9 @@ def main():
         }
         if encoded is not None:
             result["encoded"] = encoded
-        if args.end_to_end and world == 1:
+        if args.full and args.end_to_end and world == 1:
             result["end_to_end"] = end_to_end_leg(ctx, vol, d_in, d_out, params, args.stages)
-        if args.cpu_sample > 0 and world == 1:         # reported baseline: rank 0 at N = 1 only
+        if args.full and args.cpu_sample > 0 and world == 1:      # reported baseline: rank 0 at N = 1 only
             port256, result["cpu_baseline"] = cpu_baseline(seed=1000)
             # PSNR (BASELINE.json's metric names it): GPU and CPU port on the SAME 256^3 volume
             # against the clean volume the noise was added to; delta < 0.01 dB is the bar
@@ -1155,7 +1191,7 @@ def main():
                 "max_abs_u16": int(d.max()), "frac_differing": float(np.mean(d > 0)),
                 "frac_beyond_one_count": float(np.mean(d > 1)),
             }
-        if args.bm4dnet > 0 and world == 1:
+        if args.full and args.bm4dnet > 0 and world == 1:
             # BASELINE config 3's learned stage, after the timed region and outside `value`
             for buf in (d_in, d_out, d_idx, d_enc16, d_enc32):
                 buf.free()

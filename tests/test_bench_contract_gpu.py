@@ -1,6 +1,6 @@
 """The benchmark line the driver parses: `python bench.py` at a small size in a child process must
 print exactly one JSON line with the contract's keys (task statement, section "Measurement"), the
-roofline and cpu_baseline objects, and a step that includes the encode legs."""
+roofline object (and with --full the cpu_baseline one), and a step that includes the encode legs."""
 import json
 import os
 import subprocess
@@ -23,7 +23,7 @@ def _run(*extra):
 
 @pytest.mark.gpu
 def test_default_line_has_the_contract_keys():
-    d = _run()
+    d = _run("--full")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                 "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
@@ -61,6 +61,29 @@ def test_default_line_has_the_contract_keys():
     assert p["gpu_equals_cpu"] is True and p["second_launch_identical"] is True and p["gpu_vs_cpu"] is None
     assert p["gpu_vs_clean"] > p["noisy_vs_clean"] + 5.0
     assert c["encode"]["exac_v2_port"]["cratio"] > 3.0
+
+
+FULL_ONLY = ("encoded", "end_to_end", "cpu_baseline", "psnr", "bm4dnet")
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_timed_steps_and_the_line():
+    """Without --full the line has the contract keys and what the timed steps measured (roofline,
+    phase_ms, residual_std), and none of the legs that run after them."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "64", "--steps", "2",
+                          "--warmup", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "phase_ms", "residual_std"):
+        assert key in d, key
+    assert d["metric"] == "denoised+encoded voxels/s on 1024^3 uint16" and d["dtype"] == "f32"
+    assert abs(d["value"] - 64 ** 3 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert 15.0 < d["residual_std"] < 30.0 and d["phase_ms"]["encode_idx"] > 0
+    for key in FULL_ONLY:
+        assert key not in d, key
 
 
 @pytest.mark.gpu

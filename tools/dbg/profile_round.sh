@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/prof_round; rm -rf $O; mkdir -p $O
 B="python bench.py --steps 1 --warmup 0 --cpu-sample 0 --bm4dnet 0 --end-to-end 0"
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err; cut -c1-300 $O/bench.json
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err; cut -c1-300 $O/bench.json
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/trace -- python bench.py --steps 3 --warmup 1 --cpu-sample 0 --bm4dnet 0 --end-to-end 0 > $O/trace.log 2>&1 && echo trace ok
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE -d $O/fetch -- $B > $O/fetch.log 2>&1 && echo fetch ok
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE -d $O/write -- $B > $O/write.log 2>&1 && echo write ok
