@@ -24,7 +24,7 @@ EXACT_HALO = 24
 def offset_exact_in_fp32(offset):
     """(float)v - offset is exact for every uint16 v iff the offset has at most 7 fractional bits;
     only then does matching on the uint16 planes give the tables of matching on the fp32 counts
-    (csrc/exabm4d_api.hip: offset_exact_in_fp32)."""
+    (csrc/api_bm4d.hip: offset_exact_in_fp32)."""
     import numpy as np
     off = np.float32(offset)
     s = off * np.float32(128.0)

@@ -1,0 +1,304 @@
+// api_codec.hip -- chunk byte histograms, the DCT quantiser, the EXAC chunk codec and the error-bounded codec.
+// Host code only; the context and the shared helpers are in exabm4d_api.h.
+#include "exabm4d_api.h"
+
+using namespace exabm4d;
+
+// ---- chunk entropy coder: scratch, tables and the checks both encoders and decoders share -------
+// aux layout: sizes u32[nchunks] | offsets u64[nchunks + 1] | totals u64[2] | status u32[4]
+struct CodecAux { uint32_t* sizes; unsigned long long *offsets, *totals; uint32_t* status; };
+static int codec_aux(exabm4d_ctx* ctx, int nchunks, CodecAux& A) {
+    return carve(ctx, ctx->codec_aux, 0, A, [&](Carver& c, auto& r) {
+        r.sizes = c.take<uint32_t>((size_t)nchunks * 4);
+        r.offsets = c.take<unsigned long long>(((size_t)nchunks + 1) * 8);
+        r.totals = c.take<unsigned long long>(2 * 8);
+        r.status = c.take<uint32_t>(4 * 4);
+    });
+}
+// the rANS coders' reciprocal table, uploaded once per context
+static int codec_rcp(exabm4d_ctx* ctx) {
+    if (!ctx->rcp_dev.p) {
+        static uint32_t tab[4097 * 2];
+        codec_fill_rcp_table(tab);
+        HIP_TRY(ctx, hipMalloc(&ctx->rcp_dev.p, sizeof tab));
+        ctx->rcp_dev.bytes = sizeof tab;
+        HIP_TRY(ctx, hipMemcpy(ctx->rcp_dev.p, tab, sizeof tab, hipMemcpyHostToDevice));
+    }
+    return EXABM4D_OK;
+}
+// The encoders' output container: offsets_dev with it, room for the volume bound, 16-byte aligned.  `who` and
+// `bound_fn` name the encoder and its bound in the messages.
+static int check_container(exabm4d_ctx* ctx, const std::string& who, const char* bound_fn, size_t bound,
+                           const uint8_t* out, size_t out_capacity, const uint64_t* offsets_dev) {
+    if (!out) return EXABM4D_OK;
+    if (!offsets_dev) return fail(ctx, EXABM4D_ERR_INVALID, who + ": offsets_dev is required with out");
+    if (out_capacity < bound)
+        return fail(ctx, EXABM4D_ERR_INVALID, who + ": out_capacity is below " + bound_fn + "()");
+    if ((uintptr_t)out & 15) return fail(ctx, EXABM4D_ERR_INVALID, who + ": out must be 16-byte aligned");
+    return EXABM4D_OK;
+}
+// The decoders' status word, fetched after the last kernel: nonzero is a malformed chunk stream.
+static int check_stream_status(exabm4d_ctx* ctx, const uint32_t* status, const char* who) {
+    uint32_t st = 0;
+    if (int rc = fetch(ctx, &st, status, sizeof st)) return rc;
+    if (!st) return EXABM4D_OK;
+    char msg[96];
+    std::snprintf(msg, sizeof msg, "%s: malformed chunk stream (status 0x%x)", who, st);
+    return fail(ctx, EXABM4D_ERR_INVALID, msg);
+}
+
+// ---- error-bounded lossy chunk codec: step ladder, geometry, scratch layouts -----------------
+// The step ladder Q[j] = (float) 2^((j - 4) / 4): the kernels take it as a table, none of them computes it.
+struct BqLadder {
+    float q[BQ_STEPS];
+    BqLadder() {
+        for (int j = 0; j < BQ_STEPS; j++) q[j] = (float)std::pow(2.0, (j - 4) / 4.0);
+    }
+};
+static const BqLadder& bq_ladder() {
+    static const BqLadder t;
+    return t;
+}
+
+static int bq_geom(exabm4d_ctx* ctx, int nz, int ny, int nx, int cz, int cy, int cx, BoundedGeom& g, CodecGeom& lossy,
+                   CodecGeom& lossless) {
+    if (make_bounded_geom(nz, ny, nx, cz, cy, cx, g) ||
+        make_codec_geom(4, g.nchunks * g.nb, 8, 64, g.nb, 8, 64, lossy, 2) ||
+        make_codec_geom(2, nz, ny, nx, cz, cy, cx, lossless, 2))
+        return fail(ctx, EXABM4D_ERR_INVALID,
+                    "bounded codec: sizes >= 1, chunk axes multiples of 8 in [8, 65528], chunk <= 2^28 voxels");
+    return EXABM4D_OK;
+}
+
+static size_t bq_volume_bound(const BoundedGeom& g) {
+    const size_t a = codec_chunk_bound((size_t)g.nb * BVOX, 4), b = codec_chunk_bound((size_t)g.cz * g.cy * g.cx, 2);
+    return (size_t)g.nchunks * (BQ_HEADER + ((std::max(a, b) + 15) & ~(size_t)15));
+}
+
+// bounded encode's scratch: ladder, per-step errors, choices, indices, the two candidate streams, the container
+struct BqEncodeScratch {
+    float *qtab, *qsel;
+    uint32_t *err, *lsz, *usz, *sizes;
+    int32_t *jsel, *idx;
+    unsigned long long *loff, *uoff, *tot, *offsets;     // tot: lossy, lossless, bounded {exact, container}
+    uint8_t *lbuf, *ubuf, *slot;
+};
+// bounded decode's scratch: ladder, chunk modes and steps, the two decode lists, lossy indices
+struct BqDecodeScratch {
+    float *qtab, *qv;
+    uint32_t *mode, *lchunk, *lstat;     // lstat: list counts [2], status
+    unsigned long long* lrange;
+    int32_t* idx;
+};
+
+extern "C" {
+
+// ---- encode front end (row f-1) ---------------------------------------------------------------------
+int exabm4d_chunk_byte_histograms_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, int ny, int nx,
+                                      int cz, int cy, int cx, uint32_t* hist) {
+    if (!ctx || !vol || !hist) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (nz < 1 || ny < 1 || nx < 1 || cz < 1 || cy < 1 || cx < 1)
+        return fail(ctx, EXABM4D_ERR_INVALID, "bad sizes");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_chunk_hist(vol, nz, ny, nx, cz, cy, cx, hist, ctx->stream));
+    return EXABM4D_OK;
+}
+
+// ---- transform quantiser (row f-1) ------------------------------------------------------
+int exabm4d_dctq_forward_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, int ny, int nx, float q,
+                             int32_t* idx) {
+    if (!ctx || !vol || !idx) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (nz < 1 || ny < 1 || nx < 1 || !(q > 0.0f)) return fail(ctx, EXABM4D_ERR_INVALID, "bad sizes / step");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_dctq_forward(vol, nz, ny, nx, dct_table(), q, idx, ctx->stream));
+    return EXABM4D_OK;
+}
+int exabm4d_dctq_inverse_dev(exabm4d_ctx* ctx, const int32_t* idx, int nz, int ny, int nx, float q,
+                             uint16_t* vol) {
+    if (!ctx || !vol || !idx) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (nz < 1 || ny < 1 || nx < 1 || !(q > 0.0f)) return fail(ctx, EXABM4D_ERR_INVALID, "bad sizes / step");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_dctq_inverse(idx, nz, ny, nx, dct_table(), q, vol, ctx->stream));
+    return EXABM4D_OK;
+}
+
+// ---- chunk entropy coder (row f-1) --------------------------------------------------------
+size_t exabm4d_codec_chunk_bound(size_t n_elems, int typesize) {
+    if (typesize != 2 && typesize != 4) return 0;
+    return codec_chunk_bound(n_elems, typesize);
+}
+size_t exabm4d_codec_volume_bound(int typesize, int nz, int ny, int nx, int cz, int cy, int cx) {
+    CodecGeom g;
+    if (make_codec_geom(typesize, nz, ny, nx, cz, cy, cx, g)) return 0;
+    return codec_volume_bound(g);
+}
+
+int exabm4d_codec_encode_dev(exabm4d_ctx* ctx, const void* vol, int typesize, int version, int nz, int ny, int nx,
+                             int cz, int cy, int cx, uint8_t* out, size_t out_capacity,
+                             uint64_t* offsets_dev, uint32_t* sizes_dev, uint64_t* totals_host) {
+    if (!ctx || !vol) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (version < 0 || version > 2) return fail(ctx, EXABM4D_ERR_INVALID, "codec: version must be 0 (context default), 1 or 2");
+    CodecGeom g;
+    if (make_codec_geom(typesize, nz, ny, nx, cz, cy, cx, g, version ? version : ctx->codec_version))
+        return fail(ctx, EXABM4D_ERR_INVALID, "codec: typesize must be 2 or 4, sizes >= 1, chunk <= 2^28 elements");
+    int rc = check_container(ctx, "codec", "exabm4d_codec_volume_bound", codec_volume_bound(g), out, out_capacity,
+                             offsets_dev);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = codec_rcp(ctx);
+    if (rc) return rc;
+    CodecAux A;
+    rc = codec_aux(ctx, g.nchunks, A);
+    if (rc) return rc;
+    rc = ensure_scratch(ctx, align256((size_t)g.nchunks * g.slot_bytes) + (g.version == 2 ? codec2_work_bytes(g) : 0));
+    if (rc) return rc;
+    if (sizes_dev) A.sizes = sizes_dev;
+    if (offsets_dev) A.offsets = reinterpret_cast<unsigned long long*>(offsets_dev);
+    HIP_TRY(ctx, launch_rans_encode(vol, g, ctx->rcp_dev.as<uint32_t>(), ctx->scratch.as<uint8_t>(), A.sizes,
+                                    A.offsets, A.totals, out, ctx->stream));
+    return totals_host ? fetch(ctx, totals_host, A.totals, 2 * sizeof(uint64_t)) : EXABM4D_OK;
+}
+int exabm4d_codec_decode_dev(exabm4d_ctx* ctx, const uint8_t* in, size_t in_bytes, const uint64_t* offsets_dev,
+                             int typesize, int nz, int ny, int nx, int cz, int cy, int cx, void* vol) {
+    if (!ctx || !in || !offsets_dev || !vol) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if ((uintptr_t)in & 15) return fail(ctx, EXABM4D_ERR_INVALID, "codec: in must be 16-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the format version is the third byte of every chunk stream: look at the first one
+    uint64_t first[2] = {0, 0};
+    int rc = fetch(ctx, first, offsets_dev, sizeof first);
+    if (rc) return rc;
+    if (first[0] > first[1] || first[1] > in_bytes || first[1] - first[0] < 4)
+        return fail(ctx, EXABM4D_ERR_INVALID, "codec: malformed chunk stream (offsets outside the buffer)");
+    uint8_t magic[4] = {0, 0, 0, 0};
+    rc = fetch(ctx, magic, in + first[0], 4);
+    if (rc) return rc;
+    if (magic[0] != 'E' || magic[1] != 'X' || (magic[2] != 1 && magic[2] != 2))
+        return fail(ctx, EXABM4D_ERR_INVALID, "codec: malformed chunk stream (not an EXAC v1 / v2 stream)");
+    CodecGeom g;
+    if (make_codec_geom(typesize, nz, ny, nx, cz, cy, cx, g, magic[2]))
+        return fail(ctx, EXABM4D_ERR_INVALID, "codec: typesize must be 2 or 4, sizes >= 1, chunk <= 2^28 elements");
+    CodecAux A;
+    rc = codec_aux(ctx, g.nchunks, A);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(A.status, 0, 16, ctx->stream));
+    HIP_TRY(ctx, launch_rans_decode(in, in_bytes, reinterpret_cast<const unsigned long long*>(offsets_dev), g,
+                                    vol, A.status, ctx->stream));
+    return check_stream_status(ctx, A.status, "codec");
+}
+
+// ---- error-bounded lossy chunk codec -----------------------------------------------------------
+size_t exabm4d_bounded_volume_bound(int nz, int ny, int nx, int cz, int cy, int cx) {
+    BoundedGeom g;
+    if (make_bounded_geom(nz, ny, nx, cz, cy, cx, g)) return 0;
+    return bq_volume_bound(g);
+}
+
+int exabm4d_dctq_ladder_errors_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, int ny, int nx, int cz, int cy,
+                                   int cx, uint32_t* err) {
+    if (!ctx || !vol || !err) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    BoundedGeom g;
+    CodecGeom gl, gu;
+    int rc = bq_geom(ctx, nz, ny, nx, cz, cy, cx, g, gl, gu);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = ensure_scratch(ctx, align256(sizeof(BqLadder)));
+    if (rc) return rc;
+    float* qtab = ctx->scratch.as<float>();
+    HIP_TRY(ctx, hipMemcpyAsync(qtab, bq_ladder().q, sizeof(BqLadder), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(err, 0, (size_t)g.nchunks * BQ_STEPS * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, launch_bq_ladder(vol, g, dct_table(), qtab, err, ctx->stream));
+    return EXABM4D_OK;
+}
+
+int exabm4d_bounded_encode_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, int ny, int nx, int cz, int cy, int cx,
+                               int max_error, uint8_t* out, size_t out_capacity, uint64_t* offsets_dev,
+                               uint32_t* sizes_dev, uint64_t* totals_host) {
+    if (!ctx || !vol) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (max_error < 0 || max_error > 65535) return fail(ctx, EXABM4D_ERR_INVALID, "bounded codec: max_error must be in [0, 65535]");
+    BoundedGeom g;
+    CodecGeom gl, gu;
+    int rc = bq_geom(ctx, nz, ny, nx, cz, cy, cx, g, gl, gu);
+    if (rc) return rc;
+    rc = check_container(ctx, "bounded codec", "exabm4d_bounded_volume_bound", bq_volume_bound(g), out,
+                         out_capacity, offsets_dev);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = codec_rcp(ctx);
+    if (rc) return rc;
+    const size_t nc = (size_t)g.nchunks;
+    const size_t slots = std::max(align256((size_t)gl.nchunks * gl.slot_bytes) + codec2_work_bytes(gl),
+                                  align256((size_t)gu.nchunks * gu.slot_bytes) + codec2_work_bytes(gu));
+    BqEncodeScratch S;
+    rc = carve(ctx, ctx->scratch, GUARD_BYTES, S, [&](Carver& c, auto& r) {
+        r.qtab = c.take<float>(sizeof(BqLadder));
+        r.err = c.take<uint32_t>(nc * BQ_STEPS * sizeof(uint32_t));
+        r.jsel = c.take<int32_t>(nc * sizeof(int32_t));
+        r.qsel = c.take<float>(nc * sizeof(float));
+        r.idx = c.take<int32_t>(nc * g.nb * BVOX * sizeof(int32_t));
+        r.lsz = c.take<uint32_t>(nc * sizeof(uint32_t));
+        r.loff = c.take<unsigned long long>((nc + 1) * 8);
+        r.lbuf = out ? c.take<uint8_t>(codec_volume_bound(gl)) : nullptr;
+        r.usz = c.take<uint32_t>(nc * sizeof(uint32_t));
+        r.uoff = c.take<unsigned long long>((nc + 1) * 8);
+        r.ubuf = out ? c.take<uint8_t>(codec_volume_bound(gu)) : nullptr;
+        r.tot = c.take<unsigned long long>(6 * 8);
+        r.sizes = c.take<uint32_t>(nc * sizeof(uint32_t));
+        r.offsets = c.take<unsigned long long>((nc + 1) * 8);
+        r.slot = c.take<uint8_t>(slots);
+    });
+    if (rc) return rc;
+    if (sizes_dev) S.sizes = sizes_dev;
+    if (offsets_dev) S.offsets = reinterpret_cast<unsigned long long*>(offsets_dev);
+    const float* dct = dct_table();
+    const uint32_t* rcp = ctx->rcp_dev.as<uint32_t>();
+    hipStream_t s = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(S.qtab, bq_ladder().q, sizeof(BqLadder), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(S.err, 0, nc * BQ_STEPS * sizeof(uint32_t), s));
+    HIP_TRY(ctx, launch_bq_ladder(vol, g, dct, S.qtab, S.err, s));
+    HIP_TRY(ctx, launch_bq_select(S.err, g.nchunks, (uint32_t)max_error, S.qtab, S.jsel, S.qsel, s));
+    HIP_TRY(ctx, launch_bq_forward(vol, g, dct, S.qsel, S.idx, s));
+    // the two candidates of every chunk through the existing chunk coder: the index chunks, then the voxels
+    HIP_TRY(ctx, launch_rans_encode(S.idx, gl, rcp, S.slot, S.lsz, S.loff, S.tot, S.lbuf, s));
+    HIP_TRY(ctx, launch_rans_encode(vol, gu, rcp, S.slot, S.usz, S.uoff, S.tot + 2, S.ubuf, s));
+    HIP_TRY(ctx, launch_bq_assemble(g, S.jsel, S.qsel, S.lbuf, S.loff, S.lsz, S.ubuf, S.uoff, S.usz, S.sizes,
+                                    S.offsets, S.tot + 4, out, s));
+    return totals_host ? fetch(ctx, totals_host, S.tot + 4, 2 * sizeof(uint64_t)) : EXABM4D_OK;
+}
+
+int exabm4d_bounded_decode_dev(exabm4d_ctx* ctx, const uint8_t* in, size_t in_bytes, const uint64_t* offsets_dev,
+                               int nz, int ny, int nx, int cz, int cy, int cx, uint16_t* vol) {
+    if (!ctx || !in || !offsets_dev || !vol) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if ((uintptr_t)in & 15) return fail(ctx, EXABM4D_ERR_INVALID, "bounded codec: in must be 16-byte aligned");
+    BoundedGeom g;
+    CodecGeom gl, gu;
+    int rc = bq_geom(ctx, nz, ny, nx, cz, cy, cx, g, gl, gu);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t nc = (size_t)g.nchunks;
+    BqDecodeScratch S;
+    rc = carve(ctx, ctx->scratch, GUARD_BYTES, S, [&](Carver& c, auto& r) {
+        r.qtab = c.take<float>(sizeof(BqLadder));
+        r.mode = c.take<uint32_t>(nc * sizeof(uint32_t));
+        r.qv = c.take<float>(nc * sizeof(float));
+        r.lchunk = c.take<uint32_t>(2 * nc * sizeof(uint32_t));
+        r.lrange = c.take<unsigned long long>(4 * nc * 8);
+        r.lstat = c.take<uint32_t>(4 * sizeof(uint32_t));
+        r.idx = c.take<int32_t>(nc * g.nb * BVOX * sizeof(int32_t));
+    });
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    uint32_t* status = S.lstat + 2;
+    HIP_TRY(ctx, hipMemcpyAsync(S.qtab, bq_ladder().q, sizeof(BqLadder), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(S.lstat, 0, 4 * sizeof(uint32_t), s));
+    HIP_TRY(ctx, launch_bq_parse(in, in_bytes, reinterpret_cast<const unsigned long long*>(offsets_dev), g, S.qtab,
+                                 S.mode, S.qv, S.lchunk, S.lrange, S.lstat, status, s));
+    // lossless chunks straight into the volume, lossy chunks' indices into the chunk-major scratch, then their inverse
+    HIP_TRY(ctx, launch_rans2_decode_list(in, in_bytes, DecodeList{S.lchunk, S.lrange, S.lstat}, (unsigned)nc, gu, vol,
+                                          status, s));
+    HIP_TRY(ctx, launch_rans2_decode_list(in, in_bytes, DecodeList{S.lchunk + nc, S.lrange + 2 * nc, S.lstat + 1},
+                                          (unsigned)nc, gl, S.idx, status, s));
+    HIP_TRY(ctx, launch_bq_inverse(S.idx, g, dct_table(), S.mode, S.qv, vol, s));
+    return check_stream_status(ctx, status, "bounded codec");
+}
+
+}  // extern "C"

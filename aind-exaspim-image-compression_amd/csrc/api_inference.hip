@@ -1,0 +1,213 @@
+// api_inference.hip -- the BM4DNet stage's NDHWC GroupNorm, pooling and up-sampling, the intensity transforms and
+// overlap tiling (what inference.py and transforms.py call).  Host code only; shared helpers: exabm4d_api.h.
+#include <type_traits>
+
+#include "exabm4d_api.h"
+
+using namespace exabm4d;
+
+// The prologue of the entries that take an exabm4d_transform: arguments, the transform's constants, the device.
+static int tf_entry(exabm4d_ctx* ctx, bool ptrs_ok, const exabm4d_transform* t, TfDev& d) {
+    if (!ctx || !ptrs_ok) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (!t) return fail(ctx, EXABM4D_ERR_INVALID, "transform is NULL");
+    if (t->size != sizeof(exabm4d_transform))
+        return fail(ctx, EXABM4D_ERR_INVALID, "transform.size does not match this library");
+    if (t->kind < 0 || t->kind > 2) return fail(ctx, EXABM4D_ERR_INVALID, "unknown transform kind");
+    std::memset(&d, 0, sizeof d);
+    d.kind = t->kind;
+    d.wrapped = t->wrapped ? 1 : 0;
+    d.woff = (float)t->wrap_offset;
+    d.maxc = (float)t->max_count;
+    d.off = (float)t->offset;
+    d.scale = (float)t->scale;
+    d.norm = (float)t->norm;
+    d.gain = (float)t->gain;
+    d.c38g2 = (float)((3.0 / 8.0) * t->gain * t->gain);
+    d.rn2 = (float)(t->read_noise * t->read_noise);
+    d.two_over_gain = (float)(2.0 / t->gain);
+    d.cinvg2 = (float)(t->c_inv * t->gain * t->gain);
+    d.mn = (float)t->mn;
+    d.fden = (float)(t->mx - t->mn + 1e-8);
+    d.clip = (float)t->clip;
+    d.range = (float)(t->mx - t->mn);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return EXABM4D_OK;
+}
+
+// The fp32 entries are the dtype-coded ones with EXABM4D_DTYPE_F32; the element type picks the template
+// instance of nn_kernels.hip (_Float16 / __bf16 storage for fp16 / bf16, 8-byte four-channel vectors).
+static bool nn_dtype_ok(int dtype) {
+    return dtype == EXABM4D_DTYPE_F32 || dtype == EXABM4D_DTYPE_F16 || dtype == EXABM4D_DTYPE_BF16;
+}
+static uintptr_t nn_align_mask(int dtype) { return dtype == EXABM4D_DTYPE_F32 ? 15u : 7u; }
+// Calls f with a null pointer of the element type of `dtype` (nn_dtype_ok), which picks the launcher's instance.
+template <typename F>
+static hipError_t nn_dispatch(int dtype, F&& f) {
+    if (dtype == EXABM4D_DTYPE_F32) return f(static_cast<float*>(nullptr));
+    if (dtype == EXABM4D_DTYPE_F16) return f(static_cast<_Float16*>(nullptr));
+    return f(static_cast<__bf16*>(nullptr));
+}
+
+extern "C" {
+
+// ---- BM4DNet stage: fused GroupNorm + LeakyReLU on NDHWC tensors (nn_kernels.hip) ------------------------
+size_t exabm4d_groupnorm_workspace_bytes(int batch, size_t spatial, int channels, int groups) {
+    if (batch < 1 || channels < 1 || groups < 1) return 0;
+    return groupnorm_workspace_bytes(batch, spatial, channels, groups);
+}
+int exabm4d_groupnorm_lrelu_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* x, void* y,
+                                         int batch, size_t spatial, int channels, int groups, const float* gamma,
+                                         const float* beta, float eps, float slope, void* workspace,
+                                         size_t workspace_bytes, const float* conv_bias) {
+    if (!ctx || !x || !y || !workspace) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (!nn_dtype_ok(dtype)) return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_ndhwc: unknown dtype");
+    if (conv_bias && ((uintptr_t)conv_bias & 15u) != 0)
+        return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_ndhwc: conv_bias must be 16-byte aligned");
+    if (batch < 1 || batch > 65535 || spatial < 1 || channels < 4 || groups < 1 || groups > 32 ||
+        channels % groups != 0 || channels % 4 != 0 || (channels / groups) % 4 != 0 || 256 % (channels / 4) != 0)
+        return fail(ctx, EXABM4D_ERR_UNSUPPORTED,
+                    "groupnorm_lrelu_ndhwc: needs channels % 4 == 0, (channels / groups) % 4 == 0, "
+                    "256 % (channels / 4) == 0 and groups <= 32 (use the framework's GroupNorm otherwise)");
+    if (workspace_bytes < groupnorm_workspace_bytes(batch, spatial, channels, groups))
+        return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_ndhwc: workspace too small");
+    if ((((uintptr_t)x | (uintptr_t)y) & nn_align_mask(dtype)) != 0 || ((uintptr_t)workspace & 15u) != 0)
+        return fail(ctx, EXABM4D_ERR_INVALID,
+                    dtype == EXABM4D_DTYPE_F32 ? "groupnorm_lrelu_ndhwc: 16-byte aligned tensors expected"
+                                               : "groupnorm_lrelu_ndhwc: 8-byte aligned tensors and a 16-byte "
+                                                 "aligned workspace expected");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = nn_dispatch(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_groupnorm_lrelu_ndhwc(static_cast<const T*>(x), static_cast<T*>(y), batch, spatial, channels,
+                                            groups, gamma, beta, eps, slope, workspace, (hipStream_t)hip_stream,
+                                            conv_bias);
+    });
+    return e == hipSuccess ? EXABM4D_OK : fail_hip(ctx, e, "launch_groupnorm_lrelu_ndhwc");
+}
+int exabm4d_groupnorm_lrelu_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, float* y, int batch,
+                                      size_t spatial, int channels, int groups, const float* gamma,
+                                      const float* beta, float eps, float slope, void* workspace,
+                                      size_t workspace_bytes, const float* conv_bias) {
+    return exabm4d_groupnorm_lrelu_ndhwc_dt_dev(ctx, hip_stream, EXABM4D_DTYPE_F32, x, y, batch, spatial, channels,
+                                                groups, gamma, beta, eps, slope, workspace, workspace_bytes,
+                                                conv_bias);
+}
+
+static int nn_resample_checks(exabm4d_ctx* ctx, int dtype, const void* x, const void* y, int batch, int d, int h,
+                              int w, int channels) {
+    if (!ctx || !x || !y) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (!nn_dtype_ok(dtype)) return fail(ctx, EXABM4D_ERR_INVALID, "NDHWC resampling: unknown dtype");
+    if (batch < 1 || d < 1 || h < 1 || w < 1 || channels < 4 || channels % 4 != 0)
+        return fail(ctx, EXABM4D_ERR_UNSUPPORTED, "NDHWC resampling: sizes >= 1 and channels % 4 == 0");
+    if ((((uintptr_t)x | (uintptr_t)y) & nn_align_mask(dtype)) != 0)
+        return fail(ctx, EXABM4D_ERR_INVALID,
+                    dtype == EXABM4D_DTYPE_F32 ? "NDHWC resampling: 16-byte aligned tensors expected"
+                                               : "NDHWC resampling: 8-byte aligned tensors expected");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return EXABM4D_OK;
+}
+int exabm4d_maxpool2_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* x, void* y, int batch,
+                                  int d, int h, int w, int channels) {
+    int rc = nn_resample_checks(ctx, dtype, x, y, batch, d, h, w, channels);
+    if (rc) return rc;
+    const hipError_t e = nn_dispatch(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_maxpool2_ndhwc(static_cast<const T*>(x), static_cast<T*>(y), batch, d, h, w, channels,
+                                     (hipStream_t)hip_stream);
+    });
+    return e == hipSuccess ? EXABM4D_OK : fail_hip(ctx, e, "launch_maxpool2_ndhwc");
+}
+int exabm4d_upsample2_trilinear_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* x, void* y,
+                                             int batch, int d, int h, int w, int channels) {
+    int rc = nn_resample_checks(ctx, dtype, x, y, batch, d, h, w, channels);
+    if (rc) return rc;
+    const hipError_t e = nn_dispatch(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_upsample2_trilinear_ndhwc(static_cast<const T*>(x), static_cast<T*>(y), batch, d, h, w,
+                                                channels, (hipStream_t)hip_stream);
+    });
+    return e == hipSuccess ? EXABM4D_OK : fail_hip(ctx, e, "launch_upsample2_trilinear_ndhwc");
+}
+int exabm4d_maxpool2_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, float* y, int batch, int d,
+                               int h, int w, int channels) {
+    return exabm4d_maxpool2_ndhwc_dt_dev(ctx, hip_stream, EXABM4D_DTYPE_F32, x, y, batch, d, h, w, channels);
+}
+int exabm4d_upsample2_trilinear_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, float* y, int batch,
+                                          int d, int h, int w, int channels) {
+    return exabm4d_upsample2_trilinear_ndhwc_dt_dev(ctx, hip_stream, EXABM4D_DTYPE_F32, x, y, batch, d, h, w,
+                                                    channels);
+}
+
+// ---- intensity transforms ---------------------------------------------------------------------------------
+int exabm4d_transform_forward_u16_dev(exabm4d_ctx* ctx, const exabm4d_transform* t,
+                                      const uint16_t* in, float* out, size_t n) {
+    TfDev d;
+    if (int rc = tf_entry(ctx, in && out, t, d)) return rc;
+    if (d.kind == EXABM4D_TF_ASINH && n >= ((size_t)1 << 20)) {
+        // asinh is evaluated in fp64: large uint16 volumes go through a 65536-entry table
+        if (!ctx->tf_lut.p) {
+            HIP_TRY(ctx, hipMalloc(&ctx->tf_lut.p, 65536 * sizeof(float)));
+            ctx->tf_lut.bytes = 65536 * sizeof(float);
+        }
+        HIP_TRY(ctx, launch_tf_forward_u16_lut(d, ctx->tf_lut.as<float>(), in, out, n, ctx->stream));
+        return EXABM4D_OK;
+    }
+    HIP_TRY(ctx, launch_tf_forward_u16(d, in, out, n, ctx->stream));
+    return EXABM4D_OK;
+}
+int exabm4d_transform_forward_f32_dev(exabm4d_ctx* ctx, const exabm4d_transform* t,
+                                      const float* in, float* out, size_t n) {
+    TfDev d;
+    if (int rc = tf_entry(ctx, in && out, t, d)) return rc;
+    HIP_TRY(ctx, launch_tf_forward_f32(d, in, out, n, ctx->stream));
+    return EXABM4D_OK;
+}
+int exabm4d_transform_inverse_u16_dev(exabm4d_ctx* ctx, const exabm4d_transform* t,
+                                      const float* in, uint16_t* out, size_t n) {
+    TfDev d;
+    if (int rc = tf_entry(ctx, in && out, t, d)) return rc;
+    HIP_TRY(ctx, launch_tf_inverse(d, in, out, n, 1, ctx->stream));
+    return EXABM4D_OK;
+}
+int exabm4d_transform_inverse_f32_dev(exabm4d_ctx* ctx, const exabm4d_transform* t,
+                                      const float* in, float* out, size_t n) {
+    TfDev d;
+    if (int rc = tf_entry(ctx, in && out, t, d)) return rc;
+    HIP_TRY(ctx, launch_tf_inverse(d, in, out, n, 0, ctx->stream));
+    return EXABM4D_OK;
+}
+
+// ---- overlap tiling ---------------------------------------------------------------------------------------------
+int exabm4d_tile_gather_dev(exabm4d_ctx* ctx, const float* vol, int nz, int ny, int nx,
+                            const int32_t* starts, int nb, int patch, float* out) {
+    if (!ctx || !vol || !starts || !out) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (nb < 0 || patch < 1 || nz < 1 || ny < 1 || nx < 1) return fail(ctx, EXABM4D_ERR_INVALID, "bad sizes");
+    for (int i = 0; i < 3 * nb; i++)
+        if (starts[i] < 0) return fail(ctx, EXABM4D_ERR_INVALID, "negative patch start");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_tile_gather(vol, nz, ny, nx, starts, nb, patch, out, ctx->stream));
+    return EXABM4D_OK;
+}
+int exabm4d_tile_accumulate_dev(exabm4d_ctx* ctx, const float* preds, const int32_t* starts, int nb,
+                                int patch, int trim, float* accum_pred, float* accum_wgt, int nz,
+                                int ny, int nx) {
+    if (!ctx || !preds || !starts || !accum_pred || !accum_wgt)
+        return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (nb < 0 || patch < 1 || trim < 0 || 2 * trim >= patch) return fail(ctx, EXABM4D_ERR_INVALID, "bad sizes");
+    for (int i = 0; i < 3 * nb; i++)
+        if (starts[i] < 0) return fail(ctx, EXABM4D_ERR_INVALID, "negative patch start");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_tile_accumulate(preds, starts, nb, patch, trim, accum_pred, accum_wgt, nz, ny,
+                                        nx, ctx->stream));
+    return EXABM4D_OK;
+}
+int exabm4d_tile_finalize_u16_dev(exabm4d_ctx* ctx, const exabm4d_transform* t,
+                                  const float* accum_pred, const float* accum_wgt, uint16_t* out,
+                                  size_t n) {
+    TfDev d;
+    if (int rc = tf_entry(ctx, accum_pred && accum_wgt && out, t, d)) return rc;
+    HIP_TRY(ctx, launch_tile_finalize(d, accum_pred, accum_wgt, out, n, ctx->stream));
+    return EXABM4D_OK;
+}
+
+}  // extern "C"

@@ -17,12 +17,9 @@
 #include <mutex>
 #include <string>
 
-#include "../../include/exabm4d.h"
-#include "exabm4d_common.h"
+#include "exabm4d_api.h"
 
-extern "C" int exabm4d_internal_fail(exabm4d_ctx* ctx, int code, const char* msg);     // exabm4d_api.hip
-extern "C" hipStream_t exabm4d_internal_stream(exabm4d_ctx* ctx);
-extern "C" int exabm4d_internal_device(exabm4d_ctx* ctx);
+using namespace exabm4d;
 
 namespace {
 // the slice of rccl.h this file uses (the library is third-party and stays outside the link line)
@@ -81,13 +78,13 @@ void load_rccl() {
 bool rccl_ready(exabm4d_ctx* ctx, int* rc) {
     std::call_once(g_once, load_rccl);
     if (g_rccl.handle) return true;
-    *rc = exabm4d_internal_fail(ctx, EXABM4D_ERR_UNSUPPORTED,
-                                ("RCCL is not available (set EXABM4D_RCCL_LIB to librccl.so): " + g_rccl.err).c_str());
+    *rc = fail(ctx, EXABM4D_ERR_UNSUPPORTED,
+               "RCCL is not available (set EXABM4D_RCCL_LIB to librccl.so): " + g_rccl.err);
     return false;
 }
 int nccl_fail(exabm4d_ctx* ctx, ncclResult_i r, const char* what) {
     std::string m = std::string(what) + ": " + (g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "RCCL error");
-    return exabm4d_internal_fail(ctx, EXABM4D_ERR_HIP, m.c_str());
+    return fail(ctx, EXABM4D_ERR_HIP, m);
 }
 }  // namespace
 
@@ -101,7 +98,7 @@ extern "C" {
 
 int exabm4d_comm_unique_id(uint8_t id[EXABM4D_COMM_ID_BYTES]) {
     int rc = 0;
-    if (!id) return exabm4d_internal_fail(nullptr, EXABM4D_ERR_INVALID, "id is NULL");
+    if (!id) return fail(nullptr, EXABM4D_ERR_INVALID, "id is NULL");
     if (!rccl_ready(nullptr, &rc)) return rc;
     ncclUniqueId_t u;
     const ncclResult_i r = g_rccl.GetUniqueId(&u);
@@ -114,17 +111,17 @@ int exabm4d_comm_unique_id(uint8_t id[EXABM4D_COMM_ID_BYTES]) {
 int exabm4d_comm_create(exabm4d_ctx* ctx, int nranks, int rank, const uint8_t id[EXABM4D_COMM_ID_BYTES],
                         exabm4d_comm** out) {
     int rc = 0;
-    if (!ctx || !id || !out) return exabm4d_internal_fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (!ctx || !id || !out) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
     *out = nullptr;
     if (nranks < 1 || rank < 0 || rank >= nranks)
-        return exabm4d_internal_fail(ctx, EXABM4D_ERR_INVALID, "comm: need 0 <= rank < nranks");
+        return fail(ctx, EXABM4D_ERR_INVALID, "comm: need 0 <= rank < nranks");
     if (!rccl_ready(ctx, &rc)) return rc;
-    if (hipSetDevice(exabm4d_internal_device(ctx)) != hipSuccess)
-        return exabm4d_internal_fail(ctx, EXABM4D_ERR_HIP, "comm: hipSetDevice");
+    if (hipSetDevice(ctx->device) != hipSuccess)
+        return fail(ctx, EXABM4D_ERR_HIP, "comm: hipSetDevice");
     ncclUniqueId_t u;
     std::memcpy(&u, id, sizeof u);
     exabm4d_comm* c = new (std::nothrow) exabm4d_comm();
-    if (!c) return exabm4d_internal_fail(ctx, EXABM4D_ERR_NOMEM, "out of host memory");
+    if (!c) return fail(ctx, EXABM4D_ERR_NOMEM, "out of host memory");
     const ncclResult_i r = g_rccl.CommInitRank(&c->comm, nranks, u, rank);      // collective over the ranks
     if (r != 0) {
         delete c;
@@ -133,11 +130,11 @@ int exabm4d_comm_create(exabm4d_ctx* ctx, int nranks, int rank, const uint8_t id
     if (hipMalloc((void**)&c->word, sizeof(double)) != hipSuccess) {
         (void)g_rccl.CommDestroy(c->comm);
         delete c;
-        return exabm4d_internal_fail(ctx, EXABM4D_ERR_NOMEM, "comm: device scratch");
+        return fail(ctx, EXABM4D_ERR_NOMEM, "comm: device scratch");
     }
     c->nranks = nranks;
     c->rank = rank;
-    c->device = exabm4d_internal_device(ctx);
+    c->device = ctx->device;
     *out = c;
     return EXABM4D_OK;
 }
@@ -152,15 +149,15 @@ int exabm4d_comm_destroy(exabm4d_comm* comm) {
 
 int exabm4d_halo_exchange_dev(exabm4d_ctx* ctx, exabm4d_comm* comm, int lo_peer, const void* send_lo, void* recv_lo,
                               size_t bytes_lo, int hi_peer, const void* send_hi, void* recv_hi, size_t bytes_hi) {
-    if (!ctx || !comm || !comm->comm) return exabm4d_internal_fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
-    if (comm->device != exabm4d_internal_device(ctx))
-        return exabm4d_internal_fail(ctx, EXABM4D_ERR_INVALID, "halo exchange: communicator of another device");
+    if (!ctx || !comm || !comm->comm) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (comm->device != ctx->device)
+        return fail(ctx, EXABM4D_ERR_INVALID, "halo exchange: communicator of another device");
     const bool lo = lo_peer >= 0 && bytes_lo > 0, hi = hi_peer >= 0 && bytes_hi > 0;
     if ((lo && (lo_peer >= comm->nranks || !send_lo || !recv_lo)) || (hi && (hi_peer >= comm->nranks || !send_hi || !recv_hi)))
-        return exabm4d_internal_fail(ctx, EXABM4D_ERR_INVALID, "halo exchange: bad peer or NULL buffer");
+        return fail(ctx, EXABM4D_ERR_INVALID, "halo exchange: bad peer or NULL buffer");
     if (!lo && !hi) return EXABM4D_OK;
-    if (hipSetDevice(comm->device) != hipSuccess) return exabm4d_internal_fail(ctx, EXABM4D_ERR_HIP, "hipSetDevice");
-    hipStream_t s = exabm4d_internal_stream(ctx);
+    if (hipSetDevice(comm->device) != hipSuccess) return fail(ctx, EXABM4D_ERR_HIP, "hipSetDevice");
+    hipStream_t s = ctx->stream;
     ncclResult_i r = g_rccl.GroupStart();
     if (r != 0) return nccl_fail(ctx, r, "ncclGroupStart");
     // every rank posts its sends and receives in the same order (lower neighbour first): the matching of two
@@ -176,16 +173,16 @@ int exabm4d_halo_exchange_dev(exabm4d_ctx* ctx, exabm4d_comm* comm, int lo_peer,
 }
 
 int exabm4d_comm_max_f64_host(exabm4d_ctx* ctx, exabm4d_comm* comm, double* value) {
-    if (!ctx || !comm || !comm->comm || !value) return exabm4d_internal_fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
-    if (hipSetDevice(comm->device) != hipSuccess) return exabm4d_internal_fail(ctx, EXABM4D_ERR_HIP, "hipSetDevice");
-    hipStream_t s = exabm4d_internal_stream(ctx);
+    if (!ctx || !comm || !comm->comm || !value) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (hipSetDevice(comm->device) != hipSuccess) return fail(ctx, EXABM4D_ERR_HIP, "hipSetDevice");
+    hipStream_t s = ctx->stream;
     if (hipMemcpyAsync(comm->word, value, sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess)
-        return exabm4d_internal_fail(ctx, EXABM4D_ERR_HIP, "comm max: upload");
+        return fail(ctx, EXABM4D_ERR_HIP, "comm max: upload");
     const ncclResult_i r = g_rccl.AllReduce(comm->word, comm->word, 1, kNcclFloat64, kNcclMax, comm->comm, s);
     if (r != 0) return nccl_fail(ctx, r, "ncclAllReduce");
     if (hipMemcpyAsync(value, comm->word, sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
-        return exabm4d_internal_fail(ctx, EXABM4D_ERR_HIP, "comm max: download");
+        return fail(ctx, EXABM4D_ERR_HIP, "comm max: download");
     return EXABM4D_OK;
 }
 
