@@ -181,6 +181,12 @@ def evaluate_example(pred, raw, target, fg_mask, pct=0.1):
         q = 100.0 - pct
         raw_top = float(order_stats.percentile(r.order_stats(), q))
         pred_top = float(order_stats.percentile(p.order_stats(), q))
+        # np.percentile of a sample that holds a NaN is NaN (the radix selection would rank it as an extreme);
+        # the maxima say whether one is there
+        if np.isnan(vs_raw[4]):
+            pred_top = float("nan")
+        if np.isnan(vs_raw[5]):
+            raw_top = float("nan")
         return {
             "fg_mae": fg_mae,
             "bg_mae": bg_mae,

@@ -148,6 +148,8 @@ int exabm4d_blockmatch_dev(exabm4d_ctx* ctx, const float* vol, int nz, int ny, i
     int rc = arg_checks(ctx, vol && keys, p);
     if (rc) return rc;
     if (!(sigma > 0.0f) || !(c_match > 0.0f)) return fail(ctx, EXABM4D_ERR_INVALID, "sigma and c_match must be > 0");
+    if (((uintptr_t)keys & 15u) != 0)       // a reference's 16 keys leave as 16-byte vectors
+        return fail(ctx, EXABM4D_ERR_INVALID, "keys must be 16-byte aligned");
     VolGeom g;
     rc = geom_on_device(ctx, nz, ny, nx, batch, g);
     if (rc) return rc;
@@ -186,6 +188,8 @@ int exabm4d_blockmatch_u16_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, in
     int rc = arg_checks(ctx, vol && keys, p);
     if (rc) return rc;
     if (!(sigma > 0.0f) || !(c_match > 0.0f)) return fail(ctx, EXABM4D_ERR_INVALID, "sigma and c_match must be > 0");
+    if (((uintptr_t)keys & 15u) != 0)       // a reference's 16 keys leave as 16-byte vectors
+        return fail(ctx, EXABM4D_ERR_INVALID, "keys must be 16-byte aligned");
     VolGeom g;
     rc = geom_on_device(ctx, nz, ny, nx, batch, g);
     if (rc) return rc;

@@ -158,6 +158,10 @@ hipError_t launch_hist_key(const void* vol, int dtype, size_t n, int absdev, dou
 
 // ---- fixed-order final reduction of per-workgroup partials ------------------------------------------
 // partials[w * K + k]; column k is summed, or max/min-reduced when its bit is set in the masks.
+// Maxima and minima propagate a NaN the way np.max / np.min do (fmax / fmin alone would drop it, and a
+// diverged prediction would report a finite maximum next to a NaN sum); without a NaN they are fmax / fmin.
+__device__ __forceinline__ double max_nan(double a, double b) { return (a != a || b != b) ? a + b : fmax(a, b); }
+__device__ __forceinline__ double min_nan(double a, double b) { return (a != a || b != b) ? a + b : fmin(a, b); }
 constexpr int RED_T = 256;
 __global__ __launch_bounds__(RED_T) void reduce_partials_kernel(const double* __restrict__ partials,
                                                                 int nwg, int K, unsigned max_mask,
@@ -169,14 +173,14 @@ __global__ __launch_bounds__(RED_T) void reduce_partials_kernel(const double* __
         double a = is_max ? -INFINITY : (is_min ? INFINITY : 0.0);
         for (int w = threadIdx.x; w < nwg; w += RED_T) {
             const double v = partials[(size_t)w * K + k];
-            a = is_max ? fmax(a, v) : (is_min ? fmin(a, v) : a + v);
+            a = is_max ? max_nan(a, v) : (is_min ? min_nan(a, v) : a + v);
         }
         sh[threadIdx.x] = a;
         __syncthreads();
         for (int s = RED_T / 2; s > 0; s >>= 1) {
             if ((int)threadIdx.x < s) {
                 const double x = sh[threadIdx.x], y = sh[threadIdx.x + s];
-                sh[threadIdx.x] = is_max ? fmax(x, y) : (is_min ? fmin(x, y) : x + y);
+                sh[threadIdx.x] = is_max ? max_nan(x, y) : (is_min ? min_nan(x, y) : x + y);
             }
             __syncthreads();
         }
@@ -204,7 +208,7 @@ __device__ __forceinline__ void block_reduce_store(double (&v)[K], unsigned max_
         for (int s = T / 2; s > 0; s >>= 1) {
             if ((int)threadIdx.x < s) {
                 const double x = sh[threadIdx.x], y = sh[threadIdx.x + s];
-                sh[threadIdx.x] = is_max ? fmax(x, y) : (is_min ? fmin(x, y) : x + y);
+                sh[threadIdx.x] = is_max ? max_nan(x, y) : (is_min ? min_nan(x, y) : x + y);
             }
             __syncthreads();
         }
@@ -236,9 +240,9 @@ __global__ __launch_bounds__(MS_T) void masked_stats_kernel(const TP* __restrict
             v[1] += e;
             if (p > thr) v[3] += 1.0;
         }
-        v[4] = fmax(v[4], p);
-        v[5] = fmax(v[5], r);
-        v[6] = fmax(v[6], e);
+        v[4] = max_nan(v[4], p);
+        v[5] = max_nan(v[5], r);
+        v[6] = max_nan(v[6], e);
     }
     block_reduce_store<MS_K, MS_T>(v, MS_MAXMASK, 0u, partials);
 }
@@ -291,8 +295,8 @@ __global__ __launch_bounds__(MS_T) void minmax_kernel(const T* __restrict__ a, s
     double v[2] = {INFINITY, -INFINITY};
     for (size_t i = (size_t)blockIdx.x * MS_T + threadIdx.x; i < n; i += (size_t)gridDim.x * MS_T) {
         const double x = (double)a[i];
-        v[0] = fmin(v[0], x);
-        v[1] = fmax(v[1], x);
+        v[0] = min_nan(v[0], x);
+        v[1] = max_nan(v[1], x);
     }
     block_reduce_store<2, MS_T>(v, 0x2u, 0x1u, partials);
 }

@@ -1077,7 +1077,10 @@ hipError_t launch_stage(const float* noisy, const float* basic, const uint32_t* 
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (err != hipSuccess) return err;
         const f2* pairvol = nullptr;
-        if (W && pair && opt.pairvol && (pair_ready || (n % 4) == 0)) {
+        // (the interleaving kernel reads both volumes with 16-byte loads: a caller's view that is only
+        // float-aligned takes the separate gathers, which give the same bits)
+        const bool vec_ok = (n % 4) == 0 && (((uintptr_t)noisy | (uintptr_t)basic) & 15u) == 0;
+        if (W && pair && opt.pairvol && (pair_ready || vec_ok)) {
             f2* pv = reinterpret_cast<f2*>(pair);
             if (!pair_ready)
                 hipLaunchKernelGGL(interleave_pair_kernel, dim3(65536), dim3(256), 0, stream, noisy, basic, pv, n);

@@ -191,7 +191,11 @@ int exabm4d_blockmatch_plan(const exabm4d_ctx* ctx, int nz, int ny, int nx, int 
 /* Block matching.  keys: [batch][nref][16] uint32, nref = gz*gy*gx in (z,y,x) raster of the
  * reference grid.  key = (bits(S) & 0xFFFFF800) | code, S = block SSD (fp32),
  * code = 0 for the reference block itself else 1 + ((dz+5)*11 + (dy+5))*11 + (dx+5).
- * Sorted ascending; unused slots 0xFFFFFFFF.  c_match: threshold factor (c_match*sigma^2). */
+ * Sorted ascending; unused slots 0xFFFFFFFF.  c_match: threshold factor (c_match*sigma^2).
+ * Pointers: `vol` needs its natural (4-byte) alignment only -- the tiles are staged with 16-byte loads from
+ * row starts that are dword-aligned at best whenever nx is no multiple of 4, so a view into a larger buffer is
+ * the same case; `keys` must be 16-byte aligned (a reference's 16 keys are stored as four 16-byte vectors),
+ * anything else is refused with EXABM4D_ERR_INVALID before a launch. */
 int exabm4d_blockmatch_dev(exabm4d_ctx* ctx, const float* vol, int nz, int ny, int nx, int batch,
                            float sigma, float c_match, const exabm4d_params* p, uint32_t* keys);
 /* The same on uint16 counts, the way exabm4d_denoise_u16_dev / _chunked_u16_dev match in stage 1.
@@ -199,7 +203,9 @@ int exabm4d_blockmatch_dev(exabm4d_ctx* ctx, const float* vol, int nz, int ny, i
  * below 2^24 are exact in fp32 and equal their integer form: where c_match * sigma^2 * 512 < 2^24
  * and nx is even the tiles run in integer arithmetic (v_pk_sub_i16 + v_dot2_i32_i16, half the
  * vector-ALU cycles); the tables are bit-identical to exabm4d_blockmatch_dev on (float)vol.
- * Option "bm_int" = 0 forces the float kernels (the parity tests compare both). */
+ * Option "bm_int" = 0 forces the float kernels (the parity tests compare both).
+ * Pointers: `vol` needs its natural (2-byte) alignment only (it is read once, by the exabm4d_counts_from_u16_dev
+ * stream, into the library's own buffers); `keys` as for exabm4d_blockmatch_dev. */
 int exabm4d_blockmatch_u16_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, int ny, int nx, int batch,
                                float sigma, float c_match, const exabm4d_params* p, uint32_t* keys);
 /* Host decode of one reference's 16 keys at grid position (rz,ry,rx) [voxels]:
@@ -215,27 +221,37 @@ int exabm4d_match_decode(const uint32_t* keys16, int rz, int ry, int rx, int ny,
  * CW = sum of rint(u 2^40) on block corners, u = 1 / max(N_kept, 1) resp. 1 / max(sum W^2, 1).  Both are
  * WRITTEN (round 4; rounds 1-3 added into them).  data_exp = E: EXABM4D_DATA_EXP_AUTO takes, per volume of
  * the batch, the exponent with max |noisy| < 2^E (what exabm4d_denoise_f32_* do); a caller that shards one
- * volume passes one value for all shards (the uint16 pipelines use EXABM4D_DATA_EXP_U16 = 17). */
+ * volume passes one value for all shards (the uint16 pipelines use EXABM4D_DATA_EXP_U16 = 17).
+ * Pointers: natural (4-byte) alignment suffices for noisy, basic, keys, num and den -- the kernels gather through
+ * dword buffer loads and write single floats; 16-byte aligned noisy and basic additionally let the Wiener stage
+ * gather from an interleaved copy (option "stage_pairvol"), which gives the same bits. */
 #define EXABM4D_DATA_EXP_AUTO INT32_MIN
 #define EXABM4D_DATA_EXP_U16 17
 int exabm4d_stage_dev(exabm4d_ctx* ctx, const float* noisy, const float* basic,
                       const uint32_t* keys, int nz, int ny, int nx, int batch, float sigma,
                       const exabm4d_params* p, int data_exp, float* num, float* den);
 /* out = num/den, then clamp to [clip_lo, clip_hi] when clip_lo <= clip_hi (np.clip,
- * data_handling.py:333); pass clip_lo > clip_hi for no clamp. */
+ * data_handling.py:333); pass clip_lo > clip_hi for no clamp.  Pointers need their natural alignment only.
+ * A NaN quotient stays NaN without a clamp and becomes clip_lo with one (fmaxf drops the NaN). */
 int exabm4d_normalize_dev(exabm4d_ctx* ctx, const float* num, const float* den, float* out,
                           size_t n, float clip_lo, float clip_hi);
 
 /* The two ends of exabm4d_denoise_u16_dev as staged calls, for callers that run the stages
  * themselves (z-slab sharding, distributed.py): out = (float)in - offset (read_counts,
- * machine_learning/data_handling.py:337-354) ... */
+ * machine_learning/data_handling.py:337-354) ...
+ * Pointer contract of the three calls below, of the exabm4d_transform_*_dev calls and of
+ * exabm4d_tile_finalize_u16_dev: every pointer needs the natural alignment of its element type only, so views
+ * into larger buffers (tensor slices) are fine; when ALL pointers of a call are 16-byte aligned the stream runs
+ * eight voxels per lane, else one -- the results are the same bits, and nothing outside [0, n) is written.
+ * NaN: the clamp is fminf(fmaxf(x, 0), 65535) and fmaxf drops a NaN, so a NaN quantises to count 0. */
 int exabm4d_counts_from_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, float* out, size_t n, float offset);
 /* ... and out = uint16(rint(clamp(num/den + offset, 0, 65535))) (np.clip of data_handling.py:333 and
  * the cast of IntensityTransform.inverse, transforms.py:168-171). */
 int exabm4d_normalize_u16_dev(exabm4d_ctx* ctx, const float* num, const float* den, uint16_t* out,
                               size_t n, float offset);
 /* What stage 2 of the uint16 pipelines matches on: the basic estimate as the counts a uint16
- * caller would see, out = (float)rint(clamp(in + offset, 0, 65535)) - offset; in / out may alias.  For callers
+ * caller would see, out = (float)rint(clamp(in + offset, 0, 65535)) - offset (a NaN gives -offset); in / out may
+ * alias (in == out).  For callers
  * that run the stages themselves: exabm4d_blockmatch_dev on `out`, exabm4d_stage_dev on the unrounded `in`. */
 int exabm4d_round_counts_f32_dev(exabm4d_ctx* ctx, const float* in, float* out, size_t n, float offset);
 
@@ -374,7 +390,10 @@ int exabm4d_halo_exchange_dev(exabm4d_ctx* ctx, exabm4d_comm* comm, int lo_peer,
  * synchronisation): the barrier + MAX that brackets a timed region (bench.py) without torch.distributed. */
 int exabm4d_comm_max_f64_host(exabm4d_ctx* ctx, exabm4d_comm* comm, double* value);
 
-/* ---- intensity transforms (a-D, a-E) ------------------------------------------------------- */
+/* ---- intensity transforms (a-D, a-E) -------------------------------------------------------
+ * Pointers: natural alignment suffices, 16-byte alignment of both selects the vector path (see
+ * exabm4d_counts_from_u16_dev); the uint16 forward of an asinh transform on n >= 2^20 voxels goes through a
+ * 65536-entry table on either path. */
 int exabm4d_transform_forward_u16_dev(exabm4d_ctx* ctx, const exabm4d_transform* t,
                                       const uint16_t* in, float* out, size_t n);
 int exabm4d_transform_forward_f32_dev(exabm4d_ctx* ctx, const exabm4d_transform* t,
@@ -396,7 +415,8 @@ int exabm4d_tile_gather_dev(exabm4d_ctx* ctx, const float* vol, int nz, int ny, 
 int exabm4d_tile_accumulate_dev(exabm4d_ctx* ctx, const float* preds, const int32_t* starts,
                                 int nb, int patch, int trim, float* accum_pred, float* accum_wgt,
                                 int nz, int ny, int nx);
-/* out = transform.inverse(accum_pred / (accum_wgt + 1e-8f)) (inference.py:113-116). */
+/* out = transform.inverse(accum_pred / (accum_wgt + 1e-8f)) (inference.py:113-116).  Pointers: natural alignment
+ * suffices, 16-byte alignment of all three selects the vector path (see exabm4d_counts_from_u16_dev). */
 int exabm4d_tile_finalize_u16_dev(exabm4d_ctx* ctx, const exabm4d_transform* t,
                                   const float* accum_pred, const float* accum_wgt, uint16_t* out,
                                   size_t n);
@@ -426,7 +446,8 @@ int exabm4d_dctq_forward_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, int 
 int exabm4d_dctq_inverse_dev(exabm4d_ctx* ctx, const int32_t* idx, int nz, int ny, int nx, float q,
                              uint16_t* vol);
 /* Symbol histogram of n quantisation indices for an escape-coded rate estimate: bin v + 32768
- * for -32767 <= v <= 32767, bin 0 (the escape symbol) for everything else.  hist_host[65536]. */
+ * for -32767 <= v <= 32767, bin 0 (the escape symbol) for everything else.  hist_host[65536].  idx needs
+ * 4-byte alignment only; a 16-byte aligned idx is read four indices per load. */
 int exabm4d_i32_symbol_histogram_dev(exabm4d_ctx* ctx, const int32_t* idx, size_t n,
                                      uint64_t* hist_host);
 
@@ -520,11 +541,12 @@ int exabm4d_u16_histogram_dev(exabm4d_ctx* ctx, const uint16_t* vol, size_t n, u
  * data a 65536-bin histogram cannot hold -- np.percentile of float predictions and
  * np.median(|raw - median|) in machine_learning/metrics.py:375-377,413-415.  Pass `digit`
  * (0 = most significant .. 3) counts that digit of the elements whose higher digits equal
- * `prefix`.  hist_host[65536]. */
+ * `prefix`.  hist_host[65536].  vol needs the natural alignment of its element type only. */
 int exabm4d_key_histogram_dev(exabm4d_ctx* ctx, const void* vol, int dtype, size_t n, int absdev,
                               double center, int digit, uint64_t prefix, uint64_t* hist_host);
 
-/* min and max of n elements -> out_host[2] (data range of ssim3D, utils/img_util.py:985-988). */
+/* min and max of n elements -> out_host[2] (data range of ssim3D, utils/img_util.py:985-988).  A NaN among the
+ * elements makes both NaN, as np.min / np.max do.  vol needs the natural alignment of its element type only. */
 int exabm4d_minmax_dev(exabm4d_ctx* ctx, const void* vol, int dtype, size_t n, double* out_host);
 
 /* Absolute-error statistics split by a foreground mask (uint8, non-zero = foreground; NULL = all
@@ -532,7 +554,9 @@ int exabm4d_minmax_dev(exabm4d_ctx* ctx, const void* vol, int dtype, size_t n, d
  * foreground voxels, background voxels with pred > thr, max pred, max ref, max |pred-ref| }.  Replaces the
  * numpy passes of foreground_background_mae / false_bright_rate / mip_max_error
  * (machine_learning/metrics.py:306-381) and compute_mae / compute_lmax's reductions
- * (utils/img_util.py).  Sums are fp64; integer-valued inputs give exact results. */
+ * (utils/img_util.py).  Sums are fp64; integer-valued inputs give exact results.  The comparison with thr is
+ * strict.  A NaN in pred (ref) makes max pred (max ref) and max |pred-ref| NaN, like np.max, and the sum of its
+ * side NaN.  pred, ref and mask need the natural alignment of their element types only. */
 int exabm4d_masked_error_stats_dev(exabm4d_ctx* ctx, const void* pred, int pred_dtype,
                                    const void* ref, int ref_dtype, const uint8_t* mask, size_t n,
                                    double thr, double* out_host);
@@ -540,7 +564,8 @@ int exabm4d_masked_error_stats_dev(exabm4d_ctx* ctx, const void* pred, int pred_
 /* Sum over all voxels of the SSIM map of two volumes of the same element type, cubic uniform
  * window of `window` voxels (1..32; window i - window/2 .. i + window - window/2 - 1 per axis,
  * scipy.ndimage.uniform_filter's "reflect" boundary), constants c1 = (0.01 L)^2, c2 = (0.03 L)^2
- * supplied by the caller: ssim3D of utils/img_util.py:953-1003 is *sum_host / (nz ny nx). */
+ * supplied by the caller: ssim3D of utils/img_util.py:953-1003 is *sum_host / (nz ny nx).  a and b need the
+ * natural alignment of their element type only. */
 int exabm4d_ssim3d_dev(exabm4d_ctx* ctx, const void* a, const void* b, int dtype, int nz, int ny,
                        int nx, int window, double c1, double c2, double* sum_host);
 

@@ -586,3 +586,46 @@ def test_stage_tile_order_option_changes_nothing_but_the_order(ctx):
             np.testing.assert_array_equal(denoise_volume(vol, SIGMA, 37.0), want, err_msg=f"stage_strip {n}")
     finally:
         ctx.set_option("stage_strip", 3)
+
+
+def test_staged_entry_points_accept_views_offset_by_one_element(ctx, oracle):
+    """include/exabm4d.h: the volumes of exabm4d_blockmatch_dev / _u16_dev / exabm4d_stage_dev (and num / den)
+    need their natural alignment only.  Every volume sits one element past 16-byte alignment inside a larger
+    buffer: the same bits as the oracle, nothing written around num / den.  The match table must be 16-byte
+    aligned; one that is not is refused before any launch."""
+    from util import GuardedView
+    shape = (24, 28, 32)                       # a multiple of 4 voxels: the Wiener stage may interleave
+    noisy, _ = synth_volume(shape, seed=31)
+    u16 = synth_volume(shape, seed=32, as_u16=True)[0]
+    basic = oracle.bm4d(noisy, SIGMA, stages=1)
+    g = [len(_native.grid_positions(n)) for n in shape]
+    nkeys = g[0] * g[1] * g[2] * 16
+    views = [GuardedView(ctx, np.float32, noisy.size, 1, noisy), GuardedView(ctx, np.uint16, u16.size, 1, u16),
+             GuardedView(ctx, np.float32, noisy.size, 1, basic), GuardedView(ctx, np.uint32, nkeys, 0),
+             GuardedView(ctx, np.float32, noisy.size, 1), GuardedView(ctx, np.float32, noisy.size, 1)]
+    v_noisy, v_u16, v_basic, v_keys, v_num, v_den = views
+    try:
+        want = oracle.blockmatch(noisy, SIGMA, 3.0)
+        ctx.blockmatch(v_noisy.ptr, shape, SIGMA, 3.0, v_keys.ptr)
+        ctx.sync()
+        v_keys.check_output(want, "blockmatch on a float view")
+        ctx.blockmatch_u16(v_u16.ptr, shape, SIGMA, 3.0, v_keys.ptr)
+        ctx.sync()
+        v_keys.check_output(oracle.blockmatch(u16.astype(np.float32), SIGMA, 3.0), "blockmatch on a uint16 view")
+        for b, vb, c_match in ((None, None, 3.0), (basic, v_basic, 0.6)):
+            keys = oracle.blockmatch(noisy if b is None else b, SIGMA, c_match)
+            v_keys.buf.upload(np.concatenate([v_keys.host[:v_keys.lo], keys.reshape(-1).view(np.uint8),
+                                              v_keys.host[v_keys.hi:]]))
+            num_w, den_w = oracle.stage(noisy, keys, SIGMA, basic=b)
+            ctx.stage(v_noisy.ptr, vb.ptr if vb else None, v_keys.ptr, shape, SIGMA, v_num.ptr, v_den.ptr)
+            ctx.sync()
+            v_num.check_output(num_w, "stage numerator on views")
+            v_den.check_output(den_w, "stage denominator on views")
+        for v in (v_noisy, v_u16, v_basic):
+            v.check_untouched("staged entry points")
+        for call in (ctx.blockmatch, ctx.blockmatch_u16):
+            with pytest.raises(ValueError, match="16-byte aligned"):
+                call(v_noisy.ptr if call == ctx.blockmatch else v_u16.ptr, shape, SIGMA, 3.0, v_keys.ptr + 4)
+    finally:
+        for v in views:
+            v.free()

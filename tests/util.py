@@ -51,6 +51,45 @@ def metric_inputs(seed, shape=(40, 36, 44)):
     return pred_u16, pred_f32, raw, target, fg
 
 
+class GuardedView:
+    """`n` elements of `dtype` at element offset `k` inside a larger DeviceBuffer, with a guard band of
+    `guard` bytes (a multiple of 16, so k = 0 is 16-byte aligned) on both sides; every byte that is not
+    data holds `fill`.  ``ptr`` is what a kernel is handed; ``check_output`` / ``check_untouched`` download
+    the WHOLE buffer, so a store outside [0, n) of the view shows wherever it lands."""
+
+    def __init__(self, ctx, dtype, n, k=0, data=None, guard=256, fill=0xA5):
+        self.dtype, self.n = np.dtype(dtype), int(n)
+        assert guard % 16 == 0
+        self.lo = guard + int(k) * self.dtype.itemsize
+        self.hi = self.lo + self.n * self.dtype.itemsize
+        self.host = np.full(self.hi + self.dtype.itemsize * 8 + guard, fill, dtype=np.uint8)
+        if data is not None:
+            data = np.ascontiguousarray(data, dtype=self.dtype).reshape(-1)
+            assert data.size == self.n
+            self.host[self.lo:self.hi] = data.view(np.uint8)
+        self.buf = ctx.to_device(self.host)
+        assert self.buf.ptr % 16 == 0
+        self.ptr = self.buf.ptr + self.lo
+
+    def _download(self):
+        return self.buf.download(self.host.shape, np.uint8)
+
+    def check_output(self, want, what=""):
+        """The view equals `want` exactly and every byte around it is as uploaded."""
+        got = self._download()
+        want = np.ascontiguousarray(want, dtype=self.dtype).reshape(-1)
+        assert want.size == self.n
+        np.testing.assert_array_equal(got[self.lo:self.hi].view(self.dtype), want, err_msg=f"{what}: values")
+        np.testing.assert_array_equal(got[:self.lo], self.host[:self.lo], err_msg=f"{what}: bytes before the view")
+        np.testing.assert_array_equal(got[self.hi:], self.host[self.hi:], err_msg=f"{what}: bytes after the view")
+
+    def check_untouched(self, what=""):
+        np.testing.assert_array_equal(self._download(), self.host, err_msg=f"{what}: an input was written")
+
+    def free(self):
+        self.buf.free()
+
+
 @contextlib.contextmanager
 def socket_dir(tmp_path, room=0):
     """A directory for the broker's AF_UNIX socket (plus `room` bytes of sub-directories): tmp_path when the
