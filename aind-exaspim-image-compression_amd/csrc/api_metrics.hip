@@ -190,6 +190,9 @@ int exabm4d_segment_stats_dev(exabm4d_ctx* ctx, const void* labels, int label_dt
     for (int i = 0; i < n_items; i++)
         if (item_patch_host[i] < 0 || item_patch_host[i] >= batch)
             return fail(ctx, EXABM4D_ERR_INVALID, "item patch index out of range");
+    for (int i = 0; i < n_items; i++)
+        if (item_key_host[i] == 0)   // the kernels' key of every background voxel
+            return fail(ctx, EXABM4D_ERR_INVALID, "item key 0 is the background, not a segment");
     if (n_items == 0) return EXABM4D_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t ob = (size_t)n_items * SEG_STATS_K * sizeof(double);

@@ -4,7 +4,8 @@
 //
 //   fg_threshold_kernel   per-patch median and MAD by an exact radix selection on order-preserving
 //                         fp32 keys, then thr = med + k * (1.4826 * mad), every step in fp32 like
-//                         make_foreground_mask (metrics.py:55-59).  One workgroup per patch.
+//                         make_foreground_mask (metrics.py:55-59); NaN wherever numpy's medians are
+//                         NaN (a NaN voxel, an infinite median).  One workgroup per patch.
 //   dilate_kernel         one iteration of scipy.ndimage.binary_dilation with the 6-neighbour cross
 //                         and border_value 0; the first iteration can read raw > thr[b] instead of
 //                         a mask (the threshold fused into the first pass).
@@ -51,11 +52,14 @@ struct AbsDev {
 
 // The keys of ranks r[0] and r[1] (0-based, ascending) of f(0 .. n-1): four passes of 8-bit digits,
 // both ranks at once.  hist: SEL_W per-wave sub-histograms of 2 x 256 counters, then 2 x 256 totals.
+// Returns whether some f(i) is NaN (the same for every thread): a NaN has a key like any other value and
+// would be ranked as an extreme, where numpy's median of such data is NaN.
 template <class F>
-__device__ void radix_select2(F f, size_t n, const uint32_t (&rank)[2], uint32_t* hist,
+__device__ bool radix_select2(F f, size_t n, const uint32_t (&rank)[2], uint32_t* hist,
                               uint32_t* state /* [4]: prefix 0, 1, remaining rank 0, 1 */,
                               uint32_t (&key)[2]) {
     const int tid = threadIdx.x, wave = tid / 64, lane = tid % 64;
+    bool nan = false;
     if (tid == 0) {
         state[0] = state[1] = 0u;
         state[2] = rank[0];
@@ -71,7 +75,9 @@ __device__ void radix_select2(F f, size_t n, const uint32_t (&rank)[2], uint32_t
             const size_t i = base + tid;
             uint32_t b0 = SEL_NONE, b1 = SEL_NONE;
             if (i < n) {
-                const uint32_t k = f32_key(f(i));
+                const float v = f(i);
+                if (pass == 0) nan |= v != v;
+                const uint32_t k = f32_key(v);
                 const uint32_t hi = pass == 0 ? 0u : (k >> (shift + 8));
                 const uint32_t d = (k >> shift) & 255u;
                 if (hi == pre0) b0 = d;
@@ -113,7 +119,7 @@ __device__ void radix_select2(F f, size_t n, const uint32_t (&rank)[2], uint32_t
     }
     key[0] = state[0];
     key[1] = state[1];
-    __syncthreads();
+    return __syncthreads_or(nan) != 0;
 }
 
 // numpy's median of float32 data: the middle value, or the float32 mean of the two middle values
@@ -131,13 +137,14 @@ __global__ __launch_bounds__(SEL_T) void fg_threshold_kernel(const T* __restrict
     const bool even = (n % 2) == 0;
     const uint32_t rank[2] = {(uint32_t)(even ? n / 2 - 1 : n / 2), (uint32_t)(n / 2)};
     uint32_t key[2];
-    radix_select2(RawVal<T>{p}, n, rank, hist, state, key);
+    bool nan = radix_select2(RawVal<T>{p}, n, rank, hist, state, key);
     const float med = median_of(key, even);
-    radix_select2(AbsDev<T>{p, med}, n, rank, hist, state, key);
+    // an infinite median makes |raw - med| NaN where raw equals it, as in numpy: caught here as well
+    nan |= radix_select2(AbsDev<T>{p, med}, n, rank, hist, state, key);
     const float mad = median_of(key, even) + (float)1e-6;   // numpy rounds the Python floats to fp32
     const float sigma = (float)1.4826 * mad;
     const float ks = k * sigma;
-    if (threadIdx.x == 0) thr[blockIdx.x] = med + ks;
+    if (threadIdx.x == 0) thr[blockIdx.x] = nan ? __uint_as_float(0x7FC00000u) : med + ks;
 }
 
 hipError_t launch_fg_threshold(const void* raw, int dtype, int batch, size_t n, float k, float* thr,
@@ -288,20 +295,26 @@ __device__ __forceinline__ uint32_t ls_hash(unsigned long long k) {
 
 // Insert c voxels of key k.  A new key is refused once LS_MAX keys are held (the check races, so up to
 // LS_T - 1 more may land: the table has 2 * LS_MAX slots and the caller flags any excess); false = refused.
+// `used` is raised after a claim, so once it reads LS_MAX the slots of LS_MAX keys are visible: a slot seen
+// empty before that is read again, since the thread that filled the set may have claimed it for this very key.
 __device__ bool ls_insert(unsigned long long* keys, uint32_t* counts, uint32_t* used, unsigned long long k,
                           uint32_t c) {
     uint32_t h = ls_hash(k);
     for (int probe = 0; probe < LS_SLOTS; probe++, h = (h + 1) & (LS_SLOTS - 1)) {
-        const unsigned long long cur = *(volatile unsigned long long*)&keys[h];
+        unsigned long long cur = *(volatile unsigned long long*)&keys[h];
         if (cur == 0ull) {
-            if (*(volatile uint32_t*)used >= (uint32_t)LS_MAX) return false;
-            const unsigned long long prev = atomicCAS(&keys[h], 0ull, k);
-            if (prev == 0ull) atomicAdd(used, 1u);
-            if (prev == 0ull || prev == k) {
-                atomicAdd(&counts[h], c);
-                return true;
+            if (*(volatile uint32_t*)used < (uint32_t)LS_MAX) {
+                cur = atomicCAS(&keys[h], 0ull, k);
+                if (cur == 0ull) {
+                    atomicAdd(used, 1u);
+                    cur = k;
+                }
+            } else {
+                cur = *(volatile unsigned long long*)&keys[h];
+                if (cur == 0ull) return false;
             }
-        } else if (cur == k) {
+        }
+        if (cur == k) {
             atomicAdd(&counts[h], c);
             return true;
         }

@@ -582,7 +582,9 @@ enum { EXABM4D_LBL_U8 = 0, EXABM4D_LBL_U32 = 1, EXABM4D_LBL_U64 = 2, EXABM4D_LBL
 /* make_foreground_mask of every patch (machine_learning/metrics.py:32-62): per patch, med =
  * median(raw) and mad = median(|raw - med|) + 1e-6 by an exact radix selection, thr = med +
  * k * (1.4826 * mad), every step rounded to fp32 as numpy does; mask = raw > thr, then `dilate`
- * iterations of scipy.ndimage.binary_dilation (6-neighbour cross, border 0).  raw: dtype
+ * iterations of scipy.ndimage.binary_dilation (6-neighbour cross, border 0).  NaN propagates as in
+ * numpy: a patch that holds a NaN, or whose median is infinite (|raw - med| then holds one), has a
+ * NaN threshold and an empty mask; other patches of the batch are not affected.  raw: dtype
  * EXABM4D_DT_U16 or EXABM4D_DT_F32; mask: batch * nz * ny * nx bytes (0 / 1) on the device;
  * thr_host: NULL or `batch` floats. */
 int exabm4d_foreground_masks_dev(exabm4d_ctx* ctx, const void* raw, int dtype, int batch, int nz, int ny,
@@ -613,7 +615,8 @@ int exabm4d_label_set_dev(exabm4d_ctx* ctx, const void* labels, int label_dtype,
 
 /* Segment statistics for local_autocorr / highfreq_energy_fraction (metrics.py:65-158), one item
  * per (patch item_patch_host[i], label item_key_host[i]); a voxel belongs to the segment when its
- * label equals the key (signed labels <= 0 never do).  Two passes, the second centred on the means
+ * label equals the key; labels <= 0 never belong to a segment, and an item key of 0 is refused with
+ * EXABM4D_ERR_INVALID.  Two passes, the second centred on the means
  * of the first; out_host[i * EXABM4D_SEG_STATS_K + .] = { n, mean raw, mean (raw - smooth), sum
  * (raw - mean)^2, sum (raw - smooth - mean)^2, then for axes 0, 1, 2: pairs (v, v + lag along the
  * axis) with both voxels in the segment, mean x = raw[v], mean y = raw[v + lag], Sxx, Syy, Sxy
