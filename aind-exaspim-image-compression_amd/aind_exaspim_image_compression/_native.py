@@ -30,6 +30,8 @@ KEY_EMPTY = 0xFFFFFFFF
 LABEL_SET_MAX = 1024        # exabm4d.h EXABM4D_LABEL_SET_MAX: distinct labels one patch's device set holds
 SEG_STATS_K = 23            # exabm4d.h EXABM4D_SEG_STATS_K
 GAUSS_MAX_RADIUS = 64       # exabm4d.h EXABM4D_GAUSS_MAX_RADIUS
+NOISE_LEVELS = 49           # exabm4d.h EXABM4D_NOISE_LEVELS
+NOISE_BINS = 4096           # exabm4d.h EXABM4D_NOISE_BINS
 # exabm4d.h label element types
 LABEL_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.uint32): 1, np.dtype(np.uint64): 2,
                 np.dtype(np.int32): 3, np.dtype(np.int64): 4}
@@ -167,6 +169,7 @@ SIGNATURES = {
                                             ctypes.c_double, c_vp]),
     "exabm4d_ssim3d_dev": (_I, [_CTX, c_vp, c_vp, _I, _I, _I, _I, _I, ctypes.c_double,
                                 ctypes.c_double, c_vp]),
+    "exabm4d_noise_table_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp, c_vp, c_vp]),
     "exabm4d_foreground_masks_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, _F, _I, c_vp, c_vp]),
     "exabm4d_binary_dilate_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp]),
     "exabm4d_gaussian_filter3d_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp, _I, c_vp]),
@@ -681,6 +684,22 @@ class Context:
                                              self.DTYPES[np.dtype(dtype)], nz, ny, nx, int(window),
                                              float(c1), float(c2), out.ctypes.data_as(c_vp)))
         return float(out[0])
+
+    # -- noise table -----------------------------------------------------------
+    def noise_table(self, vol, dtype, shape, shift=0):
+        """(hist[NOISE_LEVELS, NOISE_BINS], sum_s[NOISE_LEVELS], skipped) of a uint16 or float32 volume of
+        ``shape`` (nz, ny, nx) resident in HBM."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.uint16), np.dtype(np.float32)):
+            raise ValueError("noise_table: the volume must be uint16 or float32")
+        hist = np.empty((NOISE_LEVELS, NOISE_BINS), dtype=np.uint64)
+        sum_s = np.empty(NOISE_LEVELS, dtype=np.uint64)
+        skipped = np.empty(1, dtype=np.uint64)
+        nz, ny, nx = shape
+        self._check(lib().exabm4d_noise_table_dev(
+            self.handle, _ptr(vol), self.DTYPES[dt], int(nz), int(ny), int(nx), int(shift),
+            hist.ctypes.data_as(c_vp), sum_s.ctypes.data_as(c_vp), skipped.ctypes.data_as(c_vp)))
+        return hist, sum_s, int(skipped[0])
 
     # -- patch-cache masks and coherence gate (DESIGN.md 5.8); batches of (nz, ny, nx) patches --
     def foreground_masks(self, raw, dtype, batch, shape, k, dilate, mask):

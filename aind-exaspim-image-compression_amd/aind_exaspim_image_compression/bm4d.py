@@ -79,17 +79,28 @@ def _stages(stage_arg):
     raise ValueError(f"unknown stage_arg: {stage_arg!r}")
 
 
+def _sigma(sigma, vol, device=None, **resident):
+    """``sigma`` as a float.  The string "auto" is measured from ``vol`` on the device (``utils/noise.py``:
+    Donoho's pooled estimator on the Haar HHH detail of 2x2x2 cells) -- here, at the top of the
+    call, so that only floats travel to the broker and to worker processes."""
+    if not isinstance(sigma, str):
+        return float(np.asarray(sigma).reshape(-1)[0])
+    from aind_exaspim_image_compression.utils import noise
+    return noise.resolve_sigma(sigma, vol, device=device, **resident)
+
+
 def bm4d(z, sigma_psd, profile=None, stage_arg=None, device=None):
     """Denoise a 3-D volume (or a 4-D batch of volumes) with two-stage BM4D.
 
     ``z``: array of counts, any real dtype (computed in float32, like the reference's patches:
-    data_handling.py:353); ``sigma_psd``: noise standard deviation in the same units.  Returns a
+    data_handling.py:353); ``sigma_psd``: noise standard deviation in the same units, or "auto" for
+    ``utils.noise.estimate_sigma(z)`` (one value for the whole batch).  Returns a
     new float32 array of the same shape, NOT clipped (the reference clips at its call site,
     data_handling.py:333)."""
     arr = np.asarray(z)
     if arr.ndim not in (3, 4):
         raise ValueError("bm4d expects a 3-D volume or a 4-D batch of volumes")
-    sigma = float(np.asarray(sigma_psd).reshape(-1)[0])
+    sigma = _sigma(sigma_psd, arr, device)
     prof = profile or BM4DProfile()
     return _denoise_batched(device, arr.astype(np.float32, copy=False), sigma, prof.native(),
                             _stages(stage_arg), None)
@@ -130,11 +141,13 @@ def denoise_patches(raw, sigma, max_count=65535.0, profile=None, device=None, de
     method: nothing is forked after HIP has been initialised, and this process never touches a GPU for the
     call); the patches travel through shared memory and come back in order.  Patches are independent units
     (no halo, no collective) and each carries its own fixed-point unit, so the result equals the
-    single-device call bit for bit."""
+    single-device call bit for bit.  ``sigma="auto"`` is measured in THIS process (on ``device``, or the default
+    one) before the batch is cut: the shares only ever see the float."""
     raw = np.asarray(raw, dtype=np.float32)
     if raw.ndim == 3:
         raw = raw[None]
     prof = profile or BM4DProfile()
+    sigma = _sigma(sigma, raw, device)      # "auto": measured once, over the whole batch, before any split
     if devices is None:
         return _denoise_batched(device, raw, float(sigma), prof.native(), 2, (0.0, float(max_count)))
     if device is not None:
@@ -171,7 +184,8 @@ def denoise_volume(vol_u16, sigma, offset=0.0, profile=None, stages=2, device=No
     """uint16 volume -> uint16 volume: ``(float)v - offset`` -> BM4D -> ``+ offset`` -> clip to
     [0, 65535] -> rint -> uint16, entirely on the device (read_counts + bm4d + clip + the
     rint/uint16 cast of IntensityTransform.inverse).  The uint16 form matches its second stage on the basic
-    estimate rounded to counts: both matching passes are 16-bit integer work."""
+    estimate rounded to counts: both matching passes are 16-bit integer work.  ``sigma="auto"``
+    measures it on the uploaded volume (``utils.noise.estimate_sigma``)."""
     vol = np.ascontiguousarray(vol_u16, dtype=np.uint16)
     if vol.ndim != 3:
         raise ValueError("denoise_volume expects a 3-D uint16 volume")
@@ -180,6 +194,7 @@ def denoise_volume(vol_u16, sigma, offset=0.0, profile=None, stages=2, device=No
     d_in = ctx.to_device(vol)
     d_out = ctx.alloc(vol.nbytes)
     try:
+        sigma = _sigma(sigma, d_in, shape=vol.shape, dtype=np.uint16)
         ctx.denoise_u16(d_in, d_out, vol.shape, float(sigma), float(offset), params=prof.native(),
                         stages=int(stages))
         ctx.sync()
@@ -197,7 +212,8 @@ def denoise_chunked(vol_u16, sigma, offset=0.0, chunk=256, halo=8, profile=None,
     "edge clamping" is read as clamping the window, and the oracle processes the identical
     truncated arrays) -- and denoised in isolation -- independent units, like the reference's one-``bm4d``-call-per-patch
     pool (scripts/precompute.py:215-228) -- and only the cores are written.  One batched device
-    call (``exabm4d_denoise_chunked_u16_dev``); uint16 in, uint16 out."""
+    call (``exabm4d_denoise_chunked_u16_dev``); uint16 in, uint16 out.  ``sigma="auto"`` measures it once on the
+    uploaded volume, not per chunk."""
     vol = np.ascontiguousarray(vol_u16, dtype=np.uint16)
     if vol.ndim != 3:
         raise ValueError("denoise_chunked expects a 3-D uint16 volume")
@@ -206,6 +222,7 @@ def denoise_chunked(vol_u16, sigma, offset=0.0, chunk=256, halo=8, profile=None,
     d_in = ctx.to_device(vol)
     d_out = ctx.alloc(vol.nbytes)
     try:
+        sigma = _sigma(sigma, d_in, shape=vol.shape, dtype=np.uint16)
         ctx.denoise_chunked_u16(d_in, d_out, vol.shape, float(sigma), float(offset),
                                 chunk=int(chunk), halo=int(halo), params=prof.native(),
                                 stages=int(stages))

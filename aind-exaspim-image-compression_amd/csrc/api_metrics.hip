@@ -81,6 +81,31 @@ int exabm4d_ssim3d_dev(exabm4d_ctx* ctx, const void* a, const void* b, int dtype
     return fetch(ctx, sum_host, d, sizeof(double));
 }
 
+// ---- noise table ---------------------------------------------------------------------
+static_assert(NOISE_LEVELS == EXABM4D_NOISE_LEVELS && NOISE_BINS == EXABM4D_NOISE_BINS,
+              "exabm4d.h and exabm4d_kernels.h differ");
+
+int exabm4d_noise_table_dev(exabm4d_ctx* ctx, const void* vol, int dtype, int nz, int ny, int nx, int shift,
+                            uint64_t* hist_host, uint64_t* sum_s_host, uint64_t* skipped_host) {
+    if (!ctx || !vol || !hist_host || !sum_s_host || !skipped_host)
+        return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (dtype != EXABM4D_DT_U16 && dtype != EXABM4D_DT_F32)
+        return fail(ctx, EXABM4D_ERR_INVALID, "vol must be uint16 or float32");
+    if (shift < 0 || shift > 6) return fail(ctx, EXABM4D_ERR_INVALID, "shift must be 0..6");
+    if (nz < 2 || ny < 2 || nx < 2) return fail(ctx, EXABM4D_ERR_INVALID, "every extent must be >= 2");
+    if ((long long)nz * ny * nx > (1ll << 40) || (long long)(nz / 2) * (ny / 2) >= (1ll << 31))
+        return fail(ctx, EXABM4D_ERR_INVALID, "volume too large");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = grow(ctx, ctx->red, noise_table_bytes())) return rc;
+    unsigned long long* d = ctx->red.as<unsigned long long>();
+    if (!ctx->noise_wgs) HIP_TRY(ctx, noise_table_prepare(ctx->device, &ctx->noise_wgs));
+    HIP_TRY(ctx, launch_noise_table(vol, dtype, nz, ny, nx, shift, ctx->noise_wgs, d, ctx->stream));
+    const size_t nh = (size_t)NOISE_LEVELS * NOISE_BINS;
+    HIP_TRY(ctx, hipMemcpyAsync(hist_host, d, nh * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(sum_s_host, d + nh, NOISE_LEVELS * 8, hipMemcpyDeviceToHost, ctx->stream));
+    return fetch(ctx, skipped_host, d + nh + NOISE_LEVELS, 8);
+}
+
 // ---- patch-cache foreground masks and coherence gate ---------------------------------
 static int check_patches(exabm4d_ctx* ctx, int batch, int nz, int ny, int nx) {
     if (batch < 1 || nz < 1 || ny < 1 || nx < 1) return fail(ctx, EXABM4D_ERR_INVALID, "bad batch / sizes");

@@ -91,6 +91,7 @@ struct exabm4d_ctx {
     exabm4d::DevBuf rcp_dev;   // chunk coder: reciprocal table, [4097][2]
     exabm4d::DevBuf codec_aux; // chunk coder: sizes / offsets / totals / status
     exabm4d::DevBuf red;       // metric entry points: histogram / partials / results
+    int noise_wgs = 0;         // noise table: workgroups per launch (one per CU); 0 = noise_table_prepare() not yet run
     int force_generic_bm = 0;  // exabm4d_set_option("force_generic_bm")
     int bm_guarded_copy = 0;   // exabm4d_set_option("bm_guarded_copy"): staged block matching on a guarded copy
     exabm4d::StageOpts stage;  // exabm4d_set_option("stage_pairvol" / "stage_strip" / "stage_chunks")

@@ -55,6 +55,15 @@ hipError_t launch_masked_stats(const void* pred, int pred_dtype, const void* ref
                                double* out7, hipStream_t s);
 hipError_t launch_minmax(const void* a, int dtype, size_t n, double* partials, double* out2,
                          hipStream_t s);
+// ---- noise table (noise_kernels.hip) ----
+constexpr int NOISE_LEVELS = 49;    // quarter-octave levels of the cell mean (exabm4d.h EXABM4D_NOISE_LEVELS)
+constexpr int NOISE_BINS = 4096;    // bins of |d| >> shift per level (exabm4d.h EXABM4D_NOISE_BINS)
+size_t noise_table_bytes();         // hist[NOISE_LEVELS][NOISE_BINS], sum_s[NOISE_LEVELS], skipped: 64-bit each
+// once per device, on the current device: raises the kernels' LDS limit; *wgs = workgroups to launch (one per CU)
+hipError_t noise_table_prepare(int device, int* wgs);
+// dtype 0 uint16, 1 float32; (nz / 2) * (ny / 2) < 2^31; table: noise_table_bytes() on the device, zeroed here
+hipError_t launch_noise_table(const void* vol, int dtype, int nz, int ny, int nx, int shift, int wgs,
+                              unsigned long long* table, hipStream_t s);
 int ssim3d_partials(int nz, int ny, int nx);
 int ssim3d_max_window();
 hipError_t launch_ssim3d(const void* a, const void* b, int dtype, int nz, int ny, int nx, int w,

@@ -569,6 +569,27 @@ int exabm4d_masked_error_stats_dev(exabm4d_ctx* ctx, const void* pred, int pred_
 int exabm4d_ssim3d_dev(exabm4d_ctx* ctx, const void* a, const void* b, int dtype, int nz, int ny,
                        int nx, int window, double c1, double c2, double* sum_host);
 
+/* ---- noise table: sigma and Poisson-Gaussian parameters from the data -------------- */
+#define EXABM4D_NOISE_LEVELS 49       /* quarter-octave intensity levels of exabm4d_noise_table_dev */
+#define EXABM4D_NOISE_BINS 4096       /* magnitude bins per level of exabm4d_noise_table_dev */
+
+/* One pass over a volume resident in HBM, cut into 2x2x2 cells at even coordinates (an odd trailing plane,
+ * row or column is ignored; every extent >= 2).  Per cell s = the sum of its voxels v[dz][dy][dx] and d = the
+ * sum of (-1)^(dz+dy+dx) v (the unnormalised Haar HHH detail; Var d = 8 sigma^2 for i.i.d. noise).  The level
+ * is the quarter-octave bin of the cell mean: t = (s >> 3) + 16, e = floor(log2 t), level = 4 (e - 4) +
+ * ((t >> (e - 2)) & 3), 0 .. 48; the cell counts in hist_host[level][min(|d| >> shift, EXABM4D_NOISE_BINS - 1)]
+ * and adds s to sum_s_host[level].  shift: 0..6.  hist_host[EXABM4D_NOISE_LEVELS][EXABM4D_NOISE_BINS],
+ * sum_s_host[EXABM4D_NOISE_LEVELS] and *skipped_host are host memory; the call synchronises the context's stream.
+ * dtype EXABM4D_DT_U16: integer arithmetic throughout.  dtype EXABM4D_DT_F32 (counts minus an offset): fp32 with
+ * the fixed association s = ((v000+v001)+(v010+v011))+((v100+v101)+(v110+v111)), d = ((v000-v001)-(v010-v011))-
+ * ((v100-v101)-(v110-v111)); a cell with a non-finite s or d is not counted and adds one to *skipped_host (always
+ * 0 for uint16); otherwise s is floored and clamped to [0, 8 * 65535] and |d| is rounded half to even (|d| >= 2^24
+ * goes to the last bin), so integer-valued fp32 input in the uint16 range gives the uint16 table exactly.  All
+ * counters are integers: the table does not depend on the launch.  vol needs the natural alignment of its
+ * element type only. */
+int exabm4d_noise_table_dev(exabm4d_ctx* ctx, const void* vol, int dtype, int nz, int ny, int nx, int shift,
+                            uint64_t* hist_host, uint64_t* sum_s_host, uint64_t* skipped_host);
+
 /* ---- patch-cache foreground masks and coherence gate --
  * Batches of `batch` patches of nz x ny x nx voxels, contiguous in HBM.  Every entry point
  * synchronises the context's stream; floating-point results are deterministic (fixed mappings and
