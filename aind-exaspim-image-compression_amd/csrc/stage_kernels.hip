@@ -199,7 +199,7 @@ struct HalfGeom {
     static constexpr int PS = ((ROWS * COLS + 23) / 32) * 32 + 8;  // plane stride in elements, 8 (mod 32)
     static constexpr int NPL = NPL_;                    // ring planes: 18 live ones + slack for running
                                                         // ahead of the flush (per-block gate below)
-    static constexpr size_t LDS_FLOATS = (size_t)2 * NPL * PS + (size_t)NW * TBW + 4 + 2 * NW + 8;
+    static constexpr size_t LDS_FLOATS = (size_t)2 * NPL * PS + (size_t)NW * TBW + 4 + 2 * NW + 8 + NW;
     static_assert(NW % 2 == 0 && NW <= 16 && NPL >= 18 && NPL <= 26, "pairs of waves; at most 3 layers in flight");
     static_assert(LDS_FLOATS * sizeof(float) <= 160 * 1024, "ring + transpose buffers exceed the CU's LDS");
 };
@@ -881,6 +881,8 @@ __global__ __launch_bounds__(HalfCfg<WIENER>::NW * 64) void stage_half_kernel(
     int* lock = reinterpret_cast<int*>(lds + 2 * HNPL * HPS + HNW * C::TBW);
     int* sync = lock + 4;                                  // ready[HNW], ack[HNW]
     int* cnt = sync + 2 * HNW;                             // reports per layer (slot = layer & 7)
+    int* pub = cnt + HNCNT;                                // per pair: ticket + 1 of its current group
+    int* got = pub + HNW / 2;                              //           ... as its second wave last read it
 
     const size_t voff = (size_t)blockIdx.z * (size_t)g.nvox;
     const float* __restrict__ noisy = noisy_all + voff;
@@ -916,8 +918,8 @@ __global__ __launch_bounds__(HalfCfg<WIENER>::NW * 64) void stage_half_kernel(
     const int ize = min(g.gz, izb + layers_per_chunk);
 
     for (int i = threadIdx.x; i < 2 * HNPL * HPS; i += HNW * 64) lds[i] = 0.0f;      // (all-zero bits: the int64 ring)
-    // lock[1] = layers retired (in order); the ring itself needs no lock (fp64 LDS atomics)
-    if (threadIdx.x < 4 + 2 * HNW + HNCNT) lock[threadIdx.x] = 0;
+    // lock[0] = next ticket, lock[1] = layers retired (in order); the ring itself needs no lock (LDS atomics)
+    if (threadIdx.x < 4 + 2 * HNW + HNCNT + HNW) lock[threadIdx.x] = 0;
 
     float win[8] = {};
     if constexpr (!WIENER) {
@@ -928,6 +930,7 @@ __global__ __launch_bounds__(HalfCfg<WIENER>::NW * 64) void stage_half_kernel(
     __syncthreads();
 
     const int pairid = PM::pair(wave);
+    const bool leader = PM::half(wave) == 0;
     int seq = 0;
     int seen = 0;           // last value read of lock[1] (layers retired), see the per-block gate
     const Dct7& tab = T;
@@ -935,80 +938,111 @@ __global__ __launch_bounds__(HalfCfg<WIENER>::NW * 64) void stage_half_kernel(
     unsigned long long st[16] = {};
     const unsigned long long tk0 = stamp();
 #endif
-    for (int iz = izb; iz < ize; iz++) {
-        const int layer = iz - izb;
+    // The tile's groups are handed out by ticket: ticket t is group t % nrefs of layer t / nrefs, and a
+    // pair draws its next ticket when it is free, so the groups of a layer go to whichever pairs come
+    // first and no pair waits while another works off a second group.  Tickets come out in layer order:
+    // every group of a layer has been started before any group of the next one, which is what the ring
+    // protocol needs -- layers complete in order (a group waits for retired layers only, never for a
+    // later ticket), and a pair without a group in some layer, on an edge tile with fewer groups than
+    // pairs, is simply handed a later one.  The first wave of the pair draws (lock[0]) and publishes
+    // ticket + 1 in pub[pair]; the tickets of a pair only grow, so its partner waits for the word to
+    // change.  The partner of a one-block group meets nobody at an exchange and may lag a whole group
+    // behind: it acknowledges in got[pair], and the word is not written again before that.
+    const int total = (ize - izb) * nrefs;
+    int last = 0;           // ticket + 1 of the pair's previous group
+    for (;;) {
+        STAMP(th0);
+        int t = 0;
+        cbar();
+        if (leader) {
+            if (lane == 0) {
+                while (__hip_atomic_load(got + pairid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != last)
+                    __builtin_amdgcn_s_sleep(1);
+            }
+            cbar();
+            t = lane == 0 ? __hip_atomic_fetch_add(lock, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0;
+            t = __builtin_amdgcn_readfirstlane(t);
+            if (lane == 0)
+                __hip_atomic_store(pub + pairid, t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        } else {
+            if (lane == 0) {
+                while ((t = __hip_atomic_load(pub + pairid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == last)
+                    __builtin_amdgcn_s_sleep(1);
+                __hip_atomic_store(got + pairid, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            t = __builtin_amdgcn_readfirstlane(t) - 1;
+        }
+        cbar();
+        last = t + 1;
+        STAMP(th1);
+        STAMP_ADD(6, th0, th1);
+        if (t >= total) break;
+        const int layer = t / nrefs, r = t - layer * nrefs;
+        const int iz = izb + layer;
         const int z0 = grid_pos(iz, g.az, g.nz);
-        // The tile's groups go round the pairs, starting one pair further every layer, so that the
-        // extra groups rotate when they do not divide by the pairs -- but only while every pair has
-        // a group in every layer: a pair without one would skip ahead, a layer could then be
-        // complete before the one below it, and the ring protocol counts on layers completing in
-        // order (edge tiles with fewer groups than pairs keep the fixed assignment).
-        const int rot = nrefs >= HNW / 2 ? layer % (HNW / 2) : 0;
-        for (int r = (pairid + rot) % (HNW / 2); r < nrefs; r += HNW / 2) {
-            const int jy = r / tg.nrx, jx = r - jy * tg.nrx;
-            const int iy = iy0 + jy, ix = ix0 + jx;
-            const int ry = grid_pos(iy, g.ay, g.ny), rx = grid_pos(ix, g.ax, g.nx);
-            const uint32_t* kk = keys + ((size_t)((size_t)iz * g.gy + iy) * g.gx + ix) * MAXG;
+        const int jy = r / tg.nrx, jx = r - jy * tg.nrx;
+        const int iy = iy0 + jy, ix = ix0 + jx;
+        const int ry = grid_pos(iy, g.ay, g.ny), rx = grid_pos(ix, g.ax, g.nx);
+        const uint32_t* kk = keys + ((size_t)((size_t)iz * g.gy + iy) * g.gx + ix) * MAXG;
 #if EXABM4D_PRIO
-            {
-                // A wave that starts a group of the oldest open layer holds up everybody at the
-                // gate: it gets issue priority (s_setprio) over a SIMD neighbour that started its
-                // group ahead of the retired layers.  Measured -6 % on both stage kernels; raising
-                // the priority again once a wave is past the gate gives half of that back, and a
-                // purely phase-based rule (forward transforms over inverse + ring adds) is on par.
-                int f = __hip_atomic_load(lock + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                f = __builtin_amdgcn_readfirstlane(f);
-                if (layer <= f)
-                    __builtin_amdgcn_s_setprio(1);
-                else
-                    __builtin_amdgcn_s_setprio(0);
-            }
+        {
+            // A wave that starts a group of the oldest open layer holds up everybody at the
+            // gate: it gets issue priority (s_setprio) over a SIMD neighbour that started its
+            // group ahead of the retired layers.  Measured -6 % on both stage kernels; raising
+            // the priority again once a wave is past the gate gives half of that back, and a
+            // purely phase-based rule (forward transforms over inverse + ring adds) is on par.
+            int f = __hip_atomic_load(lock + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            f = __builtin_amdgcn_readfirstlane(f);
+            if (layer <= f)
+                __builtin_amdgcn_s_setprio(1);
+            else
+                __builtin_amdgcn_s_setprio(0);
+        }
 #endif
-            const bool closer = process_half_group<WIENER>(
-                noisy, basic, kk, z0, ry, rx, tg, sy, sz, tab, win, win_g, thr, sigma2, up, ring, cvol, tb,
-                partner_tb, lock, sync, cnt, wave, seq, seen, layer, 2 * nrefs, lane, g.nvox, num, g, izb, pair
+        const bool closer = process_half_group<WIENER>(
+            noisy, basic, kk, z0, ry, rx, tg, sy, sz, tab, win, win_g, thr, sigma2, up, ring, cvol, tb,
+            partner_tb, lock, sync, cnt, wave, seq, seen, layer, 2 * nrefs, lane, g.nvox, num, g, izb, pair
 #ifdef EXABM4D_STAMPS
-                , st
+            , st
 #endif
-            );
-            if (closer) {
-                // this layer's counter slot is next used eight layers on
-                if (lane == 0)
-                    __hip_atomic_store(cnt + (layer & (HNCNT - 1)), 0, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_WORKGROUP);
-                // layers retire in order: the layers below are complete (and flushed) before this
-                // one's planes leave the ring
-                if (lane == 0) {
-                    while (__hip_atomic_load(lock + 1, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_WORKGROUP) != layer)
-                        __builtin_amdgcn_s_sleep(2);
-                }
-                cbar();
-                if (iz + 1 < ize) {
-                    const int zn = grid_pos(iz + 1, g.az, g.nz);
-                    if constexpr (!WIENER && EXABM4D_HELP_FLUSH) {
-                        if (lane == 0) {
-                            __hip_atomic_store(lock + 3, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            __hip_atomic_store(lock + 2, (layer + 1) << 16, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_WORKGROUP);
-                        }
-                        cbar();
-                        while (flush_take<C>(lock, ring, num, tg, g, izb, lane)) {
-                        }
-                        if (lane == 0) {
-                            while (__hip_atomic_load(lock + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < zn - z0)
-                                __builtin_amdgcn_s_sleep(1);
-                            __hip_atomic_store(lock + 2, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        }
-                    } else {
-                        for (int z = z0 - RAD; z < zn - RAD; z++) flush_num_plane<C>(ring, num, z, tg, g, lane);
-                    }
-                }
-                cbar();
-                if (lane == 0)
-                    __hip_atomic_store(lock + 1, layer + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                cbar();
+        );
+        if (closer) {
+            // this layer's counter slot is next used eight layers on
+            if (lane == 0)
+                __hip_atomic_store(cnt + (layer & (HNCNT - 1)), 0, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+            // layers retire in order: the layers below are complete (and flushed) before this
+            // one's planes leave the ring
+            if (lane == 0) {
+                while (__hip_atomic_load(lock + 1, __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_WORKGROUP) != layer)
+                    __builtin_amdgcn_s_sleep(2);
             }
+            cbar();
+            if (iz + 1 < ize) {
+                const int zn = grid_pos(iz + 1, g.az, g.nz);
+                if constexpr (!WIENER && EXABM4D_HELP_FLUSH) {
+                    if (lane == 0) {
+                        __hip_atomic_store(lock + 3, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        __hip_atomic_store(lock + 2, (layer + 1) << 16, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                    cbar();
+                    while (flush_take<C>(lock, ring, num, tg, g, izb, lane)) {
+                    }
+                    if (lane == 0) {
+                        while (__hip_atomic_load(lock + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < zn - z0)
+                            __builtin_amdgcn_s_sleep(1);
+                        __hip_atomic_store(lock + 2, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                } else {
+                    for (int z = z0 - RAD; z < zn - RAD; z++) flush_num_plane<C>(ring, num, z, tg, g, lane);
+                }
+            }
+            cbar();
+            if (lane == 0)
+                __hip_atomic_store(lock + 1, layer + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            cbar();
         }
     }
     __syncthreads();
