@@ -78,9 +78,34 @@ class Transform(ctypes.Structure):
     ]
 
 
+class PgNoise(ctypes.Structure):
+    """``exabm4d_pg_noise`` (include/exabm4d.h): the Poisson-Gaussian model and the inverse to use."""
+
+    _fields_ = [
+        ("size", ctypes.c_uint32),
+        ("gain", ctypes.c_float),
+        ("read_noise", ctypes.c_float),
+        ("offset", ctypes.c_float),
+        ("inverse", ctypes.c_int32),
+    ]
+
+
+PG_INVERSES = {"algebraic": 0, "asymptotic": 1, "closed_form": 2}    # exabm4d.h EXABM4D_PG_INVERSE_*
+
+
+def pg_noise(gain, read_noise, offset, inverse="closed_form"):
+    """A filled ``PgNoise``; ``inverse`` by name (PG_INVERSES) or by its code.  The library validates the values."""
+    if isinstance(inverse, str):
+        if inverse not in PG_INVERSES:
+            raise ValueError("inverse must be one of %s, not %r" % (sorted(PG_INVERSES), inverse))
+        inverse = PG_INVERSES[inverse]
+    return PgNoise(ctypes.sizeof(PgNoise), float(gain), float(read_noise), float(offset), int(inverse))
+
+
 # name -> (restype, argtypes); every symbol include/exabm4d.h declares
 _CTX = c_vp
 _PP = ctypes.POINTER(Params)
+_NP = ctypes.POINTER(PgNoise)
 _TP = ctypes.POINTER(Transform)
 _I, _F, _SZ = ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 SIGNATURES = {
@@ -121,6 +146,11 @@ SIGNATURES = {
     "exabm4d_denoise_u16_dev": (_I, [_CTX, c_vp, c_vp, _I, _I, _I, _I, _F, _F, _PP, _I]),
     "exabm4d_denoise_chunked_u16_dev": (_I, [_CTX, c_vp, c_vp, _I, _I, _I, _I, _I, _I, _I, _F, _F, _PP,
                                              _I]),
+    "exabm4d_denoise_pg_u16_dev": (_I, [_CTX, c_vp, c_vp, _I, _I, _I, _I, _NP, _PP, _I]),
+    "exabm4d_denoise_pg_chunked_u16_dev": (_I, [_CTX, c_vp, c_vp, _I, _I, _I, _I, _I, _I, _I, _NP, _PP, _I]),
+    "exabm4d_denoise_pg_chunked_u16_host": (_I, [_CTX, c_vp, c_vp, _I, _I, _I, _I, _I, _NP, _PP, _I]),
+    "exabm4d_gat_forward_u16_dev": (_I, [_CTX, _NP, c_vp, c_vp, _SZ]),
+    "exabm4d_gat_inverse_u16_dev": (_I, [_CTX, _NP, c_vp, c_vp, _SZ]),
     "exabm4d_blockmatch_plan": (_I, [_CTX, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64)]),
     "exabm4d_denoise_chunked_u16_host": (_I, [_CTX, c_vp, c_vp, _I, _I, _I, _I, _I, _F, _F, _PP, _I]),
     "exabm4d_denoise_f32_host": (_I, [_CTX, c_vp, c_vp, _I, _I, _I, _I, _F, _PP, _I, _F, _F]),
@@ -480,6 +510,40 @@ class Context:
         self._check(lib().exabm4d_denoise_chunked_u16_host(
             self.handle, src.ctypes.data, dst.ctypes.data, nz, ny, nx, int(chunk), int(halo), float(sigma),
             float(offset), ctypes.byref(p), int(stages)))
+
+    # -- BM4D under Poisson-Gaussian noise; ``noise``: a PgNoise (pg_noise(...)) ---------------
+    def denoise_pg_u16(self, src, dst, shape, noise, params=None, stages=2, batch=1):
+        """uint16 counts -> stabilised -> BM4D at sigma 1 -> inverse -> uint16, device pointers."""
+        p = params or default_params()
+        nz, ny, nx = shape
+        self._check(lib().exabm4d_denoise_pg_u16_dev(self.handle, _ptr(src), _ptr(dst), nz, ny, nx, int(batch),
+                                                     ctypes.byref(noise), ctypes.byref(p), int(stages)))
+
+    def denoise_pg_chunked_u16(self, src, dst, shape, noise, chunk=256, halo=8, core=None, params=None, stages=2):
+        """``denoise_chunked_u16`` with the stabilised pipeline on every padded chunk."""
+        p = params or default_params()
+        nz, ny, nx = shape
+        zc0, zc1 = (0, nz) if core is None else core
+        self._check(lib().exabm4d_denoise_pg_chunked_u16_dev(
+            self.handle, _ptr(src), _ptr(dst), nz, ny, nx, int(zc0), int(zc1), int(chunk), int(halo),
+            ctypes.byref(noise), ctypes.byref(p), int(stages)))
+
+    def denoise_pg_chunked_u16_host(self, src, dst, noise, chunk=256, halo=8, params=None, stages=2):
+        """``denoise_chunked_u16_host`` with the stabilised pipeline on every padded chunk."""
+        p = params or default_params()
+        check_host_volume_pair(src, dst)
+        nz, ny, nx = src.shape
+        self._check(lib().exabm4d_denoise_pg_chunked_u16_host(
+            self.handle, src.ctypes.data, dst.ctypes.data, nz, ny, nx, int(chunk), int(halo), ctypes.byref(noise),
+            ctypes.byref(p), int(stages)))
+
+    def gat_forward_u16(self, noise, src, dst, n):
+        """dst (fp32) = the un-normalised generalised Anscombe transform of the uint16 counts src."""
+        self._check(lib().exabm4d_gat_forward_u16_dev(self.handle, ctypes.byref(noise), _ptr(src), _ptr(dst), int(n)))
+
+    def gat_inverse_u16(self, noise, src, dst, n):
+        """dst (uint16) = rint(clamp(noise.inverse of the stabilised values src, 0, 65535))"""
+        self._check(lib().exabm4d_gat_inverse_u16_dev(self.handle, ctypes.byref(noise), _ptr(src), _ptr(dst), int(n)))
 
     def denoise_f32_host(self, arr, sigma, params=None, stages=2, clip=None):
         """numpy fp32 [N,]Z,Y,X in -> new numpy array out (H2D, kernels, D2H, sync)."""

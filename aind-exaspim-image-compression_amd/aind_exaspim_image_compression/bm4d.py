@@ -89,6 +89,36 @@ def _sigma(sigma, vol, device=None, **resident):
     return noise.resolve_sigma(sigma, vol, device=device, **resident)
 
 
+def _pg_noise(noise, inverse, sigma, offset, vol=None, resident=None):
+    """The ``exabm4d_pg_noise`` of a ``noise=`` argument, or None when ``noise`` is None.
+
+    ``noise``: ``{"gain", "read_noise", "offset"}`` (what ``utils.noise.estimate_poisson_gaussian`` returns), an
+    anscombe transform cfg, or "auto": measured once on the whole volume -- the noise curve on ``resident`` (the
+    uploaded volume, where there is one), the offset by ``transforms.estimate_offset`` on the host array ``vol``.
+    The model carries the noise level and the pedestal, so ``sigma`` must be None and ``offset`` left alone."""
+    if noise is None:
+        if sigma is None:
+            raise ValueError("give sigma (a number or 'auto'), or noise= for Poisson-Gaussian data")
+        return None
+    if sigma is not None:
+        raise ValueError("give either sigma or noise=, not both: under noise= the stabilised data has sigma 1")
+    if offset not in (None, 0, 0.0):
+        raise ValueError("with noise= the offset is the model's: leave offset= alone")
+    from aind_exaspim_image_compression.utils import noise as noise_mod
+    if isinstance(noise, str):
+        if noise != "auto":
+            raise ValueError("noise must be a dict, an anscombe cfg or 'auto', not %r" % noise)
+        if vol is None:
+            raise ValueError("noise='auto' needs the counts as a host array")
+        from aind_exaspim_image_compression.machine_learning.transforms import estimate_offset
+        off = estimate_offset(vol)
+        if resident is None:
+            noise = noise_mod.estimate_poisson_gaussian(vol, offset=off)
+        else:
+            noise = noise_mod.estimate_poisson_gaussian(resident, offset=off, shape=vol.shape, dtype=np.uint16)
+    return _native.pg_noise(inverse=inverse, **noise_mod.pg_params(noise))
+
+
 def bm4d(z, sigma_psd, profile=None, stage_arg=None, device=None):
     """Denoise a 3-D volume (or a 4-D batch of volumes) with two-stage BM4D.
 
@@ -131,7 +161,33 @@ def _device_share(args):
     return b - a
 
 
-def denoise_patches(raw, sigma, max_count=65535.0, profile=None, device=None, devices=None):
+def _denoise_patches_pg(raw, nz, prof, device):
+    """uint16 patches [N, Z, Y, X] through the batch form of the stabilised pipeline, sub-batches of at most
+    _MAX_VOXELS_PER_CALL voxels."""
+    raw = np.ascontiguousarray(raw, dtype=np.uint16)
+    if raw.ndim == 3:
+        raw = raw[None]
+    if raw.ndim != 4:
+        raise ValueError("denoise_patches(noise=...) expects uint16 patches [N, Z, Y, X]")
+    ctx = _native.context(device)
+    per = max(1, _MAX_VOXELS_PER_CALL // raw[0].size)
+    out = np.empty(raw.shape, dtype=np.uint16)
+    for i in range(0, raw.shape[0], per):
+        part = raw[i:i + per]
+        d_in = ctx.to_device(part)
+        d_out = ctx.alloc(part.nbytes)
+        try:
+            ctx.denoise_pg_u16(d_in, d_out, part.shape[1:], nz, params=prof.native(), stages=2, batch=part.shape[0])
+            ctx.sync()
+            out[i:i + per] = d_out.download(part.shape, np.uint16)
+        finally:
+            d_in.free()
+            d_out.free()
+    return out
+
+
+def denoise_patches(raw, sigma=None, max_count=65535.0, profile=None, device=None, devices=None, noise=None,
+                    inverse="closed_form"):
     """``teacher = np.clip(bm4d(raw, sigma), 0, max_count)`` for a batch ``raw[N, Z, Y, X]`` of
     offset-subtracted float32 patches, in one device call (reference call pattern:
     data_handling.py:331-333 inside scripts/precompute.py:215-228).
@@ -142,7 +198,21 @@ def denoise_patches(raw, sigma, max_count=65535.0, profile=None, device=None, de
     call); the patches travel through shared memory and come back in order.  Patches are independent units
     (no halo, no collective) and each carries its own fixed-point unit, so the result equals the
     single-device call bit for bit.  ``sigma="auto"`` is measured in THIS process (on ``device``, or the default
-    one) before the batch is cut: the shares only ever see the float."""
+    one) before the batch is cut: the shares only ever see the float.
+
+    ``noise=`` (DESIGN.md 5.10): ``raw`` holds uint16 COUNTS (pedestal included) under Poisson-Gaussian noise;
+    the patches go through the stabilised pipeline's batch form in this process and come back as uint16 counts.
+    ``sigma`` must then be None; "auto" measures the model over the whole batch as one population.  ``devices=``
+    and the broker do not carry a noise model: combined with ``noise=`` they raise."""
+    if noise is not None:
+        from aind_exaspim_image_compression import broker
+        if devices is not None or (device is None and broker.enabled()):
+            raise ValueError("denoise_patches: noise= runs in this process; it cannot be combined with devices= "
+                             "or the broker")
+        counts = np.ascontiguousarray(raw, dtype=np.uint16)
+        return _denoise_patches_pg(counts, _pg_noise(noise, inverse, sigma, None, vol=counts),
+                                   profile or BM4DProfile(), device)
+    _pg_noise(None, inverse, sigma, None)
     raw = np.asarray(raw, dtype=np.float32)
     if raw.ndim == 3:
         raw = raw[None]
@@ -180,12 +250,19 @@ def denoise_patches(raw, sigma, max_count=65535.0, profile=None, device=None, de
             seg.unlink()
 
 
-def denoise_volume(vol_u16, sigma, offset=0.0, profile=None, stages=2, device=None):
+def denoise_volume(vol_u16, sigma=None, offset=0.0, profile=None, stages=2, device=None, noise=None,
+                   inverse="closed_form"):
     """uint16 volume -> uint16 volume: ``(float)v - offset`` -> BM4D -> ``+ offset`` -> clip to
     [0, 65535] -> rint -> uint16, entirely on the device (read_counts + bm4d + clip + the
     rint/uint16 cast of IntensityTransform.inverse).  The uint16 form matches its second stage on the basic
     estimate rounded to counts: both matching passes are 16-bit integer work.  ``sigma="auto"``
-    measures it on the uploaded volume (``utils.noise.estimate_sigma``)."""
+    measures it on the uploaded volume (``utils.noise.estimate_sigma``).
+
+    ``noise=`` instead of ``sigma`` is for sCMOS data, whose noise grows with the signal
+    (``var = gain (mean - offset) + read_noise^2``): the counts are variance-stabilised, denoised at sigma 1 in
+    the fp32 kernels and inverted, in one device call.  ``noise`` is a dict ``{"gain", "read_noise", "offset"}``
+    (``utils.noise.estimate_poisson_gaussian``), an anscombe transform cfg, or "auto" (measured here, once);
+    ``inverse``: "closed_form" (exact unbiased, the default), "asymptotic" or "algebraic"."""
     vol = np.ascontiguousarray(vol_u16, dtype=np.uint16)
     if vol.ndim != 3:
         raise ValueError("denoise_volume expects a 3-D uint16 volume")
@@ -194,6 +271,11 @@ def denoise_volume(vol_u16, sigma, offset=0.0, profile=None, stages=2, device=No
     d_in = ctx.to_device(vol)
     d_out = ctx.alloc(vol.nbytes)
     try:
+        nz = _pg_noise(noise, inverse, sigma, offset, vol=vol, resident=d_in)
+        if nz is not None:
+            ctx.denoise_pg_u16(d_in, d_out, vol.shape, nz, params=prof.native(), stages=int(stages))
+            ctx.sync()
+            return d_out.download(vol.shape, np.uint16)
         sigma = _sigma(sigma, d_in, shape=vol.shape, dtype=np.uint16)
         ctx.denoise_u16(d_in, d_out, vol.shape, float(sigma), float(offset), params=prof.native(),
                         stages=int(stages))
@@ -204,8 +286,8 @@ def denoise_volume(vol_u16, sigma, offset=0.0, profile=None, stages=2, device=No
         d_out.free()
 
 
-def denoise_chunked(vol_u16, sigma, offset=0.0, chunk=256, halo=8, profile=None, stages=2,
-                    device=None):
+def denoise_chunked(vol_u16, sigma=None, offset=0.0, chunk=256, halo=8, profile=None, stages=2,
+                    device=None, noise=None, inverse="closed_form"):
     """Chunk-local mode of BASELINE.json config 4: the volume is tiled by ``chunk``^3 cores, every
     core is read with ``halo`` voxels on each side -- the read window is CUT where the volume ends,
     nothing is padded or replicated at the faces (SURVEY.md appendix A item 11's
@@ -213,7 +295,9 @@ def denoise_chunked(vol_u16, sigma, offset=0.0, chunk=256, halo=8, profile=None,
     truncated arrays) -- and denoised in isolation -- independent units, like the reference's one-``bm4d``-call-per-patch
     pool (scripts/precompute.py:215-228) -- and only the cores are written.  One batched device
     call (``exabm4d_denoise_chunked_u16_dev``); uint16 in, uint16 out.  ``sigma="auto"`` measures it once on the
-    uploaded volume, not per chunk."""
+    uploaded volume, not per chunk.  ``noise=`` / ``inverse=`` as in ``denoise_volume``: every padded chunk goes
+    through the stabilised pipeline (``exabm4d_denoise_pg_chunked_u16_dev``); "auto" is measured once on the
+    whole volume."""
     vol = np.ascontiguousarray(vol_u16, dtype=np.uint16)
     if vol.ndim != 3:
         raise ValueError("denoise_chunked expects a 3-D uint16 volume")
@@ -222,6 +306,12 @@ def denoise_chunked(vol_u16, sigma, offset=0.0, chunk=256, halo=8, profile=None,
     d_in = ctx.to_device(vol)
     d_out = ctx.alloc(vol.nbytes)
     try:
+        nz = _pg_noise(noise, inverse, sigma, offset, vol=vol, resident=d_in)
+        if nz is not None:
+            ctx.denoise_pg_chunked_u16(d_in, d_out, vol.shape, nz, chunk=int(chunk), halo=int(halo),
+                                       params=prof.native(), stages=int(stages))
+            ctx.sync()
+            return d_out.download(vol.shape, np.uint16)
         sigma = _sigma(sigma, d_in, shape=vol.shape, dtype=np.uint16)
         ctx.denoise_chunked_u16(d_in, d_out, vol.shape, float(sigma), float(offset),
                                 chunk=int(chunk), halo=int(halo), params=prof.native(),
@@ -233,15 +323,17 @@ def denoise_chunked(vol_u16, sigma, offset=0.0, chunk=256, halo=8, profile=None,
         d_out.free()
 
 
-def denoise_chunked_streamed(vol_u16, sigma, offset=0.0, chunk=256, halo=8, profile=None, stages=2,
-                             device=None, out=None):
+def denoise_chunked_streamed(vol_u16, sigma=None, offset=0.0, chunk=256, halo=8, profile=None, stages=2,
+                             device=None, out=None, noise=None, inverse="closed_form"):
     """``denoise_chunked`` for volumes that should not (or cannot) sit on the device whole -- the
     reference's production harness denoises whole images (scripts/evaluate_bm4dnet.py:51-181), and
     BASELINE config 4's tile is 64 GiB.  ``vol_u16`` is a C-contiguous uint16 array or ``np.memmap``;
     layers of chunks travel up, are denoised chunk by chunk in isolation and travel down while the
     next layer is in the kernels (``exabm4d_denoise_chunked_u16_host``).  ``out`` may name the
     destination (another array / writeable memmap of the same shape); the result equals
-    ``denoise_chunked`` on the whole volume."""
+    ``denoise_chunked`` on the whole volume.  ``noise=`` / ``inverse=`` as in ``denoise_volume``; "auto" uploads
+    the whole volume once to measure it, so for a volume that does not fit the device measure a sample with
+    ``utils.noise.estimate_poisson_gaussian`` and pass the dict."""
     vol = vol_u16 if isinstance(vol_u16, np.ndarray) and vol_u16.dtype == np.uint16 and \
         vol_u16.flags.c_contiguous else np.ascontiguousarray(vol_u16, dtype=np.uint16)
     if vol.ndim != 3:
@@ -250,7 +342,12 @@ def denoise_chunked_streamed(vol_u16, sigma, offset=0.0, chunk=256, halo=8, prof
         out = np.empty(vol.shape, dtype=np.uint16)
     _native.check_host_volume_pair(vol, out)
     prof = profile or BM4DProfile()
+    nz = _pg_noise(noise, inverse, sigma, offset, vol=vol)
     ctx = _native.context(device)
+    if nz is not None:
+        ctx.denoise_pg_chunked_u16_host(vol, out, nz, chunk=int(chunk), halo=int(halo), params=prof.native(),
+                                        stages=int(stages))
+        return out
     ctx.denoise_chunked_u16_host(vol, out, float(sigma), float(offset), chunk=int(chunk), halo=int(halo),
                                  params=prof.native(), stages=int(stages))
     return out

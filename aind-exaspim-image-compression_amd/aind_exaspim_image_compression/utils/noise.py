@@ -232,6 +232,53 @@ def anscombe_cfg(vol, **kw):
     return {"kind": "anscombe", "params": estimate_poisson_gaussian(vol, **kw)}
 
 
+def pg_params(noise):
+    """``{"gain", "read_noise", "offset"}`` as floats from what the denoisers' ``noise=`` accepts: that dict (the
+    return value of ``estimate_poisson_gaussian``) or an anscombe transform cfg (``anscombe_cfg``)."""
+    if isinstance(noise, dict) and noise.get("kind") is not None:
+        if noise["kind"] != "anscombe":
+            raise ValueError("noise: a transform cfg must be of kind 'anscombe', not %r" % noise["kind"])
+        noise = noise.get("params", {})
+    if not isinstance(noise, dict):
+        raise ValueError("noise must be a dict with gain, read_noise and offset, an anscombe cfg, or 'auto'")
+    try:
+        out = {k: float(noise[k]) for k in ("gain", "read_noise", "offset")}
+    except KeyError as e:
+        raise ValueError("noise: %s is missing" % e) from None
+    if not (all(math.isfinite(v) for v in out.values()) and out["gain"] > 0.0 and out["read_noise"] >= 0.0):
+        raise ValueError("noise: gain must be > 0, read_noise >= 0, all three finite (got %r)" % out)
+    return out
+
+
+def _stream(vol, dtype_in, dtype_out, device, run):
+    arr = np.ascontiguousarray(vol, dtype=dtype_in)
+    ctx = _native.context(device)
+    d_in = ctx.to_device(arr.reshape(-1))
+    d_out = ctx.alloc(max(1, arr.size) * np.dtype(dtype_out).itemsize)
+    try:
+        if arr.size:
+            run(ctx, d_in, d_out, arr.size)
+        ctx.sync()
+        return d_out.download(arr.shape, dtype_out)
+    finally:
+        d_in.free()
+        d_out.free()
+
+
+def stabilise(vol, params, device=None):
+    """The un-normalised generalised Anscombe transform of the uint16 counts ``vol`` as float32: noise of unit
+    standard deviation under ``params``.  The forward stream of ``denoise_volume(noise=...)``."""
+    nz = _native.pg_noise(**pg_params(params))
+    return _stream(vol, np.uint16, np.float32, device, lambda ctx, a, b, n: ctx.gat_forward_u16(nz, a, b, n))
+
+
+def unstabilise(D, params, inverse="closed_form", device=None):
+    """uint16 counts from stabilised float32 values: the "closed_form" (exact unbiased, Makitalo & Foi),
+    "asymptotic" (1/8) or "algebraic" (3/8) inverse, clipped to [0, 65535] and rounded half to even."""
+    nz = _native.pg_noise(inverse=inverse, **pg_params(params))
+    return _stream(D, np.float32, np.uint16, device, lambda ctx, a, b, n: ctx.gat_inverse_u16(nz, a, b, n))
+
+
 def resolve_sigma(sigma, vol, device=None, **kw):
     """``sigma`` as a float; the string "auto" is measured from ``vol`` (see ``noise_table`` for what it may be)."""
     if isinstance(sigma, str):

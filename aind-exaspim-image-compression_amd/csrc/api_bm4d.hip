@@ -111,6 +111,35 @@ static int check_offset(exabm4d_ctx* ctx, float offset) {   // |v - offset| < 2^
     return fail(ctx, EXABM4D_ERR_INVALID, "offset must lie within [-65536, 65536]");
 }
 
+// The constants of the Poisson-Gaussian stabilisation: formed in double from the struct's floats,
+// rounded once.
+static int pg_entry(exabm4d_ctx* ctx, const exabm4d_pg_noise* n, PgDev& d) {
+    if (!n) return fail(ctx, EXABM4D_ERR_INVALID, "noise is NULL");
+    if (n->size != sizeof(exabm4d_pg_noise)) return fail(ctx, EXABM4D_ERR_INVALID, "noise.size does not match this library");
+    if (!std::isfinite(n->gain) || !std::isfinite(n->read_noise) || !std::isfinite(n->offset))
+        return fail(ctx, EXABM4D_ERR_INVALID, "noise: gain, read_noise and offset must be finite");
+    if (!(n->gain > 0.0f) || !(n->read_noise >= 0.0f))
+        return fail(ctx, EXABM4D_ERR_INVALID, "noise: gain must be > 0 and read_noise >= 0");
+    if (n->inverse < 0 || n->inverse > 2) return fail(ctx, EXABM4D_ERR_INVALID, "noise.inverse must be 0, 1 or 2");
+    int rc = check_offset(ctx, n->offset);
+    if (rc) return rc;
+    const double g = n->gain, r = n->read_noise;
+    std::memset(&d, 0, sizeof d);
+    d.inverse = n->inverse;
+    d.gain = n->gain;
+    d.off = n->offset;
+    d.c38g2 = (float)((3.0 / 8.0) * g * g);
+    d.rn2 = (float)(r * r);
+    d.two_over_gain = (float)(2.0 / g);
+    d.cg2 = (float)((n->inverse == 0 ? 3.0 / 8.0 : 1.0 / 8.0) * g * g);
+    d.s2 = (float)((r / g) * (r / g));
+    d.k1 = (float)(std::sqrt(1.5) / 4.0);
+    d.k2 = (float)(11.0 / 8.0);
+    d.k3 = (float)(5.0 * std::sqrt(1.5) / 8.0);
+    d.d0 = (float)(2.0 * std::sqrt(3.0 / 8.0));
+    return EXABM4D_OK;
+}
+
 // (float)v - offset is exact in fp32 for every uint16 v iff the offset has at most 7 fractional bits
 // (17 integer bits of |v - offset| + 7 = 24) -- 0, 37, 100.5 ...; only then do two voxels of the
 // fp32 counts differ by an exact integer and the integer matching kernel reproduce the float
@@ -352,7 +381,7 @@ static int run_pipeline(exabm4d_ctx* ctx, const float* noisy, float* out_f32, ui
                         const VolGeom& g, int batch, float sigma, const exabm4d_params* p,
                         int stages, float clip_lo, float clip_hi, float u16_offset, char* scratch,
                         int noisy_guarded, int data_exp, const uint16_t* noisy16 = nullptr,
-                        int match_counts = 0, float match_offset = 0.0f) {
+                        int match_counts = 0, float match_offset = 0.0f, const PgDev* pg = nullptr) {
     // noisy16: the same volume as uint16 counts XOR 0x8000, guarded like `noisy`, when the caller
     // is a uint16 pipeline: stage-1 matching then runs in integer arithmetic (bm_tile16_kernel),
     // provided its tables equal the float kernel's -- admission bound below 2^24, even row length
@@ -364,6 +393,8 @@ static int run_pipeline(exabm4d_ctx* ctx, const float* noisy, float* out_f32, ui
     // COUNTS -- rint(clamp(basic + match_offset, 0, 65535)) -- so that it can run in integer arithmetic like
     // stage 1 (noisy16's memory is free by then and takes the rounded volume); where the integer kernel does
     // not apply, the float kernel runs on the same counts as fp32 (in `tmp`, dead between the stages).
+    // pg (uint16 output): `noisy` is the stabilised volume; the last normalisation inverts the
+    // stabilisation where it would add the offset.
     const size_t n = (size_t)g.nvox * (size_t)batch;
     const BmPlan plan = bm_plan(g, batch, ctx->bm);           // one plan for both matching launches
     Carver c{scratch};
@@ -458,7 +489,8 @@ static int run_pipeline(exabm4d_ctx* ctx, const float* noisy, float* out_f32, ui
     {
         PhaseTimer t(ctx, EXABM4D_PHASE_NORMALIZE_OUT);
         HIP_TRY(ctx, launch_normalize_zconv(num, qs, tmp, out_f32, out_u16, g.nz, g.ny, g.nx, batch, ctx->win1d,
-                                            clip_lo, clip_hi, u16_offset, s));
+                                            clip_lo, clip_hi, u16_offset, s, nullptr, nullptr, nullptr, nullptr, 0.0f,
+                                            nullptr, pg));
     }
     return EXABM4D_OK;
 }
@@ -497,17 +529,62 @@ int exabm4d_denoise_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out,
                         ctx->scratch.as<char>(), 1, EXABM4D_DATA_EXP_U16, noisy16, 1, offset);
 }
 
+// Under Poisson-Gaussian noise: counts -> D (unit sigma) -> the fp32 pipeline at sigma 1 -> the
+// inverse, fused into the last normalisation -> counts.  The scratch is the uint16 pipelines' (the uint16 shadow
+// stays unused: both matching passes are the float kernels').
+int exabm4d_denoise_pg_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out, int nz, int ny, int nx,
+                               int batch, const exabm4d_pg_noise* noise, const exabm4d_params* p, int stages) {
+    int rc = bm4d_checks(ctx, in, out, 1.0f, p, stages);
+    if (rc) return rc;
+    PgDev pg;
+    rc = pg_entry(ctx, noise, pg);
+    if (rc) return rc;
+    VolGeom g;
+    rc = geom_on_device(ctx, nz, ny, nx, batch, g);
+    if (!rc) rc = ensure_window(ctx, (double)p->kaiser_beta);
+    if (rc) return rc;
+    U16Scratch v;
+    rc = u16_pipe_scratch(ctx, g, batch, stages, v);
+    if (rc) return rc;
+    ctx->ev_used[EXABM4D_PHASE_COUNTS_FROM_U16] = false;
+    {
+        PhaseTimer t(ctx, EXABM4D_PHASE_COUNTS_FROM_U16);
+        HIP_TRY(ctx, launch_pg_forward_u16(pg, in, v.f32, (size_t)g.nvox * (size_t)batch, ctx->stream));
+    }
+    return run_pipeline(ctx, v.f32, nullptr, out, g, batch, 1.0f, p, stages, 0.0f, 0.0f, 0.0f,
+                        ctx->scratch.as<char>(), 1, EXABM4D_DATA_EXP_AUTO, nullptr, 0, 0.0f, &pg);
+}
+
+int exabm4d_gat_forward_u16_dev(exabm4d_ctx* ctx, const exabm4d_pg_noise* noise, const uint16_t* in, float* out,
+                                size_t n) {
+    if (!ctx || !in || !out) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    PgDev pg;
+    int rc = pg_entry(ctx, noise, pg);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_pg_forward_u16(pg, in, out, n, ctx->stream));
+    return EXABM4D_OK;
+}
+
+int exabm4d_gat_inverse_u16_dev(exabm4d_ctx* ctx, const exabm4d_pg_noise* noise, const float* in, uint16_t* out,
+                                size_t n) {
+    if (!ctx || !in || !out) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    PgDev pg;
+    int rc = pg_entry(ctx, noise, pg);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_pg_inverse_u16(pg, in, out, n, ctx->stream));
+    return EXABM4D_OK;
+}
+
 // Chunk-local mode: every chunk (core + halo, the halo cut off where the buffer ends) is denoised
 // in isolation, batches of equally shaped chunks per pipeline run; only the cores are written.
-
-int exabm4d_denoise_chunked_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out, int nz, int ny,
-                                    int nx, int zc0, int zc1, int chunk, int halo, float sigma,
-                                    float offset, const exabm4d_params* p, int stages) {
-    int rc = chunk_checks(ctx, in, out, nz, ny, nx, chunk, halo, sigma, p, stages);
-    if (rc) return rc;
-    if (zc0 < 0 || zc1 > nz || zc0 >= zc1) return fail(ctx, EXABM4D_ERR_INVALID, "chunked: bad core plane range");
-    rc = check_offset(ctx, offset);
-    if (rc) return rc;
+// pg == NULL: the uint16 pipeline at (sigma, offset); else the stabilised pipeline at sigma 1.
+// The arguments have been checked by the entry points below.
+static int chunked_on_device(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out, int nz, int ny, int nx, int zc0,
+                             int zc1, int chunk, int halo, float sigma, float offset, const PgDev* pg,
+                             const exabm4d_params* p, int stages) {
+    int rc = EXABM4D_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     rc = ensure_window(ctx, (double)p->kaiser_beta);
     if (rc) return rc;
@@ -549,6 +626,14 @@ int exabm4d_denoise_chunked_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, uint16
                     if (rc) return rc;
                     float* vol = v.f32;
                     uint16_t* vol16 = v.u16;
+                    if (pg) {
+                        HIP_TRY(ctx, launch_chunk_gather_pg(in, cb, *pg, vol, ctx->stream));
+                        rc = run_pipeline(ctx, vol, vol, nullptr, g, count, 1.0f, p, stages, 1.0f, 0.0f, 0.0f,
+                                          ctx->scratch.as<char>(), 1, EXABM4D_DATA_EXP_AUTO);
+                        if (rc) return rc;
+                        HIP_TRY(ctx, launch_chunk_scatter_pg(vol, cb, *pg, out, ctx->stream));
+                        continue;
+                    }
                     HIP_TRY(ctx, launch_chunk_gather(in, cb, offset, vol, ctx->stream, vol16));
                     rc = run_pipeline(ctx, vol, vol, nullptr, g, count, sigma, p, stages, 1.0f, 0.0f, 0.0f,
                                       ctx->scratch.as<char>(), 1, EXABM4D_DATA_EXP_U16,
@@ -558,6 +643,29 @@ int exabm4d_denoise_chunked_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, uint16
                 }
             }
     return EXABM4D_OK;
+}
+
+int exabm4d_denoise_chunked_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out, int nz, int ny,
+                                    int nx, int zc0, int zc1, int chunk, int halo, float sigma,
+                                    float offset, const exabm4d_params* p, int stages) {
+    int rc = chunk_checks(ctx, in, out, nz, ny, nx, chunk, halo, sigma, p, stages);
+    if (rc) return rc;
+    if (zc0 < 0 || zc1 > nz || zc0 >= zc1) return fail(ctx, EXABM4D_ERR_INVALID, "chunked: bad core plane range");
+    rc = check_offset(ctx, offset);
+    if (rc) return rc;
+    return chunked_on_device(ctx, in, out, nz, ny, nx, zc0, zc1, chunk, halo, sigma, offset, nullptr, p, stages);
+}
+
+int exabm4d_denoise_pg_chunked_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out, int nz, int ny,
+                                       int nx, int zc0, int zc1, int chunk, int halo,
+                                       const exabm4d_pg_noise* noise, const exabm4d_params* p, int stages) {
+    int rc = chunk_checks(ctx, in, out, nz, ny, nx, chunk, halo, 1.0f, p, stages);
+    if (rc) return rc;
+    if (zc0 < 0 || zc1 > nz || zc0 >= zc1) return fail(ctx, EXABM4D_ERR_INVALID, "chunked: bad core plane range");
+    PgDev pg;
+    rc = pg_entry(ctx, noise, pg);
+    if (rc) return rc;
+    return chunked_on_device(ctx, in, out, nz, ny, nx, zc0, zc1, chunk, halo, 1.0f, pg.off, &pg, p, stages);
 }
 
 // ---- chunk-local mode, host volume streamed through the device ------------------------------------
@@ -593,11 +701,12 @@ struct StreamedLayers {
 };
 }  // namespace
 
-int exabm4d_denoise_chunked_u16_host(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out, int nz, int ny,
-                                     int nx, int chunk, int halo, float sigma, float offset,
-                                     const exabm4d_params* p, int stages) {
-    int rc = chunk_checks(ctx, in, out, nz, ny, nx, chunk, halo, sigma, p, stages);
-    if (rc) return rc;
+// pg == NULL: (sigma, offset) through chunked_on_device's uint16 pipeline; else the stabilised one.  Arguments
+// checked by the entry points below.
+static int chunked_from_host(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out, int nz, int ny, int nx, int chunk,
+                             int halo, float sigma, float offset, const PgDev* pg, const exabm4d_params* p,
+                             int stages) {
+    int rc = EXABM4D_OK;
     {   // the downloads of early layers would overwrite planes that later layers still have to upload
         const size_t bytes = (size_t)nz * (size_t)ny * (size_t)nx * sizeof(uint16_t);
         const char *a = reinterpret_cast<const char*>(in), *b = reinterpret_cast<const char*>(out);
@@ -693,8 +802,8 @@ int exabm4d_denoise_chunked_u16_host(exabm4d_ctx* ctx, const uint16_t* in, uint1
         if (!st.wait_for(&StreamedLayers::uploaded, k + 1) || !st.wait_for(&StreamedLayers::downloaded, k - 1)) break;
         int w0, w1, c0, c1;
         window_of(k, w0, w1, c0, c1);
-        rc = exabm4d_denoise_chunked_u16_dev(ctx, win[k & 1], res[k & 1], w1 - w0, ny, nx, c0 - w0, c1 - w0, chunk,
-                                             halo, sigma, offset, p, stages);
+        rc = chunked_on_device(ctx, win[k & 1], res[k & 1], w1 - w0, ny, nx, c0 - w0, c1 - w0, chunk, halo, sigma,
+                               offset, pg, p, stages);
         hipError_t r = rc ? hipSuccess : hipEventRecord(comp_ev[k & 1], ctx->stream);
         if (rc || r != hipSuccess) {
             compute_err = rc ? ctx->err : std::string("hipEventRecord: ") + hipGetErrorString(r);
@@ -710,6 +819,26 @@ int exabm4d_denoise_chunked_u16_host(exabm4d_ctx* ctx, const uint16_t* in, uint1
     release();
     if (st.failed) return fail(ctx, rc ? rc : EXABM4D_ERR_HIP, "streamed chunk mode: " + st.err);
     return check_async_status(ctx);
+}
+
+int exabm4d_denoise_chunked_u16_host(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out, int nz, int ny,
+                                     int nx, int chunk, int halo, float sigma, float offset,
+                                     const exabm4d_params* p, int stages) {
+    int rc = chunk_checks(ctx, in, out, nz, ny, nx, chunk, halo, sigma, p, stages);
+    if (!rc) rc = check_offset(ctx, offset);
+    if (rc) return rc;
+    return chunked_from_host(ctx, in, out, nz, ny, nx, chunk, halo, sigma, offset, nullptr, p, stages);
+}
+
+int exabm4d_denoise_pg_chunked_u16_host(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out, int nz, int ny,
+                                        int nx, int chunk, int halo, const exabm4d_pg_noise* noise,
+                                        const exabm4d_params* p, int stages) {
+    int rc = chunk_checks(ctx, in, out, nz, ny, nx, chunk, halo, 1.0f, p, stages);
+    if (rc) return rc;
+    PgDev pg;
+    rc = pg_entry(ctx, noise, pg);
+    if (rc) return rc;
+    return chunked_from_host(ctx, in, out, nz, ny, nx, chunk, halo, 1.0f, pg.off, &pg, p, stages);
 }
 
 // A large batch goes through the device in sub-batches of about 2^26 voxels, double-buffered: while sub-batch k

@@ -55,6 +55,33 @@ __device__ __forceinline__ uint16_t quantise_u16(float c, float maxc) {
     return (uint16_t)rintf(c);           // np.rint (half-to-even) then astype(uint16)
 }
 
+// Poisson-Gaussian stabilisation (tests/pg_pyref.py states the operation order).  The forward is
+// tf_forward kind 1 without the division by norm: unit noise sigma in D.
+__device__ __forceinline__ float pg_forward(const PgDev& t, float x) {
+    float a = t.gain * (x - t.off);
+    a = a + t.c38g2;
+    a = a + t.rn2;
+    return t.two_over_gain * sqrtf(fmaxf(a, 0.0f));
+}
+__device__ __forceinline__ float pg_inverse(const PgDev& t, float D) {
+    if (t.inverse != 2) {                    // tf_inverse_float kind 1 without norm; cg2 = (3/8 or 1/8) gain^2
+        const float h = fmaxf(D, 0.0f) * t.gain / 2.0f;
+        const float u = (h * h - t.cg2) - t.rn2;
+        return t.off + u / t.gain;
+    }
+    // closed-form approximation of the exact unbiased inverse (Makitalo & Foi): the Poisson inverse, defined from
+    // d0 = 2 sqrt(3/8) (the transform of zero photons) upwards, minus s2; below d0 the 1/d^3 term would take over
+    const float d = fmaxf(D, t.d0);
+    const float d2 = d * d, d3 = d2 * d;
+    float y = d2 * 0.25f;
+    y = y + t.k1 / d;
+    y = y - t.k2 / d2;
+    y = y + t.k3 / d3;
+    y = y - 0.125f;
+    y = y - t.s2;
+    return t.off + t.gain * fmaxf(y, 0.0f);
+}
+
 constexpr int EW_THREADS = 256;
 constexpr int EW_MAX_BLOCKS = 256 * 8;
 
@@ -211,6 +238,33 @@ struct OpTfInverseU16 {
         ld8(in + i, v);
 #pragma unroll
         for (int k = 0; k < 8; k++) q[k] = quantise_u16(tf_inverse_float(t, v[k]), t.maxc);
+        st8(out + i, q);
+    }
+};
+struct OpPgForwardU16 {
+    PgDev t;
+    const uint16_t* in;
+    float* out;
+    __device__ void one(size_t i) const { out[i] = pg_forward(t, (float)in[i]); }
+    __device__ void eight(size_t i) const {
+        float v[8];
+        ld8(in + i, v);
+#pragma unroll
+        for (int k = 0; k < 8; k++) v[k] = pg_forward(t, v[k]);
+        st8(out + i, v);
+    }
+};
+struct OpPgInverseU16 {
+    PgDev t;
+    const float* in;
+    uint16_t* out;
+    __device__ void one(size_t i) const { out[i] = quantise_u16(pg_inverse(t, in[i]), 65535.0f); }
+    __device__ void eight(size_t i) const {
+        float v[8];
+        uint16_t q[8];
+        ld8(in + i, v);
+#pragma unroll
+        for (int k = 0; k < 8; k++) q[k] = quantise_u16(pg_inverse(t, v[k]), 65535.0f);
         st8(out + i, q);
     }
 };
@@ -426,6 +480,58 @@ __global__ __launch_bounds__(EW_THREADS) void chunk_scatter_kernel(const float* 
         out[((size_t)oz * cb.ny + oy) * cb.nx + ox] = quantise_u16(v + offset, 65535.0f);
     }
 }
+// The stabilised pipeline's pair: the same index maps; gather writes D = pg_forward(count), scatter
+// writes quantise(pg_inverse(estimate)).
+__global__ __launch_bounds__(EW_THREADS) void chunk_gather_pg_kernel(const uint16_t* __restrict__ in,
+                                                                     ChunkBatch cb, PgDev t,
+                                                                     float* __restrict__ out) {
+    const size_t pvox = (size_t)cb.pz * cb.py * cb.px;
+    const size_t total = pvox * (size_t)cb.count;
+    for (size_t i = (size_t)blockIdx.x * EW_THREADS + threadIdx.x; i < total;
+         i += (size_t)gridDim.x * EW_THREADS) {
+        const int b = (int)(i / pvox);
+        const size_t r = i - (size_t)b * pvox;
+        const int x = (int)(r % cb.px), y = (int)((r / cb.px) % cb.py), z = (int)(r / ((size_t)cb.px * cb.py));
+        const int c = cb.first + b;
+        const int bx = c % cb.sgx, by = (c / cb.sgx) % cb.sgy, bz = c / (cb.sgx * cb.sgy);
+        const int gz = min(max(cb.z0 + bz * cb.cz - cb.lz + z, 0), cb.nz - 1);
+        const int gy = min(max(cb.y0 + by * cb.cy - cb.ly + y, 0), cb.ny - 1);
+        const int gx = min(max(cb.x0 + bx * cb.cx - cb.lx + x, 0), cb.nx - 1);
+        out[i] = pg_forward(t, (float)in[((size_t)gz * cb.ny + gy) * cb.nx + gx]);
+    }
+}
+__global__ __launch_bounds__(EW_THREADS) void chunk_scatter_pg_kernel(const float* __restrict__ est,
+                                                                      ChunkBatch cb, PgDev t,
+                                                                      uint16_t* __restrict__ out) {
+    const size_t cvox = (size_t)cb.ez * cb.ey * cb.ex;
+    const size_t total = cvox * (size_t)cb.count;
+    const size_t pvox = (size_t)cb.pz * cb.py * cb.px;
+    for (size_t i = (size_t)blockIdx.x * EW_THREADS + threadIdx.x; i < total;
+         i += (size_t)gridDim.x * EW_THREADS) {
+        const int b = (int)(i / cvox);
+        const size_t r = i - (size_t)b * cvox;
+        const int x = (int)(r % cb.ex), y = (int)((r / cb.ex) % cb.ey), z = (int)(r / ((size_t)cb.ex * cb.ey));
+        const int c = cb.first + b;
+        const int bx = c % cb.sgx, by = (c / cb.sgx) % cb.sgy, bz = c / (cb.sgx * cb.sgy);
+        const float v = est[(size_t)b * pvox + ((size_t)(z + cb.lz) * cb.py + (y + cb.ly)) * cb.px + (x + cb.lx)];
+        const int oz = cb.z0 + bz * cb.cz + z - cb.out_z0, oy = cb.y0 + by * cb.cy + y, ox = cb.x0 + bx * cb.cx + x;
+        out[((size_t)oz * cb.ny + oy) * cb.nx + ox] = quantise_u16(pg_inverse(t, v), 65535.0f);
+    }
+}
+hipError_t launch_chunk_gather_pg(const uint16_t* in, const ChunkBatch& cb, const PgDev& t, float* out,
+                                  hipStream_t s) {
+    const size_t total = (size_t)cb.pz * cb.py * cb.px * (size_t)cb.count;
+    const unsigned blocks = (unsigned)std::min<size_t>((total + EW_THREADS - 1) / EW_THREADS, 1u << 20);
+    hipLaunchKernelGGL(chunk_gather_pg_kernel, dim3(blocks), dim3(EW_THREADS), 0, s, in, cb, t, out);
+    return hipGetLastError();
+}
+hipError_t launch_chunk_scatter_pg(const float* est, const ChunkBatch& cb, const PgDev& t, uint16_t* out,
+                                   hipStream_t s) {
+    const size_t total = (size_t)cb.ez * cb.ey * cb.ex * (size_t)cb.count;
+    const unsigned blocks = (unsigned)std::min<size_t>((total + EW_THREADS - 1) / EW_THREADS, 1u << 20);
+    hipLaunchKernelGGL(chunk_scatter_pg_kernel, dim3(blocks), dim3(EW_THREADS), 0, s, est, cb, t, out);
+    return hipGetLastError();
+}
 hipError_t launch_chunk_gather(const uint16_t* in, const ChunkBatch& cb, float offset, float* out,
                                hipStream_t s, uint16_t* out16) {
     const size_t total = (size_t)cb.pz * cb.py * cb.px * (size_t)cb.count;
@@ -556,7 +662,17 @@ __global__ __launch_bounds__(EW_THREADS) void conv8_xy4_kernel(const unsigned lo
 // out = fl32(fl64(num) 2^(E - 43)) / den (+ clip, or + offset, clamp, rint, uint16).  Saves the pass that
 // would write den and the one that would read it back; bit-identical to the separate passes of the staged
 // entry points.
-template <int W, bool U16>
+// The uint16 form's last step on the quotient r: + offset (the uint16 pipelines), or the inverse of the Poisson-
+// Gaussian stabilisation (the estimate never travels to HBM as fp32); then clamp, rint, uint16.
+struct EpiOffset {};
+struct EpiPg { PgDev t; };
+__device__ __forceinline__ uint16_t zconv_u16(const EpiOffset&, float r, float offset) {
+    return quantise_u16(r + offset, 65535.0f);
+}
+__device__ __forceinline__ uint16_t zconv_u16(const EpiPg& e, float r, float) {
+    return quantise_u16(pg_inverse(e.t, r), 65535.0f);
+}
+template <int W, bool U16, class Epi = EpiOffset>
 __global__ __launch_bounds__(EW_THREADS) void normalize_zconv_kernel(const long long* __restrict__ num,
                                                                      const double* __restrict__ qscale,
                                                                      const float* __restrict__ txy,
@@ -566,7 +682,7 @@ __global__ __launch_bounds__(EW_THREADS) void normalize_zconv_kernel(const long 
                                                                      const float* __restrict__ pair_src,
                                                                      float* __restrict__ pair_out,
                                                                      uint16_t* __restrict__ match16,
-                                                                     float match_offset) {
+                                                                     float match_offset, Epi epi) {
     // pair_out (fp32 output, W = 4 only): additionally the interleaved volume (pair_src, out) the Wiener
     // kernel gathers from, so that it does not cost a pass of its own
     // match16 (fp32 output): additionally the estimate rounded to counts, XOR 0x8000 -- what stage 2 of the
@@ -612,11 +728,11 @@ __global__ __launch_bounds__(EW_THREADS) void normalize_zconv_kernel(const long 
             if (U16) {
                 uint16_t* o16 = static_cast<uint16_t*>(out) + at;
                 if (W == 4) {
-                    const uint32_t q0 = quantise_u16(r[0] + offset, 65535.0f), q1 = quantise_u16(r[1 % W] + offset, 65535.0f);
-                    const uint32_t q2 = quantise_u16(r[2 % W] + offset, 65535.0f), q3 = quantise_u16(r[3 % W] + offset, 65535.0f);
+                    const uint32_t q0 = zconv_u16(epi, r[0], offset), q1 = zconv_u16(epi, r[1 % W], offset);
+                    const uint32_t q2 = zconv_u16(epi, r[2 % W], offset), q3 = zconv_u16(epi, r[3 % W], offset);
                     *reinterpret_cast<uint2*>(o16) = make_uint2(q0 | (q1 << 16), q2 | (q3 << 16));
                 } else {
-                    o16[0] = quantise_u16(r[0] + offset, 65535.0f);
+                    o16[0] = zconv_u16(epi, r[0], offset);
                 }
             } else {
                 float* o32 = static_cast<float*>(out) + at;
@@ -677,7 +793,7 @@ hipError_t launch_normalize_zconv(const long long* num, const double* qscale, co
                                   uint16_t* out_u16, int nz, int ny, int nx, int batch, const float* win1d,
                                   float lo, float hi, float offset, hipStream_t s, const float* pair_src,
                                   float* pair_out, int* pair_written, uint16_t* match16, float match_offset,
-                                  int* match_written) {
+                                  int* match_written, const PgDev* pg) {
     if (pair_written) *pair_written = 0;
     if (match_written) *match_written = 0;
     // (the rounded copy is of the UNCLIPPED fp32 estimate; 8-byte stores in the wide form)
@@ -694,21 +810,29 @@ hipError_t launch_normalize_zconv(const long long* num, const double* qscale, co
     const int clip = lo <= hi ? 1 : 0;
     const float* nul = nullptr;
     float* nulw = nullptr;
-    if (wide && out_u16) {
+    uint16_t* nul16 = nullptr;
+    if (pg && !out_u16) return hipErrorInvalidValue;
+    if (pg && wide) {
+        hipLaunchKernelGGL((normalize_zconv_kernel<4, true, EpiPg>), grid, dim3(EW_THREADS), 0, s, num, qscale, txy,
+                           out, nlines, plane, nz, w, lo, hi, clip, offset, nul, nulw, nul16, 0.0f, EpiPg{*pg});
+    } else if (pg) {
+        hipLaunchKernelGGL((normalize_zconv_kernel<1, true, EpiPg>), grid, dim3(EW_THREADS), 0, s, num, qscale, txy,
+                           out, nlines, plane, nz, w, lo, hi, clip, offset, nul, nulw, nul16, 0.0f, EpiPg{*pg});
+    } else if (wide && out_u16) {
         hipLaunchKernelGGL((normalize_zconv_kernel<4, true>), grid, dim3(EW_THREADS), 0, s, num, qscale, txy, out,
-                           nlines, plane, nz, w, lo, hi, clip, offset, nul, nulw, nullptr, 0.0f);
+                           nlines, plane, nz, w, lo, hi, clip, offset, nul, nulw, nullptr, 0.0f, EpiOffset{});
     } else if (wide) {
         const bool pw = pair_src && pair_out && ((uintptr_t)pair_src & 15u) == 0 && ((uintptr_t)pair_out & 15u) == 0;
         hipLaunchKernelGGL((normalize_zconv_kernel<4, false>), grid, dim3(EW_THREADS), 0, s, num, qscale, txy, out,
                            nlines, plane, nz, w, lo, hi, clip, offset, pw ? pair_src : nul, pw ? pair_out : nulw,
-                           match16, match_offset);
+                           match16, match_offset, EpiOffset{});
         if (pair_written && pw) *pair_written = 1;
     } else if (out_u16) {
         hipLaunchKernelGGL((normalize_zconv_kernel<1, true>), grid, dim3(EW_THREADS), 0, s, num, qscale, txy, out,
-                           nlines, plane, nz, w, lo, hi, clip, offset, nul, nulw, nullptr, 0.0f);
+                           nlines, plane, nz, w, lo, hi, clip, offset, nul, nulw, nullptr, 0.0f, EpiOffset{});
     } else {
         hipLaunchKernelGGL((normalize_zconv_kernel<1, false>), grid, dim3(EW_THREADS), 0, s, num, qscale, txy, out,
-                           nlines, plane, nz, w, lo, hi, clip, offset, nul, nulw, match16, match_offset);
+                           nlines, plane, nz, w, lo, hi, clip, offset, nul, nulw, match16, match_offset, EpiOffset{});
     }
     return hipGetLastError();
 }
@@ -813,6 +937,12 @@ hipError_t launch_round_counts(const float* in, float* out_f32, uint16_t* out_u1
 hipError_t launch_normalize_u16(const float* num, const float* den, uint16_t* out, size_t n,
                                 float offset, hipStream_t s) {
     return launch_stream(OpNormalizeU16{num, den, out, offset}, n, aligned16(num, den, out), s);
+}
+hipError_t launch_pg_forward_u16(const PgDev& t, const uint16_t* in, float* out, size_t n, hipStream_t s) {
+    return launch_stream(OpPgForwardU16{t, in, out}, n, aligned16(in, out), s);
+}
+hipError_t launch_pg_inverse_u16(const PgDev& t, const float* in, uint16_t* out, size_t n, hipStream_t s) {
+    return launch_stream(OpPgInverseU16{t, in, out}, n, aligned16(in, out), s);
 }
 hipError_t launch_tf_forward_u16(const TfDev& t, const uint16_t* in, float* out, size_t n,
                                  hipStream_t s) {

@@ -16,6 +16,19 @@ struct TfDev {
     float mn, fden, clip, range;                      // linear: mn, mx-mn+1e-8, clip, mx-mn
 };
 
+// Poisson-Gaussian stabilisation: the un-normalised generalised Anscombe transform D of a uint16
+// count and its three inverses.  Every constant is computed in double from the caller's fp32 gain, read noise and
+// offset and rounded once.
+struct PgDev {
+    int inverse;                                      // 0 algebraic (3/8), 1 asymptotic (1/8), 2 closed form
+    float gain, off, c38g2, rn2, two_over_gain;       // forward; gain, off, rn2 also in the inverses
+    float cg2;                                        // inverse 0 / 1: c gain^2
+    float d0, s2, k1, k2, k3;                         // closed form: 2 sqrt(3/8), (read_noise / gain)^2,
+                                                      // sqrt(3/2)/4, 11/8, 5 sqrt(3/2)/8
+};
+hipError_t launch_pg_forward_u16(const PgDev& t, const uint16_t* in, float* out, size_t n, hipStream_t s);
+hipError_t launch_pg_inverse_u16(const PgDev& t, const float* in, uint16_t* out, size_t n, hipStream_t s);
+
 hipError_t launch_normalize(const float* num, const float* den, float* out, size_t n, float lo,
                             float hi, hipStream_t s);
 hipError_t launch_counts_from_u16(const uint16_t* in, float* out, size_t n, float offset,
@@ -123,7 +136,10 @@ hipError_t launch_normalize_zconv(const long long* num, const double* qscale, co
                                   // match16 (optional, unclipped fp32 output only): also the estimate rounded to
                                   // counts XOR 0x8000, rint(clamp(out + match_offset, 0, 65535))
                                   uint16_t* match16 = nullptr, float match_offset = 0.0f,
-                                  int* match_written = nullptr);
+                                  int* match_written = nullptr,
+                                  // pg (optional, uint16 output only): the quotient is a stabilised value and the
+                                  // count is quantise(pg inverse) instead of quantise(+ offset)
+                                  const PgDev* pg = nullptr);
 // BM4DNet stage: GroupNorm + LeakyReLU on an NDHWC tensor x[batch][spatial][C] (nn_kernels.hip); y may be x.
 // Requires C % 4 == 0, (C / G) % 4 == 0, 256 % (C / 4) == 0, G <= 32.  T: float, _Float16 or __bf16 (the
 // storage of torch.bfloat16); gamma, beta, cbias and the workspace's statistics are fp32 / fp64 for all three.
@@ -159,6 +175,11 @@ hipError_t launch_chunk_gather(const uint16_t* in, const ChunkBatch& cb, float o
                                hipStream_t s, uint16_t* out16 = nullptr);
 hipError_t launch_chunk_scatter(const float* est, const ChunkBatch& cb, float offset, uint16_t* out,
                                 hipStream_t s);
+// The same pair for the stabilised pipeline: gather u16 -> D, scatter D -> inverse -> u16.
+hipError_t launch_chunk_gather_pg(const uint16_t* in, const ChunkBatch& cb, const PgDev& t, float* out,
+                                  hipStream_t s);
+hipError_t launch_chunk_scatter_pg(const float* est, const ChunkBatch& cb, const PgDev& t, uint16_t* out,
+                                   hipStream_t s);
 
 // ---- chunk entropy coder (rans_kernels.hip) ----------------------------------------
 struct CodecGeom {

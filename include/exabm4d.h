@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define EXABM4D_VERSION 400 /* additive within 400: + exabm4d_dctq_ladder_errors_dev, exabm4d_bounded_volume_bound, exabm4d_bounded_encode_dev, exabm4d_bounded_decode_dev (error-bounded lossy chunk codec); + exabm4d_foreground_masks_dev, exabm4d_binary_dilate_dev, exabm4d_gaussian_filter3d_dev, exabm4d_label_set_dev, exabm4d_segment_stats_dev (patch-cache masks and coherence gate); + exabm4d_groupnorm_lrelu_ndhwc_dt_dev, exabm4d_maxpool2_ndhwc_dt_dev, exabm4d_upsample2_trilinear_ndhwc_dt_dev (fp16 / bf16 BM4DNet kernels); 0.4.0 (round 4): order-independent aggregation -- exabm4d_stage_dev takes data_exp and WRITES num / den, options "stage_pairs" / "stage_quads" / "fuse_den_z" are gone, the stage / block-matching options are per context; 0.3.2: + exabm4d_blockmatch_plan, option "stage_strip"; 0.3.1: + exabm4d_denoise_chunked_u16_host, options "bm_carry" / "bm_xcd_mode"; 0.3.0: EXAC v2 coder, exabm4d_codec_decode_dev takes in_bytes (round 3) */
+#define EXABM4D_VERSION 400 /* additive within 400: + exabm4d_pg_noise, exabm4d_denoise_pg_u16_dev, exabm4d_denoise_pg_chunked_u16_dev / _host, exabm4d_gat_forward_u16_dev, exabm4d_gat_inverse_u16_dev (denoising under Poisson-Gaussian noise); + exabm4d_dctq_ladder_errors_dev, exabm4d_bounded_volume_bound, exabm4d_bounded_encode_dev, exabm4d_bounded_decode_dev (error-bounded lossy chunk codec); + exabm4d_foreground_masks_dev, exabm4d_binary_dilate_dev, exabm4d_gaussian_filter3d_dev, exabm4d_label_set_dev, exabm4d_segment_stats_dev (patch-cache masks and coherence gate); + exabm4d_groupnorm_lrelu_ndhwc_dt_dev, exabm4d_maxpool2_ndhwc_dt_dev, exabm4d_upsample2_trilinear_ndhwc_dt_dev (fp16 / bf16 BM4DNet kernels); 0.4.0 (round 4): order-independent aggregation -- exabm4d_stage_dev takes data_exp and WRITES num / den, options "stage_pairs" / "stage_quads" / "fuse_den_z" are gone, the stage / block-matching options are per context; 0.3.2: + exabm4d_blockmatch_plan, option "stage_strip"; 0.3.1: + exabm4d_denoise_chunked_u16_host, options "bm_carry" / "bm_xcd_mode"; 0.3.0: EXAC v2 coder, exabm4d_codec_decode_dev takes in_bytes (round 3) */
 
 typedef enum exabm4d_status {
     EXABM4D_OK = 0,
@@ -303,6 +303,52 @@ int exabm4d_denoise_chunked_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, uint16
 int exabm4d_denoise_chunked_u16_host(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out, int nz, int ny,
                                      int nx, int chunk, int halo, float sigma, float offset,
                                      const exabm4d_params* p, int stages);
+/* ---- BM4D under Poisson-Gaussian noise --------------------------------------------------------
+ * sCMOS counts follow var = gain (mean - offset) + read_noise^2, which no single sigma describes.  These entry
+ * points stabilise the counts, denoise at sigma = 1 and invert, on the device in one call:
+ *   forward  D = (2 / gain) sqrt(max(gain (v - offset) + 3 gain^2 / 8 + read_noise^2, 0))       (unit noise sigma)
+ *   denoise  the fp32 pipeline of exabm4d_denoise_f32_dev on D with sigma = 1, no clip (both matching passes in
+ *            the float kernels, the numerator's unit per volume from the data)
+ *   inverse  0 algebraic:  offset + (((max(D,0) gain / 2)^2 - 3 gain^2 / 8) - read_noise^2) / gain
+ *            1 asymptotic: the same with 1 / 8 (AnscombeTransform(unbiased_inverse=True); biased at low counts)
+ *            2 closed form (Makitalo & Foi's approximation of the exact unbiased inverse; the default of the
+ *              Python surface): d = max(D, d0), d0 = 2 sqrt(3/8),
+ *              y = d^2/4 + (sqrt(3/2)/4)/d - (11/8)/d^2 + (5 sqrt(3/2)/8)/d^3 - 1/8 - (read_noise/gain)^2,
+ *              offset + gain max(y, 0)
+ *            then clamp to [0, 65535], rint, uint16.
+ * All of it is fp32, one rounding per operation, constants formed in double from the struct's floats and rounded
+ * once; tests/pg_pyref.py fixes the order of the operations, and the result equals that composition with the
+ * oracle's fp32 pipeline bit for bit.  gain > 0, read_noise >= 0, |offset| <= 65536, all finite, inverse in
+ * {0, 1, 2}; anything else is EXABM4D_ERR_INVALID before a launch. */
+enum { EXABM4D_PG_INVERSE_ALGEBRAIC = 0, EXABM4D_PG_INVERSE_ASYMPTOTIC = 1, EXABM4D_PG_INVERSE_CLOSED_FORM = 2 };
+typedef struct exabm4d_pg_noise {
+    uint32_t size;        /* = sizeof(exabm4d_pg_noise)                                     */
+    float gain;           /* counts per photo-electron: slope of variance against mean     */
+    float read_noise;     /* standard deviation of the signal-independent part, counts     */
+    float offset;         /* pedestal, counts                                               */
+    int32_t inverse;      /* EXABM4D_PG_INVERSE_*                                           */
+} exabm4d_pg_noise;
+/* Whole volume, or a batch of volumes back to back; in / out are device pointers and may alias.  Scratch: that of
+ * exabm4d_denoise_u16_dev.  The inverse rides in the last normalisation: the estimate never exists as fp32 in
+ * HBM. */
+int exabm4d_denoise_pg_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out, int nz, int ny, int nx,
+                               int batch, const exabm4d_pg_noise* noise, const exabm4d_params* p, int stages);
+/* Chunk-local mode and its host-streamed form: the geometry of exabm4d_denoise_chunked_u16_dev / _host, every
+ * padded chunk through the stabilised pipeline above in isolation. */
+int exabm4d_denoise_pg_chunked_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out, int nz, int ny,
+                                       int nx, int zc0, int zc1, int chunk, int halo,
+                                       const exabm4d_pg_noise* noise, const exabm4d_params* p, int stages);
+int exabm4d_denoise_pg_chunked_u16_host(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out, int nz, int ny,
+                                        int nx, int chunk, int halo, const exabm4d_pg_noise* noise,
+                                        const exabm4d_params* p, int stages);
+/* The two streams on their own (parity hooks): out = D of n counts; out = the chosen inverse of n stabilised
+ * values, quantised.  Pointer contract of exabm4d_counts_from_u16_dev (natural alignment suffices; 16-byte
+ * aligned pointers run eight voxels per lane, the same bits).  A NaN inverts like D = 0: fmaxf drops it. */
+int exabm4d_gat_forward_u16_dev(exabm4d_ctx* ctx, const exabm4d_pg_noise* noise, const uint16_t* in, float* out,
+                                size_t n);
+int exabm4d_gat_inverse_u16_dev(exabm4d_ctx* ctx, const exabm4d_pg_noise* noise, const float* in, uint16_t* out,
+                                size_t n);
+
 /* Host-pointer form of exabm4d_denoise_f32_dev (the bm4d(z, sigma) shim calls this). */
 int exabm4d_denoise_f32_host(exabm4d_ctx* ctx, const float* in, float* out, int nz, int ny, int nx,
                              int batch, float sigma, const exabm4d_params* p, int stages,
