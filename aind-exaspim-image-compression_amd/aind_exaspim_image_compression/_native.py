@@ -164,6 +164,18 @@ SIGNATURES = {
                                                    c_vp, _SZ, c_vp]),
     "exabm4d_maxpool2_ndhwc_dt_dev": (_I, [_CTX, c_vp, _I, c_vp, c_vp, _I, _I, _I, _I, _I]),
     "exabm4d_upsample2_trilinear_ndhwc_dt_dev": (_I, [_CTX, c_vp, _I, c_vp, c_vp, _I, _I, _I, _I, _I]),
+    "exabm4d_groupnorm_lrelu_ndhwc_train_dev": (_I, [_CTX, c_vp, c_vp, c_vp, _I, _SZ, _I, _I, c_vp, c_vp, _F, _F, c_vp,
+                                                      _SZ, c_vp]),
+    "exabm4d_groupnorm_lrelu_bwd_workspace_bytes": (_SZ, [_I, _SZ, _I, _I]),
+    "exabm4d_groupnorm_lrelu_bwd_ndhwc_dev": (_I, [_CTX, c_vp, c_vp, c_vp, c_vp, c_vp, _I, _SZ, _I, _I, c_vp, c_vp, _F,
+                                                    c_vp, c_vp, c_vp, _SZ]),
+    "exabm4d_maxpool2_bwd_ndhwc_dev": (_I, [_CTX, c_vp, c_vp, c_vp, c_vp, _I, _I, _I, _I, _I]),
+    "exabm4d_upsample2_trilinear_bwd_ndhwc_dev": (_I, [_CTX, c_vp, c_vp, c_vp, _I, _I, _I, _I, _I]),
+    "exabm4d_charbonnier_workspace_bytes": (_SZ, []),
+    "exabm4d_charbonnier_loss_dev": (_I, [_CTX, c_vp, c_vp, c_vp, c_vp, _I, _SZ, ctypes.c_double, ctypes.c_double,
+                                           c_vp, _SZ, c_vp]),
+    "exabm4d_charbonnier_loss_bwd_dev": (_I, [_CTX, c_vp, c_vp, c_vp, c_vp, _I, _SZ, ctypes.c_double,
+                                               ctypes.c_double, c_vp, c_vp]),
     "exabm4d_host_register": (_I, [_CTX, c_vp, ctypes.c_size_t]),
     "exabm4d_host_unregister": (_I, [_CTX, c_vp]),
     "exabm4d_transform_forward_u16_dev": (_I, [_CTX, _TP, c_vp, c_vp, _SZ]),
@@ -584,6 +596,44 @@ class Context:
         self._check(lib().exabm4d_upsample2_trilinear_ndhwc_dt_dev(self.handle, int(stream), int(dtype), _ptr(x),
                                                                    _ptr(y), int(batch), int(d), int(h), int(w),
                                                                    int(channels)))
+
+    # -- BM4DNet training (fp32 NDHWC; see the header) -------------------------------------------
+    def groupnorm_lrelu_ndhwc_train(self, stream, x, y, batch, spatial, channels, groups, gamma, beta, eps, slope,
+                                    workspace, workspace_bytes, mean_rstd):
+        """The fp32 forward that also writes ``mean_rstd[batch][groups][2]`` for the backward."""
+        self._check(lib().exabm4d_groupnorm_lrelu_ndhwc_train_dev(
+            self.handle, int(stream), _ptr(x), _ptr(y), int(batch), int(spatial), int(channels), int(groups),
+            _ptr(gamma), _ptr(beta), float(eps), float(slope), _ptr(workspace), int(workspace_bytes),
+            _ptr(mean_rstd)))
+
+    def groupnorm_lrelu_bwd_ndhwc(self, stream, x, y, dy, dx, batch, spatial, channels, groups, gamma, mean_rstd,
+                                  slope, dgamma, dbeta, workspace, workspace_bytes):
+        self._check(lib().exabm4d_groupnorm_lrelu_bwd_ndhwc_dev(
+            self.handle, int(stream), _ptr(x), _ptr(y), _ptr(dy), _ptr(dx), int(batch), int(spatial), int(channels),
+            int(groups), _ptr(gamma), _ptr(mean_rstd), float(slope), _ptr(dgamma), _ptr(dbeta), _ptr(workspace),
+            int(workspace_bytes)))
+
+    def maxpool2_bwd_ndhwc(self, stream, x, dy, dx, batch, d, h, w, channels):
+        """``d, h, w``: the extents of the forward's input ``x`` (and of ``dx``)."""
+        self._check(lib().exabm4d_maxpool2_bwd_ndhwc_dev(self.handle, int(stream), _ptr(x), _ptr(dy), _ptr(dx),
+                                                         int(batch), int(d), int(h), int(w), int(channels)))
+
+    def upsample2_trilinear_bwd_ndhwc(self, stream, dy, dx, batch, d, h, w, channels):
+        """``d, h, w``: the extents of the forward's input (of ``dx``); ``dy`` has twice each."""
+        self._check(lib().exabm4d_upsample2_trilinear_bwd_ndhwc_dev(self.handle, int(stream), _ptr(dy), _ptr(dx),
+                                                                    int(batch), int(d), int(h), int(w),
+                                                                    int(channels)))
+
+    def charbonnier_loss(self, stream, pred, target, mask, mask_bytes, n, fg_weight, eps, workspace,
+                         workspace_bytes, loss):
+        self._check(lib().exabm4d_charbonnier_loss_dev(
+            self.handle, int(stream), _ptr(pred), _ptr(target), _ptr(mask), int(mask_bytes), int(n),
+            float(fg_weight), float(eps), _ptr(workspace), int(workspace_bytes), _ptr(loss)))
+
+    def charbonnier_loss_bwd(self, stream, pred, target, mask, mask_bytes, n, fg_weight, eps, grad_loss, dpred):
+        self._check(lib().exabm4d_charbonnier_loss_bwd_dev(
+            self.handle, int(stream), _ptr(pred), _ptr(target), _ptr(mask), int(mask_bytes), int(n),
+            float(fg_weight), float(eps), _ptr(grad_loss), _ptr(dpred)))
 
     def host_register(self, addr, nbytes):
         """Page-lock caller memory that host entry points copy from / to repeatedly (see the header)."""

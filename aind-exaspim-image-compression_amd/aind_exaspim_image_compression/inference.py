@@ -19,6 +19,7 @@ import os
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from aind_exaspim_image_compression import _native
 from aind_exaspim_image_compression.machine_learning.transforms import (
@@ -92,6 +93,103 @@ def _miopen_defaults():
     os.environ.setdefault("MIOPEN_FIND_MODE", "2")
 
 
+def _stream(t):
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def _as_ndhwc(t):
+    """``t`` itself when its memory is dense NDHWC, else such a copy (a gradient arrives in any layout)."""
+    return t.contiguous(memory_format=torch.channels_last_3d)
+
+
+class _GroupNormLeakyReLUFn(torch.autograd.Function):
+    """``LeakyReLU(GroupNorm(x))`` on an fp32 NDHWC tensor with both directions in ``libexabm4d``
+    (csrc/nn_kernels.hip forward, which also writes the (mean, rstd) it used; csrc/nn_grad_kernels.hip
+    backward).  Out of place: the backward reads the input and the output."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, groups, eps, slope):
+        b, c = int(x.shape[0]), int(x.shape[1])
+        spatial = int(x.shape[2]) * int(x.shape[3]) * int(x.shape[4])
+        need = int(_native.lib().exabm4d_groupnorm_workspace_bytes(b, spatial, c, groups))
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        y = torch.empty_like(x, memory_format=torch.channels_last_3d)
+        stats = torch.empty((b, groups, 2), dtype=torch.float32, device=x.device)
+        _native.context(x.device.index or 0).groupnorm_lrelu_ndhwc_train(
+            _stream(x), x, y, b, spatial, c, groups, weight, bias, eps, slope, ws, need, stats)
+        ctx.save_for_backward(x, y, weight, stats)
+        ctx.groups, ctx.slope = groups, slope
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, y, weight, stats = ctx.saved_tensors
+        b, c = int(x.shape[0]), int(x.shape[1])
+        spatial = int(x.shape[2]) * int(x.shape[3]) * int(x.shape[4])
+        dy = _as_ndhwc(dy)
+        dx = torch.empty_like(x, memory_format=torch.channels_last_3d)
+        want_w = weight is not None and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        dgamma = torch.empty_like(weight) if want_w else None
+        dbeta = torch.empty_like(weight) if want_w else None
+        need = int(_native.lib().exabm4d_groupnorm_lrelu_bwd_workspace_bytes(b, spatial, c, ctx.groups))
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        _native.context(x.device.index or 0).groupnorm_lrelu_bwd_ndhwc(
+            _stream(x), x, y, dy, dx, b, spatial, c, ctx.groups, weight, stats, ctx.slope, dgamma, dbeta, ws, need)
+        return dx, dgamma, dbeta, None, None, None
+
+
+class _MaxPool2Fn(torch.autograd.Function):
+    """``MaxPool3d(2)`` on an fp32 NDHWC tensor; the backward re-reads the input's windows instead of storing
+    indices (csrc/nn_grad_kernels.hip: torch's choice among ties and NaNs)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        b, c, d, h, w = (int(v) for v in x.shape)
+        y = torch.empty((b, c, d // 2, h // 2, w // 2), dtype=x.dtype, device=x.device,
+                        memory_format=torch.channels_last_3d)
+        _native.context(x.device.index or 0).maxpool2_ndhwc(_stream(x), x, y, b, d, h, w, c)
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, = ctx.saved_tensors
+        b, c, d, h, w = (int(v) for v in x.shape)
+        dx = torch.empty_like(x, memory_format=torch.channels_last_3d)
+        _native.context(x.device.index or 0).maxpool2_bwd_ndhwc(_stream(x), x, _as_ndhwc(dy), dx, b, d, h, w, c)
+        return dx
+
+
+class _Upsample2Fn(torch.autograd.Function):
+    """Trilinear x2 up-sampling (align_corners) on an fp32 NDHWC tensor and its transpose."""
+
+    @staticmethod
+    def forward(ctx, x):
+        b, c, d, h, w = (int(v) for v in x.shape)
+        y = torch.empty((b, c, 2 * d, 2 * h, 2 * w), dtype=x.dtype, device=x.device,
+                        memory_format=torch.channels_last_3d)
+        _native.context(x.device.index or 0).upsample2_trilinear_ndhwc(_stream(x), x, y, b, d, h, w, c)
+        ctx.dims = (b, c, d, h, w)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        b, c, d, h, w = ctx.dims
+        dx = torch.empty((b, c, d, h, w), dtype=dy.dtype, device=dy.device, memory_format=torch.channels_last_3d)
+        _native.context(dy.device.index or 0).upsample2_trilinear_bwd_ndhwc(_stream(dy), _as_ndhwc(dy), dx, b, d,
+                                                                            h, w, c)
+        return dx
+
+
+def _trainable_input(x):
+    """What the training path of the NDHWC modules takes: gradients on, an fp32 CUDA NDHWC tensor."""
+    return (torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5
+            and x.is_contiguous(memory_format=torch.channels_last_3d))
+
+
 class FusedGroupNormLeakyReLU(torch.nn.Module):
     """``GroupNorm`` followed by ``LeakyReLU`` as ONE module for inference on NDHWC tensors: the pair of the
     reference's ``DoubleConv`` (unet3d.py:137-208) through ``exabm4d_groupnorm_lrelu_ndhwc_dev`` -- statistics,
@@ -99,9 +197,12 @@ class FusedGroupNormLeakyReLU(torch.nn.Module):
     convolution's output (``inplace``) or into a new tensor.  PyTorch's own GroupNorm wants NCDHW: per layer a
     layout copy in, statistics, apply, the activation and a layout copy back (45 % of the forward's kernel time).
     Falls back to the framework's two modules for anything the kernels do not take (training, other dtypes /
-    layouts / channel counts); the fallback never writes into its input."""
+    layouts / channel counts); the fallback never writes into its input.  ``trainable=True`` adds a path for
+    training: with gradients enabled, an fp32 CUDA NDHWC input of a supported shape runs ``_GroupNormLeakyReLUFn``,
+    whose backward is ``libexabm4d``'s too (out of place; needs ``negative_slope > 0`` and the convolution's bias
+    left in the convolution); half-precision tensors under gradients always fall back."""
 
-    def __init__(self, norm, act, conv_bias=None, half=False, inplace=True):
+    def __init__(self, norm, act, conv_bias=None, half=False, inplace=True, trainable=False):
         """``conv_bias``: the bias of the convolution in front, taken over from it (the caller sets that
         convolution's ``bias`` to None): added inside the kernels instead of in a pass of its own.
         ``half``: also take fp16 / bf16 tensors (the half-width kernels; gamma, beta and the bias stay fp32) --
@@ -114,6 +215,7 @@ class FusedGroupNormLeakyReLU(torch.nn.Module):
         self.conv_bias = conv_bias
         self.half = half
         self.inplace = inplace
+        self.trainable = trainable
         self._ws = None
 
     @property
@@ -125,6 +227,9 @@ class FusedGroupNormLeakyReLU(torch.nn.Module):
 
     def forward(self, x):
         n = self.norm
+        if (self.trainable and _trainable_input(x) and self.native_channels and x.shape[0] <= 65535
+                and n.affine and self.conv_bias is None and self.act.negative_slope > 0):
+            return _GroupNormLeakyReLUFn.apply(x, n.weight, n.bias, n.num_groups, n.eps, self.act.negative_slope)
         code = _native_dtype(x.dtype, self.half)
         fused = (not self.training and x.is_cuda and code is not None and x.dim() == 5
                  and x.is_contiguous(memory_format=torch.channels_last_3d) and not torch.is_grad_enabled()
@@ -155,12 +260,14 @@ class _ResampleNDHWC(torch.nn.Module):
     NDHWC tensors through ``libexabm4d`` (csrc/nn_kernels.hip: a float4 of channels per thread).  PyTorch's own
     kernels for the two walk an NDHWC tensor through generic strides (3.8 ms per call on this U-Net's tensors);
     anything else -- other parameters, layouts, dtypes, training -- runs ``inner`` on an NCDHW copy.  ``half``: as
-    for ``FusedGroupNormLeakyReLU``, fp16 / bf16 tensors run natively too."""
+    for ``FusedGroupNormLeakyReLU``, fp16 / bf16 tensors run natively too.  ``trainable=True``: with gradients
+    enabled, an fp32 CUDA NDHWC input runs ``_MaxPool2Fn`` / ``_Upsample2Fn`` (native forward and backward)."""
 
-    def __init__(self, inner, half=False):
+    def __init__(self, inner, half=False, trainable=False):
         super().__init__()
         self.inner = inner
         self.half = half
+        self.trainable = trainable
         m = inner
         if isinstance(m, torch.nn.MaxPool3d):
             ok = (_all_equal(m.kernel_size, 2) and _all_equal(m.stride if m.stride is not None else m.kernel_size, 2)
@@ -175,6 +282,11 @@ class _ResampleNDHWC(torch.nn.Module):
             self.kind = None
 
     def forward(self, x):
+        if self.trainable and self.kind is not None and _trainable_input(x) and x.shape[1] % 4 == 0:
+            if self.kind == "up":
+                return _Upsample2Fn.apply(x)
+            if min(x.shape[2:]) >= 2:
+                return _MaxPool2Fn.apply(x)
         code = _native_dtype(x.dtype, self.half)
         native = (self.kind is not None and not self.training and not torch.is_grad_enabled() and x.is_cuda
                   and code is not None and x.dim() == 5 and x.shape[1] % 4 == 0
@@ -194,11 +306,13 @@ class _ResampleNDHWC(torch.nn.Module):
         return y
 
 
-def _fuse_norm_act(module, half=False):
+def _fuse_norm_act(module, half=False, trainable=False):
     """Replace every (GroupNorm, LeakyReLU) neighbour pair inside ``nn.Sequential`` containers of ``module`` by
     a ``FusedGroupNormLeakyReLU`` + ``Identity`` (same positions: the copy's parameters are the pair's), and
     put every ``MaxPool3d`` / ``Upsample`` behind ``_ResampleNDHWC``.  For the private copy ``_ndhwc_shadow`` makes;
     its ``state_dict`` keys are not the model's any more.  ``half``: the new modules take fp16 / bf16 too.
+    ``trainable`` (``machine_learning.train.trainable_ndhwc``): the new modules get ``trainable=True``, every pair
+    writes a new tensor and every convolution keeps its bias (its gradient is then the convolution's business).
 
     What the rewrite can see is the module tree, so it stays correct only where the tree tells the data flow:
       * a pair runs in place only right behind a ``Conv3d`` in the same container (a fresh output nobody else
@@ -218,7 +332,7 @@ def _fuse_norm_act(module, half=False):
     for parent in list(module.modules()):            # unique modules; the wrappers made below are not revisited
         for name, child in list(parent._modules.items()):
             if isinstance(child, (torch.nn.MaxPool3d, torch.nn.Upsample)):
-                setattr(parent, name, _ResampleNDHWC(child, half).train(parent.training))
+                setattr(parent, name, _ResampleNDHWC(child, half, trainable).train(parent.training))
         if not isinstance(parent, torch.nn.Sequential):
             continue
         for i in range(len(parent) - 1):
@@ -227,11 +341,12 @@ def _fuse_norm_act(module, half=False):
                 conv = parent[i - 1] if i > 0 else None
                 after_conv = isinstance(conv, torch.nn.Conv3d)
                 bias = None
-                if (after_conv and conv.bias is not None and conv.out_channels == a.num_channels
-                        and len(slots[id(conv)]) == 1):
+                if (not trainable and after_conv and conv.bias is not None
+                        and conv.out_channels == a.num_channels and len(slots[id(conv)]) == 1):
                     bias, conv.bias = conv.bias, None             # added inside the fused kernels instead
                 # (a new module starts in training mode)
-                parent[i] = FusedGroupNormLeakyReLU(a, b, bias, half, inplace=after_conv).train(parent.training)
+                parent[i] = FusedGroupNormLeakyReLU(a, b, bias, half, inplace=after_conv and not trainable,
+                                                    trainable=trainable).train(parent.training)
                 parent[i + 1] = torch.nn.Identity().train(parent.training)
     return module
 

@@ -138,6 +138,109 @@ int exabm4d_upsample2_trilinear_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, co
                                                     channels);
 }
 
+// ---- BM4DNet training: the forward that keeps its statistics, the three backward passes, the loss (nn_grad_kernels.hip)
+static int gn_shape_checks(exabm4d_ctx* ctx, int batch, size_t spatial, int channels, int groups, const char* unsup) {
+    if (batch < 1 || batch > 65535 || spatial < 1 || channels < 4 || groups < 1 || groups > 32 ||
+        channels % groups != 0 || channels % 4 != 0 || (channels / groups) % 4 != 0 || 256 % (channels / 4) != 0)
+        return fail(ctx, EXABM4D_ERR_UNSUPPORTED, unsup);
+    return EXABM4D_OK;
+}
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+int exabm4d_groupnorm_lrelu_ndhwc_train_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, float* y, int batch,
+                                            size_t spatial, int channels, int groups, const float* gamma,
+                                            const float* beta, float eps, float slope, void* workspace,
+                                            size_t workspace_bytes, float* mean_rstd) {
+    if (!ctx || !x || !y || !workspace || !mean_rstd) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (int rc = gn_shape_checks(ctx, batch, spatial, channels, groups,
+                                 "groupnorm_lrelu_ndhwc_train: needs channels % 4 == 0, (channels / groups) % 4 == 0, "
+                                 "256 % (channels / 4) == 0 and groups <= 32"))
+        return rc;
+    if (!(slope > 0.0f))
+        return fail(ctx, EXABM4D_ERR_UNSUPPORTED,
+                    "groupnorm_lrelu_ndhwc_train: slope must be > 0 (the backward reads the side from y)");
+    if (workspace_bytes < groupnorm_workspace_bytes(batch, spatial, channels, groups))
+        return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_ndhwc_train: workspace too small");
+    if (!aligned16(x) || !aligned16(y) || !aligned16(workspace))
+        return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_ndhwc_train: 16-byte aligned tensors expected");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = launch_groupnorm_lrelu_ndhwc(x, y, batch, spatial, channels, groups, gamma, beta, eps, slope,
+                                                      workspace, (hipStream_t)hip_stream, nullptr, mean_rstd);
+    return e == hipSuccess ? EXABM4D_OK : fail_hip(ctx, e, "launch_groupnorm_lrelu_ndhwc");
+}
+size_t exabm4d_groupnorm_lrelu_bwd_workspace_bytes(int batch, size_t spatial, int channels, int groups) {
+    if (batch < 1 || spatial < 1 || channels < 4 || groups < 1 || channels % 4 != 0 || 256 % (channels / 4) != 0)
+        return 0;
+    return groupnorm_bwd_workspace_bytes(batch, spatial, channels, groups);
+}
+int exabm4d_groupnorm_lrelu_bwd_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, const float* y,
+                                          const float* dy, float* dx, int batch, size_t spatial, int channels,
+                                          int groups, const float* gamma, const float* mean_rstd, float slope,
+                                          float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes) {
+    if (!ctx || !x || !y || !dy || !dx || !mean_rstd || !workspace)
+        return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (int rc = gn_shape_checks(ctx, batch, spatial, channels, groups,
+                                 "groupnorm_lrelu_bwd_ndhwc: needs channels % 4 == 0, (channels / groups) % 4 == 0, "
+                                 "256 % (channels / 4) == 0 and groups <= 32"))
+        return rc;
+    if (!(slope > 0.0f))
+        return fail(ctx, EXABM4D_ERR_UNSUPPORTED,
+                    "groupnorm_lrelu_bwd_ndhwc: slope must be > 0 (the activation's side is read from y)");
+    if (workspace_bytes < groupnorm_bwd_workspace_bytes(batch, spatial, channels, groups))
+        return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_bwd_ndhwc: workspace too small");
+    if (!aligned16(x) || !aligned16(y) || !aligned16(dy) || !aligned16(dx) || !aligned16(workspace))
+        return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_bwd_ndhwc: 16-byte aligned tensors expected");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const hipError_t e =
+        launch_groupnorm_lrelu_bwd_ndhwc(x, y, dy, dx, batch, spatial, channels, groups, gamma, mean_rstd, slope,
+                                         dgamma, dbeta, workspace, (hipStream_t)hip_stream);
+    return e == hipSuccess ? EXABM4D_OK : fail_hip(ctx, e, "launch_groupnorm_lrelu_bwd_ndhwc");
+}
+int exabm4d_maxpool2_bwd_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, const float* dy, float* dx,
+                                   int batch, int d, int h, int w, int channels) {
+    if (!dy) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (int rc = nn_resample_checks(ctx, EXABM4D_DTYPE_F32, x, dx, batch, d, h, w, channels)) return rc;
+    if (d < 2 || h < 2 || w < 2) return fail(ctx, EXABM4D_ERR_UNSUPPORTED, "maxpool2_bwd_ndhwc: extents >= 2");
+    if (!aligned16(dy)) return fail(ctx, EXABM4D_ERR_INVALID, "NDHWC resampling: 16-byte aligned tensors expected");
+    const hipError_t e = launch_maxpool2_bwd_ndhwc(x, dy, dx, batch, d, h, w, channels, (hipStream_t)hip_stream);
+    return e == hipSuccess ? EXABM4D_OK : fail_hip(ctx, e, "launch_maxpool2_bwd_ndhwc");
+}
+int exabm4d_upsample2_trilinear_bwd_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* dy, float* dx,
+                                              int batch, int d, int h, int w, int channels) {
+    if (int rc = nn_resample_checks(ctx, EXABM4D_DTYPE_F32, dy, dx, batch, d, h, w, channels)) return rc;
+    const hipError_t e =
+        launch_upsample2_trilinear_bwd_ndhwc(dy, dx, batch, d, h, w, channels, (hipStream_t)hip_stream);
+    return e == hipSuccess ? EXABM4D_OK : fail_hip(ctx, e, "launch_upsample2_trilinear_bwd_ndhwc");
+}
+size_t exabm4d_charbonnier_workspace_bytes(void) { return charbonnier_workspace_bytes(); }
+static int charbonnier_checks(exabm4d_ctx* ctx, bool ptrs_ok, int mask_bytes, size_t n, double fg_weight, double eps) {
+    if (!ctx || !ptrs_ok) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (mask_bytes != 1 && mask_bytes != 4)
+        return fail(ctx, EXABM4D_ERR_UNSUPPORTED, "charbonnier_loss: mask elements of 1 (uint8 / bool) or 4 (fp32) bytes");
+    if (n < 1 || !(eps >= 0.0) || fg_weight != fg_weight)
+        return fail(ctx, EXABM4D_ERR_INVALID, "charbonnier_loss: n >= 1, eps >= 0 and a fg_weight that is a number");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return EXABM4D_OK;
+}
+int exabm4d_charbonnier_loss_dev(exabm4d_ctx* ctx, void* hip_stream, const float* pred, const float* target,
+                                 const void* mask, int mask_bytes, size_t n, double fg_weight, double eps,
+                                 void* workspace, size_t workspace_bytes, float* loss) {
+    if (int rc = charbonnier_checks(ctx, pred && target && workspace && loss, mask_bytes, n, fg_weight, eps)) return rc;
+    if (workspace_bytes < charbonnier_workspace_bytes() || ((uintptr_t)workspace & 7u) != 0)
+        return fail(ctx, EXABM4D_ERR_INVALID, "charbonnier_loss: workspace too small or not 8-byte aligned");
+    const hipError_t e = launch_charbonnier_loss(pred, target, mask, mask_bytes, n, fg_weight, eps, workspace, loss,
+                                                 (hipStream_t)hip_stream);
+    return e == hipSuccess ? EXABM4D_OK : fail_hip(ctx, e, "launch_charbonnier_loss");
+}
+int exabm4d_charbonnier_loss_bwd_dev(exabm4d_ctx* ctx, void* hip_stream, const float* pred, const float* target,
+                                     const void* mask, int mask_bytes, size_t n, double fg_weight, double eps,
+                                     const float* grad_loss, float* dpred) {
+    if (int rc = charbonnier_checks(ctx, pred && target && grad_loss && dpred, mask_bytes, n, fg_weight, eps)) return rc;
+    const hipError_t e = launch_charbonnier_loss_bwd(pred, target, mask, mask_bytes, n, fg_weight, eps, grad_loss,
+                                                     dpred, (hipStream_t)hip_stream);
+    return e == hipSuccess ? EXABM4D_OK : fail_hip(ctx, e, "launch_charbonnier_loss_bwd");
+}
+
 // ---- intensity transforms ---------------------------------------------------------------------------------
 int exabm4d_transform_forward_u16_dev(exabm4d_ctx* ctx, const exabm4d_transform* t,
                                       const uint16_t* in, float* out, size_t n) {

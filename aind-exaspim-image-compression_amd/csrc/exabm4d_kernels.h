@@ -147,12 +147,34 @@ size_t groupnorm_workspace_bytes(int batch, size_t spatial, int C, int G);
 template <typename T>
 hipError_t launch_groupnorm_lrelu_ndhwc(const T* x, T* y, int batch, size_t spatial, int C, int G,
                                         const float* gamma, const float* beta, float eps, float slope,
-                                        void* workspace, hipStream_t s, const float* cbias = nullptr);
+                                        void* workspace, hipStream_t s, const float* cbias = nullptr,
+                                        float* stats = nullptr);
 // MaxPool3d(2) (floor) and trilinear x2 up-sampling (align_corners) on NDHWC tensors of T (as above), C % 4 == 0
 template <typename T>
 hipError_t launch_maxpool2_ndhwc(const T* x, T* y, int batch, int D, int H, int W, int C, hipStream_t s);
 template <typename T>
 hipError_t launch_upsample2_trilinear_ndhwc(const T* x, T* y, int batch, int D, int H, int W, int C, hipStream_t s);
+// Backward passes of the three layers above and the training loss, fp32 (nn_grad_kernels.hip).  stats: the
+// [batch][G][2] = {mean, rstd} that launch_groupnorm_lrelu_ndhwc wrote; y: that forward's output; gamma, dgamma,
+// dbeta may be NULL; slope > 0.  The resampling gradients take the FORWARD INPUT's extents D, H, W (max-pool:
+// all >= 2); the max-pool's dx, [batch][D][H][W][C], is written completely.
+size_t groupnorm_bwd_workspace_bytes(int batch, size_t spatial, int C, int G);
+hipError_t launch_groupnorm_lrelu_bwd_ndhwc(const float* x, const float* y, const float* dy, float* dx, int batch,
+                                            size_t spatial, int C, int G, const float* gamma, const float* stats,
+                                            float slope, float* dgamma, float* dbeta, void* workspace,
+                                            hipStream_t s);
+hipError_t launch_maxpool2_bwd_ndhwc(const float* x, const float* dy, float* dx, int batch, int D, int H, int W,
+                                     int C, hipStream_t s);
+hipError_t launch_upsample2_trilinear_bwd_ndhwc(const float* dy, float* dx, int batch, int D, int H, int W, int C,
+                                                hipStream_t s);
+// mean((1 + w m) sqrt((pred - target)^2 + eps^2)) over n elements -> loss[0], and its gradient times grad_loss[0];
+// mask: NULL, or n elements of mask_bytes (4: float, 1: uint8 / bool) each
+size_t charbonnier_workspace_bytes();
+hipError_t launch_charbonnier_loss(const float* pred, const float* target, const void* mask, int mask_bytes,
+                                   size_t n, double w, double eps, void* workspace, float* loss, hipStream_t s);
+hipError_t launch_charbonnier_loss_bwd(const float* pred, const float* target, const void* mask, int mask_bytes,
+                                       size_t n, double w, double eps, const float* grad_loss, float* dpred,
+                                       hipStream_t s);
 // staged entry point: num_f = fl32(fl64(num) 2^(E - 43))
 hipError_t launch_num_to_float(const long long* num, const double* qscale, float* out, size_t nvox, int batch,
                                hipStream_t s);

@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "exabm4d_kernels.h"
+#include "nn_ndhwc.h"
 
 namespace exabm4d {
 
@@ -138,7 +139,10 @@ template <typename T>
 __global__ void gn_params_kernel(const double* __restrict__ part, int batch, int C, int G, int nchunk,
                                  double count, const float* __restrict__ gamma, const float* __restrict__ beta,
                                  float eps, float* __restrict__ a, float* __restrict__ shift,
-                                 const float* __restrict__ cbias, const T* __restrict__ x, size_t spatial) {
+                                 const float* __restrict__ cbias, const T* __restrict__ x, size_t spatial,
+                                 float* __restrict__ stats) {
+    // stats (optional): [batch][G][2] = {(float)mean, rstd}, the values the apply pass works with -- what a
+    // backward pass must use to normalise x as this forward did (nn_grad_kernels.hip)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= batch * C) return;
     const int b = i / C, c = i - b * C, cpg = C / G, g = c / cpg;
@@ -153,6 +157,10 @@ __global__ void gn_params_kernel(const double* __restrict__ part, int batch, int
     var = var < 0.0 ? 0.0 : var;                     // (a NaN stays NaN: a non-finite input makes the group NaN)
     const double mean = (double)group_pivot(x, spatial, C, b, g * cpg, cbias) + m;
     const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+    if (stats && c == g * cpg) {
+        stats[((size_t)b * G + g) * 2] = (float)mean;
+        stats[((size_t)b * G + g) * 2 + 1] = rstd;
+    }
     const float ga = gamma ? gamma[c] : 1.0f, be = beta ? beta[c] : 0.0f;
     const float av = rstd * ga;
     a[i] = av;
@@ -238,21 +246,6 @@ hipError_t launch_maxpool2_ndhwc(const T* x, T* y, int batch, int D, int H, int 
     return hipGetLastError();
 }
 
-// out extent = 2 * in; source coordinate r * o with r = (in - 1) / (out - 1) in fp32, i0 = (int)(r o),
-// i1 = i0 + (i0 < in - 1), weights (1 - lambda, lambda): PyTorch's upsample_trilinear3d with align_corners
-struct UpAxis {
-    int i0, i1;
-    float w0, w1;
-};
-__device__ __forceinline__ UpAxis up_axis(int o, int in, float r) {
-    const float src = r * (float)o;
-    UpAxis a;
-    a.i0 = (int)src;
-    a.i1 = a.i0 + (a.i0 < in - 1 ? 1 : 0);
-    a.w1 = src - (float)a.i0;
-    a.w0 = 1.0f - a.w1;
-    return a;
-}
 template <typename T>
 __global__ __launch_bounds__(GN_THREADS) void upsample2_ndhwc_kernel(const typename Pack<T>::type* __restrict__ x,
                                                                     typename Pack<T>::type* __restrict__ y,
@@ -290,12 +283,11 @@ hipError_t launch_upsample2_trilinear_ndhwc(const T* x, T* y, int batch, int D, 
     const int lanes = C / 4;
     const size_t total = (size_t)batch * (2 * (size_t)D) * (2 * (size_t)H) * (2 * (size_t)W) * lanes;
     if (total == 0) return hipSuccess;
-    auto ratio = [](int in) { return 2 * in > 1 ? (float)(in - 1) / (float)(2 * in - 1) : 0.0f; };
     size_t blocks = (total + GN_THREADS - 1) / GN_THREADS;
     if (blocks > 65536) blocks = 65536;
     hipLaunchKernelGGL(upsample2_ndhwc_kernel<T>, dim3((unsigned)blocks), dim3(GN_THREADS), 0, s,
                        reinterpret_cast<const typename Pack<T>::type*>(x), reinterpret_cast<typename Pack<T>::type*>(y),
-                       total, D, H, W, lanes, ratio(D), ratio(H), ratio(W));
+                       total, D, H, W, lanes, up_ratio(D), up_ratio(H), up_ratio(W));
     return hipGetLastError();
 }
 
@@ -307,7 +299,7 @@ size_t groupnorm_workspace_bytes(int batch, size_t spatial, int C, int G) {
 template <typename T>
 hipError_t launch_groupnorm_lrelu_ndhwc(const T* x, T* y, int batch, size_t spatial, int C, int G,
                                         const float* gamma, const float* beta, float eps, float slope,
-                                        void* workspace, hipStream_t s, const float* cbias) {
+                                        void* workspace, hipStream_t s, const float* cbias, float* stats) {
     const int lanes = C / 4;
     const int rows_per_iter = GN_THREADS / lanes;
     // chunks: enough workgroups for the chip (>= ~2048 in all), at least 2 * rows_per_iter rows each, at most 64
@@ -327,7 +319,7 @@ hipError_t launch_groupnorm_lrelu_ndhwc(const T* x, T* y, int batch, size_t spat
     const int total = batch * C;
     hipLaunchKernelGGL(gn_params_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, part, batch, C, G,
                        (int)nchunk, (double)spatial * (double)(C / G), gamma, beta, eps, a, shift, cbias, x,
-                       spatial);
+                       spatial, stats);
     const size_t n4 = spatial * (size_t)lanes;
     size_t blocks = (n4 + GN_THREADS - 1) / GN_THREADS;
     const size_t cap = (8192 + (size_t)batch - 1) / (size_t)batch;
@@ -343,7 +335,7 @@ hipError_t launch_groupnorm_lrelu_ndhwc(const T* x, T* y, int batch, size_t spat
 #define EXABM4D_NN_INSTANTIATE(T)                                                                                \
     template hipError_t launch_groupnorm_lrelu_ndhwc<T>(const T*, T*, int, size_t, int, int, const float*,        \
                                                         const float*, float, float, void*, hipStream_t,           \
-                                                        const float*);                                            \
+                                                        const float*, float*);                                    \
     template hipError_t launch_maxpool2_ndhwc<T>(const T*, T*, int, int, int, int, int, hipStream_t);             \
     template hipError_t launch_upsample2_trilinear_ndhwc<T>(const T*, T*, int, int, int, int, int, hipStream_t);
 EXABM4D_NN_INSTANTIATE(float)

@@ -405,6 +405,57 @@ int exabm4d_maxpool2_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype,
 int exabm4d_upsample2_trilinear_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* x, void* y,
                                              int batch, int d, int h, int w, int channels);
 
+/* ---- BM4DNet training on NDHWC, fp32 (csrc/nn_grad_kernels.hip): the backward halves of the three layers above
+ * and the reference's loss (machine_learning/losses.py).  All run on `hip_stream`, use no atomics and combine
+ * their fp64 partial sums in a fixed order, so each result is a deterministic function of its inputs.
+ *
+ * exabm4d_groupnorm_lrelu_ndhwc_train_dev: exabm4d_groupnorm_lrelu_ndhwc_dev without a conv_bias (the bias stays
+ * with the convolution when training), which also writes mean_rstd[batch][groups][2] = {mean, 1 / sqrt(var + eps)}
+ * in fp32 -- the two numbers its own apply pass used, so that the backward normalises x with the forward's bits.
+ * Same shape rules and workspace; slope must be > 0 (else EXABM4D_ERR_UNSUPPORTED), because the backward reads
+ * the activation's side from y.  y should not be x: the backward needs both.
+ *
+ * exabm4d_groupnorm_lrelu_bwd_ndhwc_dev: x (pre-norm), y (the forward's output), dy -> dx, and dgamma, dbeta
+ * [channels] (each may be NULL; gamma NULL: the non-affine module).  dz = dy (y > 0 ? 1 : slope) -- zero takes
+ * the slope; xh = (x - mean) rstd; dbeta = sum dz, dgamma = sum dz xh over batch and space;
+ * dx = rstd (gamma dz - m1 - xh m2), m1 and m2 the means over a (sample, group) of gamma dz and gamma dz xh.
+ * Two passes over (x, y, dy).  dx may be dy.  workspace: exabm4d_groupnorm_lrelu_bwd_workspace_bytes().
+ *
+ * exabm4d_maxpool2_bwd_ndhwc_dev: x[batch][d][h][w][channels] (the forward's input; d, h, w >= 2),
+ * dy[batch][d/2][h/2][w/2][channels] -> dx like x, every element written: dy at the position torch's max_pool3d
+ * selects (scan in (d, h, w) order, replace when v > max or v is NaN: the first of equal values, +0 == -0, the
+ * last NaN), 0 elsewhere, the trailing plane / row / column of an odd extent included.
+ *
+ * exabm4d_upsample2_trilinear_bwd_ndhwc_dev: dy[batch][2d][2h][2w][channels] -> dx[batch][d][h][w][channels], the
+ * transpose of exabm4d_upsample2_trilinear_ndhwc_dev with that kernel's own fp32 indices and weights.
+ *
+ * exabm4d_charbonnier_loss_dev: loss[0] = mean((1 + fg_weight m) sqrt((pred - target)^2 + eps^2)) over n elements
+ * in storage order, written on the device (no host synchronisation); mask: n elements of mask_bytes each
+ * (4: fp32, 1: uint8 / bool), or NULL for weight 1; n is a size_t and may exceed 2^32.  Each element is
+ * evaluated in fp64 and the sum rounded once.  workspace: exabm4d_charbonnier_workspace_bytes().
+ * exabm4d_charbonnier_loss_bwd_dev: dpred = grad_loss[0] (1 + fg_weight m) d / sqrt(d^2 + eps^2) / n, grad_loss
+ * read from device memory. */
+int exabm4d_groupnorm_lrelu_ndhwc_train_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, float* y, int batch,
+                                            size_t spatial, int channels, int groups, const float* gamma,
+                                            const float* beta, float eps, float slope, void* workspace,
+                                            size_t workspace_bytes, float* mean_rstd);
+size_t exabm4d_groupnorm_lrelu_bwd_workspace_bytes(int batch, size_t spatial, int channels, int groups);
+int exabm4d_groupnorm_lrelu_bwd_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, const float* y,
+                                          const float* dy, float* dx, int batch, size_t spatial, int channels,
+                                          int groups, const float* gamma, const float* mean_rstd, float slope,
+                                          float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes);
+int exabm4d_maxpool2_bwd_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, const float* dy, float* dx,
+                                   int batch, int d, int h, int w, int channels);
+int exabm4d_upsample2_trilinear_bwd_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* dy, float* dx,
+                                              int batch, int d, int h, int w, int channels);
+size_t exabm4d_charbonnier_workspace_bytes(void);
+int exabm4d_charbonnier_loss_dev(exabm4d_ctx* ctx, void* hip_stream, const float* pred, const float* target,
+                                 const void* mask, int mask_bytes, size_t n, double fg_weight, double eps,
+                                 void* workspace, size_t workspace_bytes, float* loss);
+int exabm4d_charbonnier_loss_bwd_dev(exabm4d_ctx* ctx, void* hip_stream, const float* pred, const float* target,
+                                     const void* mask, int mask_bytes, size_t n, double fg_weight, double eps,
+                                     const float* grad_loss, float* dpred);
+
 /* Page-lock `bytes` of caller memory at `ptr` that the host entry points will copy from / to repeatedly (the
  * broker registers every worker's shared-memory segment once): copies become DMA transfers instead of staged
  * ones.  Unregister before the memory is unmapped. */
