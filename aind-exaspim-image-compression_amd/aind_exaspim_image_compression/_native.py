@@ -171,6 +171,12 @@ SIGNATURES = {
                                                     c_vp, c_vp, c_vp, _SZ]),
     "exabm4d_maxpool2_bwd_ndhwc_dev": (_I, [_CTX, c_vp, c_vp, c_vp, c_vp, _I, _I, _I, _I, _I]),
     "exabm4d_upsample2_trilinear_bwd_ndhwc_dev": (_I, [_CTX, c_vp, c_vp, c_vp, _I, _I, _I, _I, _I]),
+    "exabm4d_groupnorm_lrelu_ndhwc_train_dt_dev": (_I, [_CTX, c_vp, _I, c_vp, c_vp, _I, _SZ, _I, _I, c_vp, c_vp, _F, _F,
+                                                         c_vp, _SZ, c_vp]),
+    "exabm4d_groupnorm_lrelu_bwd_ndhwc_dt_dev": (_I, [_CTX, c_vp, _I, c_vp, c_vp, c_vp, c_vp, _I, _SZ, _I, _I, c_vp,
+                                                       c_vp, _F, c_vp, c_vp, c_vp, _SZ]),
+    "exabm4d_maxpool2_bwd_ndhwc_dt_dev": (_I, [_CTX, c_vp, _I, c_vp, c_vp, c_vp, _I, _I, _I, _I, _I]),
+    "exabm4d_upsample2_trilinear_bwd_ndhwc_dt_dev": (_I, [_CTX, c_vp, _I, c_vp, c_vp, _I, _I, _I, _I, _I]),
     "exabm4d_charbonnier_workspace_bytes": (_SZ, []),
     "exabm4d_charbonnier_loss_dev": (_I, [_CTX, c_vp, c_vp, c_vp, c_vp, _I, _SZ, ctypes.c_double, ctypes.c_double,
                                            c_vp, _SZ, c_vp]),
@@ -597,32 +603,34 @@ class Context:
                                                                    _ptr(y), int(batch), int(d), int(h), int(w),
                                                                    int(channels)))
 
-    # -- BM4DNet training (fp32 NDHWC; see the header) -------------------------------------------
+    # -- BM4DNet training (NDHWC tensors of ``dtype``, a DTYPE_* code, fp32 by default; see the header) --------
     def groupnorm_lrelu_ndhwc_train(self, stream, x, y, batch, spatial, channels, groups, gamma, beta, eps, slope,
-                                    workspace, workspace_bytes, mean_rstd):
-        """The fp32 forward that also writes ``mean_rstd[batch][groups][2]`` for the backward."""
-        self._check(lib().exabm4d_groupnorm_lrelu_ndhwc_train_dev(
-            self.handle, int(stream), _ptr(x), _ptr(y), int(batch), int(spatial), int(channels), int(groups),
-            _ptr(gamma), _ptr(beta), float(eps), float(slope), _ptr(workspace), int(workspace_bytes),
+                                    workspace, workspace_bytes, mean_rstd, dtype=DTYPE_F32):
+        """The forward that also writes ``mean_rstd[batch][groups][2]`` (fp32 for every dtype) for the backward."""
+        self._check(lib().exabm4d_groupnorm_lrelu_ndhwc_train_dt_dev(
+            self.handle, int(stream), int(dtype), _ptr(x), _ptr(y), int(batch), int(spatial), int(channels),
+            int(groups), _ptr(gamma), _ptr(beta), float(eps), float(slope), _ptr(workspace), int(workspace_bytes),
             _ptr(mean_rstd)))
 
     def groupnorm_lrelu_bwd_ndhwc(self, stream, x, y, dy, dx, batch, spatial, channels, groups, gamma, mean_rstd,
-                                  slope, dgamma, dbeta, workspace, workspace_bytes):
-        self._check(lib().exabm4d_groupnorm_lrelu_bwd_ndhwc_dev(
-            self.handle, int(stream), _ptr(x), _ptr(y), _ptr(dy), _ptr(dx), int(batch), int(spatial), int(channels),
-            int(groups), _ptr(gamma), _ptr(mean_rstd), float(slope), _ptr(dgamma), _ptr(dbeta), _ptr(workspace),
-            int(workspace_bytes)))
+                                  slope, dgamma, dbeta, workspace, workspace_bytes, dtype=DTYPE_F32):
+        """x, y, dy, dx in ``dtype``; gamma, mean_rstd, dgamma, dbeta fp32."""
+        self._check(lib().exabm4d_groupnorm_lrelu_bwd_ndhwc_dt_dev(
+            self.handle, int(stream), int(dtype), _ptr(x), _ptr(y), _ptr(dy), _ptr(dx), int(batch), int(spatial),
+            int(channels), int(groups), _ptr(gamma), _ptr(mean_rstd), float(slope), _ptr(dgamma), _ptr(dbeta),
+            _ptr(workspace), int(workspace_bytes)))
 
-    def maxpool2_bwd_ndhwc(self, stream, x, dy, dx, batch, d, h, w, channels):
+    def maxpool2_bwd_ndhwc(self, stream, x, dy, dx, batch, d, h, w, channels, dtype=DTYPE_F32):
         """``d, h, w``: the extents of the forward's input ``x`` (and of ``dx``)."""
-        self._check(lib().exabm4d_maxpool2_bwd_ndhwc_dev(self.handle, int(stream), _ptr(x), _ptr(dy), _ptr(dx),
-                                                         int(batch), int(d), int(h), int(w), int(channels)))
+        self._check(lib().exabm4d_maxpool2_bwd_ndhwc_dt_dev(self.handle, int(stream), int(dtype), _ptr(x), _ptr(dy),
+                                                            _ptr(dx), int(batch), int(d), int(h), int(w),
+                                                            int(channels)))
 
-    def upsample2_trilinear_bwd_ndhwc(self, stream, dy, dx, batch, d, h, w, channels):
+    def upsample2_trilinear_bwd_ndhwc(self, stream, dy, dx, batch, d, h, w, channels, dtype=DTYPE_F32):
         """``d, h, w``: the extents of the forward's input (of ``dx``); ``dy`` has twice each."""
-        self._check(lib().exabm4d_upsample2_trilinear_bwd_ndhwc_dev(self.handle, int(stream), _ptr(dy), _ptr(dx),
-                                                                    int(batch), int(d), int(h), int(w),
-                                                                    int(channels)))
+        self._check(lib().exabm4d_upsample2_trilinear_bwd_ndhwc_dt_dev(self.handle, int(stream), int(dtype),
+                                                                       _ptr(dy), _ptr(dx), int(batch), int(d), int(h),
+                                                                       int(w), int(channels)))
 
     def charbonnier_loss(self, stream, pred, target, mask, mask_bytes, n, fg_weight, eps, workspace,
                          workspace_bytes, loss):

@@ -102,13 +102,19 @@ def _as_ndhwc(t):
     return t.contiguous(memory_format=torch.channels_last_3d)
 
 
+def _grad_as(dy, dtype):
+    """The incoming gradient as a dense NDHWC tensor of the forward's ``dtype`` (autograd may hand over another)."""
+    return _as_ndhwc(dy if dy.dtype == dtype else dy.to(dtype))
+
+
 class _GroupNormLeakyReLUFn(torch.autograd.Function):
-    """``LeakyReLU(GroupNorm(x))`` on an fp32 NDHWC tensor with both directions in ``libexabm4d``
+    """``LeakyReLU(GroupNorm(x))`` on an fp32, fp16 or bf16 NDHWC tensor with both directions in ``libexabm4d``
     (csrc/nn_kernels.hip forward, which also writes the (mean, rstd) it used; csrc/nn_grad_kernels.hip
-    backward).  Out of place: the backward reads the input and the output."""
+    backward).  Out of place: the backward reads the input and the output.  ``code``: the element-type code of
+    ``x``; x, y (both saved) and dx are in x's dtype, weight, bias, (mean, rstd) and their gradients fp32."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, groups, eps, slope):
+    def forward(ctx, x, weight, bias, groups, eps, slope, code=_native.DTYPE_F32):
         b, c = int(x.shape[0]), int(x.shape[1])
         spatial = int(x.shape[2]) * int(x.shape[3]) * int(x.shape[4])
         need = int(_native.lib().exabm4d_groupnorm_workspace_bytes(b, spatial, c, groups))
@@ -116,9 +122,9 @@ class _GroupNormLeakyReLUFn(torch.autograd.Function):
         y = torch.empty_like(x, memory_format=torch.channels_last_3d)
         stats = torch.empty((b, groups, 2), dtype=torch.float32, device=x.device)
         _native.context(x.device.index or 0).groupnorm_lrelu_ndhwc_train(
-            _stream(x), x, y, b, spatial, c, groups, weight, bias, eps, slope, ws, need, stats)
+            _stream(x), x, y, b, spatial, c, groups, weight, bias, eps, slope, ws, need, stats, dtype=code)
         ctx.save_for_backward(x, y, weight, stats)
-        ctx.groups, ctx.slope = groups, slope
+        ctx.groups, ctx.slope, ctx.code = groups, slope, code
         return y
 
     @staticmethod
@@ -127,7 +133,7 @@ class _GroupNormLeakyReLUFn(torch.autograd.Function):
         x, y, weight, stats = ctx.saved_tensors
         b, c = int(x.shape[0]), int(x.shape[1])
         spatial = int(x.shape[2]) * int(x.shape[3]) * int(x.shape[4])
-        dy = _as_ndhwc(dy)
+        dy = _grad_as(dy, x.dtype)
         dx = torch.empty_like(x, memory_format=torch.channels_last_3d)
         want_w = weight is not None and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
         dgamma = torch.empty_like(weight) if want_w else None
@@ -135,21 +141,23 @@ class _GroupNormLeakyReLUFn(torch.autograd.Function):
         need = int(_native.lib().exabm4d_groupnorm_lrelu_bwd_workspace_bytes(b, spatial, c, ctx.groups))
         ws = torch.empty(need, dtype=torch.uint8, device=x.device)
         _native.context(x.device.index or 0).groupnorm_lrelu_bwd_ndhwc(
-            _stream(x), x, y, dy, dx, b, spatial, c, ctx.groups, weight, stats, ctx.slope, dgamma, dbeta, ws, need)
-        return dx, dgamma, dbeta, None, None, None
+            _stream(x), x, y, dy, dx, b, spatial, c, ctx.groups, weight, stats, ctx.slope, dgamma, dbeta, ws, need,
+            dtype=ctx.code)
+        return dx, dgamma, dbeta, None, None, None, None
 
 
 class _MaxPool2Fn(torch.autograd.Function):
-    """``MaxPool3d(2)`` on an fp32 NDHWC tensor; the backward re-reads the input's windows instead of storing
-    indices (csrc/nn_grad_kernels.hip: torch's choice among ties and NaNs)."""
+    """``MaxPool3d(2)`` on an NDHWC tensor of element type ``code``; the backward re-reads the input's windows
+    instead of storing indices (csrc/nn_grad_kernels.hip: torch's choice among ties and NaNs)."""
 
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, code=_native.DTYPE_F32):
         b, c, d, h, w = (int(v) for v in x.shape)
         y = torch.empty((b, c, d // 2, h // 2, w // 2), dtype=x.dtype, device=x.device,
                         memory_format=torch.channels_last_3d)
-        _native.context(x.device.index or 0).maxpool2_ndhwc(_stream(x), x, y, b, d, h, w, c)
+        _native.context(x.device.index or 0).maxpool2_ndhwc(_stream(x), x, y, b, d, h, w, c, dtype=code)
         ctx.save_for_backward(x)
+        ctx.code = code
         return y
 
     @staticmethod
@@ -158,36 +166,42 @@ class _MaxPool2Fn(torch.autograd.Function):
         x, = ctx.saved_tensors
         b, c, d, h, w = (int(v) for v in x.shape)
         dx = torch.empty_like(x, memory_format=torch.channels_last_3d)
-        _native.context(x.device.index or 0).maxpool2_bwd_ndhwc(_stream(x), x, _as_ndhwc(dy), dx, b, d, h, w, c)
-        return dx
+        _native.context(x.device.index or 0).maxpool2_bwd_ndhwc(_stream(x), x, _grad_as(dy, x.dtype), dx, b, d, h, w,
+                                                                c, dtype=ctx.code)
+        return dx, None
 
 
 class _Upsample2Fn(torch.autograd.Function):
-    """Trilinear x2 up-sampling (align_corners) on an fp32 NDHWC tensor and its transpose."""
+    """Trilinear x2 up-sampling (align_corners) on an NDHWC tensor of element type ``code`` and its transpose."""
 
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, code=_native.DTYPE_F32):
         b, c, d, h, w = (int(v) for v in x.shape)
         y = torch.empty((b, c, 2 * d, 2 * h, 2 * w), dtype=x.dtype, device=x.device,
                         memory_format=torch.channels_last_3d)
-        _native.context(x.device.index or 0).upsample2_trilinear_ndhwc(_stream(x), x, y, b, d, h, w, c)
+        _native.context(x.device.index or 0).upsample2_trilinear_ndhwc(_stream(x), x, y, b, d, h, w, c, dtype=code)
         ctx.dims = (b, c, d, h, w)
+        ctx.code, ctx.dtype = code, x.dtype
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
         b, c, d, h, w = ctx.dims
+        dy = _grad_as(dy, ctx.dtype)
         dx = torch.empty((b, c, d, h, w), dtype=dy.dtype, device=dy.device, memory_format=torch.channels_last_3d)
-        _native.context(dy.device.index or 0).upsample2_trilinear_bwd_ndhwc(_stream(dy), _as_ndhwc(dy), dx, b, d,
-                                                                            h, w, c)
-        return dx
+        _native.context(dy.device.index or 0).upsample2_trilinear_bwd_ndhwc(_stream(dy), dy, dx, b, d, h, w, c,
+                                                                            dtype=ctx.code)
+        return dx, None
 
 
-def _trainable_input(x):
-    """What the training path of the NDHWC modules takes: gradients on, an fp32 CUDA NDHWC tensor."""
-    return (torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5
-            and x.is_contiguous(memory_format=torch.channels_last_3d))
+def _trainable_input(x, half=False):
+    """What the training path of the NDHWC modules takes: gradients on, a CUDA NDHWC tensor that is fp32 or, for a
+    module built with ``half=True``, fp16 / bf16.  Returns the tensor's element-type code, or None."""
+    if not (torch.is_grad_enabled() and x.is_cuda and x.dim() == 5
+            and x.is_contiguous(memory_format=torch.channels_last_3d)):
+        return None
+    return _native_dtype(x.dtype, half)
 
 
 class FusedGroupNormLeakyReLU(torch.nn.Module):
@@ -200,7 +214,9 @@ class FusedGroupNormLeakyReLU(torch.nn.Module):
     layouts / channel counts); the fallback never writes into its input.  ``trainable=True`` adds a path for
     training: with gradients enabled, an fp32 CUDA NDHWC input of a supported shape runs ``_GroupNormLeakyReLUFn``,
     whose backward is ``libexabm4d``'s too (out of place; needs ``negative_slope > 0`` and the convolution's bias
-    left in the convolution); half-precision tensors under gradients always fall back."""
+    left in the convolution); with ``half=True`` as well, so does the fp16 / bf16 tensor an autocast convolution
+    hands over (saved tensors and dx in that dtype, gamma, beta and their gradients fp32); with ``half=False``
+    half-precision tensors under gradients fall back."""
 
     def __init__(self, norm, act, conv_bias=None, half=False, inplace=True, trainable=False):
         """``conv_bias``: the bias of the convolution in front, taken over from it (the caller sets that
@@ -227,9 +243,11 @@ class FusedGroupNormLeakyReLU(torch.nn.Module):
 
     def forward(self, x):
         n = self.norm
-        if (self.trainable and _trainable_input(x) and self.native_channels and x.shape[0] <= 65535
+        code = _trainable_input(x, self.half) if self.trainable else None
+        if (code is not None and self.native_channels and x.shape[0] <= 65535
                 and n.affine and self.conv_bias is None and self.act.negative_slope > 0):
-            return _GroupNormLeakyReLUFn.apply(x, n.weight, n.bias, n.num_groups, n.eps, self.act.negative_slope)
+            return _GroupNormLeakyReLUFn.apply(x, n.weight, n.bias, n.num_groups, n.eps, self.act.negative_slope,
+                                               code)
         code = _native_dtype(x.dtype, self.half)
         fused = (not self.training and x.is_cuda and code is not None and x.dim() == 5
                  and x.is_contiguous(memory_format=torch.channels_last_3d) and not torch.is_grad_enabled()
@@ -261,7 +279,8 @@ class _ResampleNDHWC(torch.nn.Module):
     kernels for the two walk an NDHWC tensor through generic strides (3.8 ms per call on this U-Net's tensors);
     anything else -- other parameters, layouts, dtypes, training -- runs ``inner`` on an NCDHW copy.  ``half``: as
     for ``FusedGroupNormLeakyReLU``, fp16 / bf16 tensors run natively too.  ``trainable=True``: with gradients
-    enabled, an fp32 CUDA NDHWC input runs ``_MaxPool2Fn`` / ``_Upsample2Fn`` (native forward and backward)."""
+    enabled, an fp32 CUDA NDHWC input -- with ``half=True`` also an fp16 / bf16 one -- runs ``_MaxPool2Fn`` /
+    ``_Upsample2Fn`` (native forward and backward)."""
 
     def __init__(self, inner, half=False, trainable=False):
         super().__init__()
@@ -282,11 +301,12 @@ class _ResampleNDHWC(torch.nn.Module):
             self.kind = None
 
     def forward(self, x):
-        if self.trainable and self.kind is not None and _trainable_input(x) and x.shape[1] % 4 == 0:
+        code = _trainable_input(x, self.half) if self.trainable and self.kind is not None else None
+        if code is not None and x.shape[1] % 4 == 0:
             if self.kind == "up":
-                return _Upsample2Fn.apply(x)
+                return _Upsample2Fn.apply(x, code)
             if min(x.shape[2:]) >= 2:
-                return _MaxPool2Fn.apply(x)
+                return _MaxPool2Fn.apply(x, code)
         code = _native_dtype(x.dtype, self.half)
         native = (self.kind is not None and not self.training and not torch.is_grad_enabled() and x.is_cuda
                   and code is not None and x.dim() == 5 and x.shape[1] % 4 == 0

@@ -1,5 +1,6 @@
 // api_inference.hip -- the BM4DNet stage's NDHWC GroupNorm, pooling and up-sampling, the intensity transforms and
 // overlap tiling (what inference.py and transforms.py call).  Host code only; shared helpers: exabm4d_api.h.
+#include <initializer_list>
 #include <type_traits>
 
 #include "exabm4d_api.h"
@@ -40,6 +41,16 @@ static bool nn_dtype_ok(int dtype) {
     return dtype == EXABM4D_DTYPE_F32 || dtype == EXABM4D_DTYPE_F16 || dtype == EXABM4D_DTYPE_BF16;
 }
 static uintptr_t nn_align_mask(int dtype) { return dtype == EXABM4D_DTYPE_F32 ? 15u : 7u; }
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+// whether every tensor of `ps` has the alignment its element type needs, and the message for when one has not
+static bool nn_aligned(int dtype, std::initializer_list<const void*> ps) {
+    uintptr_t bits = 0;
+    for (const void* p : ps) bits |= (uintptr_t)p;
+    return (bits & nn_align_mask(dtype)) == 0;
+}
+static const char* nn_align_msg(int dtype, const char* f32, const char* half) {
+    return dtype == EXABM4D_DTYPE_F32 ? f32 : half;
+}
 // Calls f with a null pointer of the element type of `dtype` (nn_dtype_ok), which picks the launcher's instance.
 template <typename F>
 static hipError_t nn_dispatch(int dtype, F&& f) {
@@ -61,7 +72,7 @@ int exabm4d_groupnorm_lrelu_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int
                                          size_t workspace_bytes, const float* conv_bias) {
     if (!ctx || !x || !y || !workspace) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
     if (!nn_dtype_ok(dtype)) return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_ndhwc: unknown dtype");
-    if (conv_bias && ((uintptr_t)conv_bias & 15u) != 0)
+    if (conv_bias && !aligned16(conv_bias))
         return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_ndhwc: conv_bias must be 16-byte aligned");
     if (batch < 1 || batch > 65535 || spatial < 1 || channels < 4 || groups < 1 || groups > 32 ||
         channels % groups != 0 || channels % 4 != 0 || (channels / groups) % 4 != 0 || 256 % (channels / 4) != 0)
@@ -70,11 +81,11 @@ int exabm4d_groupnorm_lrelu_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int
                     "256 % (channels / 4) == 0 and groups <= 32 (use the framework's GroupNorm otherwise)");
     if (workspace_bytes < groupnorm_workspace_bytes(batch, spatial, channels, groups))
         return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_ndhwc: workspace too small");
-    if ((((uintptr_t)x | (uintptr_t)y) & nn_align_mask(dtype)) != 0 || ((uintptr_t)workspace & 15u) != 0)
+    if (!nn_aligned(dtype, {x, y}) || !aligned16(workspace))
         return fail(ctx, EXABM4D_ERR_INVALID,
-                    dtype == EXABM4D_DTYPE_F32 ? "groupnorm_lrelu_ndhwc: 16-byte aligned tensors expected"
-                                               : "groupnorm_lrelu_ndhwc: 8-byte aligned tensors and a 16-byte "
-                                                 "aligned workspace expected");
+                    nn_align_msg(dtype, "groupnorm_lrelu_ndhwc: 16-byte aligned tensors expected",
+                                 "groupnorm_lrelu_ndhwc: 8-byte aligned tensors and a 16-byte aligned workspace "
+                                 "expected"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const hipError_t e = nn_dispatch(dtype, [&](auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
@@ -99,10 +110,10 @@ static int nn_resample_checks(exabm4d_ctx* ctx, int dtype, const void* x, const 
     if (!nn_dtype_ok(dtype)) return fail(ctx, EXABM4D_ERR_INVALID, "NDHWC resampling: unknown dtype");
     if (batch < 1 || d < 1 || h < 1 || w < 1 || channels < 4 || channels % 4 != 0)
         return fail(ctx, EXABM4D_ERR_UNSUPPORTED, "NDHWC resampling: sizes >= 1 and channels % 4 == 0");
-    if ((((uintptr_t)x | (uintptr_t)y) & nn_align_mask(dtype)) != 0)
+    if (!nn_aligned(dtype, {x, y}))
         return fail(ctx, EXABM4D_ERR_INVALID,
-                    dtype == EXABM4D_DTYPE_F32 ? "NDHWC resampling: 16-byte aligned tensors expected"
-                                               : "NDHWC resampling: 8-byte aligned tensors expected");
+                    nn_align_msg(dtype, "NDHWC resampling: 16-byte aligned tensors expected",
+                                 "NDHWC resampling: 8-byte aligned tensors expected"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return EXABM4D_OK;
 }
@@ -138,20 +149,20 @@ int exabm4d_upsample2_trilinear_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, co
                                                     channels);
 }
 
-// ---- BM4DNet training: the forward that keeps its statistics, the three backward passes, the loss (nn_grad_kernels.hip)
+// ---- BM4DNet training: the forward that keeps its statistics, the three backward passes (each dtype-coded like
+// the forward entries, the fp32 ones being these with EXABM4D_DTYPE_F32), the loss (nn_grad_kernels.hip)
 static int gn_shape_checks(exabm4d_ctx* ctx, int batch, size_t spatial, int channels, int groups, const char* unsup) {
     if (batch < 1 || batch > 65535 || spatial < 1 || channels < 4 || groups < 1 || groups > 32 ||
         channels % groups != 0 || channels % 4 != 0 || (channels / groups) % 4 != 0 || 256 % (channels / 4) != 0)
         return fail(ctx, EXABM4D_ERR_UNSUPPORTED, unsup);
     return EXABM4D_OK;
 }
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-int exabm4d_groupnorm_lrelu_ndhwc_train_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, float* y, int batch,
-                                            size_t spatial, int channels, int groups, const float* gamma,
-                                            const float* beta, float eps, float slope, void* workspace,
-                                            size_t workspace_bytes, float* mean_rstd) {
+int exabm4d_groupnorm_lrelu_ndhwc_train_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* x, void* y,
+                                               int batch, size_t spatial, int channels, int groups,
+                                               const float* gamma, const float* beta, float eps, float slope,
+                                               void* workspace, size_t workspace_bytes, float* mean_rstd) {
     if (!ctx || !x || !y || !workspace || !mean_rstd) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (!nn_dtype_ok(dtype)) return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_ndhwc_train: unknown dtype");
     if (int rc = gn_shape_checks(ctx, batch, spatial, channels, groups,
                                  "groupnorm_lrelu_ndhwc_train: needs channels % 4 == 0, (channels / groups) % 4 == 0, "
                                  "256 % (channels / 4) == 0 and groups <= 32"))
@@ -161,24 +172,41 @@ int exabm4d_groupnorm_lrelu_ndhwc_train_dev(exabm4d_ctx* ctx, void* hip_stream, 
                     "groupnorm_lrelu_ndhwc_train: slope must be > 0 (the backward reads the side from y)");
     if (workspace_bytes < groupnorm_workspace_bytes(batch, spatial, channels, groups))
         return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_ndhwc_train: workspace too small");
-    if (!aligned16(x) || !aligned16(y) || !aligned16(workspace))
-        return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_ndhwc_train: 16-byte aligned tensors expected");
+    if (!nn_aligned(dtype, {x, y}) || !aligned16(workspace))
+        return fail(ctx, EXABM4D_ERR_INVALID,
+                    nn_align_msg(dtype, "groupnorm_lrelu_ndhwc_train: 16-byte aligned tensors expected",
+                                 "groupnorm_lrelu_ndhwc_train: 8-byte aligned tensors and a 16-byte aligned "
+                                 "workspace expected"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const hipError_t e = launch_groupnorm_lrelu_ndhwc(x, y, batch, spatial, channels, groups, gamma, beta, eps, slope,
-                                                      workspace, (hipStream_t)hip_stream, nullptr, mean_rstd);
+    const hipError_t e = nn_dispatch(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_groupnorm_lrelu_ndhwc(static_cast<const T*>(x), static_cast<T*>(y), batch, spatial, channels,
+                                            groups, gamma, beta, eps, slope, workspace, (hipStream_t)hip_stream,
+                                            nullptr, mean_rstd);
+    });
     return e == hipSuccess ? EXABM4D_OK : fail_hip(ctx, e, "launch_groupnorm_lrelu_ndhwc");
+}
+int exabm4d_groupnorm_lrelu_ndhwc_train_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, float* y, int batch,
+                                            size_t spatial, int channels, int groups, const float* gamma,
+                                            const float* beta, float eps, float slope, void* workspace,
+                                            size_t workspace_bytes, float* mean_rstd) {
+    return exabm4d_groupnorm_lrelu_ndhwc_train_dt_dev(ctx, hip_stream, EXABM4D_DTYPE_F32, x, y, batch, spatial,
+                                                      channels, groups, gamma, beta, eps, slope, workspace,
+                                                      workspace_bytes, mean_rstd);
 }
 size_t exabm4d_groupnorm_lrelu_bwd_workspace_bytes(int batch, size_t spatial, int channels, int groups) {
     if (batch < 1 || spatial < 1 || channels < 4 || groups < 1 || channels % 4 != 0 || 256 % (channels / 4) != 0)
         return 0;
     return groupnorm_bwd_workspace_bytes(batch, spatial, channels, groups);
 }
-int exabm4d_groupnorm_lrelu_bwd_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, const float* y,
-                                          const float* dy, float* dx, int batch, size_t spatial, int channels,
-                                          int groups, const float* gamma, const float* mean_rstd, float slope,
-                                          float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes) {
+int exabm4d_groupnorm_lrelu_bwd_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* x,
+                                             const void* y, const void* dy, void* dx, int batch, size_t spatial,
+                                             int channels, int groups, const float* gamma, const float* mean_rstd,
+                                             float slope, float* dgamma, float* dbeta, void* workspace,
+                                             size_t workspace_bytes) {
     if (!ctx || !x || !y || !dy || !dx || !mean_rstd || !workspace)
         return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (!nn_dtype_ok(dtype)) return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_bwd_ndhwc: unknown dtype");
     if (int rc = gn_shape_checks(ctx, batch, spatial, channels, groups,
                                  "groupnorm_lrelu_bwd_ndhwc: needs channels % 4 == 0, (channels / groups) % 4 == 0, "
                                  "256 % (channels / 4) == 0 and groups <= 32"))
@@ -188,29 +216,63 @@ int exabm4d_groupnorm_lrelu_bwd_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, co
                     "groupnorm_lrelu_bwd_ndhwc: slope must be > 0 (the activation's side is read from y)");
     if (workspace_bytes < groupnorm_bwd_workspace_bytes(batch, spatial, channels, groups))
         return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_bwd_ndhwc: workspace too small");
-    if (!aligned16(x) || !aligned16(y) || !aligned16(dy) || !aligned16(dx) || !aligned16(workspace))
-        return fail(ctx, EXABM4D_ERR_INVALID, "groupnorm_lrelu_bwd_ndhwc: 16-byte aligned tensors expected");
+    if (!nn_aligned(dtype, {x, y, dy, dx}) || !aligned16(workspace))
+        return fail(ctx, EXABM4D_ERR_INVALID,
+                    nn_align_msg(dtype, "groupnorm_lrelu_bwd_ndhwc: 16-byte aligned tensors expected",
+                                 "groupnorm_lrelu_bwd_ndhwc: 8-byte aligned tensors and a 16-byte aligned "
+                                 "workspace expected"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const hipError_t e =
-        launch_groupnorm_lrelu_bwd_ndhwc(x, y, dy, dx, batch, spatial, channels, groups, gamma, mean_rstd, slope,
-                                         dgamma, dbeta, workspace, (hipStream_t)hip_stream);
+    const hipError_t e = nn_dispatch(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_groupnorm_lrelu_bwd_ndhwc(static_cast<const T*>(x), static_cast<const T*>(y),
+                                                static_cast<const T*>(dy), static_cast<T*>(dx), batch, spatial,
+                                                channels, groups, gamma, mean_rstd, slope, dgamma, dbeta, workspace,
+                                                (hipStream_t)hip_stream);
+    });
     return e == hipSuccess ? EXABM4D_OK : fail_hip(ctx, e, "launch_groupnorm_lrelu_bwd_ndhwc");
+}
+int exabm4d_groupnorm_lrelu_bwd_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, const float* y,
+                                          const float* dy, float* dx, int batch, size_t spatial, int channels,
+                                          int groups, const float* gamma, const float* mean_rstd, float slope,
+                                          float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes) {
+    return exabm4d_groupnorm_lrelu_bwd_ndhwc_dt_dev(ctx, hip_stream, EXABM4D_DTYPE_F32, x, y, dy, dx, batch, spatial,
+                                                    channels, groups, gamma, mean_rstd, slope, dgamma, dbeta,
+                                                    workspace, workspace_bytes);
+}
+int exabm4d_maxpool2_bwd_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* x, const void* dy,
+                                      void* dx, int batch, int d, int h, int w, int channels) {
+    if (!dy) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (int rc = nn_resample_checks(ctx, dtype, x, dx, batch, d, h, w, channels)) return rc;
+    if (d < 2 || h < 2 || w < 2) return fail(ctx, EXABM4D_ERR_UNSUPPORTED, "maxpool2_bwd_ndhwc: extents >= 2");
+    if (!nn_aligned(dtype, {dy}))
+        return fail(ctx, EXABM4D_ERR_INVALID,
+                    nn_align_msg(dtype, "NDHWC resampling: 16-byte aligned tensors expected",
+                                 "NDHWC resampling: 8-byte aligned tensors expected"));
+    const hipError_t e = nn_dispatch(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_maxpool2_bwd_ndhwc(static_cast<const T*>(x), static_cast<const T*>(dy), static_cast<T*>(dx),
+                                         batch, d, h, w, channels, (hipStream_t)hip_stream);
+    });
+    return e == hipSuccess ? EXABM4D_OK : fail_hip(ctx, e, "launch_maxpool2_bwd_ndhwc");
 }
 int exabm4d_maxpool2_bwd_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* x, const float* dy, float* dx,
                                    int batch, int d, int h, int w, int channels) {
-    if (!dy) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
-    if (int rc = nn_resample_checks(ctx, EXABM4D_DTYPE_F32, x, dx, batch, d, h, w, channels)) return rc;
-    if (d < 2 || h < 2 || w < 2) return fail(ctx, EXABM4D_ERR_UNSUPPORTED, "maxpool2_bwd_ndhwc: extents >= 2");
-    if (!aligned16(dy)) return fail(ctx, EXABM4D_ERR_INVALID, "NDHWC resampling: 16-byte aligned tensors expected");
-    const hipError_t e = launch_maxpool2_bwd_ndhwc(x, dy, dx, batch, d, h, w, channels, (hipStream_t)hip_stream);
-    return e == hipSuccess ? EXABM4D_OK : fail_hip(ctx, e, "launch_maxpool2_bwd_ndhwc");
+    return exabm4d_maxpool2_bwd_ndhwc_dt_dev(ctx, hip_stream, EXABM4D_DTYPE_F32, x, dy, dx, batch, d, h, w, channels);
+}
+int exabm4d_upsample2_trilinear_bwd_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* dy,
+                                                 void* dx, int batch, int d, int h, int w, int channels) {
+    if (int rc = nn_resample_checks(ctx, dtype, dy, dx, batch, d, h, w, channels)) return rc;
+    const hipError_t e = nn_dispatch(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_upsample2_trilinear_bwd_ndhwc(static_cast<const T*>(dy), static_cast<T*>(dx), batch, d, h, w,
+                                                    channels, (hipStream_t)hip_stream);
+    });
+    return e == hipSuccess ? EXABM4D_OK : fail_hip(ctx, e, "launch_upsample2_trilinear_bwd_ndhwc");
 }
 int exabm4d_upsample2_trilinear_bwd_ndhwc_dev(exabm4d_ctx* ctx, void* hip_stream, const float* dy, float* dx,
                                               int batch, int d, int h, int w, int channels) {
-    if (int rc = nn_resample_checks(ctx, EXABM4D_DTYPE_F32, dy, dx, batch, d, h, w, channels)) return rc;
-    const hipError_t e =
-        launch_upsample2_trilinear_bwd_ndhwc(dy, dx, batch, d, h, w, channels, (hipStream_t)hip_stream);
-    return e == hipSuccess ? EXABM4D_OK : fail_hip(ctx, e, "launch_upsample2_trilinear_bwd_ndhwc");
+    return exabm4d_upsample2_trilinear_bwd_ndhwc_dt_dev(ctx, hip_stream, EXABM4D_DTYPE_F32, dy, dx, batch, d, h, w,
+                                                        channels);
 }
 size_t exabm4d_charbonnier_workspace_bytes(void) { return charbonnier_workspace_bytes(); }
 static int charbonnier_checks(exabm4d_ctx* ctx, bool ptrs_ok, int mask_bytes, size_t n, double fg_weight, double eps) {

@@ -154,18 +154,21 @@ template <typename T>
 hipError_t launch_maxpool2_ndhwc(const T* x, T* y, int batch, int D, int H, int W, int C, hipStream_t s);
 template <typename T>
 hipError_t launch_upsample2_trilinear_ndhwc(const T* x, T* y, int batch, int D, int H, int W, int C, hipStream_t s);
-// Backward passes of the three layers above and the training loss, fp32 (nn_grad_kernels.hip).  stats: the
-// [batch][G][2] = {mean, rstd} that launch_groupnorm_lrelu_ndhwc wrote; y: that forward's output; gamma, dgamma,
-// dbeta may be NULL; slope > 0.  The resampling gradients take the FORWARD INPUT's extents D, H, W (max-pool:
-// all >= 2); the max-pool's dx, [batch][D][H][W][C], is written completely.
+// Backward passes of the three layers above, on tensors of T as above (x, y, dy, dx in T; gamma, stats, dgamma,
+// dbeta fp32; the arithmetic is the fp32 instance's, each dx element rounded once), and the training loss, fp32
+// (nn_grad_kernels.hip).  stats: the [batch][G][2] = {mean, rstd} that launch_groupnorm_lrelu_ndhwc wrote; y: that
+// forward's output; gamma, dgamma, dbeta may be NULL; slope > 0.  The resampling gradients take the FORWARD
+// INPUT's extents D, H, W (max-pool: all >= 2); the max-pool's dx, [batch][D][H][W][C], is written completely.
 size_t groupnorm_bwd_workspace_bytes(int batch, size_t spatial, int C, int G);
-hipError_t launch_groupnorm_lrelu_bwd_ndhwc(const float* x, const float* y, const float* dy, float* dx, int batch,
-                                            size_t spatial, int C, int G, const float* gamma, const float* stats,
-                                            float slope, float* dgamma, float* dbeta, void* workspace,
-                                            hipStream_t s);
-hipError_t launch_maxpool2_bwd_ndhwc(const float* x, const float* dy, float* dx, int batch, int D, int H, int W,
-                                     int C, hipStream_t s);
-hipError_t launch_upsample2_trilinear_bwd_ndhwc(const float* dy, float* dx, int batch, int D, int H, int W, int C,
+template <typename T>
+hipError_t launch_groupnorm_lrelu_bwd_ndhwc(const T* x, const T* y, const T* dy, T* dx, int batch, size_t spatial,
+                                            int C, int G, const float* gamma, const float* stats, float slope,
+                                            float* dgamma, float* dbeta, void* workspace, hipStream_t s);
+template <typename T>
+hipError_t launch_maxpool2_bwd_ndhwc(const T* x, const T* dy, T* dx, int batch, int D, int H, int W, int C,
+                                     hipStream_t s);
+template <typename T>
+hipError_t launch_upsample2_trilinear_bwd_ndhwc(const T* dy, T* dx, int batch, int D, int H, int W, int C,
                                                 hipStream_t s);
 // mean((1 + w m) sqrt((pred - target)^2 + eps^2)) over n elements -> loss[0], and its gradient times grad_loss[0];
 // mask: NULL, or n elements of mask_bytes (4: float, 1: uint8 / bool) each

@@ -1,12 +1,21 @@
-// Backward passes of the BM4DNet stage's NDHWC layers (nn_kernels.hip) and the training loss, fp32.
+// Backward passes of the BM4DNet stage's NDHWC layers (nn_kernels.hip) and the training loss.
 //
 // What a training step of the U-Net needs besides the framework's convolutions: the gradients of GroupNorm +
 // LeakyReLU, MaxPool3d(2) and trilinear x2 up-sampling on the layout the convolutions use, and the
 // foreground-weighted Charbonnier loss (reference machine_learning/losses.py) with its gradient.  The geometry is
-// the forward's: x[b][s][c], c fastest, a thread moves a float4 of channels, C % 4 == 0 and for the norm
+// the forward's: x[b][s][c], c fastest, a thread moves four channels, C % 4 == 0 and for the norm
 // (C / G) % 4 == 0, 256 % (C / 4) == 0, G <= 32.  No atomics anywhere: every sum is formed by one thread or
 // combined in a fixed order from fp64 partials, so every result is a deterministic function of its inputs.
 // -ffp-contract=off holds: each fma below is written out.
+//
+// The three layer gradients are templates on the storage type T of the activations and their gradients (float,
+// _Float16, __bf16; Pack<T> of nn_ndhwc.h, as in the forward): a thread's four channels are 16 bytes of fp32 or 8
+// of a half type, so grids, chunk plan and combination order are the same for all three.  Loads are widened
+// exactly, the arithmetic is the fp32 kernel's expression by expression, and each output element is rounded once
+// to T (nearest even; an fp16 overflow becomes +-inf).  So from half inputs dgamma, dbeta and coef are the bits
+// the fp32 instance gives on the widened inputs, and dx is that instance's dx rounded once.  gamma, stats, coef,
+// dgamma and dbeta are fp32, the partial sums fp64, for every T.  The loss stays fp32 (under autocast the
+// network's residual sum is fp32).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -51,10 +60,13 @@ size_t groupnorm_bwd_workspace_bytes(int batch, size_t spatial, int C, int G) {
 
 __device__ __forceinline__ float lrelu_grad(float dy, float y, float slope) { return y > 0.0f ? dy : dy * slope; }
 
+template <typename T>
 __global__ __launch_bounds__(NG_THREADS) void gn_bwd_partial_kernel(
-    const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dy, size_t spatial, int C,
+    const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ dy, size_t spatial, int C,
     int G, int nchunk, size_t rows_per_chunk, const float* __restrict__ stats, float slope,
     double* __restrict__ part) {
+    using P = Pack<T>;
+    using V = typename P::type;
     const int b = blockIdx.y, chunk = blockIdx.x;
     const int lanes = C / 4;                         // four-channel lanes per row; lanes divides NG_THREADS
     const int rows_per_iter = NG_THREADS / lanes;
@@ -64,12 +76,12 @@ __global__ __launch_bounds__(NG_THREADS) void gn_bwd_partial_kernel(
     const int g = 4 * lane / (C / G);
     const float mean = stats[((size_t)b * G + g) * 2], rstd = stats[((size_t)b * G + g) * 2 + 1];
     const size_t off = (size_t)b * spatial * C;
-    const float4* x4 = reinterpret_cast<const float4*>(x + off) + lane;
-    const float4* y4 = reinterpret_cast<const float4*>(y + off) + lane;
-    const float4* d4 = reinterpret_cast<const float4*>(dy + off) + lane;
+    const V* x4 = reinterpret_cast<const V*>(x + off) + lane;
+    const V* y4 = reinterpret_cast<const V*>(y + off) + lane;
+    const V* d4 = reinterpret_cast<const V*>(dy + off) + lane;
     double sb[4] = {0.0, 0.0, 0.0, 0.0}, sg[4] = {0.0, 0.0, 0.0, 0.0};   // the thread's sums: fp64 from the start
     for (size_t r = r0 + rsub; r < r1; r += rows_per_iter) {
-        const float4 xv = x4[r * lanes], yv = y4[r * lanes], dv = d4[r * lanes];
+        const float4 xv = P::unpack(x4[r * lanes]), yv = P::unpack(y4[r * lanes]), dv = P::unpack(d4[r * lanes]);
         const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ys[4] = {yv.x, yv.y, yv.z, yv.w};
         const float ds[4] = {dv.x, dv.y, dv.z, dv.w};
 #pragma unroll
@@ -144,18 +156,21 @@ __global__ void gn_bwd_finish_kernel(const double* __restrict__ cs, int batch, i
     }
 }
 
+template <typename T>
 __global__ __launch_bounds__(NG_THREADS) void gn_bwd_apply_kernel(
-    const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dy, float* __restrict__ dx,
-    size_t spatial, int C, int G, const float* __restrict__ gamma, const float* __restrict__ stats,
-    const float* __restrict__ coef, float slope) {
+    const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ dy, T* __restrict__ dx, size_t spatial,
+    int C, int G, const float* __restrict__ gamma, const float* __restrict__ stats, const float* __restrict__ coef,
+    float slope) {
+    using P = Pack<T>;
+    using V = typename P::type;
     const int b = blockIdx.y;
     const int lanes = C / 4;
     const size_t n4 = spatial * (size_t)lanes;
     const size_t off = (size_t)b * spatial * C;
-    const float4* x4 = reinterpret_cast<const float4*>(x + off);
-    const float4* y4 = reinterpret_cast<const float4*>(y + off);
-    const float4* d4 = reinterpret_cast<const float4*>(dy + off);
-    float4* o4 = reinterpret_cast<float4*>(dx + off);
+    const V* x4 = reinterpret_cast<const V*>(x + off);
+    const V* y4 = reinterpret_cast<const V*>(y + off);
+    const V* d4 = reinterpret_cast<const V*>(dy + off);
+    V* o4 = reinterpret_cast<V*>(dx + off);
     // NG_THREADS is a multiple of `lanes` (checked by the caller), so is the grid stride: a thread keeps its lane
     const size_t stride = (size_t)gridDim.x * NG_THREADS;
     size_t i = (size_t)blockIdx.x * NG_THREADS + threadIdx.x;
@@ -166,7 +181,7 @@ __global__ __launch_bounds__(NG_THREADS) void gn_bwd_apply_kernel(
     const float mean = stats[((size_t)b * G + g) * 2], rstd = stats[((size_t)b * G + g) * 2 + 1];
     const float m1 = coef[((size_t)b * G + g) * 2], m2 = coef[((size_t)b * G + g) * 2 + 1];
     for (; i < n4; i += stride) {
-        const float4 xv = x4[i], yv = y4[i], dv = d4[i];
+        const float4 xv = P::unpack(x4[i]), yv = P::unpack(y4[i]), dv = P::unpack(d4[i]);
         const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ys[4] = {yv.x, yv.y, yv.z, yv.w};
         const float ds[4] = {dv.x, dv.y, dv.z, dv.w};
         float r[4];
@@ -177,20 +192,20 @@ __global__ __launch_bounds__(NG_THREADS) void gn_bwd_apply_kernel(
             const float t = fmaf(-xh, m2, ga[j] * dz - m1);
             r[j] = rstd * t;
         }
-        o4[i] = make_float4(r[0], r[1], r[2], r[3]);
+        o4[i] = P::pack(make_float4(r[0], r[1], r[2], r[3]));
     }
 }
 
-hipError_t launch_groupnorm_lrelu_bwd_ndhwc(const float* x, const float* y, const float* dy, float* dx, int batch,
-                                            size_t spatial, int C, int G, const float* gamma, const float* stats,
-                                            float slope, float* dgamma, float* dbeta, void* workspace,
-                                            hipStream_t s) {
+template <typename T>
+hipError_t launch_groupnorm_lrelu_bwd_ndhwc(const T* x, const T* y, const T* dy, T* dx, int batch, size_t spatial,
+                                            int C, int G, const float* gamma, const float* stats, float slope,
+                                            float* dgamma, float* dbeta, void* workspace, hipStream_t s) {
     const GnGradPlan p = gn_grad_plan(batch, spatial, C);
     const int lanes = C / 4;
     double* part = static_cast<double*>(workspace);
     double* cs = part + (size_t)batch * p.nchunk * C * 2;
     float* coef = reinterpret_cast<float*>(cs + (size_t)batch * C * 2);
-    hipLaunchKernelGGL(gn_bwd_partial_kernel, dim3((unsigned)p.nchunk, (unsigned)batch), dim3(NG_THREADS), 0, s, x, y,
+    hipLaunchKernelGGL(gn_bwd_partial_kernel<T>, dim3((unsigned)p.nchunk, (unsigned)batch), dim3(NG_THREADS), 0, s, x, y,
                        dy, spatial, C, G, (int)p.nchunk, p.rows_per_chunk, stats, slope, part);
     const int bc = batch * C;
     hipLaunchKernelGGL(gn_bwd_chunksum_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, s, part, batch, C,
@@ -203,7 +218,7 @@ hipError_t launch_groupnorm_lrelu_bwd_ndhwc(const float* x, const float* y, cons
     const size_t cap = (8192 + (size_t)batch - 1) / (size_t)batch;
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3((unsigned)blocks, (unsigned)batch), dim3(NG_THREADS), 0, s, x, y, dy,
+    hipLaunchKernelGGL(gn_bwd_apply_kernel<T>, dim3((unsigned)blocks, (unsigned)batch), dim3(NG_THREADS), 0, s, x, y, dy,
                        dx, spatial, C, G, gamma, stats, coef, slope);
     return hipGetLastError();
 }
@@ -213,12 +228,16 @@ hipError_t launch_groupnorm_lrelu_bwd_ndhwc(const float* x, const float* y, cons
 // scan in (d, h, w) order, replace the running maximum when v > max or v is NaN -- ties go to the first of the
 // equal values (+0 == -0), a window with NaNs to its last NaN.  Stride = kernel: windows do not overlap, the
 // thread writes dy there and 0 to the other seven, and the threads of the last windows along an odd extent also
-// write 0 to its trailing plane / row / column, so every element of dx is written exactly once.
-__global__ __launch_bounds__(NG_THREADS) void maxpool2_bwd_ndhwc_kernel(const float4* __restrict__ x,
-                                                                       const float4* __restrict__ dy,
-                                                                       float4* __restrict__ dx, size_t total,
-                                                                       int OD, int OH, int OW, int D, int H, int W,
-                                                                       int lanes) {
+// write 0 to its trailing plane / row / column, so every element of dx is written exactly once.  Half types: the
+// comparison runs on the widened values (exact, so the choice is the one among the stored values), and what is
+// written is dy's element widened and rounded back, which is that element (a signalling NaN comes back quiet).
+template <typename T>
+__global__ __launch_bounds__(NG_THREADS) void maxpool2_bwd_ndhwc_kernel(const typename Pack<T>::type* __restrict__ x,
+                                                                       const typename Pack<T>::type* __restrict__ dy,
+                                                                       typename Pack<T>::type* __restrict__ dx,
+                                                                       size_t total, int OD, int OH, int OW, int D,
+                                                                       int H, int W, int lanes) {
+    using P = Pack<T>;
     for (size_t o = (size_t)blockIdx.x * NG_THREADS + threadIdx.x; o < total; o += (size_t)gridDim.x * NG_THREADS) {
         const int l = (int)(o % lanes);
         size_t t = o / lanes;
@@ -228,38 +247,40 @@ __global__ __launch_bounds__(NG_THREADS) void maxpool2_bwd_ndhwc_kernel(const fl
         const size_t b = t / OD;
         const size_t base = (((b * D + 2 * od) * H + 2 * oh) * (size_t)W + 2 * ow) * lanes + l;
         auto at = [&](int kd, int kh, int kw) { return base + (((size_t)kd * H + kh) * W + kw) * lanes; };
-        float4 m = x[base];
+        float4 m = P::unpack(x[base]);
         int ix = 0, iy = 0, iz = 0, iw = 0;
 #pragma unroll
         for (int k = 1; k < 8; k++) {
-            const float4 v = x[at(k >> 2, (k >> 1) & 1, k & 1)];
+            const float4 v = P::unpack(x[at(k >> 2, (k >> 1) & 1, k & 1)]);
             if (v.x > m.x || v.x != v.x) { m.x = v.x; ix = k; }
             if (v.y > m.y || v.y != v.y) { m.y = v.y; iy = k; }
             if (v.z > m.z || v.z != v.z) { m.z = v.z; iz = k; }
             if (v.w > m.w || v.w != v.w) { m.w = v.w; iw = k; }
         }
-        const float4 g = dy[o];
+        const float4 g = P::unpack(dy[o]);
         const int nd = 2 + ((od == OD - 1) & (D & 1)), nh = 2 + ((oh == OH - 1) & (H & 1));
         const int nw = 2 + ((ow == OW - 1) & (W & 1));
         for (int kd = 0; kd < nd; kd++)
             for (int kh = 0; kh < nh; kh++)
                 for (int kw = 0; kw < nw; kw++) {
                     const int k = (kd < 2 && kh < 2 && kw < 2) ? kd * 4 + kh * 2 + kw : -1;   // -1: trailing voxel
-                    dx[at(kd, kh, kw)] = make_float4(ix == k ? g.x : 0.0f, iy == k ? g.y : 0.0f,
-                                                     iz == k ? g.z : 0.0f, iw == k ? g.w : 0.0f);
+                    dx[at(kd, kh, kw)] = P::pack(make_float4(ix == k ? g.x : 0.0f, iy == k ? g.y : 0.0f,
+                                                             iz == k ? g.z : 0.0f, iw == k ? g.w : 0.0f));
                 }
     }
 }
-hipError_t launch_maxpool2_bwd_ndhwc(const float* x, const float* dy, float* dx, int batch, int D, int H, int W,
-                                     int C, hipStream_t s) {
+template <typename T>
+hipError_t launch_maxpool2_bwd_ndhwc(const T* x, const T* dy, T* dx, int batch, int D, int H, int W, int C,
+                                     hipStream_t s) {
+    using V = typename Pack<T>::type;
     const int OD = D / 2, OH = H / 2, OW = W / 2, lanes = C / 4;     // D, H, W >= 2 (checked by the caller)
     const size_t total = (size_t)batch * OD * OH * OW * lanes;
     if (total == 0) return hipSuccess;
     size_t blocks = (total + NG_THREADS - 1) / NG_THREADS;
     if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(maxpool2_bwd_ndhwc_kernel, dim3((unsigned)blocks), dim3(NG_THREADS), 0, s,
-                       reinterpret_cast<const float4*>(x), reinterpret_cast<const float4*>(dy),
-                       reinterpret_cast<float4*>(dx), total, OD, OH, OW, D, H, W, lanes);
+    hipLaunchKernelGGL(maxpool2_bwd_ndhwc_kernel<T>, dim3((unsigned)blocks), dim3(NG_THREADS), 0, s,
+                       reinterpret_cast<const V*>(x), reinterpret_cast<const V*>(dy), reinterpret_cast<V*>(dx), total,
+                       OD, OH, OW, D, H, W, lanes);
     return hipGetLastError();
 }
 
@@ -270,6 +291,7 @@ hipError_t launch_maxpool2_bwd_ndhwc(const float* x, const float* dy, float* dx,
 // found by evaluating the forward's own up_axis on that window, so an output belongs to the run exactly when
 // the forward read the voxel for it, with the forward's weight.  The sums are nested as the forward's lerps are
 // (w, then h, then d), each in ascending o.  Extent 1 (out 2): both outputs have i0 = i1 = 0, weight 1.
+// Half types: dy widened exactly, the sums in fp32 as for fp32 storage, dx rounded once.
 __device__ __forceinline__ float up_weight(int o, int i, int in, float r) {
     const UpAxis a = up_axis(o, in, r);
     return (a.i0 == i ? a.w0 : 0.0f) + (a.i1 == i ? a.w1 : 0.0f);
@@ -288,10 +310,12 @@ __device__ __forceinline__ void up_run(int i, int in, float r, int& lo, int& hi)
         }
     }
 }
-__global__ __launch_bounds__(NG_THREADS) void upsample2_bwd_ndhwc_kernel(const float4* __restrict__ dy,
-                                                                        float4* __restrict__ dx, size_t total,
-                                                                        int D, int H, int W, int lanes, float rd,
-                                                                        float rh, float rw) {
+template <typename T>
+__global__ __launch_bounds__(NG_THREADS) void upsample2_bwd_ndhwc_kernel(const typename Pack<T>::type* __restrict__ dy,
+                                                                        typename Pack<T>::type* __restrict__ dx,
+                                                                        size_t total, int D, int H, int W, int lanes,
+                                                                        float rd, float rh, float rw) {
+    using P = Pack<T>;
     const int OH = 2 * H, OW = 2 * W;
     for (size_t n = (size_t)blockIdx.x * NG_THREADS + threadIdx.x; n < total; n += (size_t)gridDim.x * NG_THREADS) {
         const int l = (int)(n % lanes);
@@ -304,7 +328,7 @@ __global__ __launch_bounds__(NG_THREADS) void upsample2_bwd_ndhwc_kernel(const f
         up_run(d, D, rd, dlo, dhi);
         up_run(h, H, rh, hlo, hhi);
         up_run(w, W, rw, wlo, whi);
-        const float4* base = dy + (b * (2 * (size_t)D) * OH * OW) * lanes + l;
+        const typename P::type* base = dy + (b * (2 * (size_t)D) * OH * OW) * lanes + l;
         float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         for (int od = dlo; od <= dhi; od++) {
             const float wd = up_weight(od, d, D, rd);
@@ -314,7 +338,7 @@ __global__ __launch_bounds__(NG_THREADS) void upsample2_bwd_ndhwc_kernel(const f
                 float4 aw = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 for (int ow = wlo; ow <= whi; ow++) {
                     const float ww = up_weight(ow, w, W, rw);
-                    const float4 g = base[(((size_t)od * OH + oh) * OW + ow) * lanes];
+                    const float4 g = P::unpack(base[(((size_t)od * OH + oh) * OW + ow) * lanes]);
                     aw.x = fmaf(ww, g.x, aw.x); aw.y = fmaf(ww, g.y, aw.y);
                     aw.z = fmaf(ww, g.z, aw.z); aw.w = fmaf(ww, g.w, aw.w);
                 }
@@ -324,21 +348,34 @@ __global__ __launch_bounds__(NG_THREADS) void upsample2_bwd_ndhwc_kernel(const f
             acc.x = fmaf(wd, ah.x, acc.x); acc.y = fmaf(wd, ah.y, acc.y);
             acc.z = fmaf(wd, ah.z, acc.z); acc.w = fmaf(wd, ah.w, acc.w);
         }
-        dx[n] = acc;
+        dx[n] = P::pack(acc);
     }
 }
-hipError_t launch_upsample2_trilinear_bwd_ndhwc(const float* dy, float* dx, int batch, int D, int H, int W, int C,
+template <typename T>
+hipError_t launch_upsample2_trilinear_bwd_ndhwc(const T* dy, T* dx, int batch, int D, int H, int W, int C,
                                                 hipStream_t s) {
+    using V = typename Pack<T>::type;
     const int lanes = C / 4;
     const size_t total = (size_t)batch * D * H * (size_t)W * lanes;
     if (total == 0) return hipSuccess;
     size_t blocks = (total + NG_THREADS - 1) / NG_THREADS;
     if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(upsample2_bwd_ndhwc_kernel, dim3((unsigned)blocks), dim3(NG_THREADS), 0, s,
-                       reinterpret_cast<const float4*>(dy), reinterpret_cast<float4*>(dx), total, D, H, W, lanes,
-                       up_ratio(D), up_ratio(H), up_ratio(W));
+    hipLaunchKernelGGL(upsample2_bwd_ndhwc_kernel<T>, dim3((unsigned)blocks), dim3(NG_THREADS), 0, s,
+                       reinterpret_cast<const V*>(dy), reinterpret_cast<V*>(dx), total, D, H, W, lanes, up_ratio(D),
+                       up_ratio(H), up_ratio(W));
     return hipGetLastError();
 }
+
+#define EXABM4D_NN_GRAD_INSTANTIATE(T)                                                                           \
+    template hipError_t launch_groupnorm_lrelu_bwd_ndhwc<T>(const T*, const T*, const T*, T*, int, size_t, int,   \
+                                                            int, const float*, const float*, float, float*,       \
+                                                            float*, void*, hipStream_t);                          \
+    template hipError_t launch_maxpool2_bwd_ndhwc<T>(const T*, const T*, T*, int, int, int, int, int, hipStream_t); \
+    template hipError_t launch_upsample2_trilinear_bwd_ndhwc<T>(const T*, T*, int, int, int, int, int, hipStream_t);
+EXABM4D_NN_GRAD_INSTANTIATE(float)
+EXABM4D_NN_GRAD_INSTANTIATE(_Float16)
+EXABM4D_NN_GRAD_INSTANTIATE(__bf16)
+#undef EXABM4D_NN_GRAD_INSTANTIATE
 
 // ---- foreground-weighted Charbonnier loss (reference machine_learning/losses.py) ---------------------------
 // L = mean((1 + w m) sqrt(d^2 + eps^2)), d = pred - target, over n elements in storage order.  The loss is one

@@ -30,31 +30,6 @@ namespace exabm4d {
 
 constexpr int GN_THREADS = 256;
 
-// Four consecutive channels in storage type T: Pack<T>::type is what one thread loads or stores, unpack widens
-// it to fp32 exactly, pack rounds each element once, to nearest even (v_cvt_f16_f32 / v_cvt_pk_bf16_f32).
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-typedef float float4_t __attribute__((ext_vector_type(4)));
-template <typename T> struct Pack;
-template <> struct Pack<float> {
-    using type = float4;
-    static __device__ __forceinline__ float4 unpack(const float4 v) { return v; }
-    static __device__ __forceinline__ float4 pack(const float4 v) { return v; }
-};
-template <typename V> struct HalfPack {
-    using type = V;
-    static __device__ __forceinline__ float4 unpack(const V v) {
-        const float4_t f = __builtin_convertvector(v, float4_t);
-        return make_float4(f.x, f.y, f.z, f.w);
-    }
-    static __device__ __forceinline__ V pack(const float4 v) {
-        const float4_t f = {v.x, v.y, v.z, v.w};
-        return __builtin_convertvector(f, V);
-    }
-};
-template <> struct Pack<_Float16> : HalfPack<half4_t> {};
-template <> struct Pack<__bf16> : HalfPack<bf16x4_t> {};
-
 // Partial sums of one (sample, chunk of rows) about the group's reference p:
 // part[((b * nchunk + chunk) * G + g) * 2 + {0: sum of (x - p), 1: sum of (x - p)^2}]
 template <typename T>

@@ -405,7 +405,8 @@ int exabm4d_maxpool2_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype,
 int exabm4d_upsample2_trilinear_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* x, void* y,
                                              int batch, int d, int h, int w, int channels);
 
-/* ---- BM4DNet training on NDHWC, fp32 (csrc/nn_grad_kernels.hip): the backward halves of the three layers above
+/* ---- BM4DNet training on NDHWC (csrc/nn_grad_kernels.hip; fp32, and fp16 / bf16 through the *_dt_dev entries
+ * at the end of this section): the backward halves of the three layers above
  * and the reference's loss (machine_learning/losses.py).  All run on `hip_stream`, use no atomics and combine
  * their fp64 partial sums in a fixed order, so each result is a deterministic function of its inputs.
  *
@@ -455,6 +456,30 @@ int exabm4d_charbonnier_loss_dev(exabm4d_ctx* ctx, void* hip_stream, const float
 int exabm4d_charbonnier_loss_bwd_dev(exabm4d_ctx* ctx, void* hip_stream, const float* pred, const float* target,
                                      const void* mask, int mask_bytes, size_t n, double fg_weight, double eps,
                                      const float* grad_loss, float* dpred);
+/* The training forward and the three backward passes on tensors of `dtype` (an exabm4d_dtype), for a step under
+ * fp16 / bf16 autocast; the fp32 entries above are these with EXABM4D_DTYPE_F32.  x, y, dy and dx are `dtype`;
+ * gamma, beta, mean_rstd, dgamma and dbeta stay fp32 and the partial sums fp64.  A thread widens its four channels
+ * exactly, evaluates the fp32 kernel's expressions and rounds each output element once, to nearest even (an fp16
+ * overflow gives +-inf): from half inputs dgamma and dbeta are the bits the fp32 entry gives on the widened
+ * inputs, and dx is that entry's dx rounded once.  The max-pool gradient compares the widened values and places
+ * dy's elements.  A non-finite dy element is not hidden: it makes every dx of its (sample, group) non-finite and
+ * dgamma / dbeta of its own channel (a parameter gradient is a per-channel sum: the group's other channels keep
+ * their values), and nothing else.  Tensors 16-byte (fp32) or 8-byte (fp16, bf16) aligned, workspaces 16-byte;
+ * shape rules, workspace sizes and EXABM4D_ERR_UNSUPPORTED as for the fp32 entries; an unknown dtype is
+ * EXABM4D_ERR_INVALID.  The loss entries stay fp32: under autocast the network's residual sum is fp32. */
+int exabm4d_groupnorm_lrelu_ndhwc_train_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* x, void* y,
+                                               int batch, size_t spatial, int channels, int groups,
+                                               const float* gamma, const float* beta, float eps, float slope,
+                                               void* workspace, size_t workspace_bytes, float* mean_rstd);
+int exabm4d_groupnorm_lrelu_bwd_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* x,
+                                             const void* y, const void* dy, void* dx, int batch, size_t spatial,
+                                             int channels, int groups, const float* gamma, const float* mean_rstd,
+                                             float slope, float* dgamma, float* dbeta, void* workspace,
+                                             size_t workspace_bytes);
+int exabm4d_maxpool2_bwd_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* x, const void* dy,
+                                      void* dx, int batch, int d, int h, int w, int channels);
+int exabm4d_upsample2_trilinear_bwd_ndhwc_dt_dev(exabm4d_ctx* ctx, void* hip_stream, int dtype, const void* dy,
+                                                 void* dx, int batch, int d, int h, int w, int channels);
 
 /* Page-lock `bytes` of caller memory at `ptr` that the host entry points will copy from / to repeatedly (the
  * broker registers every worker's shared-memory segment once): copies become DMA transfers instead of staged
