@@ -106,6 +106,16 @@ static int chunk_checks(exabm4d_ctx* ctx, const void* in, const void* out, int n
         rc = fail(ctx, EXABM4D_ERR_INVALID, "chunked: sizes >= 1, chunk >= 1, 0 <= halo <= 64");
     return rc;
 }
+// the staged block-matching entries: NULL, params, sigma and c_match, the keys' alignment, geometry, device
+static int blockmatch_checks(exabm4d_ctx* ctx, const void* vol, int nz, int ny, int nx, int batch, float sigma,
+                             float c_match, const exabm4d_params* p, const uint32_t* keys, VolGeom& g) {
+    int rc = arg_checks(ctx, vol && keys, p);
+    if (rc) return rc;
+    if (!(sigma > 0.0f) || !(c_match > 0.0f)) return fail(ctx, EXABM4D_ERR_INVALID, "sigma and c_match must be > 0");
+    if (((uintptr_t)keys & 15u) != 0)       // a reference's 16 keys leave as 16-byte vectors
+        return fail(ctx, EXABM4D_ERR_INVALID, "keys must be 16-byte aligned");
+    return geom_on_device(ctx, nz, ny, nx, batch, g);
+}
 static int check_offset(exabm4d_ctx* ctx, float offset) {   // |v - offset| < 2^17: the uint16 pipelines' fixed unit
     if (std::fabs(offset) <= 65536.0f) return EXABM4D_OK;
     return fail(ctx, EXABM4D_ERR_INVALID, "offset must lie within [-65536, 65536]");
@@ -171,16 +181,41 @@ static int u16_pipe_scratch(exabm4d_ctx* ctx, const VolGeom& g, int batch, int s
     });
 }
 
+// ---- one pipeline run: where the volume comes from, what matching may use, where the estimate goes -----------
+constexpr bool CALLERS_BUFFER = false, IN_SCRATCH = true;      // PipeRun::in_scratch
+struct PipeRun {
+    // Input: fp32 counts on the device.  in_scratch: inside the scratch allocation, mapped memory on both sides
+    // (ensure_scratch, bm_tile_kernel); a caller's own buffer is not assumed to be.  data_exp: E of the numerator's
+    // unit, 17 for uint16 counts, EXABM4D_DATA_EXP_AUTO (every volume's largest |v|) for fp32.
+    const float* noisy; bool in_scratch; int data_exp;
+    // Matching on counts, the uint16 pipelines.  counts16: the same volume as uint16 XOR 0x8000,
+    // guarded like `noisy`, cast with counts_offset; both stages then match in integer arithmetic where
+    // int_match_ok admits it.  match_rounded: stage 2 matches on the basic estimate ROUNDED TO COUNTS,
+    // rint(clamp(basic + counts_offset, 0, 65535)); counts16's memory (free after stage 1) takes it for the integer
+    // kernel, `tmp` (dead between the stages) takes the same counts as fp32 for the float kernels.
+    uint16_t* counts16; float counts_offset; bool match_rounded;
+    // Output.  Under out.pg `noisy` is the stabilised volume and the last normalisation inverts.
+    NormOut out;
+
+    static PipeRun f32(const float* in, bool in_scratch, const NormOut& out) {
+        return {in, in_scratch, EXABM4D_DATA_EXP_AUTO, nullptr, 0.0f, false, out};
+    }
+    static PipeRun counts_to_u16(const U16Scratch& v, float offset, uint16_t* out) {
+        return {v.f32, IN_SCRATCH, EXABM4D_DATA_EXP_U16, v.u16, offset, true, NormOut::to_u16(out, offset)};
+    }
+    static PipeRun counts_in_place(const U16Scratch& v, float offset) {        // fp32 estimate over v.f32, unclipped
+        return {v.f32, IN_SCRATCH, EXABM4D_DATA_EXP_U16, v.u16, offset, true, NormOut::to_f32(v.f32)};
+    }
+    static PipeRun stabilised_to_u16(const float* d, uint16_t* out, const PgDev* pg) {
+        return f32(d, IN_SCRATCH, NormOut::to_u16_pg(out, pg));
+    }
+};
+
 // ---- staged entry points ---------------------------------------------------------------------------------
 int exabm4d_blockmatch_dev(exabm4d_ctx* ctx, const float* vol, int nz, int ny, int nx, int batch,
                            float sigma, float c_match, const exabm4d_params* p, uint32_t* keys) {
-    int rc = arg_checks(ctx, vol && keys, p);
-    if (rc) return rc;
-    if (!(sigma > 0.0f) || !(c_match > 0.0f)) return fail(ctx, EXABM4D_ERR_INVALID, "sigma and c_match must be > 0");
-    if (((uintptr_t)keys & 15u) != 0)       // a reference's 16 keys leave as 16-byte vectors
-        return fail(ctx, EXABM4D_ERR_INVALID, "keys must be 16-byte aligned");
     VolGeom g;
-    rc = geom_on_device(ctx, nz, ny, nx, batch, g);
+    int rc = blockmatch_checks(ctx, vol, nz, ny, nx, batch, sigma, c_match, p, keys, g);
     if (rc) return rc;
     const BmPlan plan = bm_plan(g, batch, ctx->bm);
     if (ctx->bm_guarded_copy) {
@@ -214,13 +249,8 @@ int exabm4d_blockmatch_dev(exabm4d_ctx* ctx, const float* vol, int nz, int ny, i
 // kernel's (else the float kernel), one-wave kernel for clamped last grid positions.
 int exabm4d_blockmatch_u16_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, int ny, int nx, int batch,
                                float sigma, float c_match, const exabm4d_params* p, uint32_t* keys) {
-    int rc = arg_checks(ctx, vol && keys, p);
-    if (rc) return rc;
-    if (!(sigma > 0.0f) || !(c_match > 0.0f)) return fail(ctx, EXABM4D_ERR_INVALID, "sigma and c_match must be > 0");
-    if (((uintptr_t)keys & 15u) != 0)       // a reference's 16 keys leave as 16-byte vectors
-        return fail(ctx, EXABM4D_ERR_INVALID, "keys must be 16-byte aligned");
     VolGeom g;
-    rc = geom_on_device(ctx, nz, ny, nx, batch, g);
+    int rc = blockmatch_checks(ctx, vol, nz, ny, nx, batch, sigma, c_match, p, keys, g);
     if (rc) return rc;
     const size_t n = (size_t)g.nvox * (size_t)batch;
     const BmPlan plan = bm_plan(g, batch, ctx->bm);
@@ -376,28 +406,13 @@ static int zero_join(exabm4d_ctx* ctx, hipStream_t s) {
 }
 
 // ---- whole pipeline -----------------------------------------------------------------------------------------
-// noisy: fp32 counts on device.  Exactly one of out_f32 / out_u16 is written.
-static int run_pipeline(exabm4d_ctx* ctx, const float* noisy, float* out_f32, uint16_t* out_u16,
-                        const VolGeom& g, int batch, float sigma, const exabm4d_params* p,
-                        int stages, float clip_lo, float clip_hi, float u16_offset, char* scratch,
-                        int noisy_guarded, int data_exp, const uint16_t* noisy16 = nullptr,
-                        int match_counts = 0, float match_offset = 0.0f, const PgDev* pg = nullptr) {
-    // noisy16: the same volume as uint16 counts XOR 0x8000, guarded like `noisy`, when the caller
-    // is a uint16 pipeline: stage-1 matching then runs in integer arithmetic (bm_tile16_kernel),
-    // provided its tables equal the float kernel's -- admission bound below 2^24, even row length
-    // noisy_guarded: `noisy` lies inside the scratch allocation (mapped memory on both sides, see
-    // ensure_scratch and bm_tile_kernel); a caller's own device buffer is not assumed to.
-    // data_exp: E of the numerator's unit: 17 from the uint16 entry points,
-    // EXABM4D_DATA_EXP_AUTO (from every volume's largest |v|) from the fp32 ones.
-    // match_counts (the uint16 entry points): stage 2 matches on the basic estimate ROUNDED TO
-    // COUNTS -- rint(clamp(basic + match_offset, 0, 65535)) -- so that it can run in integer arithmetic like
-    // stage 1 (noisy16's memory is free by then and takes the rounded volume); where the integer kernel does
-    // not apply, the float kernel runs on the same counts as fp32 (in `tmp`, dead between the stages).
-    // pg (uint16 output): `noisy` is the stabilised volume; the last normalisation inverts the
-    // stabilisation where it would add the offset.
+static int run_pipeline(exabm4d_ctx* ctx, const VolGeom& g, int batch, float sigma, const exabm4d_params* p,
+                        int stages, const PipeRun& run) {
+    const float* noisy = run.noisy;
+    uint16_t* const counts16 = run.counts16;
     const size_t n = (size_t)g.nvox * (size_t)batch;
     const BmPlan plan = bm_plan(g, batch, ctx->bm);           // one plan for both matching launches
-    Carver c{scratch};
+    Carver c{ctx->scratch.as<char>()};
     PipeLayout L;
     pipe_layout(c, L, n, (size_t)g.nref * (size_t)batch, batch, stages, plan.carry_bytes);
     const auto [keys, num, basic, cw, tmp, pairvol, qs, maxbits, carry] = L;     // basic: only touched when stages >= 2
@@ -405,15 +420,16 @@ static int run_pipeline(exabm4d_ctx* ctx, const float* noisy, float* out_f32, ui
     const float thr = (float)((double)p->lambda_ht * (double)sigma);
     const float sigma2 = (float)((double)sigma * (double)sigma);
     hipStream_t s = ctx->stream;
-    int pair_ready = 0;      // the first normalisation wrote the Wiener stage's (noisy, basic) volume
+    // what the first normalisation wrote besides `basic`: the Wiener stage's (noisy, basic) volume, the rounded counts
+    NormWrote basic_wrote{hipSuccess, false, false};
     // stage 2 of a uint16 pipeline in the integer kernel?  Decided here because the first
-    // normalisation then also writes the rounded estimate (into noisy16's memory: stage 1 is done with it)
-    const bool match_use16 = match_counts && stages >= 2 &&
-                             int_match_ok(ctx, p->c_match_wie, sigma, g, noisy16, n, match_offset);
-    int match16_ready = 0;
+    // normalisation then also writes the rounded estimate (into counts16's memory: stage 1 is done with it)
+    const bool match_use16 = run.match_rounded && stages >= 2 &&
+                             int_match_ok(ctx, p->c_match_wie, sigma, g, counts16, n, run.counts_offset);
+    const NormSums sums{num, qs, tmp, g.nz, g.ny, g.nx, batch, ctx->win1d};
     if (ctx->profile)
         for (int i = 1; i < EXABM4D_PHASE_COUNT; i++) ctx->ev_used[i] = false;
-    if ((noisy_guarded && !guarded_region_ok(ctx, noisy, n * sizeof(float))) ||
+    if ((run.in_scratch && !guarded_region_ok(ctx, noisy, n * sizeof(float))) ||
         (stages >= 2 && !guarded_region_ok(ctx, basic, n * sizeof(float))))
         return fail(ctx, EXABM4D_ERR_INVALID, "internal: guarded volume without mapped slack around it");
 
@@ -421,13 +437,13 @@ static int run_pipeline(exabm4d_ctx* ctx, const float* noisy, float* out_f32, ui
         PhaseTimer t(ctx, EXABM4D_PHASE_ZERO_ACC_1);
         int rc = zero_begin(ctx, num, cw, n, s);
         if (rc) return rc;
-        HIP_TRY(ctx, launch_qscale(noisy, (size_t)g.nvox, batch, data_exp, maxbits, qs, s, ctx->status_dev));
+        HIP_TRY(ctx, launch_qscale(noisy, (size_t)g.nvox, batch, run.data_exp, maxbits, qs, s, ctx->status_dev));
     }
     {
         PhaseTimer t(ctx, EXABM4D_PHASE_BLOCKMATCH_HT);
-        const bool use16 = int_match_ok(ctx, p->c_match_ht, sigma, g, noisy16, n, u16_offset);
+        const bool use16 = int_match_ok(ctx, p->c_match_ht, sigma, g, counts16, n, run.counts_offset);
         HIP_TRY(ctx, launch_blockmatch(noisy, g, batch, keymax_of(sigma, p->c_match_ht), keys, s,
-                                       ctx->force_generic_bm, noisy_guarded, use16 ? noisy16 : nullptr, plan,
+                                       ctx->force_generic_bm, run.in_scratch, use16 ? counts16 : nullptr, plan,
                                        carry, ctx->status_dev));
     }
     {
@@ -442,10 +458,10 @@ static int run_pipeline(exabm4d_ctx* ctx, const float* noisy, float* out_f32, ui
         {
             PhaseTimer t(ctx, EXABM4D_PHASE_NORMALIZE_BASIC);
             // ... and, where it can, the Wiener stage's interleaved (noisy, basic) volume
-            HIP_TRY(ctx, launch_normalize_zconv(num, qs, tmp, basic, nullptr, g.nz, g.ny, g.nx, batch, ctx->win1d,
-                                                1.0f, 0.0f, 0.0f, s, ctx->stage.pairvol ? noisy : nullptr, pairvol,
-                                                &pair_ready, match_use16 ? const_cast<uint16_t*>(noisy16) : nullptr,
-                                                match_offset, &match16_ready));
+            const NormSide side{ctx->stage.pairvol ? noisy : nullptr, pairvol, match_use16 ? counts16 : nullptr,
+                                run.counts_offset};
+            basic_wrote = launch_normalize_zconv(sums, NormOut::to_f32(basic), s, &side);
+            HIP_TRY(ctx, basic_wrote.err);
         }
         {
             PhaseTimer t(ctx, EXABM4D_PHASE_ZERO_ACC_2);
@@ -457,18 +473,17 @@ static int run_pipeline(exabm4d_ctx* ctx, const float* noisy, float* out_f32, ui
             const float* match_on = basic;
             const uint16_t* match16 = nullptr;
             int match_guarded = 1;
-            if (match_counts) {
+            if (run.match_rounded) {
                 if (match_use16) {
-                    uint16_t* m16 = const_cast<uint16_t*>(noisy16);      // our own scratch; stage 1 is done with it
-                    if (!match16_ready)                                  // (normally written by the normalisation)
-                        HIP_TRY(ctx, launch_round_counts(basic, nullptr, m16, n, match_offset, s));
-                    match16 = m16;
+                    if (!basic_wrote.round16)                            // (normally written by the normalisation)
+                        HIP_TRY(ctx, launch_round_counts(basic, nullptr, counts16, n, run.counts_offset, s));
+                    match16 = counts16;
                 }
                 // reference blocks at clamped grid positions (an extent - 8 that is no multiple of 4) go through
                 // the one-wave kernel, which reads fp32: it needs the same counts as fp32
                 const bool generic_too = ctx->force_generic_bm || g.gz != g.az || g.gy != g.ay || g.gx != g.ax;
                 if (!match_use16 || generic_too) {
-                    HIP_TRY(ctx, launch_round_counts(basic, tmp, nullptr, n, match_offset, s));
+                    HIP_TRY(ctx, launch_round_counts(basic, tmp, nullptr, n, run.counts_offset, s));
                     match_on = tmp;
                     match_guarded = guarded_region_ok(ctx, tmp, n * sizeof(float)) ? 1 : 0;
                 }
@@ -482,15 +497,13 @@ static int run_pipeline(exabm4d_ctx* ctx, const float* noisy, float* out_f32, ui
             int rc = zero_join(ctx, s);
             if (rc) return rc;
             HIP_TRY(ctx, launch_stage(noisy, basic, keys, g, batch, ctx->dct, ctx->win_dev.as<float>(), thr, sigma2, qs, num, cw,
-                                      s, ctx->stage, pairvol, pair_ready));
+                                      s, ctx->stage, pairvol, basic_wrote.pair ? 1 : 0));
             HIP_TRY(ctx, launch_den_xy_from_corners(cw, tmp, g.nz, g.ny, g.nx, batch, ctx->win1d, s));
         }
     }
     {
         PhaseTimer t(ctx, EXABM4D_PHASE_NORMALIZE_OUT);
-        HIP_TRY(ctx, launch_normalize_zconv(num, qs, tmp, out_f32, out_u16, g.nz, g.ny, g.nx, batch, ctx->win1d,
-                                            clip_lo, clip_hi, u16_offset, s, nullptr, nullptr, nullptr, nullptr, 0.0f,
-                                            nullptr, pg));
+        HIP_TRY(ctx, launch_normalize_zconv(sums, run.out, s).err);
     }
     return EXABM4D_OK;
 }
@@ -503,8 +516,28 @@ int exabm4d_denoise_f32_dev(exabm4d_ctx* ctx, const float* in, float* out, int n
     if (rc) return rc;
     rc = ensure_scratch(ctx, pipe_bytes(ctx->bm, nz, ny, nx, batch, stages));
     if (rc) return rc;
-    return run_pipeline(ctx, in, out, nullptr, g, batch, sigma, p, stages, clip_lo, clip_hi, 0.0f,
-                        ctx->scratch.as<char>(), 0, EXABM4D_DATA_EXP_AUTO);
+    return run_pipeline(ctx, g, batch, sigma, p, stages,
+                        PipeRun::f32(in, CALLERS_BUFFER, NormOut::to_f32_abi_clip(out, clip_lo, clip_hi)));
+}
+
+// The body of the two uint16 device entries: scratch, the forward pass (counts - offset and the uint16 shadow, or
+// under pg the stabilisation) as phase COUNTS_FROM_U16, the pipeline.
+static int run_u16_pipeline(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out, const VolGeom& g, int batch,
+                            float sigma, float offset, const PgDev* pg, const exabm4d_params* p, int stages) {
+    const size_t n = (size_t)g.nvox * (size_t)batch;
+    U16Scratch v;
+    int rc = u16_pipe_scratch(ctx, g, batch, stages, v);
+    if (rc) return rc;
+    ctx->ev_used[EXABM4D_PHASE_COUNTS_FROM_U16] = false;
+    {
+        PhaseTimer t(ctx, EXABM4D_PHASE_COUNTS_FROM_U16);
+        if (pg)
+            HIP_TRY(ctx, launch_pg_forward_u16(*pg, in, v.f32, n, ctx->stream));
+        else
+            HIP_TRY(ctx, launch_counts_from_u16(in, v.f32, n, offset, ctx->stream, v.u16));
+    }
+    return run_pipeline(ctx, g, batch, sigma, p, stages,
+                        pg ? PipeRun::stabilised_to_u16(v.f32, out, pg) : PipeRun::counts_to_u16(v, offset, out));
 }
 
 int exabm4d_denoise_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out, int nz, int ny,
@@ -515,18 +548,7 @@ int exabm4d_denoise_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out,
     if (rc) return rc;
     rc = check_offset(ctx, offset);
     if (rc) return rc;
-    U16Scratch v;
-    rc = u16_pipe_scratch(ctx, g, batch, stages, v);
-    if (rc) return rc;
-    float* noisy = v.f32;
-    uint16_t* noisy16 = v.u16;
-    ctx->ev_used[EXABM4D_PHASE_COUNTS_FROM_U16] = false;
-    {
-        PhaseTimer t(ctx, EXABM4D_PHASE_COUNTS_FROM_U16);
-        HIP_TRY(ctx, launch_counts_from_u16(in, noisy, (size_t)g.nvox * (size_t)batch, offset, ctx->stream, noisy16));
-    }
-    return run_pipeline(ctx, noisy, nullptr, out, g, batch, sigma, p, stages, 0.0f, 0.0f, offset,
-                        ctx->scratch.as<char>(), 1, EXABM4D_DATA_EXP_U16, noisy16, 1, offset);
+    return run_u16_pipeline(ctx, in, out, g, batch, sigma, offset, nullptr, p, stages);
 }
 
 // Under Poisson-Gaussian noise: counts -> D (unit sigma) -> the fp32 pipeline at sigma 1 -> the
@@ -543,16 +565,7 @@ int exabm4d_denoise_pg_u16_dev(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* o
     rc = geom_on_device(ctx, nz, ny, nx, batch, g);
     if (!rc) rc = ensure_window(ctx, (double)p->kaiser_beta);
     if (rc) return rc;
-    U16Scratch v;
-    rc = u16_pipe_scratch(ctx, g, batch, stages, v);
-    if (rc) return rc;
-    ctx->ev_used[EXABM4D_PHASE_COUNTS_FROM_U16] = false;
-    {
-        PhaseTimer t(ctx, EXABM4D_PHASE_COUNTS_FROM_U16);
-        HIP_TRY(ctx, launch_pg_forward_u16(pg, in, v.f32, (size_t)g.nvox * (size_t)batch, ctx->stream));
-    }
-    return run_pipeline(ctx, v.f32, nullptr, out, g, batch, 1.0f, p, stages, 0.0f, 0.0f, 0.0f,
-                        ctx->scratch.as<char>(), 1, EXABM4D_DATA_EXP_AUTO, nullptr, 0, 0.0f, &pg);
+    return run_u16_pipeline(ctx, in, out, g, batch, 1.0f, 0.0f, &pg, p, stages);
 }
 
 int exabm4d_gat_forward_u16_dev(exabm4d_ctx* ctx, const exabm4d_pg_noise* noise, const uint16_t* in, float* out,
@@ -596,6 +609,7 @@ static int chunked_on_device(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out
             if (r.e + r.lo + r.hi < 8)
                 return fail(ctx, EXABM4D_ERR_INVALID, "chunked: a padded chunk would be thinner than one block (8)");
     ctx->ev_used[EXABM4D_PHASE_COUNTS_FROM_U16] = false;
+    const ChunkMap map{offset, pg};
     for (const ChunkRun& rz : runs[0])
         for (const ChunkRun& ry : runs[1])
             for (const ChunkRun& rx : runs[2]) {
@@ -624,22 +638,13 @@ static int chunked_on_device(exabm4d_ctx* ctx, const uint16_t* in, uint16_t* out
                     U16Scratch v;
                     rc = u16_pipe_scratch(ctx, g, count, stages, v);
                     if (rc) return rc;
-                    float* vol = v.f32;
-                    uint16_t* vol16 = v.u16;
-                    if (pg) {
-                        HIP_TRY(ctx, launch_chunk_gather_pg(in, cb, *pg, vol, ctx->stream));
-                        rc = run_pipeline(ctx, vol, vol, nullptr, g, count, 1.0f, p, stages, 1.0f, 0.0f, 0.0f,
-                                          ctx->scratch.as<char>(), 1, EXABM4D_DATA_EXP_AUTO);
-                        if (rc) return rc;
-                        HIP_TRY(ctx, launch_chunk_scatter_pg(vol, cb, *pg, out, ctx->stream));
-                        continue;
-                    }
-                    HIP_TRY(ctx, launch_chunk_gather(in, cb, offset, vol, ctx->stream, vol16));
-                    rc = run_pipeline(ctx, vol, vol, nullptr, g, count, sigma, p, stages, 1.0f, 0.0f, 0.0f,
-                                      ctx->scratch.as<char>(), 1, EXABM4D_DATA_EXP_U16,
-                                      offset_exact_in_fp32(offset) ? vol16 : nullptr, 1, offset);
+                    // under pg the chunks are stabilised volumes: the fp32 pipeline at sigma 1, in place
+                    HIP_TRY(ctx, launch_chunk_gather(in, cb, map, v.f32, ctx->stream, pg ? nullptr : v.u16));
+                    rc = run_pipeline(ctx, g, count, sigma, p, stages,
+                                      pg ? PipeRun::f32(v.f32, IN_SCRATCH, NormOut::to_f32(v.f32))
+                                         : PipeRun::counts_in_place(v, offset));
                     if (rc) return rc;
-                    HIP_TRY(ctx, launch_chunk_scatter(vol, cb, offset, out, ctx->stream));
+                    HIP_TRY(ctx, launch_chunk_scatter(v.f32, cb, map, out, ctx->stream));
                 }
             }
     return EXABM4D_OK;
@@ -865,7 +870,6 @@ static int denoise_f32_host_pipelined(exabm4d_ctx* ctx, const float* in, float* 
         HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
         for (int i = 0; i < 3; i++) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->copy_ev[i], hipEventDisableTiming));
     }
-    char* scratch = ctx->scratch.as<char>();
     float* const* buf = L.buf;
     hipStream_t cs = ctx->copy_stream, s = ctx->stream;
     const int nsub = (batch + sub - 1) / sub;
@@ -883,8 +887,8 @@ static int denoise_f32_host_pipelined(exabm4d_ctx* ctx, const float* in, float* 
         }
         HIP_TRY(ctx, hipEventRecord(ctx->copy_ev[2], cs));                     // input k is up
         HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->copy_ev[2], 0));
-        rc = run_pipeline(ctx, buf[k & 1], buf[k & 1], nullptr, gk, cnt, sigma, p, stages, clip_lo, clip_hi, 0.0f,
-                          scratch, 1, EXABM4D_DATA_EXP_AUTO);
+        rc = run_pipeline(ctx, gk, cnt, sigma, p, stages,
+                          PipeRun::f32(buf[k & 1], IN_SCRATCH, NormOut::to_f32_abi_clip(buf[k & 1], clip_lo, clip_hi)));
         if (rc) return rc;
         HIP_TRY(ctx, hipEventRecord(ctx->copy_ev[k & 1], s));                  // result k is ready
         if (k >= 1) {                                                          // result k - 1 down, under compute k
@@ -924,12 +928,11 @@ static int host_batch(exabm4d_ctx* ctx, const float* const* in, float* const* ou
             r = c.take<float>(n * sizeof(float));
         });
         if (rc) return rc;
-        char* scratch = ctx->scratch.as<char>();
         for (int i = 0; i < pieces; i++)
             HIP_TRY(ctx, hipMemcpyAsync(vol + (size_t)i * per_piece, in[i], per_piece * sizeof(float),
                                         hipMemcpyHostToDevice, ctx->stream));
-        rc = run_pipeline(ctx, vol, vol, nullptr, g, batch, sigma, p, stages, clip_lo, clip_hi, 0.0f,
-                          scratch, 1, EXABM4D_DATA_EXP_AUTO);
+        rc = run_pipeline(ctx, g, batch, sigma, p, stages,
+                          PipeRun::f32(vol, IN_SCRATCH, NormOut::to_f32_abi_clip(vol, clip_lo, clip_hi)));
         if (rc) return rc;
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         unsigned fired = 0;

@@ -436,114 +436,91 @@ hipError_t launch_chunk_hist(const uint16_t* vol, int nz, int ny, int nx, int cz
     return hipGetLastError();
 }
 
+// ---- counts <-> the pipelines' fp32 values ----------------------------------------------------------------------
+// The uint16 pipelines work on counts - offset and write quantise(estimate + offset); under Poisson-Gaussian noise
+//  on the stabilised D = pg_forward(count), and write quantise(pg_inverse(estimate)).  The chunk
+// kernels and the fused normalisation below take either as their `Epi`.
+struct EpiOffset { float offset; };
+struct EpiPg { PgDev t; };
+__device__ __forceinline__ float epi_f32(const EpiOffset& e, unsigned v) { return (float)v - e.offset; }
+__device__ __forceinline__ float epi_f32(const EpiPg& e, unsigned v) { return pg_forward(e.t, (float)v); }
+__device__ __forceinline__ uint16_t epi_u16(const EpiOffset& e, float r) {
+    return quantise_u16(r + e.offset, 65535.0f);
+}
+__device__ __forceinline__ uint16_t epi_u16(const EpiPg& e, float r) {
+    return quantise_u16(pg_inverse(e.t, r), 65535.0f);
+}
+
 // ---- chunk-local mode (BASELINE config 4) ------------------------------
 // A batch of padded chunks: chunk (bz, by, bx) of a sub-grid has its core at (z0 + bz*cz, ...),
 // extent (ez, ey, ex), and is read with (lz, ly, lx) voxels in front and (pz - ez - lz, ...) behind
-// it -- the halo, cut off where the buffer ends.  gather: u16 -> (float) - offset into [batch][pz][py][px];
-// scatter: the denoised padded chunks' cores -> + offset -> clip -> rint -> u16 into the output.
-__global__ __launch_bounds__(EW_THREADS) void chunk_gather_kernel(const uint16_t* __restrict__ in,
-                                                                  ChunkBatch cb, float offset,
-                                                                  float* __restrict__ out,
+// it -- the halo, cut off where the buffer ends.  gather: u16 -> epi_f32 into [batch][pz][py][px] (out16: also the
+// counts XOR 0x8000); scatter: the denoised padded chunks' cores -> epi_u16 into the output.
+// Element i of a batch of (ez, ey, ex) boxes, one box per chunk: batch entry b, the place (z, y, x) in its box, and
+// the buffer coordinates (cz0, cy0, cx0) of that chunk's core.
+struct ChunkVoxel { int b, z, y, x, cz0, cy0, cx0; };
+__device__ __forceinline__ ChunkVoxel chunk_voxel(const ChunkBatch& cb, size_t i, int ez, int ey, int ex) {
+    const size_t vox = (size_t)ez * ey * ex;
+    ChunkVoxel v;
+    v.b = (int)(i / vox);
+    const size_t r = i - (size_t)v.b * vox;
+    v.x = (int)(r % ex); v.y = (int)((r / ex) % ey); v.z = (int)(r / ((size_t)ex * ey));
+    const int c = cb.first + v.b;
+    const int bx = c % cb.sgx, by = (c / cb.sgx) % cb.sgy, bz = c / (cb.sgx * cb.sgy);
+    v.cz0 = cb.z0 + bz * cb.cz; v.cy0 = cb.y0 + by * cb.cy; v.cx0 = cb.x0 + bx * cb.cx;
+    return v;
+}
+template <class Epi>
+__global__ __launch_bounds__(EW_THREADS) void chunk_gather_kernel(const uint16_t* __restrict__ in, ChunkBatch cb,
+                                                                  Epi epi, float* __restrict__ out,
                                                                   uint16_t* __restrict__ out16) {
-    const size_t pvox = (size_t)cb.pz * cb.py * cb.px;
-    const size_t total = pvox * (size_t)cb.count;
+    const size_t total = (size_t)cb.pz * cb.py * cb.px * (size_t)cb.count;
     for (size_t i = (size_t)blockIdx.x * EW_THREADS + threadIdx.x; i < total;
          i += (size_t)gridDim.x * EW_THREADS) {
-        const int b = (int)(i / pvox);
-        const size_t r = i - (size_t)b * pvox;
-        const int x = (int)(r % cb.px), y = (int)((r / cb.px) % cb.py), z = (int)(r / ((size_t)cb.px * cb.py));
-        const int c = cb.first + b;
-        const int bx = c % cb.sgx, by = (c / cb.sgx) % cb.sgy, bz = c / (cb.sgx * cb.sgy);
-        const int gz = min(max(cb.z0 + bz * cb.cz - cb.lz + z, 0), cb.nz - 1);
-        const int gy = min(max(cb.y0 + by * cb.cy - cb.ly + y, 0), cb.ny - 1);
-        const int gx = min(max(cb.x0 + bx * cb.cx - cb.lx + x, 0), cb.nx - 1);
+        const ChunkVoxel p = chunk_voxel(cb, i, cb.pz, cb.py, cb.px);
+        const int gz = min(max(p.cz0 - cb.lz + p.z, 0), cb.nz - 1);
+        const int gy = min(max(p.cy0 - cb.ly + p.y, 0), cb.ny - 1);
+        const int gx = min(max(p.cx0 - cb.lx + p.x, 0), cb.nx - 1);
         const unsigned v = in[((size_t)gz * cb.ny + gy) * cb.nx + gx];
-        out[i] = (float)v - offset;
+        out[i] = epi_f32(epi, v);
         if (out16) out16[i] = (uint16_t)(v ^ 0x8000u);
     }
 }
-__global__ __launch_bounds__(EW_THREADS) void chunk_scatter_kernel(const float* __restrict__ est,
-                                                                   ChunkBatch cb, float offset,
-                                                                   uint16_t* __restrict__ out) {
-    const size_t cvox = (size_t)cb.ez * cb.ey * cb.ex;
-    const size_t total = cvox * (size_t)cb.count;
-    const size_t pvox = (size_t)cb.pz * cb.py * cb.px;
-    for (size_t i = (size_t)blockIdx.x * EW_THREADS + threadIdx.x; i < total;
-         i += (size_t)gridDim.x * EW_THREADS) {
-        const int b = (int)(i / cvox);
-        const size_t r = i - (size_t)b * cvox;
-        const int x = (int)(r % cb.ex), y = (int)((r / cb.ex) % cb.ey), z = (int)(r / ((size_t)cb.ex * cb.ey));
-        const int c = cb.first + b;
-        const int bx = c % cb.sgx, by = (c / cb.sgx) % cb.sgy, bz = c / (cb.sgx * cb.sgy);
-        const float v = est[(size_t)b * pvox + ((size_t)(z + cb.lz) * cb.py + (y + cb.ly)) * cb.px + (x + cb.lx)];
-        const int oz = cb.z0 + bz * cb.cz + z - cb.out_z0, oy = cb.y0 + by * cb.cy + y, ox = cb.x0 + bx * cb.cx + x;
-        out[((size_t)oz * cb.ny + oy) * cb.nx + ox] = quantise_u16(v + offset, 65535.0f);
-    }
-}
-// The stabilised pipeline's pair: the same index maps; gather writes D = pg_forward(count), scatter
-// writes quantise(pg_inverse(estimate)).
-__global__ __launch_bounds__(EW_THREADS) void chunk_gather_pg_kernel(const uint16_t* __restrict__ in,
-                                                                     ChunkBatch cb, PgDev t,
-                                                                     float* __restrict__ out) {
-    const size_t pvox = (size_t)cb.pz * cb.py * cb.px;
-    const size_t total = pvox * (size_t)cb.count;
-    for (size_t i = (size_t)blockIdx.x * EW_THREADS + threadIdx.x; i < total;
-         i += (size_t)gridDim.x * EW_THREADS) {
-        const int b = (int)(i / pvox);
-        const size_t r = i - (size_t)b * pvox;
-        const int x = (int)(r % cb.px), y = (int)((r / cb.px) % cb.py), z = (int)(r / ((size_t)cb.px * cb.py));
-        const int c = cb.first + b;
-        const int bx = c % cb.sgx, by = (c / cb.sgx) % cb.sgy, bz = c / (cb.sgx * cb.sgy);
-        const int gz = min(max(cb.z0 + bz * cb.cz - cb.lz + z, 0), cb.nz - 1);
-        const int gy = min(max(cb.y0 + by * cb.cy - cb.ly + y, 0), cb.ny - 1);
-        const int gx = min(max(cb.x0 + bx * cb.cx - cb.lx + x, 0), cb.nx - 1);
-        out[i] = pg_forward(t, (float)in[((size_t)gz * cb.ny + gy) * cb.nx + gx]);
-    }
-}
-__global__ __launch_bounds__(EW_THREADS) void chunk_scatter_pg_kernel(const float* __restrict__ est,
-                                                                      ChunkBatch cb, PgDev t,
-                                                                      uint16_t* __restrict__ out) {
-    const size_t cvox = (size_t)cb.ez * cb.ey * cb.ex;
-    const size_t total = cvox * (size_t)cb.count;
-    const size_t pvox = (size_t)cb.pz * cb.py * cb.px;
-    for (size_t i = (size_t)blockIdx.x * EW_THREADS + threadIdx.x; i < total;
-         i += (size_t)gridDim.x * EW_THREADS) {
-        const int b = (int)(i / cvox);
-        const size_t r = i - (size_t)b * cvox;
-        const int x = (int)(r % cb.ex), y = (int)((r / cb.ex) % cb.ey), z = (int)(r / ((size_t)cb.ex * cb.ey));
-        const int c = cb.first + b;
-        const int bx = c % cb.sgx, by = (c / cb.sgx) % cb.sgy, bz = c / (cb.sgx * cb.sgy);
-        const float v = est[(size_t)b * pvox + ((size_t)(z + cb.lz) * cb.py + (y + cb.ly)) * cb.px + (x + cb.lx)];
-        const int oz = cb.z0 + bz * cb.cz + z - cb.out_z0, oy = cb.y0 + by * cb.cy + y, ox = cb.x0 + bx * cb.cx + x;
-        out[((size_t)oz * cb.ny + oy) * cb.nx + ox] = quantise_u16(pg_inverse(t, v), 65535.0f);
-    }
-}
-hipError_t launch_chunk_gather_pg(const uint16_t* in, const ChunkBatch& cb, const PgDev& t, float* out,
-                                  hipStream_t s) {
-    const size_t total = (size_t)cb.pz * cb.py * cb.px * (size_t)cb.count;
-    const unsigned blocks = (unsigned)std::min<size_t>((total + EW_THREADS - 1) / EW_THREADS, 1u << 20);
-    hipLaunchKernelGGL(chunk_gather_pg_kernel, dim3(blocks), dim3(EW_THREADS), 0, s, in, cb, t, out);
-    return hipGetLastError();
-}
-hipError_t launch_chunk_scatter_pg(const float* est, const ChunkBatch& cb, const PgDev& t, uint16_t* out,
-                                   hipStream_t s) {
+template <class Epi>
+__global__ __launch_bounds__(EW_THREADS) void chunk_scatter_kernel(const float* __restrict__ est, ChunkBatch cb,
+                                                                   Epi epi, uint16_t* __restrict__ out) {
     const size_t total = (size_t)cb.ez * cb.ey * cb.ex * (size_t)cb.count;
-    const unsigned blocks = (unsigned)std::min<size_t>((total + EW_THREADS - 1) / EW_THREADS, 1u << 20);
-    hipLaunchKernelGGL(chunk_scatter_pg_kernel, dim3(blocks), dim3(EW_THREADS), 0, s, est, cb, t, out);
-    return hipGetLastError();
+    const size_t pvox = (size_t)cb.pz * cb.py * cb.px;
+    for (size_t i = (size_t)blockIdx.x * EW_THREADS + threadIdx.x; i < total;
+         i += (size_t)gridDim.x * EW_THREADS) {
+        const ChunkVoxel p = chunk_voxel(cb, i, cb.ez, cb.ey, cb.ex);
+        const float v =
+            est[(size_t)p.b * pvox + ((size_t)(p.z + cb.lz) * cb.py + (p.y + cb.ly)) * cb.px + (p.x + cb.lx)];
+        const int oz = p.cz0 + p.z - cb.out_z0, oy = p.cy0 + p.y, ox = p.cx0 + p.x;
+        out[((size_t)oz * cb.ny + oy) * cb.nx + ox] = epi_u16(epi, v);
+    }
 }
-hipError_t launch_chunk_gather(const uint16_t* in, const ChunkBatch& cb, float offset, float* out,
+static unsigned chunk_blocks(size_t total) {
+    return (unsigned)std::min<size_t>((total + EW_THREADS - 1) / EW_THREADS, 1u << 20);
+}
+hipError_t launch_chunk_gather(const uint16_t* in, const ChunkBatch& cb, const ChunkMap& m, float* out,
                                hipStream_t s, uint16_t* out16) {
-    const size_t total = (size_t)cb.pz * cb.py * cb.px * (size_t)cb.count;
-    const unsigned blocks = (unsigned)std::min<size_t>((total + EW_THREADS - 1) / EW_THREADS, 1u << 20);
-    hipLaunchKernelGGL(chunk_gather_kernel, dim3(blocks), dim3(EW_THREADS), 0, s, in, cb, offset, out, out16);
+    const dim3 grid(chunk_blocks((size_t)cb.pz * cb.py * cb.px * (size_t)cb.count));
+    if (m.pg)
+        hipLaunchKernelGGL(chunk_gather_kernel<EpiPg>, grid, dim3(EW_THREADS), 0, s, in, cb, EpiPg{*m.pg}, out, out16);
+    else
+        hipLaunchKernelGGL(chunk_gather_kernel<EpiOffset>, grid, dim3(EW_THREADS), 0, s, in, cb, EpiOffset{m.offset},
+                           out, out16);
     return hipGetLastError();
 }
-hipError_t launch_chunk_scatter(const float* est, const ChunkBatch& cb, float offset, uint16_t* out,
+hipError_t launch_chunk_scatter(const float* est, const ChunkBatch& cb, const ChunkMap& m, uint16_t* out,
                                 hipStream_t s) {
-    const size_t total = (size_t)cb.ez * cb.ey * cb.ex * (size_t)cb.count;
-    const unsigned blocks = (unsigned)std::min<size_t>((total + EW_THREADS - 1) / EW_THREADS, 1u << 20);
-    hipLaunchKernelGGL(chunk_scatter_kernel, dim3(blocks), dim3(EW_THREADS), 0, s, est, cb, offset, out);
+    const dim3 grid(chunk_blocks((size_t)cb.ez * cb.ey * cb.ex * (size_t)cb.count));
+    if (m.pg)
+        hipLaunchKernelGGL(chunk_scatter_kernel<EpiPg>, grid, dim3(EW_THREADS), 0, s, est, cb, EpiPg{*m.pg}, out);
+    else
+        hipLaunchKernelGGL(chunk_scatter_kernel<EpiOffset>, grid, dim3(EW_THREADS), 0, s, est, cb, EpiOffset{m.offset},
+                           out);
     return hipGetLastError();
 }
 
@@ -662,27 +639,21 @@ __global__ __launch_bounds__(EW_THREADS) void conv8_xy4_kernel(const unsigned lo
 // out = fl32(fl64(num) 2^(E - 43)) / den (+ clip, or + offset, clamp, rint, uint16).  Saves the pass that
 // would write den and the one that would read it back; bit-identical to the separate passes of the staged
 // entry points.
-// The uint16 form's last step on the quotient r: + offset (the uint16 pipelines), or the inverse of the Poisson-
-// Gaussian stabilisation (the estimate never travels to HBM as fp32); then clamp, rint, uint16.
-struct EpiOffset {};
-struct EpiPg { PgDev t; };
-__device__ __forceinline__ uint16_t zconv_u16(const EpiOffset&, float r, float offset) {
-    return quantise_u16(r + offset, 65535.0f);
-}
-__device__ __forceinline__ uint16_t zconv_u16(const EpiPg& e, float r, float) {
-    return quantise_u16(pg_inverse(e.t, r), 65535.0f);
-}
-template <int W, bool U16, class Epi = EpiOffset>
+// The uint16 form's last step on the quotient r is the Epi's epi_u16 (under EpiPg the estimate never travels to
+// HBM as fp32).
+template <int W, bool U16, class Epi>
 __global__ __launch_bounds__(EW_THREADS) void normalize_zconv_kernel(const long long* __restrict__ num,
                                                                      const double* __restrict__ qscale,
                                                                      const float* __restrict__ txy,
                                                                      void* __restrict__ out, size_t nlines,
                                                                      size_t plane, int nz, Win1D w, float lo,
-                                                                     float hi, int do_clip, float offset,
+                                                                     float hi, int do_clip, Epi epi,
                                                                      const float* __restrict__ pair_src,
                                                                      float* __restrict__ pair_out,
                                                                      uint16_t* __restrict__ match16,
-                                                                     float match_offset, Epi epi) {
+                                                                     float match_offset) {
+    // epi: what the uint16 form does to the quotient.  In front of the by-products on purpose: as the last argument
+    // it costs the wide uint16 instance 70 VGPRs instead of 56, one wave per SIMD less
     // pair_out (fp32 output, W = 4 only): additionally the interleaved volume (pair_src, out) the Wiener
     // kernel gathers from, so that it does not cost a pass of its own
     // match16 (fp32 output): additionally the estimate rounded to counts, XOR 0x8000 -- what stage 2 of the
@@ -728,11 +699,11 @@ __global__ __launch_bounds__(EW_THREADS) void normalize_zconv_kernel(const long 
             if (U16) {
                 uint16_t* o16 = static_cast<uint16_t*>(out) + at;
                 if (W == 4) {
-                    const uint32_t q0 = zconv_u16(epi, r[0], offset), q1 = zconv_u16(epi, r[1 % W], offset);
-                    const uint32_t q2 = zconv_u16(epi, r[2 % W], offset), q3 = zconv_u16(epi, r[3 % W], offset);
+                    const uint32_t q0 = epi_u16(epi, r[0]), q1 = epi_u16(epi, r[1 % W]);
+                    const uint32_t q2 = epi_u16(epi, r[2 % W]), q3 = epi_u16(epi, r[3 % W]);
                     *reinterpret_cast<uint2*>(o16) = make_uint2(q0 | (q1 << 16), q2 | (q3 << 16));
                 } else {
-                    o16[0] = zconv_u16(epi, r[0], offset);
+                    o16[0] = epi_u16(epi, r[0]);
                 }
             } else {
                 float* o32 = static_cast<float*>(out) + at;
@@ -788,53 +759,47 @@ hipError_t launch_den_xy_from_corners(const unsigned long long* cw, float* tmp, 
     return hipGetLastError();
 }
 
-// out = fl32(fl64(num) 2^(E - 43)) / (txy (*)_z win): exactly one of out_f32 / out_u16
-hipError_t launch_normalize_zconv(const long long* num, const double* qscale, const float* txy, float* out_f32,
-                                  uint16_t* out_u16, int nz, int ny, int nx, int batch, const float* win1d,
-                                  float lo, float hi, float offset, hipStream_t s, const float* pair_src,
-                                  float* pair_out, int* pair_written, uint16_t* match16, float match_offset,
-                                  int* match_written, const PgDev* pg) {
-    if (pair_written) *pair_written = 0;
-    if (match_written) *match_written = 0;
-    // (the rounded copy is of the UNCLIPPED fp32 estimate; 8-byte stores in the wide form)
-    if (out_u16 || lo <= hi || ((uintptr_t)match16 & 7u) != 0) match16 = nullptr;
-    if (match16 && match_written) *match_written = 1;
+// out = fl32(fl64(num) 2^(E - 43)) / (txy (*)_z win)
+template <int W, bool U16, class Epi>
+static void zconv_launch(const NormSums& in, const NormOut& out, hipStream_t s, const NormSide& side, const Epi& epi) {
     Win1D w;
-    for (int t = 0; t < 8; t++) w.k[t] = win1d[t];
-    const size_t plane = (size_t)ny * nx;
-    void* out = out_u16 ? static_cast<void*>(out_u16) : static_cast<void*>(out_f32);
-    const bool wide = plane % 4 == 0 && ((uintptr_t)num & 15u) == 0 && ((uintptr_t)txy & 15u) == 0 &&
-                      ((uintptr_t)out & 15u) == 0 && ((size_t)nz * plane) % 4 == 0;
-    const size_t nlines = (size_t)batch * (wide ? plane / 4 : plane);
-    const dim3 grid = conv_blocks(nlines);
-    const int clip = lo <= hi ? 1 : 0;
-    const float* nul = nullptr;
-    float* nulw = nullptr;
-    uint16_t* nul16 = nullptr;
-    if (pg && !out_u16) return hipErrorInvalidValue;
-    if (pg && wide) {
-        hipLaunchKernelGGL((normalize_zconv_kernel<4, true, EpiPg>), grid, dim3(EW_THREADS), 0, s, num, qscale, txy,
-                           out, nlines, plane, nz, w, lo, hi, clip, offset, nul, nulw, nul16, 0.0f, EpiPg{*pg});
-    } else if (pg) {
-        hipLaunchKernelGGL((normalize_zconv_kernel<1, true, EpiPg>), grid, dim3(EW_THREADS), 0, s, num, qscale, txy,
-                           out, nlines, plane, nz, w, lo, hi, clip, offset, nul, nulw, nul16, 0.0f, EpiPg{*pg});
-    } else if (wide && out_u16) {
-        hipLaunchKernelGGL((normalize_zconv_kernel<4, true>), grid, dim3(EW_THREADS), 0, s, num, qscale, txy, out,
-                           nlines, plane, nz, w, lo, hi, clip, offset, nul, nulw, nullptr, 0.0f, EpiOffset{});
-    } else if (wide) {
-        const bool pw = pair_src && pair_out && ((uintptr_t)pair_src & 15u) == 0 && ((uintptr_t)pair_out & 15u) == 0;
-        hipLaunchKernelGGL((normalize_zconv_kernel<4, false>), grid, dim3(EW_THREADS), 0, s, num, qscale, txy, out,
-                           nlines, plane, nz, w, lo, hi, clip, offset, pw ? pair_src : nul, pw ? pair_out : nulw,
-                           match16, match_offset, EpiOffset{});
-        if (pair_written && pw) *pair_written = 1;
-    } else if (out_u16) {
-        hipLaunchKernelGGL((normalize_zconv_kernel<1, true>), grid, dim3(EW_THREADS), 0, s, num, qscale, txy, out,
-                           nlines, plane, nz, w, lo, hi, clip, offset, nul, nulw, nullptr, 0.0f, EpiOffset{});
-    } else {
-        hipLaunchKernelGGL((normalize_zconv_kernel<1, false>), grid, dim3(EW_THREADS), 0, s, num, qscale, txy, out,
-                           nlines, plane, nz, w, lo, hi, clip, offset, nul, nulw, match16, match_offset, EpiOffset{});
+    for (int t = 0; t < 8; t++) w.k[t] = in.win1d[t];
+    const size_t plane = (size_t)in.ny * in.nx, nlines = (size_t)in.batch * (plane / W);
+    void* dst = U16 ? static_cast<void*>(out.u16) : static_cast<void*>(out.f32);
+    hipLaunchKernelGGL((normalize_zconv_kernel<W, U16, Epi>), conv_blocks(nlines), dim3(EW_THREADS), 0, s, in.num,
+                       in.qscale, in.txy, dst, nlines, plane, in.nz, w, out.lo, out.hi, out.clip ? 1 : 0, epi,
+                       side.pair_src, side.pair_out, side.round16, side.round_offset);
+}
+NormWrote launch_normalize_zconv(const NormSums& in, const NormOut& out, hipStream_t s, const NormSide* side) {
+    if (out.pg && !out.u16) return {hipErrorInvalidValue, false, false};
+    const size_t plane = (size_t)in.ny * in.nx;
+    const void* dst = out.u16 ? static_cast<const void*>(out.u16) : static_cast<const void*>(out.f32);
+    const bool wide = plane % 4 == 0 && ((uintptr_t)in.num & 15u) == 0 && ((uintptr_t)in.txy & 15u) == 0 &&
+                      ((uintptr_t)dst & 15u) == 0 && ((size_t)in.nz * plane) % 4 == 0;
+    NormSide can{nullptr, nullptr, nullptr, 0.0f};      // the by-products this launch writes
+    if (side && out.f32) {
+        // the pair volume only in the wide form (16-byte stores), the rounded copy only of the UNCLIPPED estimate
+        // (8-byte stores in the wide form)
+        if (wide && side->pair_src && side->pair_out && ((uintptr_t)side->pair_src & 15u) == 0 &&
+            ((uintptr_t)side->pair_out & 15u) == 0) {
+            can.pair_src = side->pair_src;
+            can.pair_out = side->pair_out;
+        }
+        if (!out.clip && ((uintptr_t)side->round16 & 7u) == 0) {
+            can.round16 = side->round16;
+            can.round_offset = side->round_offset;
+        }
     }
-    return hipGetLastError();
+    const EpiOffset off{out.offset};
+    if (out.pg) {
+        const EpiPg pg{*out.pg};
+        wide ? zconv_launch<4, true>(in, out, s, can, pg) : zconv_launch<1, true>(in, out, s, can, pg);
+    } else if (out.u16) {
+        wide ? zconv_launch<4, true>(in, out, s, can, off) : zconv_launch<1, true>(in, out, s, can, off);
+    } else {
+        wide ? zconv_launch<4, false>(in, out, s, can, off) : zconv_launch<1, false>(in, out, s, can, off);
+    }
+    return {hipGetLastError(), can.pair_out != nullptr, can.round16 != nullptr};
 }
 
 // the staged entry point's form: all three passes, den written

@@ -127,19 +127,32 @@ hipError_t launch_den_from_corners(const unsigned long long* cw, float* tmp, flo
 // out = fl32(fl64(num) 2^(E - 43)) / (tmp (*)_z win), then clip (f32) or + offset, clamp, rint (uint16).
 hipError_t launch_den_xy_from_corners(const unsigned long long* cw, float* tmp, int nz, int ny, int nx, int batch,
                                       const float* win1d, hipStream_t s);
-// pair_src / pair_out (optional, fp32 output only): also write the interleaved (pair_src, out) volume of the
-// Wiener stage's gathers; *pair_written says whether this launch could do it (16-byte aligned float4 form)
-hipError_t launch_normalize_zconv(const long long* num, const double* qscale, const float* txy, float* out_f32,
-                                  uint16_t* out_u16, int nz, int ny, int nx, int batch, const float* win1d,
-                                  float lo, float hi, float offset, hipStream_t s, const float* pair_src = nullptr,
-                                  float* pair_out = nullptr, int* pair_written = nullptr,
-                                  // match16 (optional, unclipped fp32 output only): also the estimate rounded to
-                                  // counts XOR 0x8000, rint(clamp(out + match_offset, 0, 65535))
-                                  uint16_t* match16 = nullptr, float match_offset = 0.0f,
-                                  int* match_written = nullptr,
-                                  // pg (optional, uint16 output only): the quotient is a stabilised value and the
-                                  // count is quantise(pg inverse) instead of quantise(+ offset)
-                                  const PgDev* pg = nullptr);
+// What the fused normalisation -- and so a whole pipeline run -- writes, exactly one of: fp32, optionally clamped
+// to [lo, hi]; uint16 = quantise(estimate + offset); uint16 = quantise(pg inverse(estimate)).
+struct NormOut {
+    float* f32; bool clip; float lo, hi;
+    uint16_t* u16; float offset; const PgDev* pg;
+    static NormOut to_f32(float* out) { return {out, false, 0.0f, 0.0f, nullptr, 0.0f, nullptr}; }
+    // the C ABI's convention, translated here and nowhere else: clip_lo > clip_hi means "no clip"
+    static NormOut to_f32_abi_clip(float* out, float clip_lo, float clip_hi) {
+        return {out, clip_lo <= clip_hi, clip_lo, clip_hi, nullptr, 0.0f, nullptr};
+    }
+    static NormOut to_u16(uint16_t* out, float offset) { return {nullptr, false, 0.0f, 0.0f, out, offset, nullptr}; }
+    static NormOut to_u16_pg(uint16_t* out, const PgDev* pg) { return {nullptr, false, 0.0f, 0.0f, out, 0.0f, pg}; }
+};
+// The sums a normalisation reads: the int64 numerator, its units, the denominator after its x / y passes.
+struct NormSums {
+    const long long* num; const double* qscale; const float* txy;
+    int nz, ny, nx, batch;
+    const float* win1d;
+};
+// Optional by-products of an fp32 normalisation, each written only where the launch can (NormWrote says which).
+// pair: the interleaved (pair_src, out) volume of the Wiener stage's gathers; wide form, 16-byte aligned.
+// round16: the UNCLIPPED estimate rounded to counts XOR 0x8000, rint(clamp(out + round_offset, 0, 65535)), what
+// stage 2 of the uint16 pipelines matches on; 8-byte aligned.
+struct NormSide { const float* pair_src; float* pair_out; uint16_t* round16; float round_offset; };
+struct NormWrote { hipError_t err; bool pair, round16; };
+NormWrote launch_normalize_zconv(const NormSums& in, const NormOut& out, hipStream_t s, const NormSide* side = nullptr);
 // BM4DNet stage: GroupNorm + LeakyReLU on an NDHWC tensor x[batch][spatial][C] (nn_kernels.hip); y may be x.
 // Requires C % 4 == 0, (C / G) % 4 == 0, 256 % (C / 4) == 0, G <= 32.  T: float, _Float16 or __bf16 (the
 // storage of torch.bfloat16); gamma, beta, cbias and the workspace's statistics are fp32 / fp64 for all three.
@@ -196,15 +209,14 @@ struct ChunkBatch {
     int first, count;        // batch = sub-grid chunks [first, first + count)
     int out_z0;              // output plane 0 is input plane out_z0
 };
-hipError_t launch_chunk_gather(const uint16_t* in, const ChunkBatch& cb, float offset, float* out,
+// What a chunk's voxels are on the fp32 side: counts - offset (pg == NULL), or the stabilised D.
+// gather: u16 -> fp32 padded chunks (out16, offset form only: also the counts XOR 0x8000); scatter: the cores back,
+// + offset or the pg inverse, clamp, rint, u16.
+struct ChunkMap { float offset; const PgDev* pg; };
+hipError_t launch_chunk_gather(const uint16_t* in, const ChunkBatch& cb, const ChunkMap& m, float* out,
                                hipStream_t s, uint16_t* out16 = nullptr);
-hipError_t launch_chunk_scatter(const float* est, const ChunkBatch& cb, float offset, uint16_t* out,
+hipError_t launch_chunk_scatter(const float* est, const ChunkBatch& cb, const ChunkMap& m, uint16_t* out,
                                 hipStream_t s);
-// The same pair for the stabilised pipeline: gather u16 -> D, scatter D -> inverse -> u16.
-hipError_t launch_chunk_gather_pg(const uint16_t* in, const ChunkBatch& cb, const PgDev& t, float* out,
-                                  hipStream_t s);
-hipError_t launch_chunk_scatter_pg(const float* est, const ChunkBatch& cb, const PgDev& t, uint16_t* out,
-                                   hipStream_t s);
 
 // ---- chunk entropy coder (rans_kernels.hip) ----------------------------------------
 struct CodecGeom {

@@ -167,3 +167,63 @@ def test_streamed_host_volume_errors(ctx):
     # the context is usable afterwards
     close_u16(denoise_chunked_streamed(vol, SIGMA, OFFSET, chunk=16, halo=8),
               denoise_chunked(vol, SIGMA, OFFSET, chunk=16, halo=8))
+
+
+
+@pytest.mark.parametrize("offset", [36.73, 100.5])
+@pytest.mark.parametrize("shape", [(24, 28, 40), (24, 28, 41)])
+def test_chunk_local_gate_of_the_integer_kernel_reads_the_counts_offset(ctx, oracle, shape, offset):
+    """Chunk-local mode writes fp32 in place, so the offset the counts were cast with is no output parameter there:
+    the integer matching kernel's gate must still see it.  16^3 cores + 4: padded rows of 20 / 24 /
+    12 voxels (all even: the integer kernel is admissible) at nx = 40, a 13-voxel row (the float kernel) at nx = 41;
+    36.73 is not exact in fp32 (the float kernel whatever the row), 100.5 is.  One result: the oracle's, with every
+    kernel allowed and with the integer / the tile kernels forced off."""
+    vol, _ = synth_volume(shape, seed=sum(shape), as_u16=True)
+    want = oracle.bm4d_u16_chunked(vol, SIGMA, offset, 16, 4)
+    for option, value in ((None, 0), ("bm_int", 0), ("force_generic_bm", 1)):
+        if option:
+            ctx.set_option(option, value)
+        try:
+            got = denoise_chunked(vol, SIGMA, offset, chunk=16, halo=4, stages=2)
+        finally:
+            if option:
+                ctx.set_option(option, 1 - value)
+        np.testing.assert_array_equal(got, want, err_msg=f"{option} = {value}")
+
+
+@pytest.mark.parametrize("form", ["f32", "f32_clipped", "u16", "pg_u16"])
+@pytest.mark.parametrize("shape", [(16, 16, 16), (13, 11, 10)])
+def test_every_output_form_in_both_launch_widths(ctx, oracle, shape, form):
+    """The last normalisation's three output kinds -- fp32 (with and without a clip range), uint16 + offset, uint16
+    through the Poisson-Gaussian inverse -- in the wide launch (plane % 4 == 0: 16^3) and the narrow one (11 x 10
+    planes), through the device entry points, each against its oracle bit for bit."""
+    import pg_pyref as P
+    if form in ("f32", "f32_clipped"):
+        vol, _ = synth_volume(shape, seed=sum(shape))
+        want = oracle.bm4d(vol, SIGMA)
+        clip = None
+        if form == "f32_clipped":
+            clip = tuple(float(np.float32(np.percentile(want, q))) for q in (30, 70))
+            assert np.count_nonzero(want < clip[0]) and np.count_nonzero(want > clip[1])     # the range cuts the data
+            want = np.clip(want, np.float32(clip[0]), np.float32(clip[1]))
+        run = lambda a, b: ctx.denoise_f32(a, b, shape, SIGMA, clip=clip)
+    elif form == "u16":
+        vol, _ = synth_volume(shape, seed=sum(shape), as_u16=True)
+        want = oracle.bm4d_u16(vol, SIGMA, OFFSET)
+        run = lambda a, b: ctx.denoise_u16(a, b, shape, SIGMA, OFFSET)
+    else:
+        params = (4.0, 6.0, 37.0)                     # gain, read noise, offset
+        _, clean = synth_volume(shape, seed=sum(shape), pedestal=params[2])
+        vol = P.pg_volume(clean, *params, np.random.default_rng(sum(shape)))
+        want = P.inverse(oracle.bm4d(P.forward(vol, params), 1.0), params, "closed_form")
+        run = lambda a, b: ctx.denoise_pg_u16(a, b, shape, _native.pg_noise(*params))
+    d_in, d_out = ctx.to_device(vol), ctx.alloc(vol.nbytes).fill(0xA5)
+    try:
+        run(d_in, d_out)
+        ctx.sync()
+        got = d_out.download(shape, vol.dtype)
+    finally:
+        d_in.free()
+        d_out.free()
+    np.testing.assert_array_equal(got, want)
+    assert np.any(got != vol)                         # it denoised something
