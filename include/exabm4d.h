@@ -551,7 +551,9 @@ int exabm4d_tile_finalize_u16_dev(exabm4d_ctx* ctx, const exabm4d_transform* t,
  * [nchunks][2][256] uint32 counts (plane 0 = low bytes), chunks in (z,y,x) raster order of
  * ceil(n/c) chunks per axis, edge chunks truncated like numpy slicing.  From these the host
  * derives a zeroth-order entropy bound of the shuffled stream (a rate proxy; the exact Blosc/zstd
- * byte counts need the third-party codec). */
+ * byte counts need the third-party codec).  Pointers: vol and hist need the natural alignment of their element
+ * types only (2 and 4 bytes); vol is only read, and of hist exactly the nchunks * 512 counts are written, every
+ * one of them (hist need not be zeroed). */
 int exabm4d_chunk_byte_histograms_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, int ny, int nx,
                                       int cz, int cy, int cx, uint32_t* hist);
 
@@ -562,7 +564,11 @@ int exabm4d_chunk_byte_histograms_dev(exabm4d_ctx* ctx, const uint16_t* vol, int
  * transforms, idx = (int32) rintf(c / q) (clamped to +-2^30).  idx receives ceil(nz/8) *
  * ceil(ny/8) * ceil(nx/8) blocks of 512 coefficients (block raster, then (uz, uy, ux) raster).
  * The inverse dequantises, inverts, clamps to [0, 65535] and rounds half to even.  Indices are
- * bit-exact against the oracle (orc_dctq_forward). */
+ * bit-exact against the oracle (orc_dctq_forward).  Pointers: vol and idx need the natural alignment of their
+ * element types only (2 and 4 bytes), so views at any element offset of a larger buffer work and give the same
+ * values.  The forward writes every index of every block and nothing else; the inverse writes every one of the
+ * nz * ny * nx voxels and nothing else -- no voxel of the blocks' overhang beyond an extent that is not a multiple
+ * of 8 is stored.  The input of either is only read. */
 int exabm4d_dctq_forward_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, int ny, int nx, float q,
                              int32_t* idx);
 int exabm4d_dctq_inverse_dev(exabm4d_ctx* ctx, const int32_t* idx, int nz, int ny, int nx, float q,
@@ -596,7 +602,19 @@ int exabm4d_i32_symbol_histogram_dev(exabm4d_ctx* ctx, const int32_t* idx, size_
  * may be NULL when out is NULL) receives the start of every chunk's stream and the container length;
  * sizes_dev[nchunks] (device, may be NULL) the exact stream lengths, i.e. len(codec.encode(chunk));
  * totals_host[2] (host, may be NULL; non-NULL makes the call synchronise) = { sum of the exact
- * lengths, container bytes }.  Chunks are numbered in (z, y, x) raster order. */
+ * lengths, container bytes }.  Chunks are numbered in (z, y, x) raster order.
+ *
+ * Pointers of the encoder.  vol needs the natural alignment of its element type only (2 or 4 bytes) and is only
+ * read; streams and sizes do not depend on where it lies (EXAC v1 counts its byte histograms 16 bytes per lane
+ * where a chunk of whole 64-element rows starts on a 4-byte boundary and one element per lane elsewhere: the same
+ * counts).  out must be 16-byte aligned and offsets_dev is required with it; a misaligned out, an out without
+ * offsets_dev or an out_capacity below the bound gives EXABM4D_ERR_INVALID before anything is launched or
+ * written.  offsets_dev needs 8-byte and sizes_dev 4-byte alignment.  Of out exactly the container
+ * [0, offsets_dev[nchunks]) is written -- every stream, and zeros from the end of each stream to the next
+ * multiple of 16 -- whatever out held before; [offsets_dev[nchunks], out_capacity) is unspecified (a caller must
+ * not rely on it being kept or cleared), and nothing outside [out, out + out_capacity) is touched.  An
+ * out_capacity of exactly the bound is accepted.  Every element of offsets_dev and sizes_dev is
+ * written, and nothing around them. */
 size_t exabm4d_codec_chunk_bound(size_t n_elems, int typesize);
 size_t exabm4d_codec_volume_bound(int typesize, int nz, int ny, int nx, int cz, int cy, int cx);
 int exabm4d_codec_encode_dev(exabm4d_ctx* ctx, const void* vol, int typesize, int version, int nz, int ny, int nx,
@@ -607,7 +625,10 @@ int exabm4d_codec_encode_dev(exabm4d_ctx* ctx, const void* vol, int typesize, in
  * from the first chunk's header.  Synchronises.  A malformed container -- offsets that are not
  * ascending, not 2-byte aligned or beyond in_bytes, bad magic, wrong element count or chunk shape,
  * truncated tables or words, symbols outside the alphabet -- gives EXABM4D_ERR_INVALID and never
- * reads outside [in, in + in_bytes). */
+ * reads outside [in, in + in_bytes).  Pointers: in must be 16-byte aligned (EXABM4D_ERR_INVALID otherwise, before
+ * anything is launched); offsets_dev needs 8-byte alignment, vol the natural alignment of its element type only.
+ * in_bytes may be exactly offsets_dev[nchunks].  in and offsets_dev are only read; every one of the nz * ny * nx
+ * elements of vol is written, whatever it held before, and nothing around them. */
 int exabm4d_codec_decode_dev(exabm4d_ctx* ctx, const uint8_t* in, size_t in_bytes, const uint64_t* offsets_dev,
                              int typesize, int nz, int ny, int nx, int cz, int cy, int cx, void* vol);
 
@@ -635,7 +656,17 @@ int exabm4d_codec_decode_dev(exabm4d_ctx* ctx, const uint8_t* in, size_t in_byte
  * launches.  Synchronises.  A malformed container -- offsets not ascending, unaligned or beyond in_bytes, a bad
  * header (magic, version, mode, q != Q[j*], E or C not those of the chunk), an EXAC payload that does not match
  * the header's mode and shapes, or any error the EXAC decoder finds -- gives EXABM4D_ERR_INVALID and never reads
- * outside [in, in + in_bytes).  Scratch comes from the context. */
+ * outside [in, in + in_bytes).  Scratch comes from the context.
+ *
+ * Pointers: those of the chunk coder.  vol (encoder, ladder) needs 2-byte alignment only and is only read; err needs
+ * 4-byte alignment, and every one of its nchunks * 29 entries is written (it need not be zeroed).  out and in must
+ * be 16-byte aligned -- their headers and payloads move 16 bytes at a time -- and a misaligned one, an out without
+ * offsets_dev or an out_capacity below exabm4d_bounded_volume_bound() gives EXABM4D_ERR_INVALID before anything
+ * is launched; offsets_dev needs 8-byte and sizes_dev 4-byte alignment.  Of out exactly the container
+ * [0, offsets_dev[nchunks]) is written, padding included; [offsets_dev[nchunks], out_capacity) is unspecified and
+ * nothing outside [out, out + out_capacity) is touched; a capacity of exactly the bound is enough.  The decoder's
+ * vol needs 2-byte alignment only; every one of its nz * ny * nx voxels is written and nothing around them, in
+ * and offsets_dev are only read, and in_bytes may be exactly offsets_dev[nchunks]. */
 int exabm4d_dctq_ladder_errors_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, int ny, int nx, int cz, int cy,
                                    int cx, uint32_t* err);
 size_t exabm4d_bounded_volume_bound(int nz, int ny, int nx, int cz, int cy, int cx);

@@ -74,12 +74,16 @@ class GuardedView:
     def _download(self):
         return self.buf.download(self.host.shape, np.uint8)
 
-    def check_output(self, want, what=""):
-        """The view equals `want` exactly and every byte around it is as uploaded."""
+    def check_output(self, want, what="", upto=None):
+        """The view equals `want` exactly and every byte around it is as uploaded.  With `upto`, `want` holds
+        only the view's first `upto` elements: those are compared, the rest of the view is left unspecified,
+        and the bytes around the view are checked all the same."""
         got = self._download()
         want = np.ascontiguousarray(want, dtype=self.dtype).reshape(-1)
-        assert want.size == self.n
-        np.testing.assert_array_equal(got[self.lo:self.hi].view(self.dtype), want, err_msg=f"{what}: values")
+        n = self.n if upto is None else int(upto)
+        assert want.size == n <= self.n
+        np.testing.assert_array_equal(got[self.lo:self.lo + n * self.dtype.itemsize].view(self.dtype), want,
+                                      err_msg=f"{what}: values")
         np.testing.assert_array_equal(got[:self.lo], self.host[:self.lo], err_msg=f"{what}: bytes before the view")
         np.testing.assert_array_equal(got[self.hi:], self.host[self.hi:], err_msg=f"{what}: bytes after the view")
 
