@@ -209,6 +209,11 @@ SIGNATURES = {
     "exabm4d_bounded_volume_bound": (_SZ, [_I, _I, _I, _I, _I, _I]),
     "exabm4d_bounded_encode_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, _I, _I, c_vp, _SZ, c_vp, c_vp, c_vp]),
     "exabm4d_bounded_decode_dev": (_I, [_CTX, c_vp, _SZ, c_vp, _I, _I, _I, _I, _I, _I, c_vp]),
+    "exabm4d_block_bounded_volume_bound": (_SZ, [_I, _I, _I, _I, _I, _I]),
+    "exabm4d_block_bounded_steps_dev": (_I, [_CTX, c_vp, c_vp, _I, _I, _I, _I, _I, _I, _I, _I, c_vp]),
+    "exabm4d_block_bounded_encode_dev": (_I, [_CTX, c_vp, c_vp, _I, _I, _I, _I, _I, _I, _I, _I, c_vp, _SZ, c_vp, c_vp,
+                                              c_vp]),
+    "exabm4d_block_bounded_decode_dev": (_I, [_CTX, c_vp, _SZ, c_vp, _I, _I, _I, _I, _I, _I, c_vp]),
     "exabm4d_u16_histogram_dev": (_I, [_CTX, c_vp, _SZ, c_vp]),
     "exabm4d_key_histogram_dev": (_I, [_CTX, c_vp, _I, _SZ, _I, ctypes.c_double, _I,
                                        ctypes.c_uint64, c_vp]),
@@ -762,6 +767,35 @@ class Context:
             self.handle, _ptr(data), int(nbytes), _ptr(offsets), nz, ny, nx, int(chunk[0]), int(chunk[1]),
             int(chunk[2]), _ptr(vol)))
 
+    # -- error-bounded codec, a step per 8^3 block and a per-voxel bound ------------
+    def block_bounded_steps(self, vol, shape, chunk, max_error, fg_max_error, plane, mask=None):
+        """plane (device, uint8 [nchunks][nb rounded up to 16]) <- the step plane of every chunk (0xFE verbatim, 0xFF
+        outside the volume), whatever mode the chunk would be stored in.  Asynchronous."""
+        nz, ny, nx = shape
+        self._check(lib().exabm4d_block_bounded_steps_dev(
+            self.handle, _ptr(vol), _ptr(mask), nz, ny, nx, int(chunk[0]), int(chunk[1]), int(chunk[2]),
+            int(max_error), int(fg_max_error), _ptr(plane)))
+
+    def block_bounded_encode(self, vol, shape, chunk, max_error, fg_max_error, mask=None, out=None, out_capacity=0,
+                             offsets=None, sizes=None, totals=True):
+        """``bounded_encode`` with a step per block; ``mask`` (device uint8 of the volume's shape, or None) marks
+        the voxels whose bound is ``fg_max_error``."""
+        nz, ny, nx = shape
+        tot = np.zeros(2, dtype=np.uint64)
+        self._check(lib().exabm4d_block_bounded_encode_dev(
+            self.handle, _ptr(vol), _ptr(mask), nz, ny, nx, int(chunk[0]), int(chunk[1]), int(chunk[2]),
+            int(max_error), int(fg_max_error), _ptr(out), int(out_capacity), _ptr(offsets), _ptr(sizes),
+            tot.ctypes.data_as(c_vp) if totals else None))
+        return (int(tot[0]), int(tot[1])) if totals else None
+
+    def block_bounded_decode(self, data, nbytes, offsets, shape, chunk, vol):
+        """``data``: ``nbytes`` bytes of block-bounded chunk streams on the device -> uint16 ``vol``; malformed
+        containers raise ValueError without a read outside them."""
+        nz, ny, nx = shape
+        self._check(lib().exabm4d_block_bounded_decode_dev(
+            self.handle, _ptr(data), int(nbytes), _ptr(offsets), nz, ny, nx, int(chunk[0]), int(chunk[1]),
+            int(chunk[2]), _ptr(vol)))
+
     # -- background offset + quality metrics (row f-4); inputs on device, scalars to the host ----
     DTYPES = {np.dtype(np.uint16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}
 
@@ -1101,6 +1135,14 @@ def bounded_volume_bound(shape, chunk):
     b = int(lib().exabm4d_bounded_volume_bound(*(int(s) for s in shape), *(int(c) for c in chunk)))
     if b == 0:
         raise ValueError("bounded codec: sizes >= 1, chunk axes multiples of 8 in [8, 65528], chunk <= 2^28 voxels")
+    return b
+
+
+def block_bounded_volume_bound(shape, chunk):
+    b = int(lib().exabm4d_block_bounded_volume_bound(*(int(s) for s in shape), *(int(c) for c in chunk)))
+    if b == 0:
+        raise ValueError("block-bounded codec: sizes >= 1, chunk axes multiples of 8 in [8, 65528], "
+                         "chunk <= 2^28 voxels")
     return b
 
 

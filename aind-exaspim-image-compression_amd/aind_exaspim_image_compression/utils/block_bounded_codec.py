@@ -1,0 +1,272 @@
+"""Error-bounded lossy chunk codec with a ladder step per 8^3 block and a per-voxel bound.
+
+``BoundedDctCodec`` picks one quantiser step per chunk, so one bright structure sets the step of
+all 512 blocks of a 64^3 chunk, and its bound is the same for every voxel.  Here every 8^3 block takes the coarsest
+step of the same ladder whose reconstruction stays within the bound of each of ITS voxels, and the bound of a voxel
+is ``fg_max_error`` where a caller-supplied mask is set and ``max_error`` elsewhere: neurites exact (or within one
+count) and the background within eight is one stored array.  A block that no step satisfies is stored verbatim, and a
+chunk whose block stream is not shorter than its lossless EXAC stream is stored as the latter, so the guarantee
+``|decoded - input| <= bound`` holds for any mask and any ``fg_max_error <= max_error``.
+
+The format ("EB" version 1) is a sibling of the bounded codec's "EQ" version 1, with its own magic, codec id and
+C-ABI entries; step choice, quantiser, both entropy coders, assembly and decode run on the MI355X
+(``csrc/block_bounded_kernels.hip``, ``exabm4d_block_bounded_*``).
+"""
+import numpy as np
+
+from aind_exaspim_image_compression import _native
+from aind_exaspim_image_compression.utils.bounded_codec import HEADER_BYTES, LADDER, STEPS, _nominal_chunk
+from aind_exaspim_image_compression.utils.chunk_codec import EncodedVolume, _shape3
+
+FORMAT_VERSION = 1
+MODE_LOSSLESS, MODE_BLOCKS = 0, 1
+STEP_VERBATIM, STEP_OUTSIDE = 0xFE, 0xFF
+__all__ = ["BlockBoundedCodec", "pack_header", "parse_header", "plane_bytes", "LADDER", "STEPS"]
+
+
+def plane_bytes(chunk):
+    """Bytes of a chunk's step plane: one per block of the nominal grid, padded to a multiple of 16."""
+    nb = (int(chunk[0]) // 8) * (int(chunk[1]) // 8) * (int(chunk[2]) // 8)
+    return -(-nb // 16) * 16
+
+
+def pack_header(mode, extent, chunk):
+    """The 32-byte header of a chunk stream (mode 0: lossless EXAC uint16 payload; mode 1: step plane, then the EXAC
+    int32 stream of the block indices)."""
+    h = bytearray(HEADER_BYTES)
+    h[0:4] = bytes((ord("E"), ord("B"), FORMAT_VERSION, int(mode)))
+    h[12:24] = np.array(list(extent) + list(chunk), dtype="<u2").tobytes()
+    return bytes(h)
+
+
+def _inside_blocks(extent, chunk):
+    """bool [nb]: the blocks of the nominal grid, raster order, that hold a voxel of the chunk's extent."""
+    cb = tuple(c // 8 for c in chunk)
+    lb = tuple(-(-e // 8) for e in extent)
+    z, y, x = np.meshgrid(*(np.arange(n) for n in cb), indexing="ij")
+    return ((z < lb[0]) & (y < lb[1]) & (x < lb[2])).reshape(-1)
+
+
+def parse_header(blob):
+    """-> dict(mode, extent, chunk, steps) of a chunk stream.  ``steps`` is None for mode 0 and the int16 plane for
+    mode 1 (-1 verbatim, -2 outside).  Everything that can be said about a stream without decoding its EXAC payload is
+    checked here, on the host: ``ValueError`` for a bad magic, version or mode, a non-zero reserved byte, shapes
+    outside ``1 <= E <= C`` with ``C`` a multiple of 8, a plane byte that is no step or 0xFE on an inside block or not
+    0xFF on an outside one, non-zero plane padding, a payload whose EXAC header does not match mode, ``E`` and ``C``,
+    and a stream too short for any of it."""
+    raw = bytes(blob)
+    if len(raw) <= HEADER_BYTES:
+        raise ValueError("block-bounded chunk stream: truncated (no payload behind the 32-byte header)")
+    if raw[0:2] != b"EB":
+        raise ValueError("block-bounded chunk stream: bad magic")
+    if raw[2] != FORMAT_VERSION:
+        raise ValueError(f"block-bounded chunk stream: unknown format version {raw[2]}")
+    mode = raw[3]
+    if mode not in (MODE_LOSSLESS, MODE_BLOCKS):
+        raise ValueError(f"block-bounded chunk stream: unknown mode {mode}")
+    if raw[4:12] != bytes(8) or raw[24:32] != bytes(8):
+        raise ValueError("block-bounded chunk stream: reserved header bytes are not zero")
+    dims = np.frombuffer(raw[12:24], dtype="<u2").astype(int)
+    extent, chunk = tuple(int(v) for v in dims[:3]), tuple(int(v) for v in dims[3:])
+    if any(c < 8 or c % 8 for c in chunk):
+        raise ValueError("block-bounded chunk stream: chunk axes must be multiples of 8")
+    if any(e < 1 or e > c for e, c in zip(extent, chunk)):
+        raise ValueError("block-bounded chunk stream: extent outside 1..chunk")
+    steps, at = None, HEADER_BYTES
+    if mode == MODE_BLOCKS:
+        nb = (chunk[0] // 8) * (chunk[1] // 8) * (chunk[2] // 8)
+        nbp = plane_bytes(chunk)
+        if len(raw) < HEADER_BYTES + nbp:
+            raise ValueError("block-bounded chunk stream: truncated step plane")
+        plane = np.frombuffer(raw[at:at + nbp], dtype=np.uint8)
+        inside = _inside_blocks(extent, chunk)
+        if np.any(plane[nb:]):
+            raise ValueError("block-bounded chunk stream: step plane padding is not zero")
+        if np.any(plane[:nb][~inside] != STEP_OUTSIDE):
+            raise ValueError("block-bounded chunk stream: a block outside the volume carries a step")
+        if np.any((plane[:nb][inside] >= STEPS) & (plane[:nb][inside] != STEP_VERBATIM)):
+            raise ValueError("block-bounded chunk stream: a step beyond the ladder")
+        steps = plane[:nb].astype(np.int16)
+        steps[plane[:nb] == STEP_VERBATIM] = -1
+        steps[plane[:nb] == STEP_OUTSIDE] = -2
+        at += nbp
+        want = (4, nb * 512, 8, 64)
+    else:
+        want = (2, extent[0] * extent[1] * extent[2], extent[1], extent[2])
+    if len(raw) < at + 16:
+        raise ValueError("block-bounded chunk stream: truncated EXAC payload")
+    got = (raw[at + 3],) + tuple(int(v) for v in np.frombuffer(raw[at + 4:at + 16], dtype="<u4"))
+    if raw[at:at + 3] != b"EX\x02" or got != want:
+        raise ValueError("block-bounded chunk stream: the EXAC payload does not match mode, extent and chunk")
+    return {"mode": int(mode), "extent": extent, "chunk": chunk, "steps": steps}
+
+
+class BlockBoundedCodec:
+    """numcodecs-shaped codec of uint16 chunks with a per-voxel error bound and a step per 8^3 block, arithmetic on
+    the GPU."""
+
+    codec_id = "exac-dctq-block"
+    version = FORMAT_VERSION
+
+    def __init__(self, max_error, fg_max_error=None, device=None):
+        max_error = int(max_error)
+        fg_max_error = max_error if fg_max_error is None else int(fg_max_error)
+        if not 0 <= fg_max_error <= max_error <= 65535:
+            raise ValueError("0 <= fg_max_error <= max_error <= 65535 is required")
+        self.max_error = max_error
+        self.fg_max_error = fg_max_error
+        self.device = device
+
+    def get_config(self):
+        return {"id": self.codec_id, "max_error": self.max_error, "fg_max_error": self.fg_max_error,
+                "version": self.version}
+
+    @staticmethod
+    def _mask(mask, shape):
+        """None, or the mask as a contiguous uint8 array (non-zero = foreground) of the volume's 3-D shape."""
+        if mask is None:
+            return None
+        m = np.asarray(mask)
+        if _shape3(m.shape) != tuple(shape):
+            raise ValueError(f"mask shape {m.shape} differs from the volume's {tuple(shape)}")
+        return np.ascontiguousarray(m != 0, dtype=np.uint8).reshape(-1)
+
+    # -- one chunk ---------------------------------------------------------------------------
+    def encode(self, chunk, mask=None):
+        """One uint16 chunk (up to 3-D) -> bytes; its nominal chunk shape is its extent rounded up to multiples
+        of 8."""
+        a = np.ascontiguousarray(chunk)
+        if a.dtype != np.uint16:
+            raise ValueError("BlockBoundedCodec codes uint16 chunks")
+        if a.size == 0:
+            raise ValueError("cannot encode an empty chunk")
+        shape = _shape3(a.shape)
+        return self.encode_volume(a.reshape(shape), chunk=_nominal_chunk(shape), mask=mask).chunk_bytes(0)
+
+    def decode(self, buf, out=None):
+        """bytes of one chunk -> 1-D uint16 array (or filled ``out``).  Header and step plane are validated on the
+        host, before any device call."""
+        raw = bytes(buf)
+        h = parse_header(raw)
+        pad = (-len(raw)) % 16
+        data = np.frombuffer(raw + bytes(pad), dtype=np.uint8)
+        enc = EncodedVolume(data, np.array([0, data.size], dtype=np.uint64), np.array([len(raw)], dtype=np.uint32),
+                            h["extent"], h["chunk"], 2)
+        res = self.decode_volume(enc).reshape(-1)
+        if out is not None:
+            np.copyto(np.asarray(out).reshape(-1), res)
+            return out
+        return res
+
+    # -- a whole volume ------------------------------------------------------------------------
+    def encode_volume(self, vol, chunk=(64, 64, 64), mask=None, want_bytes=True):
+        """Host uint16 array (up to 3-D), optional mask of its shape -> ``EncodedVolume`` (nominal chunk shape,
+        typesize 2).  With ``want_bytes=False`` only the sizes are produced (``data`` is None)."""
+        a = np.ascontiguousarray(vol)
+        if a.dtype != np.uint16:
+            raise ValueError("BlockBoundedCodec codes uint16 volumes")
+        shape = _shape3(a.shape)
+        m = self._mask(mask, shape)
+        ctx = _native.context(self.device)
+        d_vol = ctx.to_device(a.reshape(-1))
+        d_mask = ctx.to_device(m) if m is not None else None
+        try:
+            return self.encode_device(ctx, d_vol, shape, chunk, d_mask, want_bytes)
+        finally:
+            d_vol.free()
+            if d_mask is not None:
+                d_mask.free()
+
+    def encode_device(self, ctx, d_vol, shape, chunk=(64, 64, 64), d_mask=None, want_bytes=True):
+        """The same for a volume (and a uint8 mask, or None) that already lies in HBM (device pointer holders)."""
+        shape, chunk = _shape3(shape), tuple(int(c) for c in _shape3(chunk))
+        cap = _native.block_bounded_volume_bound(shape, chunk)
+        nchunks = int(np.prod([-(-s // c) for s, c in zip(shape, chunk)]))
+        d_sizes = ctx.alloc(4 * nchunks)
+        d_off = ctx.alloc(8 * (nchunks + 1))
+        d_out = ctx.alloc(cap) if want_bytes else None
+        try:
+            _, container = ctx.block_bounded_encode(d_vol, shape, chunk, self.max_error, self.fg_max_error,
+                                                    mask=d_mask, out=d_out, out_capacity=cap if want_bytes else 0,
+                                                    offsets=d_off, sizes=d_sizes)
+            sizes = d_sizes.download((nchunks,), np.uint32)
+            offsets = d_off.download((nchunks + 1,), np.uint64)
+            data = d_out.download((container,), np.uint8) if want_bytes else None
+        finally:
+            d_sizes.free()
+            d_off.free()
+            if d_out is not None:
+                d_out.free()
+        return EncodedVolume(data, offsets, sizes, shape, chunk, 2)
+
+    def decode_volume(self, enc):
+        """``EncodedVolume`` of this format -> host uint16 array of ``enc.shape``."""
+        if enc.typesize != 2:
+            raise ValueError("the block-bounded codec stores uint16 volumes")
+        shape, chunk = _shape3(enc.shape), _shape3(enc.chunk)
+        offsets = np.ascontiguousarray(enc.offsets, dtype=np.uint64)
+        data = np.ascontiguousarray(enc.data, dtype=np.uint8)
+        nchunks = int(np.prod([-(-s // c) for s, c in zip(shape, chunk)]))
+        if offsets.size != nchunks + 1 or np.any(np.diff(offsets.astype(np.int64)) < HEADER_BYTES) or \
+                int(offsets[-1]) > data.size or np.any(offsets % 16):
+            raise ValueError("malformed block-bounded container: offsets are not ascending 16-byte steps inside "
+                             "the data")
+        _native.block_bounded_volume_bound(shape, chunk)          # raises for sizes the format does not take
+        ctx = _native.context(self.device)
+        d_in = ctx.to_device(data if data.size else np.zeros(16, np.uint8))
+        d_off = ctx.to_device(offsets)
+        d_vol = ctx.alloc(2 * int(np.prod(shape)))
+        try:
+            ctx.block_bounded_decode(d_in, data.size, d_off, shape, chunk, d_vol)
+            return d_vol.download(shape, np.uint16)
+        finally:
+            d_in.free()
+            d_off.free()
+            d_vol.free()
+
+    def chunk_sizes(self, vol, chunk=(64, 64, 64), mask=None):
+        """``len(self.encode(c))`` of every chunk of ``vol`` in one batched device call (what ``compute_cratio``
+        takes)."""
+        return self.encode_volume(vol, chunk, mask=mask, want_bytes=False).sizes
+
+    def select_steps(self, vol, chunk=(64, 64, 64), mask=None):
+        """-> int16 [gz, gy, gx, cz/8, cy/8, cx/8]: the step every block of every chunk takes under this codec's
+        bounds (-1: verbatim, -2: outside the volume), whether or not the chunk would then be stored losslessly --
+        where the bound binds, block by block."""
+        a = np.ascontiguousarray(vol)
+        if a.dtype != np.uint16:
+            raise ValueError("BlockBoundedCodec codes uint16 volumes")
+        shape, chunk = _shape3(a.shape), tuple(int(c) for c in _shape3(chunk))
+        m = self._mask(mask, shape)
+        _native.block_bounded_volume_bound(shape, chunk)
+        grid = tuple(-(-s // c) for s, c in zip(shape, chunk))
+        cb = tuple(c // 8 for c in chunk)
+        nb, nbp = int(np.prod(cb)), plane_bytes(chunk)
+        ctx = _native.context(self.device)
+        d_vol = ctx.to_device(a.reshape(-1))
+        d_mask = ctx.to_device(m) if m is not None else None
+        d_plane = ctx.alloc(nbp * int(np.prod(grid)))
+        try:
+            ctx.block_bounded_steps(d_vol, shape, chunk, self.max_error, self.fg_max_error, d_plane, mask=d_mask)
+            plane = d_plane.download((int(np.prod(grid)), nbp), np.uint8)[:, :nb]
+        finally:
+            d_vol.free()
+            d_plane.free()
+            if d_mask is not None:
+                d_mask.free()
+        steps = plane.astype(np.int16)
+        steps[plane == STEP_VERBATIM] = -1
+        steps[plane == STEP_OUTSIDE] = -2
+        return steps.reshape(grid + cb)
+
+    @staticmethod
+    def block_steps(enc):
+        """Per chunk of an ``EncodedVolume`` the int16 step plane over its nominal block grid (-1: verbatim block,
+        -2: block outside the volume), or None for a chunk stored losslessly (mode 0)."""
+        if enc.data is None:
+            raise ValueError("the EncodedVolume carries sizes only (encode with want_bytes=True)")
+        out = []
+        for i in range(len(enc.sizes)):
+            o = int(enc.offsets[i])
+            out.append(parse_header(enc.data[o:o + int(enc.sizes[i])].tobytes())["steps"])
+        return out

@@ -12,7 +12,10 @@ the MI355X in one batched call, and they go to disk in the same directory layout
 
 With ``codec=BoundedDctCodec(max_error)`` (``utils/bounded_codec.py``) the chunk streams are the
 error-bounded lossy ones, and the codec entry reads ``{"name": "exac-dctq", "configuration": {"version": 1,
-"max_error": ..., "edge_chunks": "truncated"}}``; the readers pick the decoder from ``zarr.json``.
+"max_error": ..., "edge_chunks": "truncated"}}``; with ``codec=BlockBoundedCodec(max_error, fg_max_error)``
+(``utils/block_bounded_codec.py``) and an optional ``mask`` they carry a step per 8^3 block, and the
+entry reads ``{"name": "exac-dctq-block", "configuration": {"version": 1, "max_error": ..., "fg_max_error": ...,
+"edge_chunks": "truncated"}}``.  The readers pick the decoder from ``zarr.json``.
 
 so that a chunk is addressable by its key like any Zarr chunk and ``sum(file sizes)`` is the denominator of
 ``compute_cratio`` (utils/img_util.py:401-441).  Differences from a stock Zarr array, stated in the metadata:
@@ -26,6 +29,7 @@ import os
 
 import numpy as np
 
+from aind_exaspim_image_compression.utils.block_bounded_codec import BlockBoundedCodec
 from aind_exaspim_image_compression.utils.bounded_codec import BoundedDctCodec
 from aind_exaspim_image_compression.utils.chunk_codec import EncodedVolume, ExacCodec
 
@@ -43,8 +47,15 @@ def chunk_key(iz, iy, ix):
 
 
 def metadata(shape3, chunk3, typesize=2, version=2, attributes=None, codec=None):
-    """The ``zarr.json`` document of a stored volume (``codec``: a ``BoundedDctCodec`` stores its own entry)."""
+    """The ``zarr.json`` document of a stored volume (``codec``: a ``BoundedDctCodec`` or ``BlockBoundedCodec``
+    stores its own entry)."""
     dtype = {2: "uint16", 4: "int32"}[int(typesize)]
+    if isinstance(codec, BlockBoundedCodec):
+        meta = metadata(shape3, chunk3, 2, attributes=attributes)
+        meta["codecs"] = [{"name": BlockBoundedCodec.codec_id,
+                           "configuration": {"version": BlockBoundedCodec.version, "max_error": codec.max_error,
+                                             "fg_max_error": codec.fg_max_error, "edge_chunks": "truncated"}}]
+        return meta
     if isinstance(codec, BoundedDctCodec):
         meta = metadata(shape3, chunk3, 2, attributes=attributes)
         meta["codecs"] = [{"name": BoundedDctCodec.codec_id,
@@ -68,8 +79,8 @@ def metadata(shape3, chunk3, typesize=2, version=2, attributes=None, codec=None)
 
 def write_encoded(enc, output_path, version=2, attributes=None, overwrite=True, codec=None):
     """``EncodedVolume`` (host container: data, offsets, sizes) -> chunk store at ``output_path``.  Host work
-    only.  Returns the number of bytes written as chunk streams.  ``codec``: the ``BoundedDctCodec`` that made
-    ``enc``, if one did (its entry goes into the metadata)."""
+    only.  Returns the number of bytes written as chunk streams.  ``codec``: the ``BoundedDctCodec`` or
+    ``BlockBoundedCodec`` that made ``enc``, if one did (its entry goes into the metadata)."""
     if enc.data is None:
         raise ValueError("the EncodedVolume carries sizes only (encode with want_bytes=True)")
     gz, gy, gx = _grid(enc.shape, enc.chunk)
@@ -105,11 +116,18 @@ def read_encoded(path):
         if meta["zarr_format"] != 3 or meta["node_type"] != "array":
             raise ValueError("not a Zarr v3 array")
         codecs = meta["codecs"]
-        if len(codecs) != 1 or codecs[0]["name"] not in ("exac", BoundedDctCodec.codec_id):
-            raise ValueError("the array's codec chain is not [exac] or [exac-dctq]")
-        bounded = codecs[0]["name"] == BoundedDctCodec.codec_id
+        if len(codecs) != 1 or codecs[0]["name"] not in ("exac", BoundedDctCodec.codec_id,
+                                                         BlockBoundedCodec.codec_id):
+            raise ValueError("the array's codec chain is not [exac], [exac-dctq] or [exac-dctq-block]")
+        block = codecs[0]["name"] == BlockBoundedCodec.codec_id
+        bounded = block or codecs[0]["name"] == BoundedDctCodec.codec_id
         cfg = codecs[0]["configuration"]
-        if bounded:
+        if block:
+            if int(cfg["version"]) != BlockBoundedCodec.version or \
+                    not 0 <= int(cfg["fg_max_error"]) <= int(cfg["max_error"]) <= 65535:
+                raise ValueError("unsupported exac-dctq-block configuration")
+            typesize = 2
+        elif bounded:
             if int(cfg["version"]) != BoundedDctCodec.version or not 0 <= int(cfg["max_error"]) <= 65535:
                 raise ValueError("unsupported exac-dctq configuration")
             typesize = 2
@@ -141,17 +159,18 @@ def read_encoded(path):
     data = np.zeros(int(offsets[-1]), dtype=np.uint8)
     for b, o in zip(blobs, offsets[:-1]):
         data[int(o):int(o) + len(b)] = np.frombuffer(b, dtype=np.uint8)
-    # the bounded format keeps the nominal chunk shape (its index chunks are sized by it)
+    # the bounded formats keep the nominal chunk shape (their index chunks are sized by it)
     chunk_eff = chunk3 if bounded else tuple(min(c, s) for c, s in zip(chunk3, shape3))
     return EncodedVolume(data, offsets, sizes, shape3, chunk_eff, typesize), meta
 
 
-def write_zarr(img, output_path, chunks=(1, 1, 64, 64, 64), codec=None, attributes=None):
+def write_zarr(img, output_path, chunks=(1, 1, 64, 64, 64), codec=None, attributes=None, mask=None):
     """The reference's ``write_zarr(img, output_path, chunks=(1, 1, 64, 64, 64))`` with the EXAC chunk coder in
     the place of Blosc (utils/img_util.py:898-950): ``img`` (uint16, promoted to 5-D like the reference; t and
     c must be 1) is coded on the device in one batched call and written as a chunk store.  Returns the
     compression ratio raw bytes / stored chunk bytes -- what ``compute_cratio(img, codec, chunks[2:])`` reports,
-    unrounded."""
+    unrounded.  ``mask`` (``BlockBoundedCodec`` only; the shape of ``img`` or of its volume) marks the voxels held to
+    the codec's ``fg_max_error``."""
     img = np.asarray(img)
     while img.ndim < 5:
         img = img[np.newaxis, ...]
@@ -161,8 +180,13 @@ def write_zarr(img, output_path, chunks=(1, 1, 64, 64, 64), codec=None, attribut
         raise ValueError("chunks must be (1, 1, cz, cy, cx)")
     codec = codec or ExacCodec(2)
     vol = np.ascontiguousarray(img[0, 0])
-    enc = codec.encode_volume(vol, chunk=tuple(int(c) for c in chunks[2:]))
-    if isinstance(codec, BoundedDctCodec):
+    if isinstance(codec, BlockBoundedCodec):
+        enc = codec.encode_volume(vol, chunk=tuple(int(c) for c in chunks[2:]), mask=mask)
+    elif mask is not None:
+        raise ValueError("only a BlockBoundedCodec takes a mask")
+    else:
+        enc = codec.encode_volume(vol, chunk=tuple(int(c) for c in chunks[2:]))
+    if isinstance(codec, (BoundedDctCodec, BlockBoundedCodec)):
         stored = write_encoded(enc, output_path, attributes=attributes, codec=codec)
     else:
         stored = write_encoded(enc, output_path, version=codec.version, attributes=attributes)
@@ -194,6 +218,9 @@ def read_chunk(path, iz, iy, ix, codec=None):
 def _codec_of(meta):
     """The decoder a store's ``zarr.json`` names."""
     entry = meta["codecs"][0]
+    if entry["name"] == BlockBoundedCodec.codec_id:
+        return BlockBoundedCodec(int(entry["configuration"]["max_error"]),
+                                 int(entry["configuration"]["fg_max_error"]))
     if entry["name"] == BoundedDctCodec.codec_id:
         return BoundedDctCodec(int(entry["configuration"]["max_error"]))
     return ExacCodec(int(entry["configuration"]["typesize"]))

@@ -1,4 +1,4 @@
-// api_codec.hip -- chunk byte histograms, the DCT quantiser, the EXAC chunk codec and the error-bounded codec.
+// api_codec.hip -- chunk byte histograms, the DCT quantiser, the EXAC chunk codec and the two error-bounded codecs.
 // Host code only; the context and the shared helpers are in exabm4d_api.h.
 #include "exabm4d_api.h"
 
@@ -86,6 +86,28 @@ struct BqEncodeScratch {
 // bounded decode's scratch: ladder, chunk modes and steps, the two decode lists, lossy indices
 struct BqDecodeScratch {
     float *qtab, *qv;
+    uint32_t *mode, *lchunk, *lstat;     // lstat: list counts [2], status
+    unsigned long long* lrange;
+    int32_t* idx;
+};
+
+// ---- error-bounded codec, a step per block: the bounded codec's geometry and ladder -----------
+// A mode-1 stream is stored only when it is shorter than the mode-0 one, so the lossless bound holds every stream.
+static size_t bb_volume_bound(const BoundedGeom& g) {
+    const size_t b = codec_chunk_bound((size_t)g.cz * g.cy * g.cx, 2);
+    return (size_t)g.nchunks * (BQ_HEADER + ((b + 15) & ~(size_t)15));
+}
+// encode's scratch: ladder, step planes, indices, the two candidate streams, the container
+struct BbEncodeScratch {
+    float* qtab;
+    uint8_t *plane, *lbuf, *ubuf, *slot;
+    int32_t* idx;
+    uint32_t *lsz, *usz, *sizes;
+    unsigned long long *loff, *uoff, *tot, *offsets;     // tot: lossy, lossless, container {exact, container}
+};
+// decode's scratch: ladder, chunk modes, the two decode lists, indices of the mode-1 chunks
+struct BbDecodeScratch {
+    float* qtab;
     uint32_t *mode, *lchunk, *lstat;     // lstat: list counts [2], status
     unsigned long long* lrange;
     int32_t* idx;
@@ -299,6 +321,127 @@ int exabm4d_bounded_decode_dev(exabm4d_ctx* ctx, const uint8_t* in, size_t in_by
                                           (unsigned)nc, gl, S.idx, status, s));
     HIP_TRY(ctx, launch_bq_inverse(S.idx, g, dct_table(), S.mode, S.qv, vol, s));
     return check_stream_status(ctx, status, "bounded codec");
+}
+
+// ---- error-bounded codec, a step per block and a per-voxel bound -------------------------------
+size_t exabm4d_block_bounded_volume_bound(int nz, int ny, int nx, int cz, int cy, int cx) {
+    BoundedGeom g;
+    if (make_bounded_geom(nz, ny, nx, cz, cy, cx, g)) return 0;
+    return bb_volume_bound(g);
+}
+
+int exabm4d_block_bounded_steps_dev(exabm4d_ctx* ctx, const uint16_t* vol, const uint8_t* mask, int nz, int ny,
+                                    int nx, int cz, int cy, int cx, int max_error, int fg_max_error, uint8_t* plane) {
+    if (!ctx || !vol || !plane) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (fg_max_error < 0 || fg_max_error > max_error || max_error > 65535)
+        return fail(ctx, EXABM4D_ERR_INVALID, "block-bounded codec: 0 <= fg_max_error <= max_error <= 65535");
+    BoundedGeom g;
+    CodecGeom gl, gu;
+    int rc = bq_geom(ctx, nz, ny, nx, cz, cy, cx, g, gl, gu);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t nc = (size_t)g.nchunks;
+    struct { float* qtab; int32_t* idx; } S;
+    rc = carve(ctx, ctx->scratch, GUARD_BYTES, S, [&](Carver& c, auto& r) {
+        r.qtab = c.take<float>(sizeof(BqLadder));
+        r.idx = c.take<int32_t>(nc * g.nb * BVOX * sizeof(int32_t));
+    });
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(S.qtab, bq_ladder().q, sizeof(BqLadder), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(plane, 0, nc * bb_plane_bytes(g), s));
+    HIP_TRY(ctx, launch_bb_select(vol, mask, g, dct_table(), S.qtab, (uint32_t)max_error, (uint32_t)fg_max_error,
+                                  plane, S.idx, s));
+    return EXABM4D_OK;
+}
+
+int exabm4d_block_bounded_encode_dev(exabm4d_ctx* ctx, const uint16_t* vol, const uint8_t* mask, int nz, int ny,
+                                     int nx, int cz, int cy, int cx, int max_error, int fg_max_error, uint8_t* out,
+                                     size_t out_capacity, uint64_t* offsets_dev, uint32_t* sizes_dev,
+                                     uint64_t* totals_host) {
+    if (!ctx || !vol) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if (fg_max_error < 0 || fg_max_error > max_error || max_error > 65535)
+        return fail(ctx, EXABM4D_ERR_INVALID, "block-bounded codec: 0 <= fg_max_error <= max_error <= 65535");
+    BoundedGeom g;
+    CodecGeom gl, gu;
+    int rc = bq_geom(ctx, nz, ny, nx, cz, cy, cx, g, gl, gu);
+    if (rc) return rc;
+    rc = check_container(ctx, "block-bounded codec", "exabm4d_block_bounded_volume_bound", bb_volume_bound(g), out,
+                         out_capacity, offsets_dev);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = codec_rcp(ctx);
+    if (rc) return rc;
+    const size_t nc = (size_t)g.nchunks, nbp = bb_plane_bytes(g);
+    const size_t slots = std::max(align256((size_t)gl.nchunks * gl.slot_bytes) + codec2_work_bytes(gl),
+                                  align256((size_t)gu.nchunks * gu.slot_bytes) + codec2_work_bytes(gu));
+    BbEncodeScratch S;
+    rc = carve(ctx, ctx->scratch, GUARD_BYTES, S, [&](Carver& c, auto& r) {
+        r.qtab = c.take<float>(sizeof(BqLadder));
+        r.plane = c.take<uint8_t>(nc * nbp);
+        r.idx = c.take<int32_t>(nc * g.nb * BVOX * sizeof(int32_t));
+        r.lsz = c.take<uint32_t>(nc * sizeof(uint32_t));
+        r.loff = c.take<unsigned long long>((nc + 1) * 8);
+        r.lbuf = out ? c.take<uint8_t>(codec_volume_bound(gl)) : nullptr;
+        r.usz = c.take<uint32_t>(nc * sizeof(uint32_t));
+        r.uoff = c.take<unsigned long long>((nc + 1) * 8);
+        r.ubuf = out ? c.take<uint8_t>(codec_volume_bound(gu)) : nullptr;
+        r.tot = c.take<unsigned long long>(6 * 8);
+        r.sizes = c.take<uint32_t>(nc * sizeof(uint32_t));
+        r.offsets = c.take<unsigned long long>((nc + 1) * 8);
+        r.slot = c.take<uint8_t>(slots);
+    });
+    if (rc) return rc;
+    if (sizes_dev) S.sizes = sizes_dev;
+    if (offsets_dev) S.offsets = reinterpret_cast<unsigned long long*>(offsets_dev);
+    const uint32_t* rcp = ctx->rcp_dev.as<uint32_t>();
+    hipStream_t s = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(S.qtab, bq_ladder().q, sizeof(BqLadder), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(S.plane, 0, nc * nbp, s));        // the planes' padding
+    HIP_TRY(ctx, launch_bb_select(vol, mask, g, dct_table(), S.qtab, (uint32_t)max_error, (uint32_t)fg_max_error,
+                                  S.plane, S.idx, s));
+    // the two candidates of every chunk through the existing chunk coder: the index chunks, then the voxels
+    HIP_TRY(ctx, launch_rans_encode(S.idx, gl, rcp, S.slot, S.lsz, S.loff, S.tot, S.lbuf, s));
+    HIP_TRY(ctx, launch_rans_encode(vol, gu, rcp, S.slot, S.usz, S.uoff, S.tot + 2, S.ubuf, s));
+    HIP_TRY(ctx, launch_bb_assemble(g, S.plane, S.lbuf, S.loff, S.lsz, S.ubuf, S.uoff, S.usz, S.sizes, S.offsets,
+                                    S.tot + 4, out, s));
+    return totals_host ? fetch(ctx, totals_host, S.tot + 4, 2 * sizeof(uint64_t)) : EXABM4D_OK;
+}
+
+int exabm4d_block_bounded_decode_dev(exabm4d_ctx* ctx, const uint8_t* in, size_t in_bytes,
+                                     const uint64_t* offsets_dev, int nz, int ny, int nx, int cz, int cy, int cx,
+                                     uint16_t* vol) {
+    if (!ctx || !in || !offsets_dev || !vol) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if ((uintptr_t)in & 15) return fail(ctx, EXABM4D_ERR_INVALID, "block-bounded codec: in must be 16-byte aligned");
+    BoundedGeom g;
+    CodecGeom gl, gu;
+    int rc = bq_geom(ctx, nz, ny, nx, cz, cy, cx, g, gl, gu);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t nc = (size_t)g.nchunks;
+    BbDecodeScratch S;
+    rc = carve(ctx, ctx->scratch, GUARD_BYTES, S, [&](Carver& c, auto& r) {
+        r.qtab = c.take<float>(sizeof(BqLadder));
+        r.mode = c.take<uint32_t>(nc * sizeof(uint32_t));
+        r.lchunk = c.take<uint32_t>(2 * nc * sizeof(uint32_t));
+        r.lrange = c.take<unsigned long long>(4 * nc * 8);
+        r.lstat = c.take<uint32_t>(4 * sizeof(uint32_t));
+        r.idx = c.take<int32_t>(nc * g.nb * BVOX * sizeof(int32_t));
+    });
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    const unsigned long long* offsets = reinterpret_cast<const unsigned long long*>(offsets_dev);
+    uint32_t* status = S.lstat + 2;
+    HIP_TRY(ctx, hipMemcpyAsync(S.qtab, bq_ladder().q, sizeof(BqLadder), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(S.lstat, 0, 4 * sizeof(uint32_t), s));
+    HIP_TRY(ctx, launch_bb_parse(in, in_bytes, offsets, g, S.mode, S.lchunk, S.lrange, S.lstat, status, s));
+    // mode-0 chunks straight into the volume, mode-1 chunks' indices into the chunk-major scratch, then their blocks
+    HIP_TRY(ctx, launch_rans2_decode_list(in, in_bytes, DecodeList{S.lchunk, S.lrange, S.lstat}, (unsigned)nc, gu, vol,
+                                          status, s));
+    HIP_TRY(ctx, launch_rans2_decode_list(in, in_bytes, DecodeList{S.lchunk + nc, S.lrange + 2 * nc, S.lstat + 1},
+                                          (unsigned)nc, gl, S.idx, status, s));
+    HIP_TRY(ctx, launch_bb_inverse(S.idx, in, offsets, g, dct_table(), S.qtab, S.mode, vol, status, s));
+    return check_stream_status(ctx, status, "block-bounded codec");
 }
 
 }  // extern "C"

@@ -16,54 +16,12 @@
 // dctq_inverse_kernel's (codec_kernels.hip), with the seven-magnitude form of the DCT chains, which is
 // bit-identical to the 64-entry table (dct_pairs.h): the error the ladder measures is the error every decoder
 // produces.
-#include "dct_pairs.h"
-#include "exabm4d_kernels.h"
+#include "bounded_pairs.h"
 #include "rans_common.h"
 
 namespace exabm4d {
 
 namespace {
-
-constexpr int BQ_WAVES = 4;
-constexpr int BQ_PAIRS = 16;                 // block pairs per wave and workgroup (a chunk takes several workgroups)
-constexpr float BQ_IDX_MAX = 1073741824.0f;  // indices are clamped to +-2^30
-
-__device__ __forceinline__ int bq_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-// the blocks of chunk c: first block in the volume's block grid, and ceil(E / 8) blocks per axis inside the volume
-struct ChunkBlocks {
-    int bz0, by0, bx0;
-    int lbz, lby, lbx;
-};
-__device__ __forceinline__ ChunkBlocks chunk_blocks(const BoundedGeom& g, int c) {
-    const int kx = c % g.gx, ky = (c / g.gx) % g.gy, kz = c / (g.gx * g.gy);
-    ChunkBlocks b;
-    b.bz0 = kz * g.cbz;
-    b.by0 = ky * g.cby;
-    b.bx0 = kx * g.cbx;
-    b.lbz = min(g.cbz, (g.nz - kz * g.cz + 7) / 8);
-    b.lby = min(g.cby, (g.ny - ky * g.cy + 7) / 8);
-    b.lbx = min(g.cbx, (g.nx - kx * g.cx + 7) / 8);
-    return b;
-}
-
-// layout L1 (lane = (z, x), registers = y) of two x-adjacent blocks, edge voxels replicated: dctq_forward_kernel's load
-__device__ __forceinline__ void load_pair(const uint16_t* __restrict__ vol, const BoundedGeom& g, int bz, int by,
-                                          int bxa, int bxb, int hi, int lo, f2 (&v)[8]) {
-    const size_t zrow = (size_t)bq_clamp(8 * bz + hi, 0, g.nz - 1) * g.ny;
-    const int xa = bq_clamp(8 * bxa + lo, 0, g.nx - 1), xb = bq_clamp(8 * bxb + lo, 0, g.nx - 1);
-#pragma unroll
-    for (int y = 0; y < 8; y++) {
-        const size_t row = (zrow + bq_clamp(8 * by + y, 0, g.ny - 1)) * g.nx;
-        v[y] = mk2((float)vol[row + xa], (float)vol[row + xb]);
-    }
-}
-
-__device__ __forceinline__ int32_t quantise(float c, float q) {
-    return (int32_t)fminf(fmaxf(rintf(c / q), -BQ_IDX_MAX), BQ_IDX_MAX);
-}
-
-__device__ __forceinline__ float to_voxel(float v) { return rintf(fminf(fmaxf(v, 0.0f), 65535.0f)); }
 
 __global__ __launch_bounds__(BQ_WAVES * 64) void bq_ladder_kernel(const uint16_t* __restrict__ vol, BoundedGeom g,
                                                                   Dct7 T, const float* __restrict__ qtab, int slices,
@@ -73,7 +31,7 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void bq_ladder_kernel(const uint16_t
     const int hi = lane >> 3, lo = lane & 7;
     f2* tb = reinterpret_cast<f2*>(lds + wave * 2 * TBUF);
     const int c = blockIdx.x / slices, w = (blockIdx.x % slices) * BQ_WAVES + wave;
-    const ChunkBlocks cb = chunk_blocks(g, c);
+    const BqChunkBlocks cb = bq_chunk_blocks(g, c);
     // pairs inside the chunk: both blocks of a pair belong to chunk c
     const int pairs_x = (cb.lbx + 1) / 2, npairs = cb.lbz * cb.lby * pairs_x;
     uint32_t acc = 0;           // lane j < BQ_STEPS: largest error of step j over this wave's pairs
@@ -82,7 +40,7 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void bq_ladder_kernel(const uint16_t
         const int by = cb.by0 + t % cb.lby, bz = cb.bz0 + t / cb.lby;
         const int bxa = cb.bx0 + 2 * px, bxb = cb.bx0 + min(2 * px + 1, cb.lbx - 1);
         f2 v[8], o[8];
-        load_pair(vol, g, bz, by, bxa, bxb, hi, lo, v);
+        bq_load_pair(vol, g, bz, by, bxa, bxb, hi, lo, v);
 #pragma unroll
         for (int y = 0; y < 8; y++) o[y] = v[y];
         pair_fwd(T, tb, hi, lo, v);
@@ -95,14 +53,15 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void bq_ladder_kernel(const uint16_t
             const float q = qtab[j];
             f2 r[8];
 #pragma unroll
-            for (int u = 0; u < 8; u++) r[u] = mk2((float)quantise(v[u].x, q) * q, (float)quantise(v[u].y, q) * q);
+            for (int u = 0; u < 8; u++)
+                r[u] = mk2((float)bq_quantise(v[u].x, q) * q, (float)bq_quantise(v[u].y, q) * q);
             pair_inv(T, tb, hi, lo, r);
             float m = 0.0f;
 #pragma unroll
             for (int y = 0; y < 8; y++) {
                 if (y < yv) {
-                    if (oka) m = fmaxf(m, fabsf(to_voxel(r[y].x) - o[y].x));
-                    if (okb) m = fmaxf(m, fabsf(to_voxel(r[y].y) - o[y].y));
+                    if (oka) m = fmaxf(m, fabsf(bq_to_voxel(r[y].x) - o[y].x));
+                    if (okb) m = fmaxf(m, fabsf(bq_to_voxel(r[y].y) - o[y].y));
                 }
             }
             const uint32_t mw = wave_max((uint32_t)m);
@@ -132,7 +91,7 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void bq_forward_kernel(const uint16_
     const int hi = lane >> 3, lo = lane & 7;
     f2* tb = reinterpret_cast<f2*>(lds + wave * 2 * TBUF);
     const int c = blockIdx.x / slices, w = (blockIdx.x % slices) * BQ_WAVES + wave;
-    const ChunkBlocks cb = chunk_blocks(g, c);
+    const BqChunkBlocks cb = bq_chunk_blocks(g, c);
     const float q = qsel[c];
     // pairs of the chunk's NOMINAL block grid: every index of the chunk is written
     const int pairs_x = (g.cbx + 1) / 2, npairs = g.cbz * g.cby * pairs_x;
@@ -155,12 +114,12 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void bq_forward_kernel(const uint16_
             continue;
         }
         f2 v[8];
-        load_pair(vol, g, cb.bz0 + lz, cb.by0 + ly, cb.bx0 + lxa, cb.bx0 + lxb, hi, lo, v);
+        bq_load_pair(vol, g, cb.bz0 + lz, cb.by0 + ly, cb.bx0 + lxa, cb.bx0 + lxb, hi, lo, v);
         pair_fwd(T, tb, hi, lo, v);
 #pragma unroll
         for (int u = 0; u < 8; u++) {
-            oa[u * 64] = quantise(v[u].x, q);
-            if (lxb != lxa) ob[u * 64] = inb ? quantise(v[u].y, q) : 0;
+            oa[u * 64] = bq_quantise(v[u].x, q);
+            if (lxb != lxa) ob[u * 64] = inb ? bq_quantise(v[u].y, q) : 0;
         }
     }
 }
@@ -268,7 +227,7 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void bq_inverse_kernel(const int32_t
     const int c = blockIdx.x / slices, w = (blockIdx.x % slices) * BQ_WAVES + wave;
     if (mode[c] != 1u) return;
     const float q = qv[c];
-    const ChunkBlocks cb = chunk_blocks(g, c);
+    const BqChunkBlocks cb = bq_chunk_blocks(g, c);
     const int pairs_x = (cb.lbx + 1) / 2, npairs = cb.lbz * cb.lby * pairs_x;
     const int32_t* base = idx + (size_t)c * g.nb * BVOX + lo * 8 + hi;
     for (int p = w; p < npairs; p += slices * BQ_WAVES) {
@@ -287,32 +246,11 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void bq_inverse_kernel(const int32_t
             const int yy = 8 * (cb.by0 + ly) + y;
             if (z < g.nz && yy < g.ny) {
                 const size_t row = ((size_t)z * g.ny + yy) * g.nx;
-                if (xa < g.nx) vol[row + xa] = (uint16_t)(int)to_voxel(v[y].x);
-                if (lxb != lxa && xb < g.nx) vol[row + xb] = (uint16_t)(int)to_voxel(v[y].y);
+                if (xa < g.nx) vol[row + xa] = (uint16_t)(int)bq_to_voxel(v[y].x);
+                if (lxb != lxa && xb < g.nx) vol[row + xb] = (uint16_t)(int)bq_to_voxel(v[y].y);
             }
         }
     }
-}
-
-// workgroups per chunk so that a wave takes about BQ_PAIRS block pairs of a full chunk
-int bq_slices(const BoundedGeom& g) {
-    const long long pairs = (long long)g.cbz * g.cby * ((g.cbx + 1) / 2);
-    const long long s = (pairs + BQ_WAVES * BQ_PAIRS - 1) / (BQ_WAVES * BQ_PAIRS);
-    return (int)(s < 1 ? 1 : s);
-}
-
-bool bq_grid(const BoundedGeom& g, unsigned& grid, int& slices) {
-    slices = bq_slices(g);
-    const long long n = (long long)g.nchunks * slices;
-    if (n > 0x7FFFFFFFll) return false;
-    grid = (unsigned)n;
-    return true;
-}
-
-bool bq_table(const float* dct64, Dct7& q7) {
-    DctTable T;
-    for (int i = 0; i < 64; i++) T.d[i] = dct64[i];
-    return make_dct7(T, q7);
 }
 
 }  // namespace

@@ -302,6 +302,31 @@ hipError_t launch_bq_parse(const uint8_t* in, size_t in_bytes, const unsigned lo
 hipError_t launch_bq_inverse(const int32_t* idx, const BoundedGeom& g, const float* dct64, const uint32_t* mode,
                              const float* qv, uint16_t* vol, hipStream_t s);
 
+// ---- error-bounded codec, a step per 8^3 block (block_bounded_kernels.hip) ------------------
+// Geometry, ladder and header length are the bounded codec's.  A chunk's step plane: one byte per block of the
+// nominal grid in raster order (step, 0xFE verbatim, 0xFF outside the volume), zero-padded to bb_plane_bytes().
+uint32_t bb_plane_bytes(const BoundedGeom& g);
+// plane[c][block] (padding zeroed by the caller) and the chunk-major indices idx[c][nb][512] in one pass: per inside
+// block the largest step whose reconstruction is within delta (delta_fg where mask != 0; mask may be NULL) of every
+// voxel of the block inside the volume, its indices at that step; its voxels if there is no such step; zeros outside
+hipError_t launch_bb_select(const uint16_t* vol, const uint8_t* mask, const BoundedGeom& g, const float* dct64,
+                            const float* qtab, uint32_t delta, uint32_t delta_fg, uint8_t* plane, int32_t* idx,
+                            hipStream_t s);
+// launch_bq_assemble with the plane in front of a mode-1 payload (plane: 16-byte aligned)
+hipError_t launch_bb_assemble(const BoundedGeom& g, const uint8_t* plane, const uint8_t* lossy,
+                              const unsigned long long* lossy_off, const uint32_t* lossy_sz, const uint8_t* lossless,
+                              const unsigned long long* lossless_off, const uint32_t* lossless_sz, uint32_t* sizes,
+                              unsigned long long* offsets, unsigned long long* totals, uint8_t* out, hipStream_t s);
+// launch_bq_parse for this format: offsets, header and step plane of every chunk; status |= 32 / 64
+hipError_t launch_bb_parse(const uint8_t* in, size_t in_bytes, const unsigned long long* offsets,
+                           const BoundedGeom& g, uint32_t* mode, uint32_t* lchunk, unsigned long long* lrange,
+                           uint32_t* lcount, uint32_t* status, hipStream_t s);
+// the mode-1 chunks' blocks into the volume, steps read from the planes launch_bb_parse validated; status |= 128 for
+// a verbatim value outside 0..65535
+hipError_t launch_bb_inverse(const int32_t* idx, const uint8_t* in, const unsigned long long* offsets,
+                             const BoundedGeom& g, const float* dct64, const float* qtab, const uint32_t* mode,
+                             uint16_t* vol, uint32_t* status, hipStream_t s);
+
 // ---- patch-cache masks and coherence gate (mask_kernels.hip) ---------------------------------------------
 constexpr int LS_MAX = 1024;        // distinct labels a patch's LDS hash set holds (exabm4d.h EXABM4D_LABEL_SET_MAX)
 constexpr int SEG_STATS_K = 23;     // doubles per (patch, label) of launch_segment_stats (EXABM4D_SEG_STATS_K)

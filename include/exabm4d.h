@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define EXABM4D_VERSION 400 /* additive within 400: + exabm4d_pg_noise, exabm4d_denoise_pg_u16_dev, exabm4d_denoise_pg_chunked_u16_dev / _host, exabm4d_gat_forward_u16_dev, exabm4d_gat_inverse_u16_dev (denoising under Poisson-Gaussian noise); + exabm4d_dctq_ladder_errors_dev, exabm4d_bounded_volume_bound, exabm4d_bounded_encode_dev, exabm4d_bounded_decode_dev (error-bounded lossy chunk codec); + exabm4d_foreground_masks_dev, exabm4d_binary_dilate_dev, exabm4d_gaussian_filter3d_dev, exabm4d_label_set_dev, exabm4d_segment_stats_dev (patch-cache masks and coherence gate); + exabm4d_groupnorm_lrelu_ndhwc_dt_dev, exabm4d_maxpool2_ndhwc_dt_dev, exabm4d_upsample2_trilinear_ndhwc_dt_dev (fp16 / bf16 BM4DNet kernels); 0.4.0 (round 4): order-independent aggregation -- exabm4d_stage_dev takes data_exp and WRITES num / den, options "stage_pairs" / "stage_quads" / "fuse_den_z" are gone, the stage / block-matching options are per context; 0.3.2: + exabm4d_blockmatch_plan, option "stage_strip"; 0.3.1: + exabm4d_denoise_chunked_u16_host, options "bm_carry" / "bm_xcd_mode"; 0.3.0: EXAC v2 coder, exabm4d_codec_decode_dev takes in_bytes (round 3) */
+#define EXABM4D_VERSION 400 /* additive within 400: + exabm4d_pg_noise, exabm4d_denoise_pg_u16_dev, exabm4d_denoise_pg_chunked_u16_dev / _host, exabm4d_gat_forward_u16_dev, exabm4d_gat_inverse_u16_dev (denoising under Poisson-Gaussian noise); + exabm4d_dctq_ladder_errors_dev, exabm4d_bounded_volume_bound, exabm4d_bounded_encode_dev, exabm4d_bounded_decode_dev (error-bounded lossy chunk codec); + exabm4d_block_bounded_volume_bound, exabm4d_block_bounded_steps_dev, exabm4d_block_bounded_encode_dev, exabm4d_block_bounded_decode_dev (error-bounded codec with a step per 8^3 block and a per-voxel bound); + exabm4d_foreground_masks_dev, exabm4d_binary_dilate_dev, exabm4d_gaussian_filter3d_dev, exabm4d_label_set_dev, exabm4d_segment_stats_dev (patch-cache masks and coherence gate); + exabm4d_groupnorm_lrelu_ndhwc_dt_dev, exabm4d_maxpool2_ndhwc_dt_dev, exabm4d_upsample2_trilinear_ndhwc_dt_dev (fp16 / bf16 BM4DNet kernels); 0.4.0 (round 4): order-independent aggregation -- exabm4d_stage_dev takes data_exp and WRITES num / den, options "stage_pairs" / "stage_quads" / "fuse_den_z" are gone, the stage / block-matching options are per context; 0.3.2: + exabm4d_blockmatch_plan, option "stage_strip"; 0.3.1: + exabm4d_denoise_chunked_u16_host, options "bm_carry" / "bm_xcd_mode"; 0.3.0: EXAC v2 coder, exabm4d_codec_decode_dev takes in_bytes (round 3) */
 
 typedef enum exabm4d_status {
     EXABM4D_OK = 0,
@@ -675,6 +675,46 @@ int exabm4d_bounded_encode_dev(exabm4d_ctx* ctx, const uint16_t* vol, int nz, in
                                uint32_t* sizes_dev, uint64_t* totals_host);
 int exabm4d_bounded_decode_dev(exabm4d_ctx* ctx, const uint8_t* in, size_t in_bytes, const uint64_t* offsets_dev,
                                int nz, int ny, int nx, int cz, int cy, int cx, uint16_t* vol);
+
+/* Error-bounded lossy chunk codec with a ladder step per 8^3 block and a per-voxel bound (format
+ * "EB" version 1).  Chunks, nominal chunk shape, the ladder Q[0..28] and the transform quantiser are those of the
+ * bounded codec above.  The bound of voxel v is b(v) = fg_max_error where mask[v] != 0, else max_error; mask is a
+ * device uint8 array of the volume's shape or NULL (b = max_error everywhere).  0 <= fg_max_error <= max_error <=
+ * 65535.  A block of the chunk's nominal grid (cz/8, cy/8, cx/8), raster order, is inside when it holds a voxel of
+ * the volume.  An inside block takes the largest step j whose reconstruction is within b(v) of each of its voxels
+ * inside the volume and stores its indices at Q[j]; with no such step it is verbatim and stores its voxels as int32 at
+ * slot (z * 8 + y) * 8 + x (edge voxels replicated); an outside block stores zeros.  Step plane: one byte per block
+ * -- j, 0xFE verbatim, 0xFF outside -- zero-padded to a multiple of 16.  Chunk stream: 32-byte header ('E' 'B' 1 mode
+ * | 8 zero bytes | Ez Ey Ex Cz Cy Cx as u16 | 8 zero bytes); mode 1: the padded step plane and the EXAC v2 int32
+ * stream of the (nb, 8, 64) indices, stored iff that stream is strictly shorter than mode 0: the EXAC v2 uint16
+ * stream of the chunk's voxels.  Every decoded voxel is within b(v) of the encoder's input; max_error = 0 is exact.
+ *
+ * exabm4d_block_bounded_volume_bound: capacity `out` needs (0 for bad sizes).
+ * exabm4d_block_bounded_steps_dev: plane[nchunks][nb rounded up to a multiple of 16] (device, uint8) <- the step plane
+ * of every chunk, padding included, whatever mode the chunk would be stored in: the per-block picture of where the
+ * bound binds.  It is not part of the store's path: it exists so that tools/bounded_sweep.py can time the select
+ * kernel alone, as exabm4d_dctq_ladder_errors_dev does for the per-chunk codec.  Every byte is written; does not
+ * synchronise.
+ * exabm4d_block_bounded_encode_dev: the contract of exabm4d_bounded_encode_dev -- out may be NULL (sizes only),
+ * offsets_dev[nchunks + 1], sizes_dev[nchunks], totals_host[2] (non-NULL synchronises), every stream at a multiple of
+ * 16 bytes with zeroed padding; a misaligned out, an out without offsets_dev or an out_capacity below the bound gives
+ * EXABM4D_ERR_INVALID before anything is launched, and nothing outside [out, out + out_capacity) is ever written.
+ * exabm4d_block_bounded_decode_dev: container -> vol[nz][ny][nx]; synchronises.  A malformed container -- offsets not
+ * ascending, unaligned or beyond in_bytes, a bad header (magic, version, mode, non-zero reserved bytes, E or C not
+ * those of the chunk), a plane byte that is no step / 0xFE on an inside block or not 0xFF on an outside one, non-zero
+ * plane padding, an EXAC payload that does not match mode and shapes, a verbatim value outside 0..65535, or any error
+ * the EXAC decoder finds -- gives EXABM4D_ERR_INVALID and never reads outside [in, in + in_bytes).
+ * Pointers: as for the bounded codec; mask needs no alignment and is only read. */
+size_t exabm4d_block_bounded_volume_bound(int nz, int ny, int nx, int cz, int cy, int cx);
+int exabm4d_block_bounded_steps_dev(exabm4d_ctx* ctx, const uint16_t* vol, const uint8_t* mask, int nz, int ny,
+                                    int nx, int cz, int cy, int cx, int max_error, int fg_max_error, uint8_t* plane);
+int exabm4d_block_bounded_encode_dev(exabm4d_ctx* ctx, const uint16_t* vol, const uint8_t* mask, int nz, int ny,
+                                     int nx, int cz, int cy, int cx, int max_error, int fg_max_error, uint8_t* out,
+                                     size_t out_capacity, uint64_t* offsets_dev, uint32_t* sizes_dev,
+                                     uint64_t* totals_host);
+int exabm4d_block_bounded_decode_dev(exabm4d_ctx* ctx, const uint8_t* in, size_t in_bytes,
+                                     const uint64_t* offsets_dev, int nz, int ny, int nx, int cz, int cy, int cx,
+                                     uint16_t* vol);
 
 /* ---- background offset + quality metrics on device (SURVEY.md section 8 "next" row f-4) --------- */
 /* Element types of the metric entry points. */

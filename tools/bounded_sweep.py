@@ -5,7 +5,18 @@ the histogram of j*, and device milliseconds (HIP events) of the ladder kernel, 
 bounded decode and today's int32 decode + dctq_inverse at that global step.
 
     python tools/bounded_sweep.py [edge=1024] [deltas=1,2,4,8,16] [sigma=24] > bounded_sweep.json
+
+With ``--granularity block`` the store with a step per 8^3 block is measured next to the per-chunk
+one, both in the same session: bits per voxel, the shares of verbatim blocks and of mode-0 chunks, the histogram of the
+block steps and what an order-0 code of the step plane would save, and device milliseconds of the select kernel, the
+whole encode and the decode, each with its ratio to the per-chunk ladder kernel, encode and decode.  ``--fg-error 0,1``
+adds the rows with that foreground bound for the bounds 4, 8 and 16 (``FG_DELTAS``); the foreground mask of the sweep is
+``denoised > offset + 3 sigma`` (it is the sweep's own choice, stated in the output; callers bring their masks).
+
+    python tools/bounded_sweep.py 1024 1,2,4,8,16 --granularity block --fg-error 0,1 \
+        > profiles/bounded/block_bounded_sweep_1024.json
 """
+import argparse
 import json
 import os
 import sys
@@ -18,12 +29,18 @@ sys.path.insert(0, ROOT)
 
 from aind_exaspim_image_compression import _native  # noqa: E402
 from aind_exaspim_image_compression.utils import dct_quant  # noqa: E402
+from aind_exaspim_image_compression.utils.block_bounded_codec import plane_bytes  # noqa: E402
 from aind_exaspim_image_compression.utils.bounded_codec import LADDER, STEPS, parse_header  # noqa: E402
 import bench  # noqa: E402
 
 
 def timed(ctx, fn, reps=3):
     """Device ms of fn() (median of reps, after one warm-up call that also sizes the scratch)."""
+    return float(np.median(timed_all(ctx, fn, reps)))
+
+
+def timed_all(ctx, fn, reps=3):
+    """The reps device times themselves, for callers that state the spread."""
     fn()
     a, b = ctx.event(), ctx.event()
     out = []
@@ -33,7 +50,7 @@ def timed(ctx, fn, reps=3):
         ctx.record(b)
         ctx.sync()
         out.append(ctx.elapsed_ms(a, b))
-    return float(np.median(out))
+    return [float(t) for t in out]
 
 
 def sweep(edge, deltas, sigma, seed=1000):
@@ -102,11 +119,111 @@ def sweep(edge, deltas, sigma, seed=1000):
             "rows": rows}
 
 
+FG_DELTAS = (4, 8, 16)      # the bounds that get --fg-error rows
+
+
+def _ms(times):
+    return {"median": float(np.median(times)), "min": min(times), "max": max(times)}
+
+
+def sweep_block(edge, deltas, sigma, fg_errors, seed=1000):
+    """The store with a step per block next to the store with a step per chunk, on one denoised volume."""
+    shape, chunk = (edge,) * 3, bench.CHUNK
+    n = edge ** 3
+    ctx = _native.context(0)
+    d_noisy, d_den, d_rec = ctx.to_device(bench.synth_u16(shape, seed)), ctx.alloc(2 * n), ctx.alloc(2 * n)
+    ctx.denoise_u16(d_noisy, d_den, shape, sigma, bench.OFFSET)
+    ctx.sync()
+    d_noisy.free()
+    grid = tuple(-(-s // c) for s, c in zip(shape, chunk))
+    nchunks = int(np.prod(grid))
+    nb, nbp = int(np.prod([c // 8 for c in chunk])), plane_bytes(chunk)
+    den = d_den.download(shape, np.uint16)
+    threshold = bench.OFFSET + 3.0 * sigma
+    mask = (den > threshold).astype(np.uint8)
+    fg_share = float(mask.mean())
+    del den
+    d_mask = ctx.to_device(mask.reshape(-1))
+    del mask
+    lossless, _ = ctx.codec_encode(d_den, 2, shape, chunk)
+    d_err = ctx.alloc(4 * STEPS * nchunks)
+    ladder = timed_all(ctx, lambda: ctx.dctq_ladder_errors(d_den, shape, chunk, d_err))
+    cap = max(_native.bounded_volume_bound(shape, chunk), _native.block_bounded_volume_bound(shape, chunk))
+    d_out, d_off, d_sz = ctx.alloc(cap), ctx.alloc(8 * (nchunks + 1)), ctx.alloc(4 * nchunks)
+    d_plane = ctx.alloc(nbp * nchunks)
+    rows = []
+    for delta in deltas:
+        v1_enc = timed_all(ctx, lambda: ctx.bounded_encode(d_den, shape, chunk, delta, out=d_out, out_capacity=cap,
+                                                           offsets=d_off, sizes=d_sz, totals=False))
+        v1_coded, v1_container = ctx.bounded_encode(d_den, shape, chunk, delta, out=d_out, out_capacity=cap,
+                                                    offsets=d_off, sizes=d_sz)
+        v1_dec = timed_all(ctx, lambda: ctx.bounded_decode(d_out, v1_container, d_off, shape, chunk, d_rec))
+        per_chunk = {"bits_per_voxel": 8.0 * v1_coded / n, "coded_bytes": int(v1_coded),
+                     "device_ms_ladder_kernel": _ms(ladder), "device_ms_encode": _ms(v1_enc),
+                     "device_ms_decode": _ms(v1_dec)}
+        for fg in [None] + [f for f in fg_errors if f <= delta and delta in FG_DELTAS]:
+            m = None if fg is None else d_mask
+            f = delta if fg is None else fg
+            sel = timed_all(ctx, lambda: ctx.block_bounded_steps(d_den, shape, chunk, delta, f, d_plane, mask=m))
+            enc = timed_all(ctx, lambda: ctx.block_bounded_encode(d_den, shape, chunk, delta, f, mask=m, out=d_out,
+                                                                  out_capacity=cap, offsets=d_off, sizes=d_sz,
+                                                                  totals=False))
+            coded, container = ctx.block_bounded_encode(d_den, shape, chunk, delta, f, mask=m, out=d_out,
+                                                        out_capacity=cap, offsets=d_off, sizes=d_sz)
+            dec = timed_all(ctx, lambda: ctx.block_bounded_decode(d_out, container, d_off, shape, chunk, d_rec))
+            err = ctx.masked_error_stats(d_rec, np.uint16, d_den, np.uint16, None, n)
+            data = d_out.download((container,), np.uint8)
+            offs = d_off.download((nchunks + 1,), np.uint64)
+            mode1 = np.array([data[int(o) + 3] for o in offs[:-1]], dtype=bool)
+            planes = np.stack([data[int(o) + 32:int(o) + 32 + nb] for o in offs[:-1][mode1]]) if mode1.any() \
+                else np.zeros((0, nb), np.uint8)
+            hist = np.bincount(planes.reshape(-1), minlength=256)
+            p = hist[hist > 0] / max(1, planes.size)
+            row = {"max_error": delta, "fg_max_error": fg, "bits_per_voxel": 8.0 * coded / n,
+                   "cratio": 2.0 * n / coded, "coded_bytes": int(coded),
+                   "bytes_vs_per_chunk": coded / v1_coded, "bytes_vs_lossless": coded / lossless,
+                   "lmax": float(err[6]), "mae": float(err[1] / n),
+                   "mode0_chunk_share": float(1.0 - mode1.mean()),
+                   "verbatim_block_share_of_mode1_blocks": float(hist[0xFE] / max(1, planes.size)),
+                   "step_histogram": {f"{float(LADDER[j]):g}": int(hist[j]) for j in range(STEPS) if hist[j]},
+                   "step_plane_bits_per_voxel": 8.0 * nbp * int(mode1.sum()) / n,
+                   "step_plane_order0_bits_per_voxel": float(-(p * np.log2(p)).sum()) * planes.size / n,
+                   "device_ms_select_kernel": _ms(sel), "device_ms_encode": _ms(enc), "device_ms_decode": _ms(dec),
+                   "select_vs_ladder_kernel": float(np.median(sel) / np.median(ladder)),
+                   "encode_vs_per_chunk": float(np.median(enc) / np.median(v1_enc)),
+                   "decode_vs_per_chunk": float(np.median(dec) / np.median(v1_dec)),
+                   "per_chunk": per_chunk}
+            rows.append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+    for b in (d_den, d_rec, d_err, d_out, d_off, d_sz, d_plane, d_mask):
+        b.free()
+    return {"volume": list(shape), "seed": seed, "denoise_sigma": sigma, "chunk": list(chunk),
+            "granularity": "block",
+            "mask": f"denoised > offset + 3 sigma = {threshold:g} (the sweep's own choice)",
+            "foreground_share": fg_share,
+            "lossless": {"bits_per_voxel": 8.0 * lossless / n, "cratio": 2.0 * n / lossless,
+                         "coded_bytes": int(lossless)},
+            "timing_note": "HIP events; median, min and max of three repeats after one warm-up call; the per-chunk "
+                           "figures are BoundedDctCodec's entries measured in the same session",
+            "rows": rows}
+
+
 def main():
-    edge = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-    deltas = [int(s) for s in (sys.argv[2] if len(sys.argv) > 2 else "1,2,4,8,16").split(",")]
-    sigma = float(sys.argv[3]) if len(sys.argv) > 3 else bench.SIGMA
-    print(json.dumps(sweep(edge, deltas, sigma), indent=1))
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("edge", nargs="?", type=int, default=1024)
+    ap.add_argument("deltas", nargs="?", default="1,2,4,8,16")
+    ap.add_argument("sigma", nargs="?", type=float, default=bench.SIGMA)
+    ap.add_argument("--granularity", choices=("chunk", "block"), default="chunk")
+    ap.add_argument("--fg-error", default="", help="comma list of foreground bounds (block granularity only)")
+    a = ap.parse_args()
+    deltas = [int(s) for s in a.deltas.split(",")]
+    fg = [int(s) for s in a.fg_error.split(",") if s != ""]
+    if a.granularity == "chunk":
+        if fg:
+            ap.error("--fg-error needs --granularity block")
+        print(json.dumps(sweep(a.edge, deltas, a.sigma), indent=1))
+    else:
+        print(json.dumps(sweep_block(a.edge, deltas, a.sigma, fg), indent=1))
 
 
 if __name__ == "__main__":
