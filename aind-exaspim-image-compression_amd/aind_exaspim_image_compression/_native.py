@@ -213,6 +213,9 @@ SIGNATURES = {
     "exabm4d_block_bounded_steps_dev": (_I, [_CTX, c_vp, c_vp, _I, _I, _I, _I, _I, _I, _I, _I, c_vp]),
     "exabm4d_block_bounded_encode_dev": (_I, [_CTX, c_vp, c_vp, _I, _I, _I, _I, _I, _I, _I, _I, c_vp, _SZ, c_vp, c_vp,
                                               c_vp]),
+    "exabm4d_block_bounded_steps_tab_dev": (_I, [_CTX, c_vp, c_vp, _I, _I, _I, _I, _I, _I, _I, _I, c_vp, c_vp]),
+    "exabm4d_block_bounded_encode_tab_dev": (_I, [_CTX, c_vp, c_vp, _I, _I, _I, _I, _I, _I, _I, _I, c_vp, _SZ, c_vp,
+                                                  c_vp, c_vp, c_vp]),
     "exabm4d_block_bounded_decode_dev": (_I, [_CTX, c_vp, _SZ, c_vp, _I, _I, _I, _I, _I, _I, c_vp]),
     "exabm4d_u16_histogram_dev": (_I, [_CTX, c_vp, _SZ, c_vp]),
     "exabm4d_key_histogram_dev": (_I, [_CTX, c_vp, _I, _SZ, _I, ctypes.c_double, _I,
@@ -768,24 +771,32 @@ class Context:
             int(chunk[2]), _ptr(vol)))
 
     # -- error-bounded codec, a step per 8^3 block and a per-voxel bound ------------
-    def block_bounded_steps(self, vol, shape, chunk, max_error, fg_max_error, plane, mask=None):
+    def block_bounded_steps(self, vol, shape, chunk, max_error, fg_max_error, plane, mask=None, table=None):
         """plane (device, uint8 [nchunks][nb rounded up to 16]) <- the step plane of every chunk (0xFE verbatim, 0xFF
-        outside the volume), whatever mode the chunk would be stored in.  Asynchronous."""
+        outside the volume), whatever mode the chunk would be stored in.  ``table`` (device, 65536 uint16, or None):
+        the bound table of DESIGN.md 3.10d, through the ``_tab`` entry.  Asynchronous."""
         nz, ny, nx = shape
-        self._check(lib().exabm4d_block_bounded_steps_dev(
-            self.handle, _ptr(vol), _ptr(mask), nz, ny, nx, int(chunk[0]), int(chunk[1]), int(chunk[2]),
-            int(max_error), int(fg_max_error), _ptr(plane)))
+        args = (self.handle, _ptr(vol), _ptr(mask), nz, ny, nx, int(chunk[0]), int(chunk[1]), int(chunk[2]),
+                int(max_error), int(fg_max_error), _ptr(plane))
+        if table is None:
+            self._check(lib().exabm4d_block_bounded_steps_dev(*args))
+        else:
+            self._check(lib().exabm4d_block_bounded_steps_tab_dev(*args, _ptr(table)))
 
     def block_bounded_encode(self, vol, shape, chunk, max_error, fg_max_error, mask=None, out=None, out_capacity=0,
-                             offsets=None, sizes=None, totals=True):
+                             offsets=None, sizes=None, totals=True, table=None):
         """``bounded_encode`` with a step per block; ``mask`` (device uint8 of the volume's shape, or None) marks
-        the voxels whose bound is ``fg_max_error``."""
+        the voxels whose bound is ``fg_max_error``, and ``table`` (device, 65536 uint16, or None) caps the bound of
+        a voxel by ``table[its value]``, through the ``_tab`` entry."""
         nz, ny, nx = shape
         tot = np.zeros(2, dtype=np.uint64)
-        self._check(lib().exabm4d_block_bounded_encode_dev(
-            self.handle, _ptr(vol), _ptr(mask), nz, ny, nx, int(chunk[0]), int(chunk[1]), int(chunk[2]),
-            int(max_error), int(fg_max_error), _ptr(out), int(out_capacity), _ptr(offsets), _ptr(sizes),
-            tot.ctypes.data_as(c_vp) if totals else None))
+        args = (self.handle, _ptr(vol), _ptr(mask), nz, ny, nx, int(chunk[0]), int(chunk[1]), int(chunk[2]),
+                int(max_error), int(fg_max_error), _ptr(out), int(out_capacity), _ptr(offsets), _ptr(sizes),
+                tot.ctypes.data_as(c_vp) if totals else None)
+        if table is None:
+            self._check(lib().exabm4d_block_bounded_encode_dev(*args))
+        else:
+            self._check(lib().exabm4d_block_bounded_encode_tab_dev(*args, _ptr(table)))
         return (int(tot[0]), int(tot[1])) if totals else None
 
     def block_bounded_decode(self, data, nbytes, offsets, shape, chunk, vol):

@@ -8,10 +8,17 @@ count) and the background within eight is one stored array.  A block that no ste
 chunk whose block stream is not shorter than its lossless EXAC stream is stored as the latter, so the guarantee
 ``|decoded - input| <= bound`` holds for any mask and any ``fg_max_error <= max_error``.
 
+With a ``bound_table`` the bound of a voxel is further capped by the table's entry at the voxel's own
+value: ``b(v) = min(T[V(v)], where(mask, fg_max_error, max_error))``.  ``BlockBoundedCodec.from_noise(noise, k)`` makes
+the table from measured Poisson-Gaussian parameters (``utils/noise.py``), so that no voxel is off by more than ``k``
+noise standard deviations of its own intensity.  Only the encoder sees the table; streams and decoder are unchanged.
+
 The format ("EB" version 1) is a sibling of the bounded codec's "EQ" version 1, with its own magic, codec id and
 C-ABI entries; step choice, quantiser, both entropy coders, assembly and decode run on the MI355X
 (``csrc/block_bounded_kernels.hip``, ``exabm4d_block_bounded_*``).
 """
+import hashlib
+
 import numpy as np
 
 from aind_exaspim_image_compression import _native
@@ -108,18 +115,42 @@ class BlockBoundedCodec:
     codec_id = "exac-dctq-block"
     version = FORMAT_VERSION
 
-    def __init__(self, max_error, fg_max_error=None, device=None):
+    def __init__(self, max_error=65535, fg_max_error=None, bound_table=None, device=None):
         max_error = int(max_error)
         fg_max_error = max_error if fg_max_error is None else int(fg_max_error)
         if not 0 <= fg_max_error <= max_error <= 65535:
             raise ValueError("0 <= fg_max_error <= max_error <= 65535 is required")
+        if bound_table is not None:
+            if not isinstance(bound_table, np.ndarray) or bound_table.dtype != np.uint16 or \
+                    bound_table.shape != (65536,):
+                raise ValueError("bound_table must be a uint16 array of shape (65536,)")
+            bound_table = np.ascontiguousarray(bound_table).copy()
+            bound_table.setflags(write=False)
         self.max_error = max_error
         self.fg_max_error = fg_max_error
+        self.bound_table = bound_table
+        self.bound = None if bound_table is None else \
+            {"kind": "table", "sha256": hashlib.sha256(bound_table.astype("<u2").tobytes()).hexdigest()}
         self.device = device
 
+    @classmethod
+    def from_noise(cls, noise, k, max_error=65535, fg_max_error=None, device=None):
+        """The codec whose bound of a voxel is ``k`` noise standard deviations of the voxel's own value under the
+        Poisson-Gaussian parameters ``noise`` (what ``estimate_poisson_gaussian`` returns), rounded down, and never
+        more than ``max_error`` / ``fg_max_error``: ``bound_table=noise.bound_table(noise, k)``."""
+        from aind_exaspim_image_compression.utils.noise import bound_table, pg_params
+        codec = cls(max_error, fg_max_error, bound_table=bound_table(noise, k), device=device)
+        codec.bound = dict({"kind": "poisson-gaussian"}, **pg_params(noise), k=float(k))
+        return codec
+
     def get_config(self):
-        return {"id": self.codec_id, "max_error": self.max_error, "fg_max_error": self.fg_max_error,
-                "version": self.version}
+        """``"bound"`` describes the table, if there is one: the model and ``k`` it came from, or its SHA-256 (of the
+        little-endian bytes).  It documents the store; no decoder needs it."""
+        cfg = {"id": self.codec_id, "max_error": self.max_error, "fg_max_error": self.fg_max_error,
+               "version": self.version}
+        if self.bound is not None:
+            cfg["bound"] = dict(self.bound)
+        return cfg
 
     @staticmethod
     def _mask(mask, shape):
@@ -170,15 +201,21 @@ class BlockBoundedCodec:
         ctx = _native.context(self.device)
         d_vol = ctx.to_device(a.reshape(-1))
         d_mask = ctx.to_device(m) if m is not None else None
+        d_table = ctx.to_device(self.bound_table) if self.bound_table is not None else None
         try:
-            return self.encode_device(ctx, d_vol, shape, chunk, d_mask, want_bytes)
+            return self.encode_device(ctx, d_vol, shape, chunk, d_mask, want_bytes, d_table)
         finally:
             d_vol.free()
             if d_mask is not None:
                 d_mask.free()
+            if d_table is not None:
+                d_table.free()
 
-    def encode_device(self, ctx, d_vol, shape, chunk=(64, 64, 64), d_mask=None, want_bytes=True):
-        """The same for a volume (and a uint8 mask, or None) that already lies in HBM (device pointer holders)."""
+    def encode_device(self, ctx, d_vol, shape, chunk=(64, 64, 64), d_mask=None, want_bytes=True, d_table=None):
+        """The same for a volume (and a uint8 mask, or None) that already lies in HBM (device pointer holders).
+        ``d_table``: this codec's ``bound_table`` on the device (65536 uint16); a codec that has one needs it."""
+        if (d_table is None) != (self.bound_table is None):
+            raise ValueError("encode_device: d_table goes with a codec that has a bound_table, and only with one")
         shape, chunk = _shape3(shape), tuple(int(c) for c in _shape3(chunk))
         cap = _native.block_bounded_volume_bound(shape, chunk)
         nchunks = int(np.prod([-(-s // c) for s, c in zip(shape, chunk)]))
@@ -188,7 +225,7 @@ class BlockBoundedCodec:
         try:
             _, container = ctx.block_bounded_encode(d_vol, shape, chunk, self.max_error, self.fg_max_error,
                                                     mask=d_mask, out=d_out, out_capacity=cap if want_bytes else 0,
-                                                    offsets=d_off, sizes=d_sizes)
+                                                    offsets=d_off, sizes=d_sizes, table=d_table)
             sizes = d_sizes.download((nchunks,), np.uint32)
             offsets = d_off.download((nchunks + 1,), np.uint64)
             data = d_out.download((container,), np.uint8) if want_bytes else None
@@ -246,14 +283,18 @@ class BlockBoundedCodec:
         d_vol = ctx.to_device(a.reshape(-1))
         d_mask = ctx.to_device(m) if m is not None else None
         d_plane = ctx.alloc(nbp * int(np.prod(grid)))
+        d_table = ctx.to_device(self.bound_table) if self.bound_table is not None else None
         try:
-            ctx.block_bounded_steps(d_vol, shape, chunk, self.max_error, self.fg_max_error, d_plane, mask=d_mask)
+            ctx.block_bounded_steps(d_vol, shape, chunk, self.max_error, self.fg_max_error, d_plane, mask=d_mask,
+                                    table=d_table)
             plane = d_plane.download((int(np.prod(grid)), nbp), np.uint8)[:, :nb]
         finally:
             d_vol.free()
             d_plane.free()
             if d_mask is not None:
                 d_mask.free()
+            if d_table is not None:
+                d_table.free()
         steps = plane.astype(np.int16)
         steps[plane == STEP_VERBATIM] = -1
         steps[plane == STEP_OUTSIDE] = -2

@@ -15,7 +15,8 @@ error-bounded lossy ones, and the codec entry reads ``{"name": "exac-dctq", "con
 "max_error": ..., "edge_chunks": "truncated"}}``; with ``codec=BlockBoundedCodec(max_error, fg_max_error)``
 (``utils/block_bounded_codec.py``) and an optional ``mask`` they carry a step per 8^3 block, and the
 entry reads ``{"name": "exac-dctq-block", "configuration": {"version": 1, "max_error": ..., "fg_max_error": ...,
-"edge_chunks": "truncated"}}``.  The readers pick the decoder from ``zarr.json``.
+"edge_chunks": "truncated"}}``, plus ``"bound": {...}`` (the noise model and k, or the table's SHA-256) when the
+codec has a bound table.  The readers pick the decoder from ``zarr.json`` and ignore ``"bound"``.
 
 so that a chunk is addressable by its key like any Zarr chunk and ``sum(file sizes)`` is the denominator of
 ``compute_cratio`` (utils/img_util.py:401-441).  Differences from a stock Zarr array, stated in the metadata:
@@ -55,6 +56,8 @@ def metadata(shape3, chunk3, typesize=2, version=2, attributes=None, codec=None)
         meta["codecs"] = [{"name": BlockBoundedCodec.codec_id,
                            "configuration": {"version": BlockBoundedCodec.version, "max_error": codec.max_error,
                                              "fg_max_error": codec.fg_max_error, "edge_chunks": "truncated"}}]
+        if codec.bound is not None:             # where the bound table came from; no reader needs it
+            meta["codecs"][0]["configuration"]["bound"] = dict(codec.bound)
         return meta
     if isinstance(codec, BoundedDctCodec):
         meta = metadata(shape3, chunk3, 2, attributes=attributes)

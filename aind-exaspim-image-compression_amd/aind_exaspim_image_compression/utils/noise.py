@@ -250,6 +250,26 @@ def pg_params(noise):
     return out
 
 
+def bound_table(noise, k, cap=65535):
+    """uint16 [65536]: ``T[c] = min(cap, floor(k sqrt(gain max(c - offset, 0) + read_noise^2)))``, k noise standard
+    deviations of a voxel of ``c`` counts under the Poisson-Gaussian model -- the table ``BlockBoundedCodec`` takes as
+    its per-voxel error bound.  ``noise``: what ``pg_params`` accepts.  Host float64 throughout
+    (IEEE products and square root), so the table is the same on every machine.  Host work only."""
+    p = pg_params(noise)
+    try:
+        k = float(k)
+    except (TypeError, ValueError):
+        raise ValueError("bound_table: k must be a number") from None
+    if not (math.isfinite(k) and k >= 0.0):
+        raise ValueError("bound_table: k must be finite and >= 0 (got %r)" % k)
+    cap = int(cap)
+    if not 0 <= cap <= 65535:
+        raise ValueError("bound_table: cap must be in [0, 65535]")
+    c = np.arange(65536, dtype=np.float64)
+    sigma = np.sqrt(p["gain"] * np.maximum(c - p["offset"], 0.0) + p["read_noise"] * p["read_noise"])
+    return np.minimum(np.floor(k * sigma), float(cap)).astype(np.uint16)
+
+
 def _stream(vol, dtype_in, dtype_out, device, run):
     arr = np.ascontiguousarray(vol, dtype=dtype_in)
     ctx = _native.context(device)

@@ -332,7 +332,16 @@ size_t exabm4d_block_bounded_volume_bound(int nz, int ny, int nx, int cz, int cy
 
 int exabm4d_block_bounded_steps_dev(exabm4d_ctx* ctx, const uint16_t* vol, const uint8_t* mask, int nz, int ny,
                                     int nx, int cz, int cy, int cx, int max_error, int fg_max_error, uint8_t* plane) {
+    return exabm4d_block_bounded_steps_tab_dev(ctx, vol, mask, nz, ny, nx, cz, cy, cx, max_error, fg_max_error, plane,
+                                               nullptr);
+}
+
+int exabm4d_block_bounded_steps_tab_dev(exabm4d_ctx* ctx, const uint16_t* vol, const uint8_t* mask, int nz, int ny,
+                                        int nx, int cz, int cy, int cx, int max_error, int fg_max_error,
+                                        uint8_t* plane, const uint16_t* bound_table) {
     if (!ctx || !vol || !plane) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if ((uintptr_t)bound_table & 1)
+        return fail(ctx, EXABM4D_ERR_INVALID, "block-bounded codec: bound_table must be 2-byte aligned");
     if (fg_max_error < 0 || fg_max_error > max_error || max_error > 65535)
         return fail(ctx, EXABM4D_ERR_INVALID, "block-bounded codec: 0 <= fg_max_error <= max_error <= 65535");
     BoundedGeom g;
@@ -350,8 +359,8 @@ int exabm4d_block_bounded_steps_dev(exabm4d_ctx* ctx, const uint16_t* vol, const
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx, hipMemcpyAsync(S.qtab, bq_ladder().q, sizeof(BqLadder), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemsetAsync(plane, 0, nc * bb_plane_bytes(g), s));
-    HIP_TRY(ctx, launch_bb_select(vol, mask, g, dct_table(), S.qtab, (uint32_t)max_error, (uint32_t)fg_max_error,
-                                  plane, S.idx, s));
+    HIP_TRY(ctx, launch_bb_select(vol, mask, bound_table, g, dct_table(), S.qtab, (uint32_t)max_error,
+                                  (uint32_t)fg_max_error, plane, S.idx, s));
     return EXABM4D_OK;
 }
 
@@ -359,7 +368,17 @@ int exabm4d_block_bounded_encode_dev(exabm4d_ctx* ctx, const uint16_t* vol, cons
                                      int nx, int cz, int cy, int cx, int max_error, int fg_max_error, uint8_t* out,
                                      size_t out_capacity, uint64_t* offsets_dev, uint32_t* sizes_dev,
                                      uint64_t* totals_host) {
+    return exabm4d_block_bounded_encode_tab_dev(ctx, vol, mask, nz, ny, nx, cz, cy, cx, max_error, fg_max_error, out,
+                                                out_capacity, offsets_dev, sizes_dev, totals_host, nullptr);
+}
+
+int exabm4d_block_bounded_encode_tab_dev(exabm4d_ctx* ctx, const uint16_t* vol, const uint8_t* mask, int nz, int ny,
+                                         int nx, int cz, int cy, int cx, int max_error, int fg_max_error,
+                                         uint8_t* out, size_t out_capacity, uint64_t* offsets_dev,
+                                         uint32_t* sizes_dev, uint64_t* totals_host, const uint16_t* bound_table) {
     if (!ctx || !vol) return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    if ((uintptr_t)bound_table & 1)
+        return fail(ctx, EXABM4D_ERR_INVALID, "block-bounded codec: bound_table must be 2-byte aligned");
     if (fg_max_error < 0 || fg_max_error > max_error || max_error > 65535)
         return fail(ctx, EXABM4D_ERR_INVALID, "block-bounded codec: 0 <= fg_max_error <= max_error <= 65535");
     BoundedGeom g;
@@ -398,8 +417,8 @@ int exabm4d_block_bounded_encode_dev(exabm4d_ctx* ctx, const uint16_t* vol, cons
     hipStream_t s = ctx->stream;
     HIP_TRY(ctx, hipMemcpyAsync(S.qtab, bq_ladder().q, sizeof(BqLadder), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemsetAsync(S.plane, 0, nc * nbp, s));        // the planes' padding
-    HIP_TRY(ctx, launch_bb_select(vol, mask, g, dct_table(), S.qtab, (uint32_t)max_error, (uint32_t)fg_max_error,
-                                  S.plane, S.idx, s));
+    HIP_TRY(ctx, launch_bb_select(vol, mask, bound_table, g, dct_table(), S.qtab, (uint32_t)max_error,
+                                  (uint32_t)fg_max_error, S.plane, S.idx, s));
     // the two candidates of every chunk through the existing chunk coder: the index chunks, then the voxels
     HIP_TRY(ctx, launch_rans_encode(S.idx, gl, rcp, S.slot, S.lsz, S.loff, S.tot, S.lbuf, s));
     HIP_TRY(ctx, launch_rans_encode(vol, gu, rcp, S.slot, S.usz, S.uoff, S.tot + 2, S.ubuf, s));

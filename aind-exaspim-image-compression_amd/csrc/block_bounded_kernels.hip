@@ -10,6 +10,8 @@
 //             -- the branch is wave-uniform.  A block belongs to one wave: its step goes straight into the chunk's
 //             step plane and its indices at that step (its voxels if no step is admissible, zeros if it lies outside
 //             the volume) into the chunk-major index volume, from the coefficients still in registers.
+//             With a bound table the bound of a voxel is further capped by table[its value]: a
+//             second instantiation gathers the 16 bounds of a lane once per pair and keeps them packed in registers.
 //   assemble: per chunk the smaller of header + step plane + EXAC v2 of the indices and header + EXAC v2 of the
 //             voxels, offsets by scan, everything copied 16 bytes at a time
 //   decode:   one wave per chunk validates offsets, header and step plane and lists the chunk for the EXAC decoder
@@ -40,12 +42,25 @@ __device__ __forceinline__ PairAt pair_at(const BoundedGeom& g, int p, int pairs
     return a;
 }
 
-__global__ __launch_bounds__(BQ_WAVES * 64) void bb_select_kernel(const uint16_t* __restrict__ vol,
-                                                                  const uint8_t* __restrict__ mask, BoundedGeom g,
-                                                                  Dct7 T, const float* __restrict__ qtab, int slices,
-                                                                  float delta, float delta_fg, uint32_t nbp,
-                                                                  uint8_t* __restrict__ plane,
-                                                                  int32_t* __restrict__ idx) {
+// what bounds a voxel: max_error / fg_max_error, and with TABLE a device table of 65536 bounds indexed by its value
+template <bool TABLE>
+struct BbBound {
+    float delta, delta_fg;
+};
+template <>
+struct BbBound<true> {
+    float delta, delta_fg;
+    const uint16_t* table;
+};
+
+// waves_per_eu: left alone the compiler gives the table instantiation 131 VGPRs, three over what four waves per SIMD
+// allow; a minimum of 1 is the default, so the other instantiation is what it was
+template <bool TABLE>
+__global__ __launch_bounds__(BQ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(TABLE ? 4 : 1))) void
+bb_select_kernel(const uint16_t* __restrict__ vol, const uint8_t* __restrict__ mask, BoundedGeom g, Dct7 T,
+                 const float* __restrict__ qtab, int slices, BbBound<TABLE> bound, uint32_t nbp,
+                 uint8_t* __restrict__ plane, int32_t* __restrict__ idx) {
+    const float delta = bound.delta, delta_fg = bound.delta_fg;
     __shared__ __align__(16) float lds[BQ_WAVES * 2 * TBUF];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int hi = lane >> 3, lo = lane & 7;
@@ -86,10 +101,37 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void bb_select_kernel(const uint16_t
         const int z = 8 * bz + hi, xa = 8 * bxa + lo, xb = 8 * bxb + lo;
         const bool oka = z < g.nz && xa < g.nx, okb = inb && z < g.nz && xb < g.nx;
         uint32_t ina_y = 0, inb_y = 0, fga = 0, fgb = 0;
+        // TABLE: voxel y of block a / b in the low half of pa[y] / pb[y], its bound in the high half; these replace
+        // o[] and the four bit sets in the walk, so the variant holds no more registers than the other.  The voxels
+        // are exact in o[], edge replicas included, so every gather is in range; a voxel outside the volume gets
+        // 65535, which no error of two uint16 exceeds, so it casts no vote.
+        uint32_t pa[8], pb[8];
+        if constexpr (TABLE) {
+            const uint16_t* __restrict__ table = bound.table;
+            const uint32_t d = (uint32_t)delta, dfg = (uint32_t)delta_fg;
+            uint32_t ta[8], tb[8];
+#pragma unroll
+            for (int y = 0; y < 8; y++) {
+                ta[y] = table[(uint32_t)o[y].x & 0xFFFFu];     // the mask changes no value: it lets the address be
+                tb[y] = table[(uint32_t)o[y].y & 0xFFFFu];     // the table's base plus a 32-bit offset
+            }
+#pragma unroll
+            for (int y = 0; y < 8; y++) {
+                const int yy = 8 * by + y;
+                uint32_t ba = 65535u, bb = 65535u;
+                if (yy < g.ny) {
+                    const size_t row = ((size_t)z * g.ny + yy) * g.nx;
+                    if (oka) ba = min(ta[y], mask && mask[row + xa] ? dfg : d);
+                    if (okb) bb = min(tb[y], mask && mask[row + xb] ? dfg : d);
+                }
+                pa[y] = (uint32_t)o[y].x | (ba << 16);
+                pb[y] = (uint32_t)o[y].y | (bb << 16);
+            }
+        }
 #pragma unroll
         for (int y = 0; y < 8; y++) {
             const int yy = 8 * by + y;
-            if (yy < g.ny) {
+            if (!TABLE && yy < g.ny) {
                 const size_t row = ((size_t)z * g.ny + yy) * g.nx;
                 if (oka) {
                     ina_y |= 1u << y;
@@ -115,9 +157,14 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void bb_select_kernel(const uint16_t
             bool bada = false, badb = false;
 #pragma unroll
             for (int y = 0; y < 8; y++) {
-                const float ba = (fga >> y) & 1u ? delta_fg : delta, bb = (fgb >> y) & 1u ? delta_fg : delta;
-                bada = bada || (((ina_y >> y) & 1u) && fabsf(bq_to_voxel(r[y].x) - o[y].x) > ba);
-                badb = badb || (((inb_y >> y) & 1u) && fabsf(bq_to_voxel(r[y].y) - o[y].y) > bb);
+                if constexpr (TABLE) {
+                    bada = bada || fabsf(bq_to_voxel(r[y].x) - (float)(pa[y] & 0xFFFFu)) > (float)(pa[y] >> 16);
+                    badb = badb || fabsf(bq_to_voxel(r[y].y) - (float)(pb[y] & 0xFFFFu)) > (float)(pb[y] >> 16);
+                } else {
+                    const float ba = (fga >> y) & 1u ? delta_fg : delta, bb = (fgb >> y) & 1u ? delta_fg : delta;
+                    bada = bada || (((ina_y >> y) & 1u) && fabsf(bq_to_voxel(r[y].x) - o[y].x) > ba);
+                    badb = badb || (((inb_y >> y) & 1u) && fabsf(bq_to_voxel(r[y].y) - o[y].y) > bb);
+                }
             }
             if (needa && __ballot(bada) == 0ull) {
                 ja = j;
@@ -138,7 +185,7 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void bb_select_kernel(const uint16_t
             for (int u = 0; u < 8; u++) oa[u * 64] = bq_quantise(v[u].x, q);
         } else {
 #pragma unroll
-            for (int y = 0; y < 8; y++) ra[y * 8] = (int32_t)o[y].x;
+            for (int y = 0; y < 8; y++) ra[y * 8] = TABLE ? (int32_t)(pa[y] & 0xFFFFu) : (int32_t)o[y].x;
         }
         if (two) {
             if (!inb) {
@@ -150,7 +197,7 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void bb_select_kernel(const uint16_t
                 for (int u = 0; u < 8; u++) ob[u * 64] = bq_quantise(v[u].y, q);
             } else {
 #pragma unroll
-                for (int y = 0; y < 8; y++) rb[y * 8] = (int32_t)o[y].y;
+                for (int y = 0; y < 8; y++) rb[y * 8] = TABLE ? (int32_t)(pb[y] & 0xFFFFu) : (int32_t)o[y].y;
             }
         }
         if (lane == 0) {
@@ -342,15 +389,19 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void bb_inverse_kernel(const int32_t
 
 uint32_t bb_plane_bytes(const BoundedGeom& g) { return ((uint32_t)g.nb + 15u) & ~15u; }
 
-hipError_t launch_bb_select(const uint16_t* vol, const uint8_t* mask, const BoundedGeom& g, const float* dct64,
-                            const float* qtab, uint32_t delta, uint32_t delta_fg, uint8_t* plane, int32_t* idx,
-                            hipStream_t s) {
+hipError_t launch_bb_select(const uint16_t* vol, const uint8_t* mask, const uint16_t* table, const BoundedGeom& g,
+                            const float* dct64, const float* qtab, uint32_t delta, uint32_t delta_fg, uint8_t* plane,
+                            int32_t* idx, hipStream_t s) {
     Dct7 T;
     unsigned grid;
     int slices;
     if (!bq_table(dct64, T) || !bq_grid(g, grid, slices)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bb_select_kernel, dim3(grid), dim3(BQ_WAVES * 64), 0, s, vol, mask, g, T, qtab, slices,
-                       (float)delta, (float)delta_fg, bb_plane_bytes(g), plane, idx);
+    if (table)
+        hipLaunchKernelGGL(bb_select_kernel<true>, dim3(grid), dim3(BQ_WAVES * 64), 0, s, vol, mask, g, T, qtab,
+                           slices, BbBound<true>{(float)delta, (float)delta_fg, table}, bb_plane_bytes(g), plane, idx);
+    else
+        hipLaunchKernelGGL(bb_select_kernel<false>, dim3(grid), dim3(BQ_WAVES * 64), 0, s, vol, mask, g, T, qtab,
+                           slices, BbBound<false>{(float)delta, (float)delta_fg}, bb_plane_bytes(g), plane, idx);
     return hipGetLastError();
 }
 

@@ -308,10 +308,12 @@ hipError_t launch_bq_inverse(const int32_t* idx, const BoundedGeom& g, const flo
 uint32_t bb_plane_bytes(const BoundedGeom& g);
 // plane[c][block] (padding zeroed by the caller) and the chunk-major indices idx[c][nb][512] in one pass: per inside
 // block the largest step whose reconstruction is within delta (delta_fg where mask != 0; mask may be NULL) of every
-// voxel of the block inside the volume, its indices at that step; its voxels if there is no such step; zeros outside
-hipError_t launch_bb_select(const uint16_t* vol, const uint8_t* mask, const BoundedGeom& g, const float* dct64,
-                            const float* qtab, uint32_t delta, uint32_t delta_fg, uint8_t* plane, int32_t* idx,
-                            hipStream_t s);
+// voxel of the block inside the volume, its indices at that step; its voxels if there is no such step; zeros outside.
+// table: NULL, or 65536 uint16 on the device; the bound of a voxel of value V is then further capped by table[V]
+// 
+hipError_t launch_bb_select(const uint16_t* vol, const uint8_t* mask, const uint16_t* table, const BoundedGeom& g,
+                            const float* dct64, const float* qtab, uint32_t delta, uint32_t delta_fg, uint8_t* plane,
+                            int32_t* idx, hipStream_t s);
 // launch_bq_assemble with the plane in front of a mode-1 payload (plane: 16-byte aligned)
 hipError_t launch_bb_assemble(const BoundedGeom& g, const uint8_t* plane, const uint8_t* lossy,
                               const unsigned long long* lossy_off, const uint32_t* lossy_sz, const uint8_t* lossless,

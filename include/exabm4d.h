@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define EXABM4D_VERSION 400 /* additive within 400: + exabm4d_pg_noise, exabm4d_denoise_pg_u16_dev, exabm4d_denoise_pg_chunked_u16_dev / _host, exabm4d_gat_forward_u16_dev, exabm4d_gat_inverse_u16_dev (denoising under Poisson-Gaussian noise); + exabm4d_dctq_ladder_errors_dev, exabm4d_bounded_volume_bound, exabm4d_bounded_encode_dev, exabm4d_bounded_decode_dev (error-bounded lossy chunk codec); + exabm4d_block_bounded_volume_bound, exabm4d_block_bounded_steps_dev, exabm4d_block_bounded_encode_dev, exabm4d_block_bounded_decode_dev (error-bounded codec with a step per 8^3 block and a per-voxel bound); + exabm4d_foreground_masks_dev, exabm4d_binary_dilate_dev, exabm4d_gaussian_filter3d_dev, exabm4d_label_set_dev, exabm4d_segment_stats_dev (patch-cache masks and coherence gate); + exabm4d_groupnorm_lrelu_ndhwc_dt_dev, exabm4d_maxpool2_ndhwc_dt_dev, exabm4d_upsample2_trilinear_ndhwc_dt_dev (fp16 / bf16 BM4DNet kernels); 0.4.0 (round 4): order-independent aggregation -- exabm4d_stage_dev takes data_exp and WRITES num / den, options "stage_pairs" / "stage_quads" / "fuse_den_z" are gone, the stage / block-matching options are per context; 0.3.2: + exabm4d_blockmatch_plan, option "stage_strip"; 0.3.1: + exabm4d_denoise_chunked_u16_host, options "bm_carry" / "bm_xcd_mode"; 0.3.0: EXAC v2 coder, exabm4d_codec_decode_dev takes in_bytes (round 3) */
+#define EXABM4D_VERSION 400 /* additive within 400: + exabm4d_pg_noise, exabm4d_denoise_pg_u16_dev, exabm4d_denoise_pg_chunked_u16_dev / _host, exabm4d_gat_forward_u16_dev, exabm4d_gat_inverse_u16_dev (denoising under Poisson-Gaussian noise); + exabm4d_dctq_ladder_errors_dev, exabm4d_bounded_volume_bound, exabm4d_bounded_encode_dev, exabm4d_bounded_decode_dev (error-bounded lossy chunk codec); + exabm4d_block_bounded_volume_bound, exabm4d_block_bounded_steps_dev, exabm4d_block_bounded_encode_dev, exabm4d_block_bounded_decode_dev (error-bounded codec with a step per 8^3 block and a per-voxel bound); + exabm4d_block_bounded_steps_tab_dev, exabm4d_block_bounded_encode_tab_dev (that codec's bound from a table of the voxel's value); + exabm4d_foreground_masks_dev, exabm4d_binary_dilate_dev, exabm4d_gaussian_filter3d_dev, exabm4d_label_set_dev, exabm4d_segment_stats_dev (patch-cache masks and coherence gate); + exabm4d_groupnorm_lrelu_ndhwc_dt_dev, exabm4d_maxpool2_ndhwc_dt_dev, exabm4d_upsample2_trilinear_ndhwc_dt_dev (fp16 / bf16 BM4DNet kernels); 0.4.0 (round 4): order-independent aggregation -- exabm4d_stage_dev takes data_exp and WRITES num / den, options "stage_pairs" / "stage_quads" / "fuse_den_z" are gone, the stage / block-matching options are per context; 0.3.2: + exabm4d_blockmatch_plan, option "stage_strip"; 0.3.1: + exabm4d_denoise_chunked_u16_host, options "bm_carry" / "bm_xcd_mode"; 0.3.0: EXAC v2 coder, exabm4d_codec_decode_dev takes in_bytes (round 3) */
 
 typedef enum exabm4d_status {
     EXABM4D_OK = 0,
@@ -704,7 +704,16 @@ int exabm4d_bounded_decode_dev(exabm4d_ctx* ctx, const uint8_t* in, size_t in_by
  * those of the chunk), a plane byte that is no step / 0xFE on an inside block or not 0xFF on an outside one, non-zero
  * plane padding, an EXAC payload that does not match mode and shapes, a verbatim value outside 0..65535, or any error
  * the EXAC decoder finds -- gives EXABM4D_ERR_INVALID and never reads outside [in, in + in_bytes).
- * Pointers: as for the bounded codec; mask needs no alignment and is only read. */
+ * Pointers: as for the bounded codec; mask needs no alignment and is only read.
+ *
+ * exabm4d_block_bounded_steps_tab_dev, exabm4d_block_bounded_encode_tab_dev: the two entries above
+ * with a bound table.  bound_table is a device array of 65536 uint16 and caps the bound by the voxel's own value:
+ * b(v) = min(bound_table[vol[v]], fg_max_error where mask[v] != 0 else max_error).  Everything else -- blocks, steps,
+ * modes, the stream, which the decoder reads without the table -- and every other contract of the two entries is
+ * unchanged, and every decoded voxel is within this b(v) of the encoder's input; a table of zeros is exact.
+ * bound_table needs 2-byte alignment (a misaligned one gives EXABM4D_ERR_INVALID before anything is launched);
+ * exactly its 65536 entries are read and nothing is written through it.  NULL: the entries above, which forward
+ * here with NULL. */
 size_t exabm4d_block_bounded_volume_bound(int nz, int ny, int nx, int cz, int cy, int cx);
 int exabm4d_block_bounded_steps_dev(exabm4d_ctx* ctx, const uint16_t* vol, const uint8_t* mask, int nz, int ny,
                                     int nx, int cz, int cy, int cx, int max_error, int fg_max_error, uint8_t* plane);
@@ -712,6 +721,13 @@ int exabm4d_block_bounded_encode_dev(exabm4d_ctx* ctx, const uint16_t* vol, cons
                                      int nx, int cz, int cy, int cx, int max_error, int fg_max_error, uint8_t* out,
                                      size_t out_capacity, uint64_t* offsets_dev, uint32_t* sizes_dev,
                                      uint64_t* totals_host);
+int exabm4d_block_bounded_steps_tab_dev(exabm4d_ctx* ctx, const uint16_t* vol, const uint8_t* mask, int nz, int ny,
+                                        int nx, int cz, int cy, int cx, int max_error, int fg_max_error,
+                                        uint8_t* plane, const uint16_t* bound_table);
+int exabm4d_block_bounded_encode_tab_dev(exabm4d_ctx* ctx, const uint16_t* vol, const uint8_t* mask, int nz, int ny,
+                                         int nx, int cz, int cy, int cx, int max_error, int fg_max_error,
+                                         uint8_t* out, size_t out_capacity, uint64_t* offsets_dev,
+                                         uint32_t* sizes_dev, uint64_t* totals_host, const uint16_t* bound_table);
 int exabm4d_block_bounded_decode_dev(exabm4d_ctx* ctx, const uint8_t* in, size_t in_bytes,
                                      const uint64_t* offsets_dev, int nz, int ny, int nx, int cz, int cy, int cx,
                                      uint16_t* vol);

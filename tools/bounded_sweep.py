@@ -15,6 +15,15 @@ adds the rows with that foreground bound for the bounds 4, 8 and 16 (``FG_DELTAS
 
     python tools/bounded_sweep.py 1024 1,2,4,8,16 --granularity block --fg-error 0,1 \
         > profiles/bounded/block_bounded_sweep_1024.json
+
+With ``--noise-k 0.25,0.5,1,2`` (block granularity) the bound comes from the data: a Poisson-Gaussian
+volume is made, its parameters are re-estimated from it (``estimate_poisson_gaussian``), and for every k the store under
+``bound_table(params, k)`` is measured next to the two constant bounds a user would otherwise choose between, the
+table's value at the pedestal and at the 99.9th-percentile intensity: bits per voxel, mode-0 and verbatim shares, step
+histogram, and device milliseconds of the select kernel with and without the table.
+
+    python tools/bounded_sweep.py 1024 --granularity block --noise-k 0.25,0.5,1,2 \
+        > profiles/bounded/noise_bounded_sweep_1024.json
 """
 import argparse
 import json
@@ -208,6 +217,132 @@ def sweep_block(edge, deltas, sigma, fg_errors, seed=1000):
             "rows": rows}
 
 
+PG_NOISE = {"gain": 4.0, "read_noise": 6.0, "offset": 37.0}     # its timing volume, its first quality row
+PG_BRICK, PG_SLAB = 128, 8
+PG_GENERATOR = ("clean: tests/util.py synth_volume((128, 128, 128), seed=3, pedestal=offset)[1], mirror-tiled to the "
+                "volume; counts: tests/pg_pyref.py pg_volume(clean, gain, read_noise, offset, rng) per slab of 8 "
+                "planes with rng = default_rng([7, slab]) -- the generator of the DESIGN.md 5.10 quality table, its "
+                "clean brick tiled because synth_volume does not reach 1024^3")
+
+
+def pg_bench_volume(shape, noise=PG_NOISE):
+    """The uint16 Poisson-Gaussian volume ``PG_GENERATOR`` describes; slabs on host threads."""
+    from concurrent.futures import ThreadPoolExecutor
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from pg_pyref import pg_volume
+    from util import synth_volume
+    brick = synth_volume((PG_BRICK,) * 3, seed=3, pedestal=noise["offset"])[1]
+
+    def tile_axis(n):
+        i = np.arange(n) % (2 * PG_BRICK)
+        return np.where(i < PG_BRICK, i, 2 * PG_BRICK - 1 - i)
+
+    iz, iy, ix = (tile_axis(n) for n in shape)
+    out = np.empty(shape, dtype=np.uint16)
+
+    def fill(k):
+        z0, z1 = k * PG_SLAB, min((k + 1) * PG_SLAB, shape[0])
+        clean = brick[iz[z0:z1]][:, iy][:, :, ix]
+        out[z0:z1] = pg_volume(clean, noise["gain"], noise["read_noise"], noise["offset"], np.random.default_rng([7, k]))
+
+    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+        list(pool.map(fill, range(-(-shape[0] // PG_SLAB))))
+    return out
+
+
+def sweep_noise(edge, ks, volume_npy=None):
+    """The store under a bound table from measured noise parameters next to the two constant bounds of its ends."""
+    from aind_exaspim_image_compression.machine_learning.transforms import estimate_offset_device
+    from aind_exaspim_image_compression.utils.noise import bound_table, estimate_poisson_gaussian
+    shape, chunk = (edge,) * 3, bench.CHUNK
+    n = edge ** 3
+    if volume_npy and os.path.exists(volume_npy):
+        vol = np.load(volume_npy)
+        if vol.shape != shape or vol.dtype != np.uint16:
+            raise SystemExit(f"{volume_npy} holds another volume")
+    else:
+        vol = pg_bench_volume(shape)
+        if volume_npy:
+            np.save(volume_npy, vol)
+    ctx = _native.context(0)
+    d_vol, d_rec = ctx.to_device(vol.reshape(-1)), ctx.alloc(2 * n)
+    hist = ctx.u16_histogram(d_vol, n)
+    p999 = int(np.searchsorted(np.cumsum(hist), 0.999 * n))
+    offset = estimate_offset_device(ctx, d_vol, n)
+    params = estimate_poisson_gaussian(d_vol, offset=offset, shape=shape, dtype=np.uint16)
+    grid = tuple(-(-s // c) for s, c in zip(shape, chunk))
+    nchunks = int(np.prod(grid))
+    nb, nbp = int(np.prod([c // 8 for c in chunk])), plane_bytes(chunk)
+    lossless, _ = ctx.codec_encode(d_vol, 2, shape, chunk)
+    cap = _native.block_bounded_volume_bound(shape, chunk)
+    d_out, d_off, d_sz = ctx.alloc(cap), ctx.alloc(8 * (nchunks + 1)), ctx.alloc(4 * nchunks)
+    d_plane = ctx.alloc(nbp * nchunks)
+
+    def measure(delta, table, verify=False):
+        """One store: ``delta`` everywhere (table None) or the table under max_error = 65535."""
+        d_tab = None if table is None else ctx.to_device(table)
+        sel = timed_all(ctx, lambda: ctx.block_bounded_steps(d_vol, shape, chunk, delta, delta, d_plane, table=d_tab),
+                        reps=5)
+        coded, container = ctx.block_bounded_encode(d_vol, shape, chunk, delta, delta, out=d_out, out_capacity=cap,
+                                                    offsets=d_off, sizes=d_sz, table=d_tab)
+        ctx.block_bounded_decode(d_out, container, d_off, shape, chunk, d_rec)
+        err = ctx.masked_error_stats(d_rec, np.uint16, d_vol, np.uint16, None, n)
+        data = d_out.download((container,), np.uint8)
+        offs = d_off.download((nchunks + 1,), np.uint64)
+        if d_tab is not None:
+            d_tab.free()
+        mode1 = np.array([data[int(o) + 3] for o in offs[:-1]], dtype=bool)
+        planes = np.stack([data[int(o) + 32:int(o) + 32 + nb] for o in offs[:-1][mode1]]) if mode1.any() \
+            else np.zeros((0, nb), np.uint8)
+        h = np.bincount(planes.reshape(-1), minlength=256)
+        row = {"max_error": int(delta), "bits_per_voxel": 8.0 * coded / n, "cratio": 2.0 * n / coded,
+               "coded_bytes": int(coded), "bytes_vs_lossless": coded / lossless, "lmax": float(err[6]),
+               "mae": float(err[1] / n), "mode0_chunk_share": float(1.0 - mode1.mean()),
+               "verbatim_block_share_of_mode1_blocks": float(h[0xFE] / max(1, planes.size)),
+               "step_histogram": {f"{float(LADDER[j]):g}": int(h[j]) for j in range(STEPS) if h[j]},
+               "device_ms_select_kernel": _ms(sel)}
+        if verify:                              # the guarantee itself, voxel by voxel, on the host
+            rec = d_rec.download(shape, np.uint16)
+            worst = -65535
+            for z0 in range(0, edge, 64):
+                v = vol[z0:z0 + 64]
+                excess = np.abs(rec[z0:z0 + 64].astype(np.int32) - v) - table[v].astype(np.int32)
+                worst = max(worst, int(excess.max()))
+            row["largest_error_minus_bound"] = worst
+        return row
+
+    rows = []
+    # the estimate is what a user has; the generator's own parameters show the bound under the true model
+    for source, noise in (("estimated", params), ("generator", PG_NOISE)):
+        pedestal = int(round(noise["offset"]))
+        for k in ks:
+            table = bound_table(noise, k)
+            d_ped, d_999 = int(table[pedestal]), int(table[p999])
+            row = {"noise": source, "k": k, "pedestal": pedestal, "table_at_pedestal": d_ped, "table_at_p999": d_999,
+                   "table": measure(65535, table, verify=True),
+                   "constant_at_pedestal": measure(d_ped, None),
+                   "constant_at_p999": measure(d_999, None),
+                   # the block decisions of the two rows above, through the table instantiation
+                   "constant_table_at_pedestal": measure(65535, np.full(65536, d_ped, np.uint16)),
+                   "constant_table_at_p999": measure(65535, np.full(65536, d_999, np.uint16))}
+            rows.append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+    for b in (d_vol, d_rec, d_out, d_off, d_sz, d_plane):
+        b.free()
+    return {"volume": list(shape), "chunk": list(chunk), "granularity": "block", "generator": PG_GENERATOR,
+            "generator_noise": PG_NOISE, "estimated_noise": params,
+            "pedestal_note": "the offset of the parameters in use, rounded: the estimate's offset is "
+                             "transforms.estimate_offset, the 1st percentile of the non-zero counts",
+            "p999_intensity": p999,
+            "lossless": {"bits_per_voxel": 8.0 * lossless / n, "cratio": 2.0 * n / lossless,
+                         "coded_bytes": int(lossless)},
+            "timing_note": "HIP events around exabm4d_block_bounded_steps(_tab)_dev (plane memset + select kernel); "
+                           "median, min and max of five repeats after one warm-up call, all in one session; "
+                           "'table' and 'constant_table_at_*' run the table instantiation, 'constant_at_*' the "
+                           "instantiation without a table",
+            "rows": rows}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("edge", nargs="?", type=int, default=1024)
@@ -215,10 +350,19 @@ def main():
     ap.add_argument("sigma", nargs="?", type=float, default=bench.SIGMA)
     ap.add_argument("--granularity", choices=("chunk", "block"), default="chunk")
     ap.add_argument("--fg-error", default="", help="comma list of foreground bounds (block granularity only)")
+    ap.add_argument("--noise-k", default="", help="comma list of k: bound = k noise standard deviations of the voxel "
+                                                  "(block granularity only; deltas and sigma are not used)")
+    ap.add_argument("--volume-npy", default="", help="with --noise-k: load the volume from this file if it exists, "
+                                                     "else make it and save it there")
     a = ap.parse_args()
     deltas = [int(s) for s in a.deltas.split(",")]
     fg = [int(s) for s in a.fg_error.split(",") if s != ""]
-    if a.granularity == "chunk":
+    ks = [float(s) for s in a.noise_k.split(",") if s != ""]
+    if ks:
+        if a.granularity != "block" or fg:
+            ap.error("--noise-k needs --granularity block and takes no --fg-error")
+        print(json.dumps(sweep_noise(a.edge, ks, a.volume_npy or None), indent=1))
+    elif a.granularity == "chunk":
         if fg:
             ap.error("--fg-error needs --granularity block")
         print(json.dumps(sweep(a.edge, deltas, a.sigma), indent=1))
