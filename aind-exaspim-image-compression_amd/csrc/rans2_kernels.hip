@@ -869,6 +869,8 @@ hipError_t launch_rans2_encode(const void* vol, const CodecGeom& g, const uint32
     uint32_t* ghist = reinterpret_cast<uint32_t*>(work + cbytes);
     hipError_t e = hipMemsetAsync(ghist, 0, (size_t)g.nchunks * NCTX * NSYM * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
+    // The three conditions below are restated by form_of() in tests/codec_sweep_cases.py, which sorts the
+    // sweep's cases by model kernel: the two mirror each other, change them together.
     // every chunk of the volume has ex = min(cx, rest of the row): the strips form needs 64 everywhere
     const bool strips = g.ts == 2 && g.cx == 64 && (g.nx % 64) == 0 && g.cy <= STRIP * MODEL_WAVES;
     if (strips) {
