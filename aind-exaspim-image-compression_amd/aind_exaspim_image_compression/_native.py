@@ -32,6 +32,10 @@ SEG_STATS_K = 23            # exabm4d.h EXABM4D_SEG_STATS_K
 GAUSS_MAX_RADIUS = 64       # exabm4d.h EXABM4D_GAUSS_MAX_RADIUS
 NOISE_LEVELS = 49           # exabm4d.h EXABM4D_NOISE_LEVELS
 NOISE_BINS = 4096           # exabm4d.h EXABM4D_NOISE_BINS
+EVAL_K = 16                 # exabm4d.h EXABM4D_EVAL_K: doubles per patch of Context.evaluate_batch
+# exabm4d.h EXABM4D_EVAL_*: the columns of such a row after those of masked_error_stats (0..5)
+EVAL_MED, EVAL_MAD, EVAL_THR, EVAL_RAW_LO, EVAL_RAW_HI, EVAL_PRED_LO, EVAL_PRED_HI = 6, 7, 8, 9, 10, 11, 12
+EVAL_PRED_NAN, EVAL_RAW_NAN, EVAL_TARGET_NAN = 13, 14, 15
 # exabm4d.h label element types
 LABEL_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.uint32): 1, np.dtype(np.uint64): 2,
                 np.dtype(np.int32): 3, np.dtype(np.int64): 4}
@@ -232,6 +236,8 @@ SIGNATURES = {
     "exabm4d_label_set_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp]),
     "exabm4d_segment_stats_dev": (_I, [_CTX, c_vp, _I, c_vp, _I, c_vp, _I, _I, _I, _I, _I, c_vp, c_vp, _I,
                                        c_vp]),
+    "exabm4d_evaluate_batch_dev": (_I, [_CTX, c_vp, _I, c_vp, _I, c_vp, _I, c_vp, _I, _SZ, ctypes.c_double, c_u32p,
+                                        c_vp]),
 }
 
 _lib = None
@@ -915,6 +921,19 @@ class Context:
             self.handle, _ptr(labels), LABEL_DTYPES[np.dtype(label_dtype)], _ptr(raw),
             self.DTYPES[np.dtype(raw_dtype)], _ptr(smooth), int(batch), nz, ny, nx, int(lag),
             ip.ctypes.data_as(c_vp), ik.ctypes.data_as(c_vp), len(ip), out.ctypes.data_as(c_vp)))
+        return out
+
+    # -- validation scoring ------------------------------------------------------
+    def evaluate_batch(self, pred, pred_dtype, raw, raw_dtype, target, target_dtype, mask, batch, n, k, ranks):
+        """(batch, EVAL_K) float64 rows of ``exabm4d_evaluate_batch_dev``: the sums, counts, maxima, median, MAD,
+        threshold and rank values ``evaluate_example`` is made of, for ``batch`` patches of ``n`` voxels on the
+        device.  ``ranks``: the two median ranks, then the two percentile ranks (0-based)."""
+        rk = (ctypes.c_uint32 * 4)(*[int(r) for r in ranks])
+        out = np.empty((int(batch), EVAL_K), dtype=np.float64)
+        self._check(lib().exabm4d_evaluate_batch_dev(
+            self.handle, _ptr(pred), self.DTYPES[np.dtype(pred_dtype)], _ptr(raw),
+            self.DTYPES[np.dtype(raw_dtype)], _ptr(target), self.DTYPES[np.dtype(target_dtype)], _ptr(mask),
+            int(batch), int(n), float(k), rk, out.ctypes.data_as(c_vp)))
         return out
 
     def close(self):

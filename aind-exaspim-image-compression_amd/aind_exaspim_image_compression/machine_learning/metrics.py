@@ -18,6 +18,8 @@ pass each.  The per-patch median / MAD threshold, the binary dil
 smoothing (scipy's ``gaussian_filter`` bit for bit), the distinct-label set and the per-segment
 two-pass statistics are HIP kernels (``csrc/mask_kernels.hip``); the host only rasterises skeleton
 points, sorts the short label lists and applies the reference's finishing rules to the sums.
+``evaluate_examples`` is ``evaluate_example`` of every example of a (B, z, y, x) batch in one device pass
+(``exabm4d_evaluate_batch_dev``): what ``train.validate`` scores a validation set with.
 There is no CPU fallback: without a GPU they raise ``NativeError``.
 """
 import numpy as np
@@ -195,6 +197,142 @@ def evaluate_example(pred, raw, target, fg_mask, pct=0.1):
             "mip_max_error": _mip_error(vs_raw, p, r),
             "false_bright_rate": float(vs_raw[3] / n_bg) if n_bg else 0.0,
         }
+
+
+# ---- a batch of examples in one device pass ---------------------------------------
+class _AskedRanks:
+    """Stands in for a sample of ``n`` values and records the ranks ``order_stats.percentile`` reads,
+    so the ranks the kernel selects are the ones that code interpolates between."""
+
+    def __init__(self, n):
+        self.n, self.asked = n, []
+
+    def at(self, k):
+        self.asked.append(k + self.n if k < 0 else k)
+        return np.float64(0.0)
+
+
+class _RankValues:
+    """The values the kernel selected at those ranks, for ``order_stats.percentile(..., at=...)``."""
+
+    def __init__(self, n, ranks, values):
+        self.n = n
+        self.values = {int(r): np.float64(v) for r, v in zip(ranks, values)}
+        self.any = np.float64(values[0])
+
+    def at(self, k):
+        return self.values.get(k + self.n if k < 0 else k, self.any)    # any value answers the dtype probe
+
+
+class _OrigDtype:
+    def __init__(self, dtype):
+        self.orig_dtype = np.dtype(dtype)
+
+
+def _is_device_tensor(a):
+    return hasattr(a, "data_ptr") and getattr(a, "is_cuda", False)
+
+
+def _torch_np_dtype(t):
+    import torch
+    table = {torch.float32: np.float32, torch.float64: np.float64, torch.float16: np.float16,
+             torch.uint8: np.uint8, torch.bool: np.bool_, torch.int16: np.int16, torch.int32: np.int32}
+    if hasattr(torch, "uint16"):
+        table[torch.uint16] = np.uint16
+    return np.dtype(table.get(t.dtype, np.void))
+
+
+def _example_images(arrays, names):
+    """(B, z, y, x) uint16 / float32 operands, all numpy arrays or all CUDA tensors of one shape."""
+    on_device = [_is_device_tensor(a) for a in arrays]
+    if any(on_device) and not all(on_device):
+        raise ValueError("pred, raw, target and fg_mask must all be host arrays or all be CUDA tensors")
+    if not on_device[0]:
+        arrays = [np.asarray(a) for a in arrays]
+    shape = tuple(int(s) for s in arrays[0].shape)
+    if len(shape) != 4:
+        raise ValueError(f"{names[0]} must be (B, z, y, x), got shape {shape}")
+    for a, name in zip(arrays, names):
+        if tuple(int(s) for s in a.shape) != shape:
+            raise ValueError(f"{name} has shape {tuple(a.shape)}, {names[0]} has {shape}")
+    dtypes = [_torch_np_dtype(a) if on_device[0] else a.dtype for a in arrays]
+    for dt, name in zip(dtypes[:3], names):
+        if dt not in (np.uint16, np.float32):
+            raise ValueError(f"{name} must be uint16 or float32, not {dt}")
+    if dtypes[3].kind not in "buf" or (dtypes[3].kind == "u" and dtypes[3] != np.uint8):
+        raise ValueError(f"fg_mask must be bool, uint8 or float, not {dtypes[3]}")
+    return arrays, dtypes, shape, on_device[0]
+
+
+def evaluate_examples(pred, raw, target, fg_mask, pct=0.1):
+    """``evaluate_example`` of every example of a batch: a list of B dicts with its keys and values.
+
+    ``pred`` / ``raw`` / ``target``: (B, z, y, x) uint16 or float32, each its own type; ``fg_mask``: bool, uint8
+    (non-zero = foreground) or float (``> 0.5``).  All four are numpy arrays (one upload each) or CUDA tensors
+    of one device (read in place on torch's current stream).  One device pass and one synchronisation for the
+    whole batch (``Context.evaluate_batch``): medians, MAD, threshold and the percentile neighbours are
+    selected per patch inside the kernel; the host finishes each row with the arithmetic ``evaluate_example``
+    uses."""
+    arrays, dtypes, shape, on_device = _example_images([pred, raw, target, fg_mask],
+                                                       ["pred", "raw", "target", "fg_mask"])
+    batch, n = shape[0], shape[1] * shape[2] * shape[3]
+    if batch == 0:
+        return []
+    if n == 0:
+        raise ValueError("empty image")
+    q = 100.0 - pct
+    asked = _AskedRanks(n)
+    order_stats.percentile(asked, q, at=asked.at)        # raises for a pct outside [0, 100]
+    pct_ranks = sorted(asked.asked[-2:])
+    ranks = [(n - 1) // 2, n // 2] + pct_ranks
+    p, r, t, m = arrays
+    if on_device:
+        import torch
+        dev = p.device
+        if any(a.device != dev for a in arrays):
+            raise ValueError("pred, raw, target and fg_mask must be on one device")
+        m = (m > 0.5) if dtypes[3].kind == "f" else m
+        ops = [a.contiguous() for a in (p, r, t, m)]
+        ctx = _native.context(dev.index or 0)
+        with torch.cuda.device(dev):
+            ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+            try:
+                rows = ctx.evaluate_batch(ops[0], dtypes[0], ops[1], dtypes[1], ops[2], dtypes[2], ops[3],
+                                          batch, n, 6.0, ranks)
+            finally:
+                ctx.reset_stream()
+    else:
+        m = (m > 0.5) if dtypes[3].kind == "f" else m
+        ctx = _native.context()
+        bufs = []
+        try:
+            for a in (p, r, t, np.ascontiguousarray(m).view(np.uint8)):
+                bufs.append(ctx.to_device(np.ascontiguousarray(a).reshape(-1)))
+            rows = ctx.evaluate_batch(bufs[0], dtypes[0], bufs[1], dtypes[1], bufs[2], dtypes[2], bufs[3], batch,
+                                      n, 6.0, ranks)
+        finally:
+            for b in bufs:
+                b.free()
+    p_dt, r_dt = _OrigDtype(dtypes[0]), _OrigDtype(dtypes[1])
+    out = []
+    for row in rows:
+        fg_mae, bg_mae = _split_mae(row, n)
+        n_bg = n - int(row[2])
+        tops = []
+        for lo in (_native.EVAL_RAW_LO, _native.EVAL_PRED_LO):
+            picked = _RankValues(n, pct_ranks, row[lo:lo + 2])
+            with np.errstate(invalid="ignore"):         # inf - inf between two infinite neighbours: NaN, as in numpy
+                tops.append(float(order_stats.percentile(picked, q, at=picked.at)))
+        raw_top, pred_top = tops
+        out.append({
+            "fg_mae": fg_mae,
+            "bg_mae": bg_mae,
+            "top_pct_error": abs(pred_top - raw_top),
+            "top_pct_preservation": pred_top / (raw_top + 1e-8),
+            "mip_max_error": _mip_error(row, p_dt, r_dt),
+            "false_bright_rate": float(row[3] / n_bg) if n_bg else 0.0,
+        })
+    return out
 
 
 def checkpoint_score(metrics, cratio, weights=None):

@@ -235,5 +235,36 @@ int exabm4d_segment_stats_dev(exabm4d_ctx* ctx, const void* labels, int label_dt
     return fetch(ctx, out_host, L.out, ob);
 }
 
+// ---- validation scoring ---------------------------------------------------------------
+static_assert(VAL_K == EXABM4D_EVAL_K && VAL_MED == EXABM4D_EVAL_MED && VAL_TARGET_NAN == EXABM4D_EVAL_TARGET_NAN,
+              "exabm4d.h and exabm4d_kernels.h differ");
+
+int exabm4d_evaluate_batch_dev(exabm4d_ctx* ctx, const void* pred, int pred_dtype, const void* raw, int raw_dtype,
+                               const void* target, int target_dtype, const uint8_t* mask, int batch, size_t n,
+                               double k, const uint32_t* ranks, double* out_host) {
+    if (!ctx || !pred || !raw || !target || !mask || !ranks || !out_host)
+        return fail(ctx, EXABM4D_ERR_INVALID, "NULL argument");
+    for (int d : {pred_dtype, raw_dtype, target_dtype})
+        if (d != EXABM4D_DT_U16 && d != EXABM4D_DT_F32)
+            return fail(ctx, EXABM4D_ERR_INVALID, "pred, raw and target must be uint16 or float32");
+    if (batch < 1 || n < 1) return fail(ctx, EXABM4D_ERR_INVALID, "bad batch / sizes");
+    if (n >= ((size_t)1 << 32) || batch > EXABM4D_EVAL_MAX_BATCH || n * (size_t)batch > ((size_t)1 << 40))
+        return fail(ctx, EXABM4D_ERR_INVALID, "patch or batch too large");
+    if (ranks[0] > ranks[1] || ranks[1] - ranks[0] > 1 || ranks[2] > ranks[3] || ranks[1] >= n || ranks[3] >= n)
+        return fail(ctx, EXABM4D_ERR_INVALID, "ranks must be two ascending pairs below n, the first one adjacent");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t ob = (size_t)batch * VAL_K * sizeof(double);
+    struct { double *rows, *partials; } L;
+    if (int rc = carve(ctx, ctx->red, 0, L, [&](Carver& c, auto& r) {
+            r.rows = c.take<double>(ob);
+            r.partials = c.take<double>(validate_partials_bytes(batch, n));
+        }))
+        return rc;
+    const ValRanks rk{{ranks[0], ranks[1], ranks[2], ranks[3]}};
+    HIP_TRY(ctx, launch_validate_batch(pred, pred_dtype, raw, raw_dtype, target, target_dtype, mask, batch, n, k, rk,
+                                       L.partials, L.rows, ctx->stream));
+    return fetch(ctx, out_host, L.rows, ob);
+}
+
 
 }  // extern "C"

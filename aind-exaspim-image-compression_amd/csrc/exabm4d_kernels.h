@@ -355,4 +355,19 @@ hipError_t launch_segment_stats(const void* labels, int ldtype, const void* raw,
                                 int nz, int ny, int nx, int lag, const int32_t* item_patch,
                                 const unsigned long long* item_key, int items, double* out, hipStream_t s);
 
+// ---- validation scoring (validate_kernels.hip) -------------------------------------------
+constexpr int VAL_K = 16;           // doubles per patch (exabm4d.h EXABM4D_EVAL_K)
+constexpr int VAL_MAX_SPLITS = 64;  // most statistics workgroups per patch
+// row columns (exabm4d.h): 0..5 are those of launch_masked_stats
+enum { VAL_MED = 6, VAL_MAD = 7, VAL_THR = 8, VAL_RAW_LO = 9, VAL_RAW_HI = 10, VAL_PRED_LO = 11, VAL_PRED_HI = 12,
+       VAL_PRED_NAN = 13, VAL_RAW_NAN = 14, VAL_TARGET_NAN = 15 };
+struct ValRanks {
+    uint32_t r[4];                  // 0-based: the two median ranks, then the two percentile ranks
+};
+size_t validate_partials_bytes(int batch, size_t n);
+// pred / raw / target: dtype 0 uint16, 1 float32, (batch, n) each; mask (batch, n) bytes; rows[batch][VAL_K]
+hipError_t launch_validate_batch(const void* pred, int pred_dtype, const void* raw, int raw_dtype,
+                                 const void* target, int target_dtype, const uint8_t* mask, int batch, size_t n,
+                                 double k, const ValRanks& rk, double* partials, double* rows, hipStream_t s);
+
 }  // namespace exabm4d

@@ -857,6 +857,36 @@ int exabm4d_segment_stats_dev(exabm4d_ctx* ctx, const void* labels, int label_dt
                               const int32_t* item_patch_host, const uint64_t* item_key_host, int n_items,
                               double* out_host);
 
+/* ---- validation scoring: evaluate_example of every patch of a batch ----------------
+ * The count-space metrics behind the reference's Trainer.validate (machine_learning/metrics.py:352-424) for
+ * `batch` patches of n voxels, contiguous in HBM: pred, raw and target are EXABM4D_DT_U16 or EXABM4D_DT_F32
+ * (each its own type), mask holds batch * n bytes (non-zero = foreground).  Every value is widened to fp64.
+ * ranks_host[4], 0-based and the same for every patch: the two median ranks ((n - 1) / 2 and n / 2) and the two
+ * neighbours of the percentile's virtual index; each pair ascending and below n, the median pair equal or
+ * adjacent.
+ * out_host[b * EXABM4D_EVAL_K + .]:
+ *    0  sum |pred - raw| over the foreground        1  sum |pred - target| over the background
+ *    2  foreground voxels                           3  background voxels with pred > thr
+ *    4  max pred                                    5  max raw                (NaN if the image holds one)
+ *    6  med = median(raw)                           7  mad = median(|raw - med|)
+ *    8  thr = med + (k * 1.4826) * (mad + 1e-6), every operation rounded on its own (no fused multiply-add)
+ *    9, 10  raw at the percentile ranks             11, 12  pred at the percentile ranks
+ *   13, 14, 15  1.0 if pred / raw / target holds a NaN, else 0.0
+ * A median of two values is (a + b) / 2 in fp64.  NaN follows numpy: a NaN in raw (or an infinite median, which
+ * makes |raw - med| hold one) gives NaN med / mad / thr and a bright count of 0; the rank values of an image
+ * that holds a NaN are NaN; the sums carry NaN through.  A patch does not affect its neighbours, and the row of a
+ * patch does not depend on the batch it is scored in.  batch <= EXABM4D_EVAL_MAX_BATCH, n < 2^32,
+ * batch * n <= 2^40.  The operands need the natural alignment of their element types only.  One
+ * synchronisation of the context's stream, at the end. */
+#define EXABM4D_EVAL_K 16             /* doubles per patch of exabm4d_evaluate_batch_dev */
+#define EXABM4D_EVAL_MAX_BATCH 65536
+enum { EXABM4D_EVAL_MED = 6, EXABM4D_EVAL_MAD = 7, EXABM4D_EVAL_THR = 8, EXABM4D_EVAL_RAW_LO = 9,
+       EXABM4D_EVAL_RAW_HI = 10, EXABM4D_EVAL_PRED_LO = 11, EXABM4D_EVAL_PRED_HI = 12, EXABM4D_EVAL_PRED_NAN = 13,
+       EXABM4D_EVAL_RAW_NAN = 14, EXABM4D_EVAL_TARGET_NAN = 15 };
+int exabm4d_evaluate_batch_dev(exabm4d_ctx* ctx, const void* pred, int pred_dtype, const void* raw, int raw_dtype,
+                               const void* target, int target_dtype, const uint8_t* mask, int batch, size_t n,
+                               double k, const uint32_t* ranks_host, double* out_host);
+
 #ifdef __cplusplus
 }
 #endif
