@@ -11,8 +11,32 @@
 // reference block's running top-16 list.
 #include "exabm4d_kernels.h"
 #include <type_traits>
+#include <utility>
+
+#ifndef EXABM4D_BM_HANDWAIT
+#define EXABM4D_BM_HANDWAIT 1    // A/B build: 0 = the integer kernel's window rows and cell plane by plain loads (hipcc's waits)
+#endif
 
 namespace exabm4d {
+
+#ifdef EXABM4D_BM_STAMPS
+// Diagnostic build only: per-phase cycle sums (s_memtime) of bm_tile16_kernel, accumulated over all waves.
+// Slots: 0 top wait, 1 wait for the cell's own plane, 2 wait in front of the window reads, 3 accumulate,
+// 4 exchange barriers, 5 selection, 6 carry waits (the poll and the tile's last drain), 7 wave lifetime.
+__device__ unsigned long long g_bm_stamps[8];
+__device__ __forceinline__ unsigned long long bm_stamp() {
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+#define BM_STAMP(var) const unsigned long long var = bm_stamp()
+#define BM_STAMP_ADD(i, a, b) st[i] += (b) - (a)
+#else
+#define BM_STAMP(var)
+#define BM_STAMP_ADD(i, a, b)
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // Tile kernel: 512 lanes = 8x8x8 cells; tiles overlap by one cell in y and x so a tile yields 7x7
@@ -23,6 +47,14 @@ namespace exabm4d {
 struct __attribute__((packed, aligned(4))) float4u {
     float x, y, z, w;
 };
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index can be an asm immediate
+template <class F, int... I>
+__device__ __forceinline__ void static_for(F&& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+__device__ __forceinline__ uint32_t lds_byte_address(const void* p) {
+    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
+}
 
 constexpr int TCZ = 8;       // cell layers per tile = waves per workgroup
 constexpr int NE = 6;        // dy values per pass (two passes: dy = -5..0 and 1..6, 6 is masked)
@@ -391,6 +423,9 @@ __global__ __launch_bounds__(512) void bm_tile_kernel(const float* __restrict__ 
         if (lower_carried && z == 2) carry_prefetch(carry_rd + (size_t)(step >> 2) * 2 * CARRY_ROUND, lower0, lane);
 
         // ---- accumulate: row rp = y + e of the cell's window -----------------------------------
+        // (Plain LDS reads, in front of the first of which hipcc drains the DMA just issued -- see
+        // bm_tile16_kernel.  Its hand-waited rows -- four asm ds_read_b128 and an lgkmcnt(0) per row -- were built
+        // here too: 249 -> 256 registers and 18 / 20 spilled ones, 76 / 84 bytes of scratch; not taken.)
         {
             const float* wrow = cur + (4 * cy) * PSTR + 4 * cx;
             float4 wq[4], wn[4];
@@ -538,6 +573,9 @@ __global__ __launch_bounds__(512) void bm_tile_kernel(const float* __restrict__ 
 // squares to > 2^29 and can never be admitted.  nx must be even (4-byte aligned LDS-DMA rows).
 // ------------------------------------------------------------------------------------------------
 typedef short s16x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef u32x4 u32x4a8 __attribute__((aligned(8)));
 template <int TCY_, int TCX_>
 struct TileShape16 : TilePlan<TCY_, TCX_> {
     using Plan = TilePlan<TCY_, TCX_>;
@@ -573,6 +611,10 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     const int cx = lane % TCX, cy = lane / TCX, cz = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ix = TRX * tx + cx, iy = TRY * ty + cy;
     const size_t sy = (size_t)g.nx, sz = (size_t)g.nx * (size_t)g.ny;
+#ifdef EXABM4D_BM_STAMPS
+    unsigned long long st[8] = {};
+    const unsigned long long tk0 = bm_stamp();
+#endif
 
     // cell layers a tile advances by (CARRY above); this tile's column and its two carry slots
     const int Ls = (carry.on ? TCZ : TCZ - 1) * tz;
@@ -603,13 +645,34 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     const bool lower_carried = carry.on && cz == 0 && tz > 0;          // the lower layer is the tile below's top layer
     const bool carries = carry.on && cz == TCZ - 1 && L + 1 <= g.az;   // ... and this wave's sums are the next tile's
     const bool ref_ok = ref_yx && active && (cz > 0 || lower_carried);
-    if ((lower_carried || carries) && tz > 0) carry_wait_for(done_col, tz, lane, carry);
+    {
+        BM_STAMP(c0);
+        if ((lower_carried || carries) && tz > 0) carry_wait_for(done_col, tz, lane, carry);
+        BM_STAMP(c1);
+        BM_STAMP_ADD(6, c0, c1);
+    }
     const int rz = STEP * iz;
 
     uint32_t list[MAXG];
 #pragma unroll
     for (int k = 0; k < MAXG; k++) list[k] = KEY_EMPTY;
     uint32_t thr = keymax;
+
+    // The cell's own plane z = step & 3: four rows of four biased uint16 (two dwords each).  Hand-waited form:
+    // loaded into `An` a step ahead of its use.  The loads are PLAIN ones: hipcc waits for them at their first
+    // use, which is the top of the next step, where the plane's LDS-DMA is retired anyway.  (Inline-asm loads
+    // would be hidden from its wait counts altogether, but it takes an asm load's destination for written when
+    // the statement ends: built that way, it copied the destination registers to those of `A` ABOVE the
+    // hand-placed wait, "=v" and "+v" operands alike, i.e. before the data had landed.)
+    u32x2 An[4];
+    auto load_cell_plane = [&](int step) {
+#pragma unroll
+        for (int y = 0; y < 4; y++) {
+            const uint32_t* ap = reinterpret_cast<const uint32_t*>(
+                vol + (size_t)(qz + (step & 3)) * sz + (size_t)(qy + y) * sy + qx);
+            An[y] = u32x2{ap[0], ap[1]};
+        }
+    };
 
     auto issue_dma = [&](int step, uint32_t* dst) {
         const int z = step & 3, pass = (step >> 2) & 1, dz = (step >> 3) - RAD;
@@ -639,6 +702,12 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
         break;
     }
     issue_dma(0, pbuf_all[cz][0]);
+    if (EXABM4D_BM_HANDWAIT) {
+        // the first step's cell plane, used (= waited for by hipcc) here: left pending into the loop, it would make
+        // hipcc wait vmcnt(0) at the first use of `An` in every step, behind the DMA of the next plane
+        load_cell_plane(0);
+        asm volatile("" ::"v"(An[0]), "v"(An[1]), "v"(An[2]), "v"(An[3]));
+    }
 
     int acc[NE][SWIN];
 #pragma unroll
@@ -659,34 +728,78 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
         uint32_t* cur = pbuf_all[cz][step & 1];
         uint32_t* nxt = pbuf_all[cz][(step + 1) & 1];
 
+        // The waits of a step (EXABM4D_BM_HANDWAIT).  The window rows are read by inline asm, which hipcc leaves
+        // out of its wait counts; so none of its own waits falls between the issue of plane step + 1 and the end
+        // of the accumulate block.  With plain window reads it waited vmcnt(0) in front of the first one -- an
+        // LDS-DMA is a pending LDS write to it, `cur` or `nxt` alike -- i.e. for the plane it had just requested,
+        // and the cell's own plane, loaded and used in the same step, cost a second exposed round trip.
+        //   vmcnt(0), here: retires the LDS-DMA of THIS step's plane into `cur`, for wave 0 that of the carried
+        //     layer into `lower0`, and the loads of this step's cell plane into `An` -- all issued during
+        //     step - 1, an accumulate block ago (before the loop for step 0).
+        //   lgkmcnt(0), row loop: retires the asm LDS reads of the next window row (`n0`, `n1`), issued in front
+        //     of the current row's arithmetic; the statement names them, so no use of them is placed above it.
+        // `nxt` may be overwritten from here on: this wave's reads of it were step - 1's window rows, each waited
+        // for (lgkmcnt(0)) before its use, and the neighbours' reads of it as an exchange buffer ended behind
+        // step - 1's last barrier.  The z == 3 exchange needs no change: it aliases `cur` and reads the
+        // neighbour's `cur` behind its own barriers, with plain LDS accesses, in front of which hipcc (and
+        // __syncthreads()) still drains the DMA into `nxt` -- by then it has had the accumulate block to land.
+        BM_STAMP(t0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        // own cell plane z: four rows of four biased uint16 (two dwords each)
-        uint2 A[4];
-#pragma unroll
-        for (int y = 0; y < 4; y++) {
-            const uint32_t* ap = reinterpret_cast<const uint32_t*>(
-                vol + (size_t)(qz + z) * sz + (size_t)(qy + y) * sy + qx);
-            A[y] = make_uint2(ap[0], ap[1]);
+        BM_STAMP(t1);
+        if (!EXABM4D_BM_HANDWAIT) {
+            load_cell_plane(step);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const u32x2 A[4] = {An[0], An[1], An[2], An[3]};
+#ifdef EXABM4D_BM_STAMPS
+        if (!EXABM4D_BM_HANDWAIT) asm volatile("" ::"v"(A[0]), "v"(A[1]), "v"(A[2]), "v"(A[3]));
+#endif
+        BM_STAMP(t2);
         if (step + 1 < NSTEP) issue_dma(step + 1, nxt);
         if (lower_carried && z == 2) carry_prefetch(carry_rd + (size_t)(step >> 2) * 2 * CARRY_ROUND, lower0, lane);
+        if (EXABM4D_BM_HANDWAIT) {
+            // the next step's cell plane, behind the DMA: retired with it at the top of the next step
+            if (step + 1 < NSTEP) load_cell_plane(step + 1);
+            asm volatile("" ::: "memory");
+        }
+        BM_STAMP(t3);
 
         {
             const uint32_t* wrow = cur + ((4 * cy) * PSTR + 4 * cx) / 2;       // dword index
-            uint2 wq[4], wn[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) wq[j] = *reinterpret_cast<const uint2*>(wrow + 2 * j);
-#pragma unroll
-            for (int rp = 0; rp < 3 + NEP; rp++) {
-                if (rp + 1 < 3 + NEP) {
-#pragma unroll
-                    for (int j = 0; j < 4; j++)
-                        wn[j] = *reinterpret_cast<const uint2*>(wrow + (rp + 1) * (PSTR / 2) + 2 * j);
+            const uint32_t wrow_lds = lds_byte_address(wrow);
+            // staged columns 0..7 / 8..15 of window row r (32 bytes, 8-byte aligned): two ds_read2_b64
+            auto read_row = [&](auto rc, u32x4& lo, u32x4& hi) {
+                constexpr int r = decltype(rc)::value;
+                constexpr int O = r * (PSTR / 4);                                  // in units of 8 bytes
+                static_assert(O + 3 < 256, "ds_read2_b64 offsets are 8 bits");
+                if (EXABM4D_BM_HANDWAIT) {
+                    asm volatile("ds_read2_b64 %0, %2 offset0:%3 offset1:%4\n\t"
+                                 "ds_read2_b64 %1, %2 offset0:%5 offset1:%6"
+                                 : "=&v"(lo), "=&v"(hi)
+                                 : "v"(wrow_lds), "n"(O), "n"(O + 1), "n"(O + 2), "n"(O + 3));
+                } else {
+                    lo = *reinterpret_cast<const u32x4a8*>(wrow + r * (PSTR / 2));
+                    hi = *reinterpret_cast<const u32x4a8*>(wrow + r * (PSTR / 2) + 4);
                 }
+            };
+            auto await_row = [&](u32x4& lo, u32x4& hi) {
+                if (EXABM4D_BM_HANDWAIT) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo), "+v"(hi));
+            };
+            u32x4 q0, q1;
+            read_row(std::integral_constant<int, 0>{}, q0, q1);
+            await_row(q0, q1);
+#ifdef EXABM4D_BM_STAMPS
+            // (a plain read has landed when something uses it)
+            if (!EXABM4D_BM_HANDWAIT) asm volatile("" : "+v"(q0), "+v"(q1));
+#endif
+            BM_STAMP(t4);
+            static_for([&](auto rc) {
+                constexpr int rp = decltype(rc)::value;
+                u32x4 n0, n1;
+                if constexpr (rp + 1 < 3 + NEP) read_row(std::integral_constant<int, rp + 1>{}, n0, n1);
                 asm volatile("" ::: "memory");
                 // W[i] = staged columns (2 i, 2 i + 1); Wo[i] = columns (2 i + 1, 2 i + 2)
-                const uint32_t W[8] = {wq[0].x, wq[0].y, wq[1].x, wq[1].y, wq[2].x, wq[2].y, wq[3].x, wq[3].y};
+                const uint32_t W[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
                 uint32_t Wo[7];
 #pragma unroll
                 for (int i = 0; i < 7; i++) Wo[i] = __builtin_amdgcn_alignbit(W[i + 1], W[i], 16);
@@ -707,11 +820,19 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
                         }
                     }
                 }
-#pragma unroll
-                for (int j = 0; j < 4; j++) wq[j] = wn[j];
-            }
+                if constexpr (rp + 1 < 3 + NEP) {
+                    await_row(n0, n1);
+                    q0 = n0;
+                    q1 = n1;
+                }
+            }, std::make_integer_sequence<int, 3 + NEP>{});
+            asm volatile("" ::: "memory");
+            BM_STAMP(t5);
+            BM_STAMP_ADD(0, t0, t1);
+            BM_STAMP_ADD(1, t1, t2);
+            BM_STAMP_ADD(2, t3, t4);
+            BM_STAMP_ADD(3, t4, t5);
         }
-        asm volatile("" ::: "memory");
 
         if (z == 3) {
             const bool vz = (rz + dz >= 0) && (rz + dz <= g.nz - BLK);
@@ -734,7 +855,9 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
                 for (int e = e0; e < (e0 + NR0 < NEP ? e0 + NR0 : NEP); e++)
 #pragma unroll
                     for (int d = 0; d < SWIN; d++) mine[64 * ((e - e0) * SWIN + d)] = pair_sum(e, d);
+                BM_STAMP(b0);
                 __syncthreads();
+                BM_STAMP(b1);
                 if (ref_ok) {
                     // a dy row's block sums first (its 22 LDS reads in flight together), then its
                     // candidates one by one: read-add-compare-branch per candidate exposed an LDS round
@@ -766,7 +889,12 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
                         }
                     }
                 }
+                BM_STAMP(b2);
                 __syncthreads();
+                BM_STAMP(b3);
+                BM_STAMP_ADD(4, b0, b1);
+                BM_STAMP_ADD(5, b1, b2);
+                BM_STAMP_ADD(4, b2, b3);
                 if (carries) {
                     // the top wave's sums are the next block's lowest layer (read there by wave 0 in
                     // this same round, i.e. before this slot is written again)
@@ -798,11 +926,28 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
 
     if (carry.on) {
         // the tile is finished when wave 7's stores have been acknowledged and wave 0's last prefetch has landed
+        BM_STAMP(c0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+        BM_STAMP(c1);
+        BM_STAMP_ADD(6, c0, c1);
         if (threadIdx.x == 0) __hip_atomic_store(done_col, tz + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+#ifdef EXABM4D_BM_STAMPS
+    st[7] = bm_stamp() - tk0;
+    if (lane == 0)
+        for (int i = 0; i < 8; i++) atomicAdd(&g_bm_stamps[i], st[i]);
+#endif
 }
+
+#ifdef EXABM4D_BM_STAMPS
+extern "C" void exabm4d_debug_bm_stamps(unsigned long long* out, int reset) {
+    unsigned long long z[8] = {};
+    (void)hipDeviceSynchronize();
+    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bm_stamps), sizeof(z));
+    if (reset) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bm_stamps), z, sizeof(z));
+}
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // Generic kernel: one wave per reference block, lanes share the 1331 candidates.  Used for the
