@@ -238,7 +238,13 @@ SIGNATURES = {
                                        c_vp]),
     "exabm4d_evaluate_batch_dev": (_I, [_CTX, c_vp, _I, c_vp, _I, c_vp, _I, c_vp, _I, _SZ, ctypes.c_double, c_u32p,
                                         c_vp]),
+    "exabm4d_gather_boxes_dev": (_I, [_CTX, c_vp, _SZ, c_vp, _I, c_vp, _I, c_vp, _I, _I, _I, _I, _I, _F,
+                                      ctypes.c_double, c_vp]),
 }
+
+# ``exabm4d_box_src`` (include/exabm4d.h): a decoded chunk in the pool ``Context.gather_boxes`` reads
+BOX_SRC = np.dtype([("base", "<u8"), ("stride_y", "<u8"), ("stride_z", "<u8"), ("z0", "<i4"), ("y0", "<i4"),
+                    ("x0", "<i4"), ("ez", "<i4"), ("ey", "<i4"), ("ex", "<i4")])
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -935,6 +941,27 @@ class Context:
             self.DTYPES[np.dtype(raw_dtype)], _ptr(target), self.DTYPES[np.dtype(target_dtype)], _ptr(mask),
             int(batch), int(n), float(k), rk, out.ctypes.data_as(c_vp)))
         return out
+
+    # -- region reads of a chunk store --------------------------------------------
+    def gather_boxes(self, pool, pool_elems, srcs, box_srcs, starts, box, out, dtype=np.uint16, offset=0.0, fill=0):
+        """out[n][z][y][x] <- the voxel at starts[n] + (z, y, x) from the first source of ``box_srcs[n]`` that holds
+        it, else ``fill``.  ``pool``: device uint16; ``srcs``: host array of ``BOX_SRC``; ``box_srcs``: host int32
+        (nbox, per_box), -1 = unused; ``starts``: host int32 (nbox, 3); ``out``: device, nbox * prod(box) elements of
+        ``dtype`` (uint16, or float32 = value - offset).  Checked on the host (ValueError, nothing written);
+        asynchronous on the context's stream."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.uint16), np.dtype(np.float32)):
+            raise ValueError("gather_boxes: out is uint16 or float32")
+        srcs = np.ascontiguousarray(srcs, dtype=BOX_SRC).reshape(-1)
+        starts = np.ascontiguousarray(starts, dtype=np.int32).reshape(-1, 3)
+        box_srcs = np.ascontiguousarray(box_srcs, dtype=np.int32)
+        if box_srcs.ndim != 2 or box_srcs.shape[0] != len(starts):
+            raise ValueError("gather_boxes: box_srcs must be (nbox, per_box)")
+        bz, by, bx = (int(b) for b in box)
+        self._check(lib().exabm4d_gather_boxes_dev(
+            self.handle, _ptr(pool), int(pool_elems), srcs.ctypes.data_as(c_vp), len(srcs),
+            box_srcs.ctypes.data_as(c_vp), box_srcs.shape[1], starts.ctypes.data_as(c_vp), len(starts), bz, by, bx,
+            self.DTYPES[dt], float(offset), float(fill), _ptr(out)))
 
     def close(self):
         if self.handle and os.getpid() == self.pid:

@@ -236,8 +236,9 @@ class BlockBoundedCodec:
                 d_out.free()
         return EncodedVolume(data, offsets, sizes, shape, chunk, 2)
 
-    def decode_volume(self, enc):
-        """``EncodedVolume`` of this format -> host uint16 array of ``enc.shape``."""
+    @staticmethod
+    def _checked(enc):
+        """(data, offsets, shape, chunk) of a container that passed the host checks."""
         if enc.typesize != 2:
             raise ValueError("the block-bounded codec stores uint16 volumes")
         shape, chunk = _shape3(enc.shape), _shape3(enc.chunk)
@@ -249,17 +250,30 @@ class BlockBoundedCodec:
             raise ValueError("malformed block-bounded container: offsets are not ascending 16-byte steps inside "
                              "the data")
         _native.block_bounded_volume_bound(shape, chunk)          # raises for sizes the format does not take
+        return data, offsets, shape, chunk
+
+    def decode_volume(self, enc):
+        """``EncodedVolume`` of this format -> host uint16 array of ``enc.shape``."""
+        shape = self._checked(enc)[2]
         ctx = _native.context(self.device)
-        d_in = ctx.to_device(data if data.size else np.zeros(16, np.uint8))
-        d_off = ctx.to_device(offsets)
         d_vol = ctx.alloc(2 * int(np.prod(shape)))
         try:
-            ctx.block_bounded_decode(d_in, data.size, d_off, shape, chunk, d_vol)
+            self.decode_device(ctx, enc, d_vol)
             return d_vol.download(shape, np.uint16)
+        finally:
+            d_vol.free()
+
+    def decode_device(self, ctx, enc, d_out):
+        """``decode_volume`` without the download: ``EncodedVolume`` -> ``d_out`` (device pointer holder or address,
+        ``prod(enc.shape)`` uint16), decoded when the call returns."""
+        data, offsets, shape, chunk = self._checked(enc)
+        d_in = ctx.to_device(data if data.size else np.zeros(16, np.uint8))
+        d_off = ctx.to_device(offsets)
+        try:
+            ctx.block_bounded_decode(d_in, data.size, d_off, shape, chunk, d_out)
         finally:
             d_in.free()
             d_off.free()
-            d_vol.free()
 
     def chunk_sizes(self, vol, chunk=(64, 64, 64), mask=None):
         """``len(self.encode(c))`` of every chunk of ``vol`` in one batched device call (what ``compute_cratio``

@@ -169,31 +169,44 @@ class ExacCodec:
                 d_out.free()
         return EncodedVolume(data, offsets, sizes, shape, chunk, self.typesize)
 
-    def decode_volume(self, enc):
-        """``EncodedVolume`` -> host array of ``enc.shape``."""
+    def _checked(self, enc):
+        """(data, offsets, element count) of a container that passed the host checks: a corrupt one must raise,
+        not fault."""
         if enc.typesize != self.typesize:
             raise ValueError("EncodedVolume of another typesize")
         offsets = np.ascontiguousarray(enc.offsets, dtype=np.uint64)
         data = np.ascontiguousarray(enc.data, dtype=np.uint8)
         nchunks = int(np.prod([-(-s // c) for s, c in zip(enc.shape, enc.chunk)]))
-        # validate the container on the host as well: a corrupt one must raise, not fault
         if offsets.size != nchunks + 1 or np.any(np.diff(offsets.astype(np.int64)) < 0) or \
                 int(offsets[-1]) > data.size or np.any(offsets % 2):
             raise ValueError("malformed EXAC container: offsets are not ascending inside the data")
         n = int(np.prod(enc.shape))
         if n < 1 or n > (1 << 40):
             raise ValueError("malformed EXAC container: implausible volume shape")
+        return data, offsets, n
+
+    def decode_volume(self, enc):
+        """``EncodedVolume`` -> host array of ``enc.shape``."""
+        n = self._checked(enc)[2]
         ctx = _native.context(self.device)
-        d_in = ctx.to_device(data)
-        d_off = ctx.to_device(offsets)
         d_vol = ctx.alloc(n * self.typesize)
         try:
-            ctx.codec_decode(d_in, data.size, d_off, self.typesize, enc.shape, enc.chunk, d_vol)
+            self.decode_device(ctx, enc, d_vol)
             return d_vol.download(enc.shape, _DTYPES[self.typesize])
+        finally:
+            d_vol.free()
+
+    def decode_device(self, ctx, enc, d_out):
+        """``decode_volume`` without the download: ``EncodedVolume`` -> ``d_out`` (device pointer holder or address,
+        ``prod(enc.shape)`` elements), decoded when the call returns."""
+        data, offsets, _ = self._checked(enc)
+        d_in = ctx.to_device(data)
+        d_off = ctx.to_device(offsets)
+        try:
+            ctx.codec_decode(d_in, data.size, d_off, self.typesize, enc.shape, enc.chunk, d_out)
         finally:
             d_in.free()
             d_off.free()
-            d_vol.free()
 
     def chunk_sizes(self, vol, chunk=(64, 64, 64)):
         """``len(self.encode(c))`` of every chunk of ``vol``, one batched device call."""

@@ -109,12 +109,9 @@ def write_encoded(enc, output_path, version=2, attributes=None, overwrite=True, 
     return total
 
 
-def read_encoded(path):
-    """Chunk store -> ``(EncodedVolume, metadata)``: the chunk files gathered into one container (every stream
-    at a multiple of 16 bytes, as the device decoder takes it).  Host work only; raises ``ValueError`` for
-    a store that is not an EXAC array of this layout and ``FileNotFoundError`` for a missing chunk."""
-    with open(os.path.join(path, "zarr.json")) as f:
-        meta = json.load(f)
+def check_metadata(meta):
+    """``(shape3, chunk3, typesize, bounded)`` of a ``zarr.json`` document this repository's readers take;
+    ``ValueError`` for anything else.  ``bounded``: the chunk streams keep the nominal chunk shape."""
     try:
         if meta["zarr_format"] != 3 or meta["node_type"] != "array":
             raise ValueError("not a Zarr v3 array")
@@ -149,6 +146,28 @@ def read_encoded(path):
     shape3, chunk3 = tuple(int(s) for s in shape5[2:]), tuple(int(c) for c in chunk5[2:])
     if min(shape3) < 1 or min(chunk3) < 1:
         raise ValueError("empty array or chunk")
+    return shape3, chunk3, typesize, bounded
+
+
+def pack_streams(blobs):
+    """Chunk streams -> ``(data, offsets, sizes)`` of a container: every stream at a multiple of 16 bytes, as the
+    device decoders take it."""
+    sizes = np.array([len(b) for b in blobs], dtype=np.uint32)
+    offsets = np.zeros(len(blobs) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum((sizes.astype(np.uint64) + 15) // 16 * 16)
+    data = np.zeros(int(offsets[-1]), dtype=np.uint8)
+    for b, o in zip(blobs, offsets[:-1]):
+        data[int(o):int(o) + len(b)] = np.frombuffer(b, dtype=np.uint8)
+    return data, offsets, sizes
+
+
+def read_encoded(path):
+    """Chunk store -> ``(EncodedVolume, metadata)``: the chunk files gathered into one container (every stream
+    at a multiple of 16 bytes, as the device decoder takes it).  Host work only; raises ``ValueError`` for
+    a store that is not an EXAC array of this layout and ``FileNotFoundError`` for a missing chunk."""
+    with open(os.path.join(path, "zarr.json")) as f:
+        meta = json.load(f)
+    shape3, chunk3, typesize, bounded = check_metadata(meta)
     gz, gy, gx = _grid(shape3, chunk3)
     blobs = []
     for iz in range(gz):
@@ -156,12 +175,7 @@ def read_encoded(path):
             for ix in range(gx):
                 with open(os.path.join(path, chunk_key(iz, iy, ix)), "rb") as f:
                     blobs.append(f.read())
-    sizes = np.array([len(b) for b in blobs], dtype=np.uint32)
-    offsets = np.zeros(len(blobs) + 1, dtype=np.uint64)
-    offsets[1:] = np.cumsum((sizes.astype(np.uint64) + 15) // 16 * 16)
-    data = np.zeros(int(offsets[-1]), dtype=np.uint8)
-    for b, o in zip(blobs, offsets[:-1]):
-        data[int(o):int(o) + len(b)] = np.frombuffer(b, dtype=np.uint8)
+    data, offsets, sizes = pack_streams(blobs)
     # the bounded formats keep the nominal chunk shape (their index chunks are sized by it)
     chunk_eff = chunk3 if bounded else tuple(min(c, s) for c, s in zip(chunk3, shape3))
     return EncodedVolume(data, offsets, sizes, shape3, chunk_eff, typesize), meta
@@ -216,6 +230,14 @@ def read_chunk(path, iz, iy, ix, codec=None):
         blob = f.read()
     codec = codec or _codec_of(meta)
     return codec.decode(blob).reshape(ext)
+
+
+def open_zarr(path, device=None, max_pool_bytes=1 << 30):
+    """Chunk store -> ``StoredArray`` (``utils/store_read.py``): the (1, 1, z, y, x) array behind
+    numpy basic indexing and ``read_patches``, which decode only the chunks a read touches.  Reads ``zarr.json``
+    only.  ``max_pool_bytes``: the most decoded chunks a read keeps on the device at a time."""
+    from aind_exaspim_image_compression.utils.store_read import StoredArray
+    return StoredArray(path, device=device, max_pool_bytes=max_pool_bytes)
 
 
 def _codec_of(meta):

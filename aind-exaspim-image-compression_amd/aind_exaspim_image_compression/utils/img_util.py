@@ -171,3 +171,49 @@ def compute_lmax(img1, img2):
     """Maximum absolute error (reference ``utils/img_util.py`` compute_lmax)."""
     out, _ = _abs_error_stats(img1, img2)
     return float(out[6])
+
+
+# -- patch coordinates (reference ``utils/img_util.py`` get_patch / get_start_end / get_slices / is_inbounds) ------
+def _half_extent(shape):
+    """The three half edge lengths, rounded down: what the reference's patch arithmetic is made of."""
+    half = np.asarray(shape)[:3] // 2
+    return [int(h) for h in half]
+
+
+def get_start_end(voxel, shape, is_center=True):
+    """(start, end) of the patch ``get_patch`` reads: per axis ``voxel - half`` .. ``voxel + half`` with ``half`` the
+    edge length halved and rounded down.  With ``is_center=False`` the start is ``voxel`` as it was passed, and --
+    the reference's quirk, kept -- the end is still ``voxel + half``."""
+    half = _half_extent(shape)
+    corner = voxel if not is_center else [voxel[a] - half[a] for a in (0, 1, 2)]
+    return corner, [voxel[a] + half[a] for a in (0, 1, 2)]
+
+
+def get_patch(img, voxel, shape, is_center=True):
+    """The patch of a 5-D (t, c, z, y, x) image at ``voxel``: ``img[0, 0, z0:z1, y0:y1, x0:x1]`` of
+    ``get_start_end``, so ``img`` may be an array or a ``chunk_store.open_zarr`` array.  Where the reference gives up
+    -- no start coordinate is non-negative, or no end coordinate lies below the image's extent -- it returns
+    ``np.ones(shape)``, and so does this."""
+    if len(img.shape) != 5:
+        raise AssertionError("get_patch reads (t, c, z, y, x) images, not %d-D ones" % len(img.shape))
+    lo, hi = get_start_end(voxel, shape, is_center=is_center)
+    extent = img.shape[2:]
+    some_start_inside = max(lo) >= 0
+    some_end_inside = min(h - n for h, n in zip(hi, extent)) < 0
+    if not (some_start_inside and some_end_inside):
+        return np.ones(shape)
+    box = tuple(slice(a, b) for a, b in zip(lo, hi))
+    return img[(0, 0) + box]
+
+
+def get_slices(center, shape):
+    """One slice per axis of the patch of ``shape`` around ``center``: it begins half an edge (rounded down) below
+    the centre and is exactly ``shape`` long."""
+    half = _half_extent(shape)
+    return tuple(slice(c - h, c - h + n) for c, h, n in zip(center, half, shape))
+
+
+def is_inbounds(voxel, shape):
+    """Whether ``voxel`` lies inside a grid of ``shape``."""
+    (z, y, x), (nz, ny, nx) = voxel, shape
+    return bool(0 <= z < nz and 0 <= y < ny and 0 <= x < nx)

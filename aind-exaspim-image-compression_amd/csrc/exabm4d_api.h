@@ -91,6 +91,12 @@ struct exabm4d_ctx {
     exabm4d::DevBuf rcp_dev;   // chunk coder: reciprocal table, [4097][2]
     exabm4d::DevBuf codec_aux; // chunk coder: sizes / offsets / totals / status
     exabm4d::DevBuf red;       // metric entry points: histogram / partials / results
+    // exabm4d_gather_boxes_dev: its tables on the device, the pinned host buffer they are copied from, and the event
+    // behind the last copy out of it (the entry does not synchronise, so the next call waits for that event instead)
+    exabm4d::DevBuf region_tab;
+    void* region_host = nullptr;
+    size_t region_host_bytes = 0;
+    hipEvent_t region_ev = nullptr;
     int noise_wgs = 0;         // noise table: workgroups per launch (one per CU); 0 = noise_table_prepare() not yet run
     int force_generic_bm = 0;  // exabm4d_set_option("force_generic_bm")
     int bm_guarded_copy = 0;   // exabm4d_set_option("bm_guarded_copy"): staged block matching on a guarded copy

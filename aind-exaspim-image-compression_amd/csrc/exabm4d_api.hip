@@ -219,8 +219,11 @@ int exabm4d_destroy(exabm4d_ctx* ctx) {
     }
     for (int i = 0; i < 3; i++)
         if (ctx->copy_ev[i]) (void)hipEventDestroy(ctx->copy_ev[i]);
-    for (DevBuf* b : {&ctx->scratch, &ctx->red, &ctx->rcp_dev, &ctx->codec_aux, &ctx->win_dev, &ctx->tf_lut})
+    for (DevBuf* b : {&ctx->scratch, &ctx->red, &ctx->rcp_dev, &ctx->codec_aux, &ctx->win_dev, &ctx->tf_lut,
+                      &ctx->region_tab})
         if (b->p) (void)hipFree(b->p);
+    if (ctx->region_host) (void)hipHostFree(ctx->region_host);
+    if (ctx->region_ev) (void)hipEventDestroy(ctx->region_ev);
     if (ctx->status_host) (void)hipHostFree(ctx->status_host);
     for (int i = 0; i < 2 * EXABM4D_PHASE_COUNT; i++)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);

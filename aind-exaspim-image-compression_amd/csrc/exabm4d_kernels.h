@@ -370,4 +370,18 @@ hipError_t launch_validate_batch(const void* pred, int pred_dtype, const void* r
                                  const void* target, int target_dtype, const uint8_t* mask, int batch, size_t n,
                                  double k, const ValRanks& rk, double* partials, double* rows, hipStream_t s);
 
+// ---- region reads of a chunk store (region_kernels.hip) ----
+// A decoded chunk in the pool: exabm4d_box_src of exabm4d.h, field for field.
+struct BoxSrc {
+    unsigned long long base, stride_y, stride_z;    // elements
+    int32_t z0, y0, x0;                             // origin in the array
+    int32_t ez, ey, ex;                             // extent
+};
+// out[n][z][y][x] (uint16, or fp32 = value - offset) <- the first source of lists[n][0..per_box) (-1: unused) that
+// holds voxel starts[n] + (z, y, x), else the fill.  srcs, lists and starts are device arrays; the caller has checked
+// that every source lies inside the pool.
+hipError_t launch_gather_boxes(const uint16_t* pool, const BoxSrc* srcs, const int32_t* lists, int per_box,
+                               const int32_t* starts, int nbox, int bz, int by, int bx, int out_f32, float offset,
+                               float fill_f32, uint16_t fill_u16, void* out, hipStream_t s);
+
 }  // namespace exabm4d

@@ -887,6 +887,35 @@ int exabm4d_evaluate_batch_dev(exabm4d_ctx* ctx, const void* pred, int pred_dtyp
                                const void* target, int target_dtype, const uint8_t* mask, int batch, size_t n,
                                double k, const uint32_t* ranks_host, double* out_host);
 
+/* ---- region reads of a chunk store: boxes gathered from decoded chunks ---------------
+ * pool (device, uint16, pool_elems elements, 2-byte alignment, only read) holds decoded chunks, each described by
+ * an exabm4d_box_src: where its first voxel lies in the pool, its row and plane strides (a row is contiguous in
+ * x), its origin in the array and its extent.  out[n][z][y][x] (device, C order, nbox * bz * by * bx elements of
+ * out_dtype: EXABM4D_DT_U16 or EXABM4D_DT_F32, natural alignment) is the voxel p = starts_host[n] + (z, y, x):
+ * the first source among box_srcs_host[n][0 .. per_box) (indices into srcs_host, -1 = unused) whose box contains
+ * p supplies pool[base + (pz - z0) stride_z + (py - y0) stride_y + (px - x0)], written as it is (uint16) or as
+ * (float)v - offset, one IEEE subtraction (fp32); where no source contains p, `fill` is written as given (no
+ * offset; for uint16 it must be an integer in 0..65535).  This is not exabm4d_tile_gather_dev, which cuts cubes
+ * out of one dense fp32 volume.
+ * The three tables are host arrays.  Everything is checked on the host before anything is launched -- every
+ * source inside [0, pool_elems), extents >= 1, list entries in [-1, nsrc), bz, by, bx >= 1, nbox, nsrc,
+ * per_box >= 0, bz * by < 2^31, nbox * bz * by * bx <= 2^40, nbox * per_box <= 2^31, pool at an even address and
+ * out at a multiple of its element size, out_dtype one of the two -- and a failure gives EXABM4D_ERR_INVALID with
+ * nothing written.  The
+ * tables are copied into the context's memory, the kernel is launched on the context's stream, and the call does
+ * not synchronise (the host tables may be released on return).  Every element of out is written exactly once
+ * and nothing around it; nbox == 0 succeeds without a launch. */
+typedef struct exabm4d_box_src {
+    uint64_t base;                 /* element index of the source's first voxel in pool */
+    uint64_t stride_y, stride_z;   /* elements; a source row is contiguous in x */
+    int32_t  z0, y0, x0;           /* its origin in the array */
+    int32_t  ez, ey, ex;           /* its extent, >= 1 */
+} exabm4d_box_src;
+int exabm4d_gather_boxes_dev(exabm4d_ctx* ctx, const uint16_t* pool, size_t pool_elems,
+                             const exabm4d_box_src* srcs_host, int nsrc, const int32_t* box_srcs_host, int per_box,
+                             const int32_t* starts_host, int nbox, int bz, int by, int bx, int out_dtype,
+                             float offset, double fill, void* out);
+
 #ifdef __cplusplus
 }
 #endif
