@@ -52,9 +52,6 @@ template <class F, int... I>
 __device__ __forceinline__ void static_for(F&& f, std::integer_sequence<int, I...>) {
     (f(std::integral_constant<int, I>{}), ...);
 }
-__device__ __forceinline__ uint32_t lds_byte_address(const void* p) {
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
-}
 
 constexpr int TCZ = 8;       // cell layers per tile = waves per workgroup
 constexpr int NE = 6;        // dy values per pass (two passes: dy = -5..0 and 1..6, 6 is masked)
@@ -122,8 +119,8 @@ struct Carry {
 constexpr int CARRY_POLL_LIMIT = 1 << 23;       // x s_sleep(32) = 2048 cycles: ~7 s at 2.4 GHz
 // Both rounds of one (dz, pass) into `dst` (2 * CARRY_ROUND elements, linear): 16 full 1 KB transfers
 // and one of 512 bytes.
-template <class T>
-__device__ __forceinline__ void carry_prefetch(const T* src, T* dst, int lane) {
+template <class T, class D>
+__device__ __forceinline__ void carry_prefetch(const T* src, D* dst, int lane) {
     static_assert(2 * CARRY_ROUND == 16 * 256 + 128, "two rounds = 16.5 KB");
 #pragma unroll
     for (int i = 0; i < 16; i++)
@@ -674,7 +671,12 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
         }
     };
 
-    auto issue_dma = [&](int step, uint32_t* dst) {
+    // The staging buffers as LDS-typed pointers: their accesses are ds_ instructions by type.  (As generic pointers
+    // they depend on hipcc tracing each one back to pbuf_all, which it gave up on for `cur` / `nxt` once a pass's
+    // steps became a loop of their own: it then failed to select the casts back to LDS.)
+    using lds_u32 = __attribute__((address_space(3))) uint32_t;
+    auto pbuf = [&](int w, int b) { return (lds_u32*)&pbuf_all[w][b][0]; };
+    auto issue_dma = [&](int step, lds_u32* dst) {
         const int z = step & 3, pass = (step >> 2) & 1, dz = (step >> 3) - RAD;
         const int dylo = pass == 0 ? -RAD : 1;
         const int pz = min(max(Z0 + z + dz, 0), g.nz - 1);
@@ -701,7 +703,7 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
         for (int i = 0; i < (NSTEP / 4) * 4; i++) __syncthreads();
         break;
     }
-    issue_dma(0, pbuf_all[cz][0]);
+    issue_dma(0, pbuf(cz, 0));
     if (EXABM4D_BM_HANDWAIT) {
         // the first step's cell plane, used (= waited for by hipcc) here: left pending into the loop, it would make
         // hipcc wait vmcnt(0) at the first use of `An` in every step, behind the DMA of the next plane
@@ -722,11 +724,9 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     // 158 ms measured).
     auto step_body = [&](auto NEc, const int step) {
         constexpr int NEP = decltype(NEc)::value;                 // dy values of this pass
-        constexpr int NR0 = (NEP + 1) / 2;                        // ... of its first exchange round
-        const int z = step & 3, dz = (step >> 3) - RAD;
-        const int dylo = NEP == NE ? -RAD : 1;
-        uint32_t* cur = pbuf_all[cz][step & 1];
-        uint32_t* nxt = pbuf_all[cz][(step + 1) & 1];
+        const int z = step & 3;
+        lds_u32* cur = pbuf(cz, step & 1);
+        lds_u32* nxt = pbuf(cz, (step + 1) & 1);
 
         // The waits of a step (EXABM4D_BM_HANDWAIT).  The window rows are read by inline asm, which hipcc leaves
         // out of its wait counts; so none of its own waits falls between the issue of plane step + 1 and the end
@@ -756,7 +756,8 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
 #endif
         BM_STAMP(t2);
         if (step + 1 < NSTEP) issue_dma(step + 1, nxt);
-        if (lower_carried && z == 2) carry_prefetch(carry_rd + (size_t)(step >> 2) * 2 * CARRY_ROUND, lower0, lane);
+        if (lower_carried && z == 2)
+            carry_prefetch(carry_rd + (size_t)(step >> 2) * 2 * CARRY_ROUND, (lds_u32*)&lower0[0], lane);
         if (EXABM4D_BM_HANDWAIT) {
             // the next step's cell plane, behind the DMA: retired with it at the top of the next step
             if (step + 1 < NSTEP) load_cell_plane(step + 1);
@@ -765,8 +766,9 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
         BM_STAMP(t3);
 
         {
-            const uint32_t* wrow = cur + ((4 * cy) * PSTR + 4 * cx) / 2;       // dword index
-            const uint32_t wrow_lds = lds_byte_address(wrow);
+            const lds_u32* wrow_l = cur + ((4 * cy) * PSTR + 4 * cx) / 2;      // dword index
+            const uint32_t wrow_lds = (uint32_t)(uintptr_t)wrow_l;
+            [[maybe_unused]] const uint32_t* wrow = (const uint32_t*)wrow_l;
             // staged columns 0..7 / 8..15 of window row r (32 bytes, 8-byte aligned): two ds_read2_b64
             auto read_row = [&](auto rc, u32x4& lo, u32x4& hi) {
                 constexpr int r = decltype(rc)::value;
@@ -833,13 +835,20 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
             BM_STAMP_ADD(2, t3, t4);
             BM_STAMP_ADD(3, t4, t5);
         }
-
-        if (z == 3) {
+    };
+    // The end of a pass, behind the accumulate block of its last step (z == 3): publish the sums, select, carry.
+    auto pass_end = [&](auto NEc, const int step) {
+        constexpr int NEP = decltype(NEc)::value;
+        constexpr int NR0 = (NEP + 1) / 2;                        // dy values of its first exchange round
+        const int dz = (step >> 3) - RAD;
+        const int dylo = NEP == NE ? -RAD : 1;
+        lds_u32* cur = pbuf(cz, step & 1);
+        {
             const bool vz = (rz + dz >= 0) && (rz + dz <= g.nz - BLK);
-            uint32_t* mine = cur + lane;
-            const uint32_t* up_w = cur + lane;                                      // own cells: the upper layer
+            lds_u32* mine = cur + lane;
+            const lds_u32* up_w = cur + lane;                                      // own cells: the upper layer
             // the lower layer: wave cz - 1's sums; for wave 0 the previous block's top layer
-            const uint32_t* lo_w = (cz > 0 ? pbuf_all[max(cz - 1, 0)][step & 1] : lower0) + lane;
+            const lds_u32* lo_w = (cz > 0 ? pbuf(max(cz - 1, 0), step & 1) : (lds_u32*)&lower0[0]) + lane;
             uint32_t* cslot = carry_wr + (size_t)((step >> 2) * 2) * CARRY_ROUND + lane;
             // sum of this cell and its x-neighbour; cell sums are capped at 2^27 so that eight of
             // them cannot wrap (a capped sum is far beyond any admissible distance)
@@ -868,8 +877,8 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
                         uint32_t Sv[1][SWIN];          // one dy row of sums at a time (registers)
 #pragma unroll
                         for (int d = 0; d < SWIN; d++) {
-                            const uint32_t* c0 = lo_w + (cz == 0 && e0 ? CARRY_ROUND : 0) + 64 * ((e - e0) * SWIN + d);
-                            const uint32_t* c1 = up_w + 64 * ((e - e0) * SWIN + d);
+                            const lds_u32* c0 = lo_w + (cz == 0 && e0 ? CARRY_ROUND : 0) + 64 * ((e - e0) * SWIN + d);
+                            const lds_u32* c1 = up_w + 64 * ((e - e0) * SWIN + d);
                             Sv[0][d] = (c0[0] + c0[TCX]) + (c1[0] + c1[TCX]);
                         }
                         asm volatile("" ::: "memory");
@@ -913,12 +922,18 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
                 for (int d = 0; d < SWIN; d++) acc[e][d] = 0;
         }
     };
+    // One loop over dz, in it the four steps of the six-row pass, its end, the four steps of the five-row
+    // pass, its end: each accumulate body is a loop of its own, so the two bodies' register assignments meet
+    // at a pass boundary, twice per dz, and not in front of every step.
+    static_assert(NSTEP == 8 * SWIN, "two passes of four planes per dz");
 #pragma unroll 1
-    for (int step = 0; step < NSTEP; step++) {
-        if (((step >> 2) & 1) == 0)
-            step_body(std::integral_constant<int, NE>{}, step);
-        else
-            step_body(std::integral_constant<int, NE - 1>{}, step);
+    for (int step0 = 0; step0 < NSTEP; step0 += 8) {
+#pragma unroll 1
+        for (int step = step0; step < step0 + 4; step++) step_body(std::integral_constant<int, NE>{}, step);
+        pass_end(std::integral_constant<int, NE>{}, step0 + 3);
+#pragma unroll 1
+        for (int step = step0 + 4; step < step0 + 8; step++) step_body(std::integral_constant<int, NE - 1>{}, step);
+        pass_end(std::integral_constant<int, NE - 1>{}, step0 + 7);
     }
 
     if (ref_ok) list_store(keys + ((size_t)((size_t)iz * g.gy + iy) * g.gx + ix) * MAXG, list);

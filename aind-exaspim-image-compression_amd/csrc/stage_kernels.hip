@@ -30,7 +30,7 @@ typedef float f16v __attribute__((ext_vector_type(16)));
 
 #ifdef EXABM4D_STAMPS
 // Diagnostic build only: per-phase cycle sums (s_memtime) accumulated over all waves.
-__device__ unsigned long long g_stamps[16];
+__device__ unsigned long long g_stamps[18];        // nine slots per kernel: hard threshold, Wiener
 __device__ __forceinline__ unsigned long long stamp() {
     unsigned long long t;
     __builtin_amdgcn_sched_barrier(0);
@@ -40,9 +40,11 @@ __device__ __forceinline__ unsigned long long stamp() {
 }
 #define STAMP(var) const unsigned long long var = stamp()
 #define STAMP_ADD(i, a, b) st[i] += (b) - (a)
+#define STAMP_MOVE(i, j, a, b) (st[i] += (b) - (a), st[j] -= (b) - (a))
 #else
 #define STAMP(var)
 #define STAMP_ADD(i, a, b)
+#define STAMP_MOVE(i, j, a, b) (void)0
 #endif
 
 constexpr float HAAR_C = 0.70710678118654752440f;
@@ -327,6 +329,31 @@ __device__ __forceinline__ void flush_num_plane(ring_t* ring, long long* __restr
     // 231.5 ms against 169.8 / 230.1 -- the waves at the ring gate wait for this flush; eleven, one
     // round, costs the Wiener kernel its registers: 275 ms)
     constexpr int N = C::ROWS * REG, U = 6;
+    // Address of region element (0, 0) of this plane: wave-uniform (z, the tile and the volume are), so it
+    // is computed once per plane in scalar registers.  Tiles at the low edges have negative origins and
+    // the ring holds planes z < 0: the base then lies before the array -- plain 64-bit integer arithmetic,
+    // never dereferenced as such.  The lane's part, (ryy * nx + rxx) * 8 bytes, is never negative and goes
+    // into the atomic as its zero-extended 32-bit vector offset (global_atomic_add_x2 v, v[], s[]):
+    // ((ROWS - 1) * nx + COLS) * 8 < 2^32, which launch_stage checks (nx below 25 million).
+    const long long e0 = ((long long)z * g.ny + tg.y0) * (long long)g.nx + tg.x0;
+    char* const sbase = reinterpret_cast<char*>(num) + e0 * 8;
+    // Element lane + 64 j sits at (ryy, rxx) = divmod(lane + 64 j, REG): no division -- the first one from the
+    // lane id by comparisons, the following ones by stepping 64 = DQ * REG + DR elements with one wrap.
+    constexpr int DQ = 64 / REG, DR = 64 % REG;
+    const unsigned row_adj = 8u * (unsigned)(g.nx - REG);          // a row further, REG columns back
+    const unsigned step = 8u * (unsigned)(DQ * g.nx + DR);
+    // (computed here, per plane: hoisted out of the kernel's loops -- which hipcc does unless the lane id is
+    // opaque -- the two values stay live through the groups and cost the Wiener kernel two more spills)
+    int rxx = lane;
+    asm volatile("" : "+v"(rxx));
+    unsigned boff = 8u * (unsigned)rxx;
+    const int lane0 = rxx;
+#pragma unroll
+    for (int j = 1; j * REG < 64; j++) {
+        const bool w = lane0 >= j * REG;
+        rxx -= w ? REG : 0;
+        boff += w ? row_adj : 0u;
+    }
     for (int rem0 = lane; rem0 < N; rem0 += 64 * U) {
         ring_t v[U];
 #pragma unroll
@@ -335,14 +362,16 @@ __device__ __forceinline__ void flush_num_plane(ring_t* ring, long long* __restr
         for (int u = 0; u < U; u++) {
             const int rem = rem0 + 64 * u;
             if (v[u] != 0) {
-                const int ryy = rem / REG, rxx = rem - ryy * REG;
                 // a non-zero sum implies a block covered this voxel, so it lies inside the volume
                 // (64-bit integer atomic, no return value: global_atomic_add_x2)
-                __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(num) +
-                                           (((size_t)z * g.ny + (tg.y0 + ryy)) * g.nx + (tg.x0 + rxx)),
+                __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(sbase + (size_t)boff),
                                        (unsigned long long)v[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 plane[rem] = 0;
             }
+            rxx += DR;
+            const bool w = rxx >= REG;
+            rxx -= w ? REG : 0;
+            boff += step + (w ? row_adj : 0u);
         }
     }
 }
@@ -759,7 +788,12 @@ __device__ __forceinline__ bool process_half_group(
                             seen = v;
                             break;
                         }
-                        if (!flush_take<C>(lock, ring, num, tg, g, izb, lane)) __builtin_amdgcn_s_sleep(4);
+                        STAMP(tf0);
+                        const bool took = flush_take<C>(lock, ring, num, tg, g, izb, lane);
+                        STAMP(tf1);
+                        // (slot 8: planes flushed from the gate count as flush, not as gate wait)
+                        if (took) STAMP_MOVE(8, 3, tf0, tf1);
+                        if (!took) __builtin_amdgcn_s_sleep(4);
                     }
                 } else {
                     int v = 0;
@@ -1007,6 +1041,7 @@ __global__ __launch_bounds__(HalfCfg<WIENER>::NW * 64) void stage_half_kernel(
 #endif
         );
         if (closer) {
+            STAMP(tc0);
             // this layer's counter slot is next used eight layers on
             if (lane == 0)
                 __hip_atomic_store(cnt + (layer & (HNCNT - 1)), 0, __ATOMIC_RELAXED,
@@ -1043,6 +1078,8 @@ __global__ __launch_bounds__(HalfCfg<WIENER>::NW * 64) void stage_half_kernel(
             if (lane == 0)
                 __hip_atomic_store(lock + 1, layer + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             cbar();
+            STAMP(tc1);
+            STAMP_ADD(8, tc0, tc1);         // close + flush of a layer (with the wait for the layers below)
         }
     }
     __syncthreads();
@@ -1053,7 +1090,7 @@ __global__ __launch_bounds__(HalfCfg<WIENER>::NW * 64) void stage_half_kernel(
 #ifdef EXABM4D_STAMPS
     st[7] = stamp() - tk0;
     if (lane == 0)
-        for (int i = 0; i < 8; i++) atomicAdd(&g_stamps[i + (WIENER ? 8 : 0)], st[i]);
+        for (int i = 0; i < 9; i++) atomicAdd(&g_stamps[i + (WIENER ? 9 : 0)], st[i]);
 #endif
 }
 
@@ -1091,7 +1128,10 @@ hipError_t launch_stage(const float* noisy, const float* basic, const uint32_t* 
     auto launch = [&](auto wiener_c) -> hipError_t {
         constexpr bool W = decltype(wiener_c)::value;
         using C = HalfCfg<W>;
-        const int hty = (g.gy + C::TY - 1) / C::TY, htx = (g.gx + C::TX - 1) / C::TX;
+        // the flush addresses a plane's region by 32-bit byte offsets from a scalar base (flush_num_plane)
+        if (((unsigned long long)(C::ROWS - 1) * (unsigned long long)g.nx + C::COLS) * 8ull > 0xFFFFFFFFull)
+            return hipErrorInvalidValue;
+        const int hty =(g.gy + C::TY - 1) / C::TY, htx = (g.gx + C::TX - 1) / C::TX;
         const long long htiles = (long long)hty * htx * batch;
         // z chunks: at least ~4 work items per CU, and -- while a chunk keeps >= 16 layers, so
         // that its ring start-up and final flush stay small -- about 128 per CU (a 1024^3
@@ -1129,7 +1169,7 @@ hipError_t launch_stage(const float* noisy, const float* basic, const uint32_t* 
 
 #ifdef EXABM4D_STAMPS
 extern "C" void exabm4d_debug_stamps(unsigned long long* out, int reset) {
-    unsigned long long z[16] = {};
+    unsigned long long z[18] = {};
     (void)hipDeviceSynchronize();
     (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), sizeof(z));
     if (reset) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, sizeof(z));

@@ -23,8 +23,8 @@ PHASES = {           # bench phase -> (kernel-name fragment, launches of it per 
     "stage_ht": "stage_half_kernel<false>",
     "stage_wie": "stage_half_kernel<true>",
     # (round 3: the pipelines' normalisations carry the z pass of the denominator convolution)
-    "normalize_basic": "normalize_zconv_kernel<4, false>",
-    "normalize_out": "normalize_zconv_kernel<4, true>",
+    "normalize_basic": "normalize_zconv_kernel<4, false",
+    "normalize_out": "normalize_zconv_kernel<4, true",
     # EXAC v2 legs are three kernels each (model, coder, pack; the pack kernel serves both legs, so its
     # per-launch mean is the mean over the two): time and counters are summed over the fragments
     "encode_u16": ["rans2_model_strips_kernel", "rans2_code_kernel<2>", "rans2_pack_kernel"],
@@ -39,7 +39,9 @@ def newest_database_only(src):
     included).  Keep the newest database of every pass."""
     import glob
     for d in sorted(os.listdir(src)):
-        dbs = sorted(glob.glob(os.path.join(src, d, "**", "*_results.db"), recursive=True), key=os.path.getmtime)
+        if d.startswith("_"):       # _pmc_only: this tool's own links to the passes, left by an earlier reduction
+            continue
+        dbs =sorted(glob.glob(os.path.join(src, d, "**", "*_results.db"), recursive=True), key=os.path.getmtime)
         for old in dbs[:-1]:
             print("removing the database of an earlier round:", old)
             os.remove(old)
