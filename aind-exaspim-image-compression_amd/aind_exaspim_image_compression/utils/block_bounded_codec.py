@@ -22,8 +22,9 @@ import hashlib
 import numpy as np
 
 from aind_exaspim_image_compression import _native
-from aind_exaspim_image_compression.utils.bounded_codec import HEADER_BYTES, LADDER, STEPS, _nominal_chunk
-from aind_exaspim_image_compression.utils.chunk_codec import EncodedVolume, _shape3
+from aind_exaspim_image_compression.utils.bounded_codec import (HEADER_BYTES, LADDER, STEPS, BoundedVolumeCodec,
+                                                                 pack_dims, parse_dims)
+from aind_exaspim_image_compression.utils.chunk_codec import _shape3
 
 FORMAT_VERSION = 1
 MODE_LOSSLESS, MODE_BLOCKS = 0, 1
@@ -42,7 +43,7 @@ def pack_header(mode, extent, chunk):
     int32 stream of the block indices)."""
     h = bytearray(HEADER_BYTES)
     h[0:4] = bytes((ord("E"), ord("B"), FORMAT_VERSION, int(mode)))
-    h[12:24] = np.array(list(extent) + list(chunk), dtype="<u2").tobytes()
+    h[12:24] = pack_dims(extent, chunk)
     return bytes(h)
 
 
@@ -73,12 +74,7 @@ def parse_header(blob):
         raise ValueError(f"block-bounded chunk stream: unknown mode {mode}")
     if raw[4:12] != bytes(8) or raw[24:32] != bytes(8):
         raise ValueError("block-bounded chunk stream: reserved header bytes are not zero")
-    dims = np.frombuffer(raw[12:24], dtype="<u2").astype(int)
-    extent, chunk = tuple(int(v) for v in dims[:3]), tuple(int(v) for v in dims[3:])
-    if any(c < 8 or c % 8 for c in chunk):
-        raise ValueError("block-bounded chunk stream: chunk axes must be multiples of 8")
-    if any(e < 1 or e > c for e, c in zip(extent, chunk)):
-        raise ValueError("block-bounded chunk stream: extent outside 1..chunk")
+    extent, chunk = parse_dims(raw, "block-bounded")
     steps, at = None, HEADER_BYTES
     if mode == MODE_BLOCKS:
         nb = (chunk[0] // 8) * (chunk[1] // 8) * (chunk[2] // 8)
@@ -108,12 +104,15 @@ def parse_header(blob):
     return {"mode": int(mode), "extent": extent, "chunk": chunk, "steps": steps}
 
 
-class BlockBoundedCodec:
+class BlockBoundedCodec(BoundedVolumeCodec):
     """numcodecs-shaped codec of uint16 chunks with a per-voxel error bound and a step per 8^3 block, arithmetic on
     the GPU."""
 
     codec_id = "exac-dctq-block"
     version = FORMAT_VERSION
+    noun = "block-bounded"
+    takes_mask = True
+    parse_header = staticmethod(parse_header)
 
     def __init__(self, max_error=65535, fg_max_error=None, bound_table=None, device=None):
         max_error = int(max_error)
@@ -162,118 +161,53 @@ class BlockBoundedCodec:
             raise ValueError(f"mask shape {m.shape} differs from the volume's {tuple(shape)}")
         return np.ascontiguousarray(m != 0, dtype=np.uint8).reshape(-1)
 
-    # -- one chunk ---------------------------------------------------------------------------
+    # -- what a chunk store asks ---------------------------------------------------------------
+    def config_entry(self):
+        cfg = {"version": self.version, "max_error": self.max_error, "fg_max_error": self.fg_max_error,
+               "edge_chunks": "truncated"}
+        if self.bound is not None:              # where the bound table came from; no reader needs it
+            cfg["bound"] = dict(self.bound)
+        return cfg
+
+    @classmethod
+    def check_config(cls, cfg):
+        if int(cfg["version"]) != cls.version or not 0 <= int(cfg["fg_max_error"]) <= int(cfg["max_error"]) <= 65535:
+            raise ValueError("unsupported exac-dctq-block configuration")
+        return 2
+
+    @classmethod
+    def from_config(cls, cfg):
+        return cls(int(cfg["max_error"]), int(cfg["fg_max_error"]))
+
+    # -- what VolumeCodec asks -----------------------------------------------------------------
+    def _bound(self, shape, chunk, want_bytes):
+        return _native.block_bounded_volume_bound(shape, chunk)
+
+    def _native_encode(self, ctx, d_vol, shape, chunk, operands, **buffers):
+        d_mask, d_table = operands
+        return ctx.block_bounded_encode(d_vol, shape, chunk, self.max_error, self.fg_max_error, mask=d_mask,
+                                        table=d_table, **buffers)
+
+    def _native_decode(self, ctx, d_in, nbytes, d_off, shape, chunk, d_out):
+        ctx.block_bounded_decode(d_in, nbytes, d_off, shape, chunk, d_out)
+
+    # -- the calls that take a mask ------------------------------------------------------------
     def encode(self, chunk, mask=None):
         """One uint16 chunk (up to 3-D) -> bytes; its nominal chunk shape is its extent rounded up to multiples
         of 8."""
-        a = np.ascontiguousarray(chunk)
-        if a.dtype != np.uint16:
-            raise ValueError("BlockBoundedCodec codes uint16 chunks")
-        if a.size == 0:
-            raise ValueError("cannot encode an empty chunk")
-        shape = _shape3(a.shape)
-        return self.encode_volume(a.reshape(shape), chunk=_nominal_chunk(shape), mask=mask).chunk_bytes(0)
+        return self._encode_chunk(chunk, mask=mask)
 
-    def decode(self, buf, out=None):
-        """bytes of one chunk -> 1-D uint16 array (or filled ``out``).  Header and step plane are validated on the
-        host, before any device call."""
-        raw = bytes(buf)
-        h = parse_header(raw)
-        pad = (-len(raw)) % 16
-        data = np.frombuffer(raw + bytes(pad), dtype=np.uint8)
-        enc = EncodedVolume(data, np.array([0, data.size], dtype=np.uint64), np.array([len(raw)], dtype=np.uint32),
-                            h["extent"], h["chunk"], 2)
-        res = self.decode_volume(enc).reshape(-1)
-        if out is not None:
-            np.copyto(np.asarray(out).reshape(-1), res)
-            return out
-        return res
-
-    # -- a whole volume ------------------------------------------------------------------------
     def encode_volume(self, vol, chunk=(64, 64, 64), mask=None, want_bytes=True):
         """Host uint16 array (up to 3-D), optional mask of its shape -> ``EncodedVolume`` (nominal chunk shape,
         typesize 2).  With ``want_bytes=False`` only the sizes are produced (``data`` is None)."""
-        a = np.ascontiguousarray(vol)
-        if a.dtype != np.uint16:
-            raise ValueError("BlockBoundedCodec codes uint16 volumes")
-        shape = _shape3(a.shape)
-        m = self._mask(mask, shape)
-        ctx = _native.context(self.device)
-        d_vol = ctx.to_device(a.reshape(-1))
-        d_mask = ctx.to_device(m) if m is not None else None
-        d_table = ctx.to_device(self.bound_table) if self.bound_table is not None else None
-        try:
-            return self.encode_device(ctx, d_vol, shape, chunk, d_mask, want_bytes, d_table)
-        finally:
-            d_vol.free()
-            if d_mask is not None:
-                d_mask.free()
-            if d_table is not None:
-                d_table.free()
+        return self._encode_volume(vol, chunk, want_bytes, lambda shape: (self._mask(mask, shape), self.bound_table))
 
     def encode_device(self, ctx, d_vol, shape, chunk=(64, 64, 64), d_mask=None, want_bytes=True, d_table=None):
         """The same for a volume (and a uint8 mask, or None) that already lies in HBM (device pointer holders).
         ``d_table``: this codec's ``bound_table`` on the device (65536 uint16); a codec that has one needs it."""
         if (d_table is None) != (self.bound_table is None):
             raise ValueError("encode_device: d_table goes with a codec that has a bound_table, and only with one")
-        shape, chunk = _shape3(shape), tuple(int(c) for c in _shape3(chunk))
-        cap = _native.block_bounded_volume_bound(shape, chunk)
-        nchunks = int(np.prod([-(-s // c) for s, c in zip(shape, chunk)]))
-        d_sizes = ctx.alloc(4 * nchunks)
-        d_off = ctx.alloc(8 * (nchunks + 1))
-        d_out = ctx.alloc(cap) if want_bytes else None
-        try:
-            _, container = ctx.block_bounded_encode(d_vol, shape, chunk, self.max_error, self.fg_max_error,
-                                                    mask=d_mask, out=d_out, out_capacity=cap if want_bytes else 0,
-                                                    offsets=d_off, sizes=d_sizes, table=d_table)
-            sizes = d_sizes.download((nchunks,), np.uint32)
-            offsets = d_off.download((nchunks + 1,), np.uint64)
-            data = d_out.download((container,), np.uint8) if want_bytes else None
-        finally:
-            d_sizes.free()
-            d_off.free()
-            if d_out is not None:
-                d_out.free()
-        return EncodedVolume(data, offsets, sizes, shape, chunk, 2)
-
-    @staticmethod
-    def _checked(enc):
-        """(data, offsets, shape, chunk) of a container that passed the host checks."""
-        if enc.typesize != 2:
-            raise ValueError("the block-bounded codec stores uint16 volumes")
-        shape, chunk = _shape3(enc.shape), _shape3(enc.chunk)
-        offsets = np.ascontiguousarray(enc.offsets, dtype=np.uint64)
-        data = np.ascontiguousarray(enc.data, dtype=np.uint8)
-        nchunks = int(np.prod([-(-s // c) for s, c in zip(shape, chunk)]))
-        if offsets.size != nchunks + 1 or np.any(np.diff(offsets.astype(np.int64)) < HEADER_BYTES) or \
-                int(offsets[-1]) > data.size or np.any(offsets % 16):
-            raise ValueError("malformed block-bounded container: offsets are not ascending 16-byte steps inside "
-                             "the data")
-        _native.block_bounded_volume_bound(shape, chunk)          # raises for sizes the format does not take
-        return data, offsets, shape, chunk
-
-    def decode_volume(self, enc):
-        """``EncodedVolume`` of this format -> host uint16 array of ``enc.shape``."""
-        shape = self._checked(enc)[2]
-        ctx = _native.context(self.device)
-        d_vol = ctx.alloc(2 * int(np.prod(shape)))
-        try:
-            self.decode_device(ctx, enc, d_vol)
-            return d_vol.download(shape, np.uint16)
-        finally:
-            d_vol.free()
-
-    def decode_device(self, ctx, enc, d_out):
-        """``decode_volume`` without the download: ``EncodedVolume`` -> ``d_out`` (device pointer holder or address,
-        ``prod(enc.shape)`` uint16), decoded when the call returns."""
-        data, offsets, shape, chunk = self._checked(enc)
-        d_in = ctx.to_device(data if data.size else np.zeros(16, np.uint8))
-        d_off = ctx.to_device(offsets)
-        try:
-            ctx.block_bounded_decode(d_in, data.size, d_off, shape, chunk, d_out)
-        finally:
-            d_in.free()
-            d_off.free()
+        return self._encode_device(ctx, d_vol, shape, chunk, want_bytes, (d_mask, d_table))
 
     def chunk_sizes(self, vol, chunk=(64, 64, 64), mask=None):
         """``len(self.encode(c))`` of every chunk of ``vol`` in one batched device call (what ``compute_cratio``
@@ -285,8 +219,7 @@ class BlockBoundedCodec:
         bounds (-1: verbatim, -2: outside the volume), whether or not the chunk would then be stored losslessly --
         where the bound binds, block by block."""
         a = np.ascontiguousarray(vol)
-        if a.dtype != np.uint16:
-            raise ValueError("BlockBoundedCodec codes uint16 volumes")
+        self._check_dtype(a.dtype, "volumes")
         shape, chunk = _shape3(a.shape), tuple(int(c) for c in _shape3(chunk))
         m = self._mask(mask, shape)
         _native.block_bounded_volume_bound(shape, chunk)

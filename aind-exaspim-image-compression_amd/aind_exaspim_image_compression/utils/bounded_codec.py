@@ -16,7 +16,7 @@ MI355X (``csrc/bounded_kernels.hip``, ``exabm4d_bounded_*``).
 import numpy as np
 
 from aind_exaspim_image_compression import _native
-from aind_exaspim_image_compression.utils.chunk_codec import EncodedVolume, _shape3
+from aind_exaspim_image_compression.utils.chunk_codec import VolumeCodec, _shape3
 
 STEPS = 29
 # Q[j] = float32(2^((j - 4) / 4)), j = 0..28: steps 0.5 .. 64
@@ -24,6 +24,23 @@ LADDER = np.array([np.float32(2.0 ** ((j - 4) / 4)) for j in range(STEPS)], dtyp
 HEADER_BYTES = 32
 FORMAT_VERSION = 1
 MODE_LOSSLESS, MODE_DCT = 0, 1
+
+
+def pack_dims(extent, chunk):
+    """Bytes 12..23 of either bounded format's header: the chunk's extent E, then its nominal shape C (u16 each)."""
+    return np.array(list(extent) + list(chunk), dtype="<u2").tobytes()
+
+
+def parse_dims(raw, who):
+    """-> (extent, chunk) from bytes 12..23 of a header; ``ValueError`` (``who``: the format, in the message) unless
+    ``C`` is made of multiples of 8 and ``1 <= E <= C``."""
+    dims = np.frombuffer(raw[12:24], dtype="<u2").astype(int)
+    extent, chunk = tuple(int(v) for v in dims[:3]), tuple(int(v) for v in dims[3:])
+    if any(c < 8 or c % 8 for c in chunk):
+        raise ValueError(f"{who} chunk stream: chunk axes must be multiples of 8")
+    if any(e < 1 or e > c for e, c in zip(extent, chunk)):
+        raise ValueError(f"{who} chunk stream: extent outside 1..chunk")
+    return extent, chunk
 
 
 def pack_header(mode, j, extent, chunk):
@@ -36,7 +53,7 @@ def pack_header(mode, j, extent, chunk):
         h[8:12] = LADDER[int(j)].tobytes()
     else:
         h[4] = 0xFF
-    h[12:24] = np.array(list(extent) + list(chunk), dtype="<u2").tobytes()
+    h[12:24] = pack_dims(extent, chunk)
     return bytes(h)
 
 
@@ -62,12 +79,7 @@ def parse_header(blob):
         q = float(LADDER[j])
     else:
         raise ValueError(f"bounded chunk stream: unknown mode {mode}")
-    dims = np.frombuffer(raw[12:24], dtype="<u2").astype(int)
-    extent, chunk = tuple(int(v) for v in dims[:3]), tuple(int(v) for v in dims[3:])
-    if any(c < 8 or c % 8 for c in chunk):
-        raise ValueError("bounded chunk stream: chunk axes must be multiples of 8")
-    if any(e < 1 or e > c for e, c in zip(extent, chunk)):
-        raise ValueError("bounded chunk stream: extent outside 1..chunk")
+    extent, chunk = parse_dims(raw, "bounded")
     return {"mode": int(mode), "j": None if mode == MODE_LOSSLESS else int(j), "q": q, "extent": extent,
             "chunk": chunk}
 
@@ -76,11 +88,49 @@ def _nominal_chunk(extent):
     return tuple(-(-int(e) // 8) * 8 for e in extent)
 
 
-class BoundedDctCodec:
+class BoundedVolumeCodec(VolumeCodec):
+    """What the two error-bounded formats add to ``VolumeCodec``: uint16 volumes, streams that keep the nominal chunk
+    shape (their index chunks are sized by it) behind a 32-byte header that states it, and a volume bound that is
+    also the format's size check.  ``noun`` names the format in messages."""
+
+    typesize = 2
+    nominal_chunks = True
+
+    @property
+    def _container(self):
+        return self.noun, 16, HEADER_BYTES, "16-byte steps "
+
+    def _check_dtype(self, dtype, what):
+        if dtype != np.uint16:
+            raise ValueError(f"{type(self).__name__} codes uint16 {what}")
+
+    def _check_typesize(self, enc):
+        if enc.typesize != 2:
+            raise ValueError(f"the {self.noun} codec stores uint16 volumes")
+
+    def _check_volume(self, shape, chunk):
+        self._bound(shape, chunk, False)        # raises for sizes the format does not take
+
+    def _stream_geometry(self, raw):
+        h = self.parse_header(raw)
+        return h["extent"], h["chunk"]
+
+    def _encode_chunk(self, chunk, **operands):
+        a = np.ascontiguousarray(chunk)
+        self._check_dtype(a.dtype, "chunks")
+        if a.size == 0:
+            raise ValueError("cannot encode an empty chunk")
+        shape = _shape3(a.shape)
+        return self.encode_volume(a.reshape(shape), chunk=_nominal_chunk(shape), **operands).chunk_bytes(0)
+
+
+class BoundedDctCodec(BoundedVolumeCodec):
     """numcodecs-shaped codec of uint16 chunks with a per-voxel error bound, arithmetic on the GPU."""
 
     codec_id = "exac-dctq"
     version = FORMAT_VERSION
+    noun = "bounded"
+    parse_header = staticmethod(parse_header)
 
     def __init__(self, max_error, device=None):
         max_error = int(max_error)
@@ -92,117 +142,40 @@ class BoundedDctCodec:
     def get_config(self):
         return {"id": self.codec_id, "max_error": self.max_error, "version": self.version}
 
-    # -- one chunk ---------------------------------------------------------------------------
+    # -- what a chunk store asks ---------------------------------------------------------------
+    def config_entry(self):
+        return {"version": self.version, "max_error": self.max_error, "edge_chunks": "truncated"}
+
+    @classmethod
+    def check_config(cls, cfg):
+        if int(cfg["version"]) != cls.version or not 0 <= int(cfg["max_error"]) <= 65535:
+            raise ValueError("unsupported exac-dctq configuration")
+        return 2
+
+    @classmethod
+    def from_config(cls, cfg):
+        return cls(int(cfg["max_error"]))
+
+    # -- what VolumeCodec asks -----------------------------------------------------------------
+    def _bound(self, shape, chunk, want_bytes):
+        return _native.bounded_volume_bound(shape, chunk)
+
+    def _native_encode(self, ctx, d_vol, shape, chunk, operands, **buffers):
+        return ctx.bounded_encode(d_vol, shape, chunk, self.max_error, **buffers)
+
+    def _native_decode(self, ctx, d_in, nbytes, d_off, shape, chunk, d_out):
+        ctx.bounded_decode(d_in, nbytes, d_off, shape, chunk, d_out)
+
     def encode(self, chunk):
         """One uint16 chunk (up to 3-D) -> bytes; its nominal chunk shape is its extent rounded up to multiples
         of 8."""
-        a = np.ascontiguousarray(chunk)
-        if a.dtype != np.uint16:
-            raise ValueError("BoundedDctCodec codes uint16 chunks")
-        if a.size == 0:
-            raise ValueError("cannot encode an empty chunk")
-        shape = _shape3(a.shape)
-        return self.encode_volume(a.reshape(shape), chunk=_nominal_chunk(shape)).chunk_bytes(0)
-
-    def decode(self, buf, out=None):
-        """bytes of one chunk -> 1-D uint16 array (or filled ``out``).  The header is validated on the host."""
-        raw = bytes(buf)
-        h = parse_header(raw)
-        pad = (-len(raw)) % 16
-        data = np.frombuffer(raw + bytes(pad), dtype=np.uint8)
-        enc = EncodedVolume(data, np.array([0, data.size], dtype=np.uint64), np.array([len(raw)], dtype=np.uint32),
-                            h["extent"], h["chunk"], 2)
-        res = self.decode_volume(enc).reshape(-1)
-        if out is not None:
-            np.copyto(np.asarray(out).reshape(-1), res)
-            return out
-        return res
-
-    # -- a whole volume ------------------------------------------------------------------------
-    def encode_volume(self, vol, chunk=(64, 64, 64), want_bytes=True):
-        """Host uint16 array (up to 3-D) -> ``EncodedVolume`` (nominal chunk shape, typesize 2).  With
-        ``want_bytes=False`` only the sizes are produced (``data`` is None)."""
-        a = np.ascontiguousarray(vol)
-        if a.dtype != np.uint16:
-            raise ValueError("BoundedDctCodec codes uint16 volumes")
-        shape = _shape3(a.shape)
-        ctx = _native.context(self.device)
-        d_vol = ctx.to_device(a.reshape(-1))
-        try:
-            return self.encode_device(ctx, d_vol, shape, chunk, want_bytes)
-        finally:
-            d_vol.free()
-
-    def encode_device(self, ctx, d_vol, shape, chunk=(64, 64, 64), want_bytes=True):
-        """The same for a volume that already lies in HBM (``d_vol``: device pointer holder)."""
-        shape, chunk = _shape3(shape), tuple(int(c) for c in _shape3(chunk))
-        cap = _native.bounded_volume_bound(shape, chunk)
-        nchunks = int(np.prod([-(-s // c) for s, c in zip(shape, chunk)]))
-        d_sizes = ctx.alloc(4 * nchunks)
-        d_off = ctx.alloc(8 * (nchunks + 1))
-        d_out = ctx.alloc(cap) if want_bytes else None
-        try:
-            _, container = ctx.bounded_encode(d_vol, shape, chunk, self.max_error, out=d_out,
-                                              out_capacity=cap if want_bytes else 0, offsets=d_off, sizes=d_sizes)
-            sizes = d_sizes.download((nchunks,), np.uint32)
-            offsets = d_off.download((nchunks + 1,), np.uint64)
-            data = d_out.download((container,), np.uint8) if want_bytes else None
-        finally:
-            d_sizes.free()
-            d_off.free()
-            if d_out is not None:
-                d_out.free()
-        return EncodedVolume(data, offsets, sizes, shape, chunk, 2)
-
-    @staticmethod
-    def _checked(enc):
-        """(data, offsets, shape, chunk) of a container that passed the host checks."""
-        if enc.typesize != 2:
-            raise ValueError("the bounded codec stores uint16 volumes")
-        shape, chunk = _shape3(enc.shape), _shape3(enc.chunk)
-        offsets = np.ascontiguousarray(enc.offsets, dtype=np.uint64)
-        data = np.ascontiguousarray(enc.data, dtype=np.uint8)
-        nchunks = int(np.prod([-(-s // c) for s, c in zip(shape, chunk)]))
-        if offsets.size != nchunks + 1 or np.any(np.diff(offsets.astype(np.int64)) < HEADER_BYTES) or \
-                int(offsets[-1]) > data.size or np.any(offsets % 16):
-            raise ValueError("malformed bounded container: offsets are not ascending 16-byte steps inside the data")
-        _native.bounded_volume_bound(shape, chunk)          # raises for sizes the format does not take
-        return data, offsets, shape, chunk
-
-    def decode_volume(self, enc):
-        """``EncodedVolume`` of this format -> host uint16 array of ``enc.shape``."""
-        shape = self._checked(enc)[2]
-        ctx = _native.context(self.device)
-        d_vol = ctx.alloc(2 * int(np.prod(shape)))
-        try:
-            self.decode_device(ctx, enc, d_vol)
-            return d_vol.download(shape, np.uint16)
-        finally:
-            d_vol.free()
-
-    def decode_device(self, ctx, enc, d_out):
-        """``decode_volume`` without the download: ``EncodedVolume`` -> ``d_out`` (device pointer holder or address,
-        ``prod(enc.shape)`` uint16), decoded when the call returns."""
-        data, offsets, shape, chunk = self._checked(enc)
-        d_in = ctx.to_device(data if data.size else np.zeros(16, np.uint8))
-        d_off = ctx.to_device(offsets)
-        try:
-            ctx.bounded_decode(d_in, data.size, d_off, shape, chunk, d_out)
-        finally:
-            d_in.free()
-            d_off.free()
-
-    def chunk_sizes(self, vol, chunk=(64, 64, 64)):
-        """``len(self.encode(c))`` of every chunk of ``vol`` in one batched device call (what ``compute_cratio``
-        takes)."""
-        return self.encode_volume(vol, chunk, want_bytes=False).sizes
+        return self._encode_chunk(chunk)
 
     def ladder_errors(self, vol, chunk=(64, 64, 64)):
         """-> uint32 [gz, gy, gx, 29]: the largest |reconstruction - voxel| of every chunk at every ladder step
         (independent of ``max_error``: the per-chunk rate-distortion picture)."""
         a = np.ascontiguousarray(vol)
-        if a.dtype != np.uint16:
-            raise ValueError("BoundedDctCodec codes uint16 volumes")
+        self._check_dtype(a.dtype, "volumes")
         shape, chunk = _shape3(a.shape), tuple(int(c) for c in _shape3(chunk))
         _native.bounded_volume_bound(shape, chunk)
         grid = tuple(-(-s // c) for s, c in zip(shape, chunk))

@@ -18,6 +18,10 @@ runs on the MI355X.  zstd itself is third-party and absent, so the byte counts a
 Besides the per-chunk calls the codec codes all chunks of a volume that is already in HBM with one
 kernel sequence (``encode_volume``), which is what ``compute_cratio`` uses when it is given this
 codec.
+
+``VolumeCodec`` is the plumbing every chunk codec of this package shares (this one and the two error-bounded ones,
+``utils/bounded_codec.py`` and ``utils/block_bounded_codec.py``): uploads, buffers, downloads and the host checks of a
+container around the codec's own native calls.
 """
 import numpy as np
 
@@ -47,6 +51,10 @@ def _shape3(shape):
     return (1,) * (3 - len(shape)) + shape
 
 
+def _nchunks(shape, chunk):
+    return int(np.prod([-(-s // c) for s, c in zip(shape, chunk)]))
+
+
 class EncodedVolume:
     """All chunk streams of one volume: ``data`` (uint8 container, every stream starting at a
     multiple of 16 bytes), ``offsets`` (uint64, nchunks + 1), ``sizes`` (uint32, exact stream
@@ -70,10 +78,145 @@ class EncodedVolume:
         return self.data[o:o + int(self.sizes[i])].tobytes()
 
 
-class ExacCodec:
+class VolumeCodec:
+    """A chunk codec whose arithmetic runs on the GPU: volume in, ``EncodedVolume`` out, and back.  A codec states
+
+    * ``typesize`` (of its elements), ``_check_dtype(dtype, what)`` and ``_check_typesize(enc)``: what it codes;
+    * ``nominal_chunks``: its streams keep the nominal chunk shape (else the chunk clamped to the array);
+    * ``_bound(shape, chunk, want_bytes)``: its volume bound, where the codec needs it (for the container, or because
+      it is also the format's size check);
+    * ``_native_encode(ctx, d_vol, shape, chunk, operands, **buffers)`` and ``_native_decode(ctx, d_in, nbytes,
+      d_off, shape, chunk, d_out)``: its calls, ``operands`` being the extra device operands of its encoder;
+    * ``_container`` = (noun of its messages, alignment of a stream's offset, least stream length, the words for
+      that rule) and ``_check_volume(shape, chunk)``: the host checks of a container;
+    * ``_stream_geometry(raw)``: (extent, chunk) of one stream from its validated header;
+    * ``config_entry()``, ``check_config(cfg)``, ``from_config(cfg)`` and ``takes_mask``: what a chunk store asks
+      (``utils/chunk_store.py``) -- its ``zarr.json`` configuration, such an entry's validation (-> typesize) and
+      decoder, and whether its encoder takes a foreground mask.
+    """
+
+    nominal_chunks = False
+    takes_mask = False
+    device = None
+
+    def _chunk(self, shape, chunk):
+        chunk = tuple(int(c) for c in _shape3(chunk))
+        return chunk if self.nominal_chunks else tuple(min(c, s) for c, s in zip(chunk, shape))
+
+    # -- one chunk ---------------------------------------------------------------------------
+    def decode(self, buf, out=None):
+        """bytes of one chunk -> 1-D array (or filled ``out``) of the codec's element type.  The header is validated
+        on the host, before any device call."""
+        raw = bytes(buf)
+        extent, chunk = self._stream_geometry(raw)
+        data = np.frombuffer(raw + bytes((-len(raw)) % 16), dtype=np.uint8)
+        enc = EncodedVolume(data, np.array([0, data.size], dtype=np.uint64), np.array([len(raw)], dtype=np.uint32),
+                            extent, chunk, self.typesize)
+        res = self.decode_volume(enc).reshape(-1)
+        if out is not None:
+            np.copyto(np.asarray(out).reshape(-1), res)
+            return out
+        return res
+
+    # -- a whole volume ------------------------------------------------------------------------
+    def encode_volume(self, vol, chunk=(64, 64, 64), want_bytes=True):
+        """Host array (up to 3-D) of the codec's element type -> ``EncodedVolume`` on the host.  With
+        ``want_bytes=False`` only the sizes are produced (``data`` is None)."""
+        return self._encode_volume(vol, chunk, want_bytes)
+
+    def _encode_volume(self, vol, chunk, want_bytes, operands=lambda shape: ()):
+        """``operands(shape)``: the host arrays (or None) behind the encoder's extra device operands, checked before
+        any device call."""
+        a = np.ascontiguousarray(vol)
+        self._check_dtype(a.dtype, "volumes")
+        shape = _shape3(a.shape)
+        host = operands(shape)
+        ctx = _native.context(self.device)
+        held = [ctx.to_device(a.reshape(-1))]
+        try:
+            for h in host:
+                held.append(ctx.to_device(h) if h is not None else None)
+            return self._encode_device(ctx, held[0], shape, chunk, want_bytes, held[1:])
+        finally:
+            for d in held:
+                if d is not None:
+                    d.free()
+
+    def encode_device(self, ctx, d_vol, shape, chunk=(64, 64, 64), want_bytes=True):
+        """The same for a volume that already lies in HBM (``d_vol``: device pointer holder)."""
+        return self._encode_device(ctx, d_vol, shape, chunk, want_bytes, ())
+
+    def _encode_device(self, ctx, d_vol, shape, chunk, want_bytes, operands):
+        shape = _shape3(shape)
+        chunk = self._chunk(shape, chunk)
+        cap = self._bound(shape, chunk, want_bytes)
+        nchunks = _nchunks(shape, chunk)
+        d_sizes = ctx.alloc(4 * nchunks)
+        d_off = ctx.alloc(8 * (nchunks + 1))
+        d_out = None
+        try:
+            if want_bytes:
+                d_out = ctx.alloc(cap)
+            _, container = self._native_encode(ctx, d_vol, shape, chunk, operands, out=d_out,
+                                               out_capacity=cap if want_bytes else 0, offsets=d_off, sizes=d_sizes)
+            sizes = d_sizes.download((nchunks,), np.uint32)
+            offsets = d_off.download((nchunks + 1,), np.uint64)
+            data = d_out.download((container,), np.uint8) if want_bytes else None
+        finally:
+            d_sizes.free()
+            d_off.free()
+            if d_out is not None:
+                d_out.free()
+        return EncodedVolume(data, offsets, sizes, shape, chunk, self.typesize)
+
+    def _checked(self, enc):
+        """(data, offsets, shape, chunk) of a container that passed the host checks: a corrupt one must raise,
+        not fault."""
+        self._check_typesize(enc)
+        noun, align, least, rule = self._container
+        shape, chunk = _shape3(enc.shape), _shape3(enc.chunk)
+        offsets = np.ascontiguousarray(enc.offsets, dtype=np.uint64)
+        data = np.ascontiguousarray(enc.data, dtype=np.uint8)
+        if offsets.size != _nchunks(shape, chunk) + 1 or np.any(np.diff(offsets.astype(np.int64)) < least) or \
+                int(offsets[-1]) > data.size or np.any(offsets % align):
+            raise ValueError(f"malformed {noun} container: offsets are not ascending {rule}inside the data")
+        self._check_volume(shape, chunk)
+        return data, offsets, shape, chunk
+
+    def decode_volume(self, enc):
+        """``EncodedVolume`` of this format -> host array of ``enc.shape``."""
+        shape = self._checked(enc)[2]
+        ctx = _native.context(self.device)
+        d_vol = ctx.alloc(self.typesize * int(np.prod(shape)))
+        try:
+            self.decode_device(ctx, enc, d_vol)
+            return d_vol.download(shape, _DTYPES[self.typesize])
+        finally:
+            d_vol.free()
+
+    def decode_device(self, ctx, enc, d_out):
+        """``decode_volume`` without the download: ``EncodedVolume`` -> ``d_out`` (device pointer holder or address,
+        ``prod(enc.shape)`` elements), decoded when the call returns."""
+        data, offsets, shape, chunk = self._checked(enc)
+        d_in = ctx.to_device(data if data.size else np.zeros(16, np.uint8))
+        d_off = ctx.to_device(offsets)
+        try:
+            self._native_decode(ctx, d_in, data.size, d_off, shape, chunk, d_out)
+        finally:
+            d_in.free()
+            d_off.free()
+
+    def chunk_sizes(self, vol, chunk=(64, 64, 64)):
+        """``len(self.encode(c))`` of every chunk of ``vol`` in one batched device call (what ``compute_cratio``
+        takes)."""
+        return self.encode_volume(vol, chunk, want_bytes=False).sizes
+
+
+class ExacCodec(VolumeCodec):
     """numcodecs-shaped codec whose arithmetic runs on the GPU (EXAC v2 by default)."""
 
     codec_id = "exac"
+    _container = ("EXAC", 2, 0, "")
 
     def __init__(self, typesize=2, device=None, version=2):
         if typesize not in (2, 4):
@@ -87,24 +230,46 @@ class ExacCodec:
     def get_config(self):
         return {"id": self.codec_id, "typesize": self.typesize, "version": self.version}
 
-    # -- one chunk ---------------------------------------------------------------------------
-    def encode(self, buf):
-        """One chunk -> bytes.  Version 2 models the chunk as the (up to) 3-D array it is -- pass
-        the chunk with its shape, as ``compute_cratio`` does; version 1 only sees the C-order
-        element sequence."""
-        a = np.ascontiguousarray(buf)
-        if _typesize(a.dtype) != self.typesize:
-            raise ValueError("element type does not match the codec's typesize")
-        if a.size == 0:
-            raise ValueError("cannot encode an empty chunk")
-        shape = _shape3(a.shape) if self.version == 2 else (1, 1, a.size)
-        enc = self.encode_volume(a.reshape(shape), chunk=shape)
-        return enc.chunk_bytes(0)
+    # -- what a chunk store asks ---------------------------------------------------------------
+    def config_entry(self):
+        return {"version": self.version, "typesize": self.typesize, "edge_chunks": "truncated"}
 
-    def decode(self, buf, out=None):
-        """bytes of one chunk (either version) -> 1-D array (or filled ``out``) of the codec's
-        element type."""
-        raw = np.frombuffer(bytes(buf), dtype=np.uint8)
+    @classmethod
+    def check_config(cls, cfg):
+        return int(cfg["typesize"])
+
+    @classmethod
+    def from_config(cls, cfg):
+        return cls(int(cfg["typesize"]))
+
+    # -- what VolumeCodec asks -----------------------------------------------------------------
+    def _check_dtype(self, dtype, what):
+        if _typesize(dtype) != self.typesize:
+            raise ValueError("element type does not match the codec's typesize")
+
+    def _check_typesize(self, enc):
+        if enc.typesize != self.typesize:
+            raise ValueError("EncodedVolume of another typesize")
+
+    def _bound(self, shape, chunk, want_bytes):
+        return _native.codec_volume_bound(self.typesize, shape, chunk) if want_bytes else 0
+
+    @staticmethod
+    def _check_volume(shape, chunk):
+        n = int(np.prod(shape))
+        if n < 1 or n > (1 << 40):
+            raise ValueError("malformed EXAC container: implausible volume shape")
+
+    def _native_encode(self, ctx, d_vol, shape, chunk, operands, **buffers):
+        # the format travels with the call (round 4): no shared context state is touched
+        return ctx.codec_encode(d_vol, self.typesize, shape, chunk, version=self.version, **buffers)
+
+    def _native_decode(self, ctx, d_in, nbytes, d_off, shape, chunk, d_out):
+        ctx.codec_decode(d_in, nbytes, d_off, self.typesize, shape, chunk, d_out)
+
+    def _stream_geometry(self, raw):
+        """Either version's header -> the chunk's shape, twice: an EXAC stream is a whole chunk."""
+        raw = np.frombuffer(raw, dtype=np.uint8)
         if raw.size < 8 or raw[0] != ord("E") or raw[1] != ord("X") or raw[3] != self.typesize:
             raise ValueError("not an EXAC stream of this codec's typesize")
         n = int(raw[4:8].view("<u4")[0])
@@ -118,99 +283,20 @@ class ExacCodec:
             if ey < 1 or ex < 1 or n % (ey * ex):
                 raise ValueError("EXAC v2 header with an inconsistent chunk shape")
             shape = (n // (ey * ex), ey, ex)
-        pad = (-raw.size) % 16
-        data = np.concatenate([raw, np.zeros(pad, np.uint8)]) if pad else raw
-        enc = EncodedVolume(data, np.array([0, raw.size], dtype=np.uint64),
-                            np.array([raw.size], dtype=np.uint32), shape, shape, self.typesize)
-        res = self.decode_volume(enc).reshape(-1)
-        if out is not None:
-            np.copyto(np.asarray(out).reshape(-1), res)
-            return out
-        return res
+        return shape, shape
 
-    # -- a whole volume ------------------------------------------------------------------------
-    def encode_volume(self, vol, chunk=(64, 64, 64), want_bytes=True):
-        """Host array (uint16 / int32, up to 3-D) -> ``EncodedVolume`` on the host.  With
-        ``want_bytes=False`` only the sizes are produced (``data`` is None)."""
-        a = np.ascontiguousarray(vol)
-        if _typesize(a.dtype) != self.typesize:
-            raise ValueError("element type does not match the codec's typesize")
-        shape = _shape3(a.shape)
-        ctx = _native.context(self.device)
-        d_vol = ctx.to_device(a.reshape(-1))
-        try:
-            return self.encode_device(ctx, d_vol, shape, chunk, want_bytes)
-        finally:
-            d_vol.free()
-
-    def encode_device(self, ctx, d_vol, shape, chunk=(64, 64, 64), want_bytes=True):
-        """The same for a volume that already lies in HBM (``d_vol``: device pointer holder)."""
-        shape = _shape3(shape)
-        chunk = tuple(min(int(c), s) for c, s in zip(_shape3(chunk), shape))
-        nchunks = int(np.prod([-(-s // c) for s, c in zip(shape, chunk)]))
-        d_sizes = ctx.alloc(4 * nchunks)
-        d_off = ctx.alloc(8 * (nchunks + 1))
-        d_out = None
-        try:
-            cap = 0
-            if want_bytes:
-                cap = _native.codec_volume_bound(self.typesize, shape, chunk)
-                d_out = ctx.alloc(cap)
-            # the format travels with the call (round 4): no shared context state is touched
-            _, container = ctx.codec_encode(d_vol, self.typesize, shape, chunk, out=d_out, out_capacity=cap,
-                                            offsets=d_off, sizes=d_sizes, version=self.version)
-            sizes = d_sizes.download((nchunks,), np.uint32)
-            offsets = d_off.download((nchunks + 1,), np.uint64)
-            data = d_out.download((container,), np.uint8) if want_bytes else None
-        finally:
-            d_sizes.free()
-            d_off.free()
-            if d_out is not None:
-                d_out.free()
-        return EncodedVolume(data, offsets, sizes, shape, chunk, self.typesize)
-
-    def _checked(self, enc):
-        """(data, offsets, element count) of a container that passed the host checks: a corrupt one must raise,
-        not fault."""
-        if enc.typesize != self.typesize:
-            raise ValueError("EncodedVolume of another typesize")
-        offsets = np.ascontiguousarray(enc.offsets, dtype=np.uint64)
-        data = np.ascontiguousarray(enc.data, dtype=np.uint8)
-        nchunks = int(np.prod([-(-s // c) for s, c in zip(enc.shape, enc.chunk)]))
-        if offsets.size != nchunks + 1 or np.any(np.diff(offsets.astype(np.int64)) < 0) or \
-                int(offsets[-1]) > data.size or np.any(offsets % 2):
-            raise ValueError("malformed EXAC container: offsets are not ascending inside the data")
-        n = int(np.prod(enc.shape))
-        if n < 1 or n > (1 << 40):
-            raise ValueError("malformed EXAC container: implausible volume shape")
-        return data, offsets, n
-
-    def decode_volume(self, enc):
-        """``EncodedVolume`` -> host array of ``enc.shape``."""
-        n = self._checked(enc)[2]
-        ctx = _native.context(self.device)
-        d_vol = ctx.alloc(n * self.typesize)
-        try:
-            self.decode_device(ctx, enc, d_vol)
-            return d_vol.download(enc.shape, _DTYPES[self.typesize])
-        finally:
-            d_vol.free()
-
-    def decode_device(self, ctx, enc, d_out):
-        """``decode_volume`` without the download: ``EncodedVolume`` -> ``d_out`` (device pointer holder or address,
-        ``prod(enc.shape)`` elements), decoded when the call returns."""
-        data, offsets, _ = self._checked(enc)
-        d_in = ctx.to_device(data)
-        d_off = ctx.to_device(offsets)
-        try:
-            ctx.codec_decode(d_in, data.size, d_off, self.typesize, enc.shape, enc.chunk, d_out)
-        finally:
-            d_in.free()
-            d_off.free()
-
-    def chunk_sizes(self, vol, chunk=(64, 64, 64)):
-        """``len(self.encode(c))`` of every chunk of ``vol``, one batched device call."""
-        return self.encode_volume(vol, chunk, want_bytes=False).sizes
+    # -- one chunk ---------------------------------------------------------------------------
+    def encode(self, buf):
+        """One chunk -> bytes.  Version 2 models the chunk as the (up to) 3-D array it is -- pass
+        the chunk with its shape, as ``compute_cratio`` does; version 1 only sees the C-order
+        element sequence."""
+        a = np.ascontiguousarray(buf)
+        self._check_dtype(a.dtype, "chunks")
+        if a.size == 0:
+            raise ValueError("cannot encode an empty chunk")
+        shape = _shape3(a.shape) if self.version == 2 else (1, 1, a.size)
+        enc = self.encode_volume(a.reshape(shape), chunk=shape)
+        return enc.chunk_bytes(0)
 
 
 class ShuffleRansCodec(ExacCodec):

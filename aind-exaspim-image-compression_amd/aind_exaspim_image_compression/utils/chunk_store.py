@@ -47,34 +47,24 @@ def chunk_key(iz, iy, ix):
     return os.path.join("c", "0", "0", str(int(iz)), str(int(iy)), str(int(ix)))
 
 
+# codec id in ``zarr.json`` -> the class that states the entry's configuration, validates one and decodes its streams
+CODECS = {cls.codec_id: cls for cls in (ExacCodec, BoundedDctCodec, BlockBoundedCodec)}
+
+
 def metadata(shape3, chunk3, typesize=2, version=2, attributes=None, codec=None):
     """The ``zarr.json`` document of a stored volume (``codec``: a ``BoundedDctCodec`` or ``BlockBoundedCodec``
     stores its own entry)."""
-    dtype = {2: "uint16", 4: "int32"}[int(typesize)]
-    if isinstance(codec, BlockBoundedCodec):
-        meta = metadata(shape3, chunk3, 2, attributes=attributes)
-        meta["codecs"] = [{"name": BlockBoundedCodec.codec_id,
-                           "configuration": {"version": BlockBoundedCodec.version, "max_error": codec.max_error,
-                                             "fg_max_error": codec.fg_max_error, "edge_chunks": "truncated"}}]
-        if codec.bound is not None:             # where the bound table came from; no reader needs it
-            meta["codecs"][0]["configuration"]["bound"] = dict(codec.bound)
-        return meta
-    if isinstance(codec, BoundedDctCodec):
-        meta = metadata(shape3, chunk3, 2, attributes=attributes)
-        meta["codecs"] = [{"name": BoundedDctCodec.codec_id,
-                           "configuration": {"version": BoundedDctCodec.version, "max_error": codec.max_error,
-                                             "edge_chunks": "truncated"}}]
-        return meta
+    codec = codec or ExacCodec(int(typesize), version=int(version))
+    name = next(k for k, cls in CODECS.items() if isinstance(codec, cls))     # a subclass stores its parent's format
     return {
         "zarr_format": 3,
         "node_type": "array",
         "shape": [1, 1] + [int(s) for s in shape3],
-        "data_type": dtype,
+        "data_type": {2: "uint16", 4: "int32"}[codec.typesize],
         "chunk_grid": {"name": "regular", "configuration": {"chunk_shape": [1, 1] + [int(c) for c in chunk3]}},
         "chunk_key_encoding": {"name": "default", "configuration": {"separator": "/"}},
         "fill_value": 0,
-        "codecs": [{"name": "exac", "configuration": {"version": int(version), "typesize": int(typesize),
-                                                      "edge_chunks": "truncated"}}],
+        "codecs": [{"name": name, "configuration": codec.config_entry()}],
         "attributes": dict(attributes or {}, exac_note=FORMAT_NOTE),
         "dimension_names": ["t", "c", "z", "y", "x"],
     }
@@ -116,23 +106,10 @@ def check_metadata(meta):
         if meta["zarr_format"] != 3 or meta["node_type"] != "array":
             raise ValueError("not a Zarr v3 array")
         codecs = meta["codecs"]
-        if len(codecs) != 1 or codecs[0]["name"] not in ("exac", BoundedDctCodec.codec_id,
-                                                         BlockBoundedCodec.codec_id):
+        if len(codecs) != 1 or codecs[0]["name"] not in CODECS:
             raise ValueError("the array's codec chain is not [exac], [exac-dctq] or [exac-dctq-block]")
-        block = codecs[0]["name"] == BlockBoundedCodec.codec_id
-        bounded = block or codecs[0]["name"] == BoundedDctCodec.codec_id
-        cfg = codecs[0]["configuration"]
-        if block:
-            if int(cfg["version"]) != BlockBoundedCodec.version or \
-                    not 0 <= int(cfg["fg_max_error"]) <= int(cfg["max_error"]) <= 65535:
-                raise ValueError("unsupported exac-dctq-block configuration")
-            typesize = 2
-        elif bounded:
-            if int(cfg["version"]) != BoundedDctCodec.version or not 0 <= int(cfg["max_error"]) <= 65535:
-                raise ValueError("unsupported exac-dctq configuration")
-            typesize = 2
-        else:
-            typesize = int(cfg["typesize"])
+        cls = CODECS[codecs[0]["name"]]
+        typesize = cls.check_config(codecs[0]["configuration"])
         shape5, chunk5 = meta["shape"], meta["chunk_grid"]["configuration"]["chunk_shape"]
         if len(shape5) != 5 or shape5[:2] != [1, 1] or len(chunk5) != 5 or chunk5[:2] != [1, 1]:
             raise ValueError("only (1, 1, z, y, x) arrays with (1, 1, cz, cy, cx) chunks are stored this way")
@@ -146,7 +123,7 @@ def check_metadata(meta):
     shape3, chunk3 = tuple(int(s) for s in shape5[2:]), tuple(int(c) for c in chunk5[2:])
     if min(shape3) < 1 or min(chunk3) < 1:
         raise ValueError("empty array or chunk")
-    return shape3, chunk3, typesize, bounded
+    return shape3, chunk3, typesize, cls.nominal_chunks
 
 
 def pack_streams(blobs):
@@ -197,17 +174,11 @@ def write_zarr(img, output_path, chunks=(1, 1, 64, 64, 64), codec=None, attribut
         raise ValueError("chunks must be (1, 1, cz, cy, cx)")
     codec = codec or ExacCodec(2)
     vol = np.ascontiguousarray(img[0, 0])
-    if isinstance(codec, BlockBoundedCodec):
-        enc = codec.encode_volume(vol, chunk=tuple(int(c) for c in chunks[2:]), mask=mask)
-    elif mask is not None:
+    if mask is not None and not codec.takes_mask:
         raise ValueError("only a BlockBoundedCodec takes a mask")
-    else:
-        enc = codec.encode_volume(vol, chunk=tuple(int(c) for c in chunks[2:]))
-    if isinstance(codec, (BoundedDctCodec, BlockBoundedCodec)):
-        stored = write_encoded(enc, output_path, attributes=attributes, codec=codec)
-    else:
-        stored = write_encoded(enc, output_path, version=codec.version, attributes=attributes)
-    return vol.nbytes / stored
+    operands = {"mask": mask} if codec.takes_mask else {}
+    enc = codec.encode_volume(vol, chunk=tuple(int(c) for c in chunks[2:]), **operands)
+    return vol.nbytes / write_encoded(enc, output_path, attributes=attributes, codec=codec)
 
 
 def read_zarr(path, codec=None):
@@ -243,9 +214,4 @@ def open_zarr(path, device=None, max_pool_bytes=1 << 30):
 def _codec_of(meta):
     """The decoder a store's ``zarr.json`` names."""
     entry = meta["codecs"][0]
-    if entry["name"] == BlockBoundedCodec.codec_id:
-        return BlockBoundedCodec(int(entry["configuration"]["max_error"]),
-                                 int(entry["configuration"]["fg_max_error"]))
-    if entry["name"] == BoundedDctCodec.codec_id:
-        return BoundedDctCodec(int(entry["configuration"]["max_error"]))
-    return ExacCodec(int(entry["configuration"]["typesize"]))
+    return CODECS[entry["name"]].from_config(entry["configuration"])

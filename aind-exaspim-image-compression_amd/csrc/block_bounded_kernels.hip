@@ -13,7 +13,8 @@
 //             With a bound table the bound of a voxel is further capped by table[its value]: a
 //             second instantiation gathers the 16 bounds of a lane once per pair and keeps them packed in registers.
 //   assemble: per chunk the smaller of header + step plane + EXAC v2 of the indices and header + EXAC v2 of the
-//             voxels, offsets by scan, everything copied 16 bytes at a time
+//             voxels, offsets by scan, everything copied 16 bytes at a time: the kernels are bq_assemble's
+//             (bounded_pairs.h), this file states the format's policy (EbPolicy)
 //   decode:   one wave per chunk validates offsets, header and step plane and lists the chunk for the EXAC decoder
 //             of its mode; the inverse reads a step (or "verbatim") per block from the validated plane
 #include "bounded_pairs.h"
@@ -25,22 +26,6 @@ namespace {
 
 constexpr uint32_t BB_VERBATIM = 0xFEu, BB_OUTSIDE = 0xFFu;
 constexpr uint32_t BB_MAGIC = 'E' | ('B' << 8) | (1u << 16);       // magic, version 1; the mode is the fourth byte
-
-struct PairAt {
-    int lz, ly, lxa, lxb;       // block coordinates inside the chunk's nominal grid; lxb == lxa: no second block
-    int blka, blkb;             // raster index in that grid
-};
-__device__ __forceinline__ PairAt pair_at(const BoundedGeom& g, int p, int pairs_x, int rows_y, int last_x) {
-    const int px = p % pairs_x, t = p / pairs_x;
-    PairAt a;
-    a.ly = t % rows_y;
-    a.lz = t / rows_y;
-    a.lxa = 2 * px;
-    a.lxb = min(2 * px + 1, last_x);
-    a.blka = (a.lz * g.cby + a.ly) * g.cbx + a.lxa;
-    a.blkb = (a.lz * g.cby + a.ly) * g.cbx + a.lxb;
-    return a;
-}
 
 // what bounds a voxel: max_error / fg_max_error, and with TABLE a device table of 65536 bounds indexed by its value
 template <bool TABLE>
@@ -207,66 +192,21 @@ bb_select_kernel(const uint16_t* __restrict__ vol, const uint8_t* __restrict__ m
     }
 }
 
-// mode 1 iff its stream (header, plane, indices) is strictly shorter than the mode-0 one (header, voxels)
-__device__ __forceinline__ bool take_blocks(uint32_t nbp, const uint32_t* lossy_sz, const uint32_t* lossless_sz,
-                                            int c) {
-    return (unsigned long long)nbp + lossy_sz[c] < (unsigned long long)lossless_sz[c];
-}
-
-__global__ __launch_bounds__(256) void bb_sizes_kernel(int nchunks, uint32_t nbp, const uint32_t* __restrict__ lossy_sz,
-                                                       const uint32_t* __restrict__ lossless_sz,
-                                                       uint32_t* __restrict__ sizes) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= nchunks) return;
-    sizes[c] = (uint32_t)BQ_HEADER + (take_blocks(nbp, lossy_sz, lossless_sz, c) ? nbp + lossy_sz[c] : lossless_sz[c]);
-}
-
-__device__ __forceinline__ void chunk_extent(const BoundedGeom& g, int c, uint32_t& ez, uint32_t& ey, uint32_t& ex) {
-    const int kx = c % g.gx, ky = (c / g.gx) % g.gy, kz = c / (g.gx * g.gy);
-    ez = (uint32_t)min(g.cz, g.nz - kz * g.cz);
-    ey = (uint32_t)min(g.cy, g.ny - ky * g.cy);
-    ex = (uint32_t)min(g.cx, g.nx - kx * g.cx);
-}
-
-// one workgroup per chunk: header, (mode 1) the padded step plane, then the chosen payload; all 16-byte aligned in
-// source and destination, and the source container's zero padding becomes the stream's
-__global__ __launch_bounds__(256) void bb_copy_kernel(BoundedGeom g, uint32_t nbp, const uint8_t* __restrict__ plane,
-                                                      const uint8_t* __restrict__ lossy,
-                                                      const unsigned long long* __restrict__ lossy_off,
-                                                      const uint32_t* __restrict__ lossy_sz,
-                                                      const uint8_t* __restrict__ lossless,
-                                                      const unsigned long long* __restrict__ lossless_off,
-                                                      const uint32_t* __restrict__ lossless_sz,
-                                                      const unsigned long long* __restrict__ offsets,
-                                                      uint8_t* __restrict__ out) {
-    const int c = blockIdx.x;
-    const bool lz = take_blocks(nbp, lossy_sz, lossless_sz, c);
-    uint4* dst = reinterpret_cast<uint4*>(out + offsets[c]);
-    if (threadIdx.x == 0) {
-        uint32_t ez, ey, ex;
-        chunk_extent(g, c, ez, ey, ex);
-        uint4 h0, h1;
-        h0.x = BB_MAGIC | ((lz ? 1u : 0u) << 24);
-        h0.y = 0u;
-        h0.z = 0u;
-        h0.w = ez | (ey << 16);                                            // E (u16 each)
-        h1.x = ex | ((uint32_t)g.cz << 16);                                // ..., C (u16 each)
-        h1.y = (uint32_t)g.cy | ((uint32_t)g.cx << 16);
-        h1.z = 0u;
-        h1.w = 0u;
-        dst[0] = h0;
-        dst[1] = h1;
+// the "EB" streams to bq_assemble (bounded_pairs.h): mode 1 carries the chunk's padded step plane in front of the
+// payload, and both modes two zero words in the header
+struct EbPolicy {
+    static constexpr uint32_t MAGIC = BB_MAGIC;
+    uint32_t nbp;
+    const uint8_t* plane;
+    // mode 1 iff its stream (header, plane, indices) is strictly shorter than the mode-0 one (header, voxels)
+    __device__ bool mode1(int c, const uint32_t* lossy_sz, const uint32_t* lossless_sz) const {
+        return (unsigned long long)nbp + lossy_sz[c] < (unsigned long long)lossless_sz[c];
     }
-    dst += 2;
-    if (lz) {
-        const uint4* pl = reinterpret_cast<const uint4*>(plane + (size_t)c * nbp);
-        for (uint32_t i = threadIdx.x; i < nbp / 16u; i += 256) dst[i] = pl[i];
-        dst += nbp / 16u;
-    }
-    const uint4* src = reinterpret_cast<const uint4*>(lz ? lossy + lossy_off[c] : lossless + lossless_off[c]);
-    const uint32_t n16 = ((lz ? lossy_sz[c] : lossless_sz[c]) + 15u) / 16u;
-    for (uint32_t i = threadIdx.x; i < n16; i += 256) dst[i] = src[i];
-}
+    __device__ uint32_t word_y(int, bool) const { return 0u; }
+    __device__ uint32_t word_z(int, bool) const { return 0u; }
+    __device__ uint32_t prefix_bytes() const { return nbp; }
+    __device__ const uint4* prefix(int c) const { return reinterpret_cast<const uint4*>(plane + (size_t)c * nbp); }
+};
 
 // one wave per chunk; status |= 64 for bad offsets, 32 for a bad header or step plane
 __global__ __launch_bounds__(64) void bb_parse_kernel(const uint8_t* __restrict__ in, size_t in_bytes,
@@ -278,18 +218,16 @@ __global__ __launch_bounds__(64) void bb_parse_kernel(const uint8_t* __restrict_
     const int c = blockIdx.x, lane = threadIdx.x;
     if (lane == 0) mode[c] = 2u;        // neither: nothing is decoded for this chunk
     const unsigned long long o0 = offsets[c], o1 = offsets[c + 1];
-    if (o0 > o1 || o1 > in_bytes || (o0 & 15ull) || o1 - o0 < (unsigned long long)BQ_HEADER) {
+    if (!bq_offsets_ok(o0, o1, in_bytes)) {
         if (lane == 0) atomicOr(status, 64u);
         return;
     }
     const uint4* h = reinterpret_cast<const uint4*>(in + o0);
     const uint4 a = h[0], b = h[1];
-    uint32_t ez, ey, ex;
-    chunk_extent(g, c, ez, ey, ex);
+    const uint3 d = bq_shape_words(g, c);
     const uint32_t md = a.x >> 24;
-    bool ok = (a.x & 0xFFFFFFu) == BB_MAGIC && md <= 1u && a.y == 0u && a.z == 0u && a.w == (ez | (ey << 16)) &&
-              b.x == (ex | ((uint32_t)g.cz << 16)) && b.y == ((uint32_t)g.cy | ((uint32_t)g.cx << 16)) &&
-              b.z == 0u && b.w == 0u;
+    bool ok = (a.x & 0xFFFFFFu) == BB_MAGIC && md <= 1u && a.y == 0u && a.z == 0u && a.w == d.x && b.x == d.y &&
+              b.y == d.z && b.z == 0u && b.w == 0u;
     ok = ok && (md == 0u || o1 - o0 >= (unsigned long long)BQ_HEADER + nbp);
     if (ok && md == 1u) {
         const BqChunkBlocks cb = bq_chunk_blocks(g, c);
@@ -311,13 +249,7 @@ __global__ __launch_bounds__(64) void bb_parse_kernel(const uint8_t* __restrict_
         if (lane == 0) atomicOr(status, 32u);
         return;
     }
-    if (lane == 0) {
-        const uint32_t k = atomicAdd(lcount + md, 1u);
-        lchunk[(size_t)md * g.nchunks + k] = (uint32_t)c;
-        lrange[2 * ((size_t)md * g.nchunks + k)] = o0 + BQ_HEADER + (md ? nbp : 0u);
-        lrange[2 * ((size_t)md * g.nchunks + k) + 1] = o1;
-        mode[c] = md;
-    }
+    if (lane == 0) bq_list_append(md, c, g.nchunks, o0 + BQ_HEADER + (md ? nbp : 0u), o1, mode, lchunk, lrange, lcount);
 }
 
 // the mode-1 chunks: every inside block at its own step, or copied; status |= 128 for a verbatim value that is no voxel
@@ -409,14 +341,8 @@ hipError_t launch_bb_assemble(const BoundedGeom& g, const uint8_t* plane, const 
                               const unsigned long long* lossy_off, const uint32_t* lossy_sz, const uint8_t* lossless,
                               const unsigned long long* lossless_off, const uint32_t* lossless_sz, uint32_t* sizes,
                               unsigned long long* offsets, unsigned long long* totals, uint8_t* out, hipStream_t s) {
-    const uint32_t nbp = bb_plane_bytes(g);
-    hipLaunchKernelGGL(bb_sizes_kernel, dim3((unsigned)((g.nchunks + 255) / 256)), dim3(256), 0, s, g.nchunks, nbp,
-                       lossy_sz, lossless_sz, sizes);
-    hipError_t e = launch_codec_scan(sizes, g.nchunks, offsets, totals, s);
-    if (e != hipSuccess || !out) return e;
-    hipLaunchKernelGGL(bb_copy_kernel, dim3((unsigned)g.nchunks), dim3(256), 0, s, g, nbp, plane, lossy, lossy_off,
-                       lossy_sz, lossless, lossless_off, lossless_sz, offsets, out);
-    return hipGetLastError();
+    return bq_assemble(g, EbPolicy{bb_plane_bytes(g), plane}, BqStreams{lossy, lossy_off, lossy_sz},
+                       BqStreams{lossless, lossless_off, lossless_sz}, sizes, offsets, totals, out, s);
 }
 
 hipError_t launch_bb_parse(const uint8_t* in, size_t in_bytes, const unsigned long long* offsets,

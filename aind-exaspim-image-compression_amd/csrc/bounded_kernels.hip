@@ -8,9 +8,10 @@
 //   select:   j* = the largest step whose error is <= the bound, per chunk
 //   forward:  indices at each chunk's own step, chunk-major: chunk c owns (nb, 8, 64) int32, zero outside the volume
 //   assemble: per chunk the smaller of the lossy candidate (EXAC v2 of its indices) and the lossless one (EXAC v2
-//             of its voxels), a 32-byte header in front, offsets by scan, payloads copied 16 bytes at a time
-//   decode:   parse + validate the headers and list the chunks of either mode (the EXAC decoder then walks each
-//             list), inverse transform of the lossy chunks at their own step
+//             of its voxels), a 32-byte header in front, offsets by scan, payloads copied 16 bytes at a time: the
+//             kernels are bq_assemble's (bounded_pairs.h), this file states the format's policy (EqPolicy)
+//   decode:   parse + validate the headers (one thread per chunk) and list the chunks of either mode (the EXAC
+//             decoder then walks each list), inverse transform of the lossy chunks at their own step
 //
 // The quantise / dequantise / inverse / clamp / round sequence is dctq_forward_kernel's followed by
 // dctq_inverse_kernel's (codec_kernels.hip), with the seven-magnitude form of the DCT chains, which is
@@ -124,55 +125,23 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void bq_forward_kernel(const uint16_
     }
 }
 
-__device__ __forceinline__ bool take_lossy(const int32_t* jsel, const uint32_t* lossy_sz, const uint32_t* lossless_sz,
-                                           int c) {
-    return jsel[c] >= 0 && lossy_sz[c] < lossless_sz[c];        // a tie goes to the lossless stream
-}
+constexpr uint32_t BQ_MAGIC = 'E' | ('Q' << 8) | (1u << 16);       // magic, version 1; the mode is the fourth byte
 
-__global__ __launch_bounds__(256) void bq_sizes_kernel(int nchunks, const int32_t* __restrict__ jsel,
-                                                       const uint32_t* __restrict__ lossy_sz,
-                                                       const uint32_t* __restrict__ lossless_sz,
-                                                       uint32_t* __restrict__ sizes) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= nchunks) return;
-    sizes[c] = (uint32_t)BQ_HEADER + (take_lossy(jsel, lossy_sz, lossless_sz, c) ? lossy_sz[c] : lossless_sz[c]);
-}
-
-// one workgroup per chunk: header, then the chosen payload (16-byte aligned in source and destination; the
-// source container's zero padding becomes the stream's)
-__global__ __launch_bounds__(256) void bq_copy_kernel(BoundedGeom g, const int32_t* __restrict__ jsel,
-                                                      const float* __restrict__ qsel,
-                                                      const uint8_t* __restrict__ lossy,
-                                                      const unsigned long long* __restrict__ lossy_off,
-                                                      const uint32_t* __restrict__ lossy_sz,
-                                                      const uint8_t* __restrict__ lossless,
-                                                      const unsigned long long* __restrict__ lossless_off,
-                                                      const uint32_t* __restrict__ lossless_sz,
-                                                      const unsigned long long* __restrict__ offsets,
-                                                      uint8_t* __restrict__ out) {
-    const int c = blockIdx.x;
-    const bool lz = take_lossy(jsel, lossy_sz, lossless_sz, c);
-    uint4* dst = reinterpret_cast<uint4*>(out + offsets[c]);
-    if (threadIdx.x == 0) {
-        const int kx = c % g.gx, ky = (c / g.gx) % g.gy, kz = c / (g.gx * g.gy);
-        const uint32_t ez = (uint32_t)min(g.cz, g.nz - kz * g.cz), ey = (uint32_t)min(g.cy, g.ny - ky * g.cy),
-                       ex = (uint32_t)min(g.cx, g.nx - kx * g.cx);
-        uint4 h0, h1;
-        h0.x = 'E' | ('Q' << 8) | (1u << 16) | ((lz ? 1u : 0u) << 24);    // magic, version 1, mode
-        h0.y = lz ? (uint32_t)jsel[c] : 0xFFu;                             // j*, three zero bytes
-        h0.z = lz ? __float_as_uint(qsel[c]) : 0u;                         // q (float32 bits)
-        h0.w = ez | (ey << 16);                                            // E (u16 each)
-        h1.x = ex | ((uint32_t)g.cz << 16);                                // ..., C (u16 each)
-        h1.y = (uint32_t)g.cy | ((uint32_t)g.cx << 16);
-        h1.z = 0u;
-        h1.w = 0u;
-        dst[0] = h0;
-        dst[1] = h1;
+// the "EQ" streams to bq_assemble (bounded_pairs.h): mode 1 carries j* and q in the header and nothing in front of
+// the payload
+struct EqPolicy {
+    static constexpr uint32_t MAGIC = BQ_MAGIC;
+    const int32_t* jsel;
+    const float* qsel;
+    __device__ bool mode1(int c, const uint32_t* lossy_sz, const uint32_t* lossless_sz) const {
+        return jsel[c] >= 0 && lossy_sz[c] < lossless_sz[c];        // a tie goes to the lossless stream
     }
-    const uint4* src = reinterpret_cast<const uint4*>(lz ? lossy + lossy_off[c] : lossless + lossless_off[c]);
-    const uint32_t n16 = ((lz ? lossy_sz[c] : lossless_sz[c]) + 15u) / 16u;
-    for (uint32_t i = threadIdx.x; i < n16; i += 256) dst[2 + i] = src[i];
-}
+    // j* and three zero bytes, then q (float32 bits)
+    __device__ uint32_t word_y(int c, bool lz) const { return lz ? (uint32_t)jsel[c] : 0xFFu; }
+    __device__ uint32_t word_z(int c, bool lz) const { return lz ? __float_as_uint(qsel[c]) : 0u; }
+    __device__ uint32_t prefix_bytes() const { return 0u; }
+    __device__ const uint4* prefix(int) const { return nullptr; }
+};
 
 __global__ __launch_bounds__(256) void bq_parse_kernel(const uint8_t* __restrict__ in, size_t in_bytes,
                                                        const unsigned long long* __restrict__ offsets, BoundedGeom g,
@@ -185,34 +154,27 @@ __global__ __launch_bounds__(256) void bq_parse_kernel(const uint8_t* __restrict
     mode[c] = 2u;                       // neither: nothing is decoded for this chunk
     qv[c] = 0.0f;
     const unsigned long long o0 = offsets[c], o1 = offsets[c + 1];
-    if (o0 > o1 || o1 > in_bytes || (o0 & 15ull) || o1 - o0 < (unsigned long long)BQ_HEADER) {
+    if (!bq_offsets_ok(o0, o1, in_bytes)) {
         atomicOr(status, 64u);
         return;
     }
     const uint4* h = reinterpret_cast<const uint4*>(in + o0);
     const uint4 a = h[0], b = h[1];
-    const int kx = c % g.gx, ky = (c / g.gx) % g.gy, kz = c / (g.gx * g.gy);
-    const uint32_t ez = (uint32_t)min(g.cz, g.nz - kz * g.cz), ey = (uint32_t)min(g.cy, g.ny - ky * g.cy),
-                   ex = (uint32_t)min(g.cx, g.nx - kx * g.cx);
+    const uint3 d = bq_shape_words(g, c);
     const uint32_t md = a.x >> 24, j = a.y & 0xFFu;
-    bool ok = (a.x & 0xFFFFFFu) == ('E' | ('Q' << 8) | (1u << 16));
+    bool ok = (a.x & 0xFFFFFFu) == BQ_MAGIC;
     if (md == 0u)
         ok = ok && j == 0xFFu && a.z == 0u;
     else if (md == 1u)
         ok = ok && j < (uint32_t)BQ_STEPS && a.z == __float_as_uint(qtab[min(j, (uint32_t)BQ_STEPS - 1u)]);
     else
         ok = false;
-    ok = ok && a.w == (ez | (ey << 16)) && b.x == (ex | ((uint32_t)g.cz << 16)) &&
-         b.y == ((uint32_t)g.cy | ((uint32_t)g.cx << 16));
+    ok = ok && a.w == d.x && b.x == d.y && b.y == d.z;
     if (!ok) {
         atomicOr(status, 32u);
         return;
     }
-    const uint32_t k = atomicAdd(lcount + md, 1u);
-    lchunk[(size_t)md * g.nchunks + k] = (uint32_t)c;
-    lrange[2 * ((size_t)md * g.nchunks + k)] = o0 + BQ_HEADER;
-    lrange[2 * ((size_t)md * g.nchunks + k) + 1] = o1;
-    mode[c] = md;
+    bq_list_append(md, c, g.nchunks, o0 + BQ_HEADER, o1, mode, lchunk, lrange, lcount);
     qv[c] = md ? __uint_as_float(a.z) : 0.0f;
 }
 
@@ -231,9 +193,8 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void bq_inverse_kernel(const int32_t
     const int pairs_x = (cb.lbx + 1) / 2, npairs = cb.lbz * cb.lby * pairs_x;
     const int32_t* base = idx + (size_t)c * g.nb * BVOX + lo * 8 + hi;
     for (int p = w; p < npairs; p += slices * BQ_WAVES) {
-        const int px = p % pairs_x, t = p / pairs_x;
-        const int ly = t % cb.lby, lz = t / cb.lby;
-        const int lxa = 2 * px, lxb = min(2 * px + 1, cb.lbx - 1);
+        const PairAt at = pair_at(g, p, pairs_x, cb.lby, cb.lbx - 1);
+        const int ly = at.ly, lz = at.lz, lxa = at.lxa, lxb = at.lxb;
         const int32_t* ia = base + ((size_t)(lz * g.cby + ly) * g.cbx + lxa) * BVOX;
         const int32_t* ib = base + ((size_t)(lz * g.cby + ly) * g.cbx + lxb) * BVOX;
         f2 v[8];
@@ -306,13 +267,8 @@ hipError_t launch_bq_assemble(const BoundedGeom& g, const int32_t* jsel, const f
                               const uint8_t* lossless, const unsigned long long* lossless_off,
                               const uint32_t* lossless_sz, uint32_t* sizes, unsigned long long* offsets,
                               unsigned long long* totals, uint8_t* out, hipStream_t s) {
-    hipLaunchKernelGGL(bq_sizes_kernel, dim3((unsigned)((g.nchunks + 255) / 256)), dim3(256), 0, s, g.nchunks, jsel,
-                       lossy_sz, lossless_sz, sizes);
-    hipError_t e = launch_codec_scan(sizes, g.nchunks, offsets, totals, s);
-    if (e != hipSuccess || !out) return e;
-    hipLaunchKernelGGL(bq_copy_kernel, dim3((unsigned)g.nchunks), dim3(256), 0, s, g, jsel, qsel, lossy, lossy_off,
-                       lossy_sz, lossless, lossless_off, lossless_sz, offsets, out);
-    return hipGetLastError();
+    return bq_assemble(g, EqPolicy{jsel, qsel}, BqStreams{lossy, lossy_off, lossy_sz},
+                       BqStreams{lossless, lossless_off, lossless_sz}, sizes, offsets, totals, out, s);
 }
 
 hipError_t launch_bq_parse(const uint8_t* in, size_t in_bytes, const unsigned long long* offsets,

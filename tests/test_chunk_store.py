@@ -58,6 +58,104 @@ def test_store_layout_and_chunk_files(tmp_path):
     assert [back.chunk_bytes(i) for i in range(27)] == blobs and not np.any(back.offsets % 16)
 
 
+# zarr.json as written for a (5, 8, 7) volume in (8, 8, 8) chunks with attributes={"sigma": 24.0}: text, so that the
+# order of the keys is pinned too.  @CODEC@: the codec's entry, below.
+_ZARR_JSON = """{
+ "zarr_format": 3,
+ "node_type": "array",
+ "shape": [
+  1,
+  1,
+  5,
+  8,
+  7
+ ],
+ "data_type": "uint16",
+ "chunk_grid": {
+  "name": "regular",
+  "configuration": {
+   "chunk_shape": [
+    1,
+    1,
+    8,
+    8,
+    8
+   ]
+  }
+ },
+ "chunk_key_encoding": {
+  "name": "default",
+  "configuration": {
+   "separator": "/"
+  }
+ },
+ "fill_value": 0,
+ "codecs": [
+  {
+@CODEC@
+  }
+ ],
+ "attributes": {
+  "sigma": 24.0,
+  "exac_note": "EXAC chunk streams (aind-exaspim-image-compression_amd, DESIGN.md 3.11b); edge chunks truncated to the array; decode with utils.chunk_codec.ExacCodec.decode or utils.chunk_store.read_zarr"
+ },
+ "dimension_names": [
+  "t",
+  "c",
+  "z",
+  "y",
+  "x"
+ ]
+}"""
+_CODEC_ENTRIES = {
+    "exac": """   "name": "exac",
+   "configuration": {
+    "version": 2,
+    "typesize": 2,
+    "edge_chunks": "truncated"
+   }""",
+    "exac-dctq": """   "name": "exac-dctq",
+   "configuration": {
+    "version": 1,
+    "max_error": 4,
+    "edge_chunks": "truncated"
+   }""",
+    "exac-dctq-block": """   "name": "exac-dctq-block",
+   "configuration": {
+    "version": 1,
+    "max_error": 8,
+    "fg_max_error": 1,
+    "edge_chunks": "truncated"
+   }""",
+    "exac-dctq-block, table": """   "name": "exac-dctq-block",
+   "configuration": {
+    "version": 1,
+    "max_error": 8,
+    "fg_max_error": 1,
+    "edge_chunks": "truncated",
+    "bound": {
+     "kind": "table",
+     "sha256": "dabea828eebfb2d4e66b8bbf343d354352b6afa6b6f52bac43d621d432a2ecdb"
+    }
+   }""",
+}
+
+
+@pytest.mark.parametrize("which", sorted(_CODEC_ENTRIES))
+def test_zarr_json_text(tmp_path, which):
+    """``write_encoded`` writes the document byte for byte, key order included, for every codec a store takes."""
+    from aind_exaspim_image_compression.utils.block_bounded_codec import BlockBoundedCodec
+    from aind_exaspim_image_compression.utils.bounded_codec import BoundedDctCodec
+    codec = {"exac": None, "exac-dctq": BoundedDctCodec(4), "exac-dctq-block": BlockBoundedCodec(8, 1),
+             "exac-dctq-block, table": BlockBoundedCodec(8, 1, bound_table=(np.arange(65536) // 4096).astype(np.uint16))
+             }[which]
+    enc = EncodedVolume(np.arange(48, dtype=np.uint8), np.array([0, 48], np.uint64), np.array([40], np.uint32),
+                        (5, 8, 7), (8, 8, 8), 2)
+    path = str(tmp_path / "v.zarr")
+    assert S.write_encoded(enc, path, attributes={"sigma": 24.0}, codec=codec) == 40
+    assert open(os.path.join(path, "zarr.json")).read() == _ZARR_JSON.replace("@CODEC@", _CODEC_ENTRIES[which])
+
+
 def test_store_reader_rejects_what_it_does_not_understand(tmp_path):
     vol = np.full((8, 8, 8), 7, np.uint16)
     enc, _ = _encoded(vol, (8, 8, 8))
