@@ -16,6 +16,9 @@
 #ifndef EXABM4D_BM_HANDWAIT
 #define EXABM4D_BM_HANDWAIT 1    // A/B build: 0 = the integer kernel's window rows and cell plane by plain loads (hipcc's waits)
 #endif
+#ifndef EXABM4D_BM_STEPADDR
+#define EXABM4D_BM_STEPADDR 1    // A/B build: 0 = the integer kernel forms every lane's 64-bit addresses anew in each step
+#endif
 
 namespace exabm4d {
 
@@ -24,6 +27,9 @@ namespace exabm4d {
 // Slots: 0 top wait, 1 wait for the cell's own plane, 2 wait in front of the window reads, 3 accumulate,
 // 4 exchange barriers, 5 selection, 6 carry waits (the poll and the tile's last drain), 7 wave lifetime.
 __device__ unsigned long long g_bm_stamps[8];
+// Slot 4 again, kept apart: [barrier of the (dz, pass): 2 round + (0 in front of / 1 behind the selection)][wave cz].
+// The wave that arrives last at a barrier waits least in it.
+__device__ unsigned long long g_bm_barrier_stamps[4][8];
 __device__ __forceinline__ unsigned long long bm_stamp() {
     unsigned long long t;
     __builtin_amdgcn_sched_barrier(0);
@@ -609,7 +615,7 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     const int ix = TRX * tx + cx, iy = TRY * ty + cy;
     const size_t sy = (size_t)g.nx, sz = (size_t)g.nx * (size_t)g.ny;
 #ifdef EXABM4D_BM_STAMPS
-    unsigned long long st[8] = {};
+    unsigned long long st[8] = {}, stb[4] = {};
     const unsigned long long tk0 = bm_stamp();
 #endif
 
@@ -661,12 +667,57 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     // would be hidden from its wait counts altogether, but it takes an asm load's destination for written when
     // the statement ends: built that way, it copied the destination registers to those of `A` ABOVE the
     // hand-placed wait, "=v" and "+v" operands alike, i.e. before the data had landed.)
-    u32x2 An[4];
-    auto load_cell_plane = [&](int step) {
+    //
+    // Step addresses (EXABM4D_BM_STEPADDR).  Which row and column a lane fetches depends on the
+    // lane, the tile and -- where staged rows clamp at a y edge -- the pass; what changes from step to step is the
+    // plane, and that is wave-uniform.  So a lane keeps 32-bit byte offsets, computed once per tile: `doff[pass][i]`
+    // for LDS-DMA chunk i, from the pass's first staged row at column X0, and `coff[y]` for its cell's four rows,
+    // from row Y0.  A step forms the plane's base in scalar registers and the loads take base + zero-extended
+    // offset (global_load_lds_dwordx4 v, s[]): the same addresses as before, without the per-chunk multiplies and
+    // 64-bit vector adds.  Rows clamp monotonically, so no offset is negative and every one is below
+    // (PROWS nx + PCOLS) 2 < 2^32 (launch_blockmatch checks).  X0 is negative in the first tile column: the base
+    // may lie before the volume -- integer arithmetic on the pointer, never dereferenced as such, and the bytes
+    // in front of the volume that a lane then does fetch are the guarded scratch's, as before.
+    // The offsets are made opaque: hipcc otherwise re-derives them from the lane id inside the step loops.
+    uint32_t doff[2][NDMA], coff[4];
+    int yb[2];                                         // a pass's first staged row, clamped
+    if (EXABM4D_BM_STEPADDR) {
+        int l = lane;
+        asm volatile("" : "+v"(l));
+#pragma unroll
+        for (int ps = 0; ps < 2; ps++) {
+            const int dylo = ps == 0 ? -RAD : 1;
+            yb[ps] = min(max(Y0 + dylo, 0), g.ny - 1);
+#pragma unroll
+            for (int i = 0; i < NDMA; i++) {
+                const unsigned p = 64u * i + (unsigned)l;
+                const unsigned r0 = (p * (65536u / PCH + 1u)) >> 16;          // p / PCH for p < 2^12
+                const unsigned r = min(r0, (unsigned)(PROWS - 1));
+                const unsigned q = min(p - r0 * PCH, (unsigned)(PCOLS / 8 - 1));
+                const int yy = min(max(Y0 + dylo + (int)r, 0), g.ny - 1);
+                doff[ps][i] = 2u * ((unsigned)(yy - yb[ps]) * (unsigned)g.nx + 8u * q);
+                asm volatile("" : "+v"(doff[ps][i]));
+            }
+        }
 #pragma unroll
         for (int y = 0; y < 4; y++) {
-            const uint32_t* ap = reinterpret_cast<const uint32_t*>(
-                vol + (size_t)(qz + (step & 3)) * sz + (size_t)(qy + y) * sy + qx);
+            coff[y] = 2u * ((unsigned)(qy - Y0 + y) * (unsigned)g.nx + (unsigned)qx);
+            asm volatile("" : "+v"(coff[y]));
+        }
+    }
+    const char* const vol_b = reinterpret_cast<const char*>(vol);
+    u32x2 An[4];
+    auto load_cell_plane = [&](int step) {
+        const char* cbase = vol_b + 2 * ((long long)(qz + (step & 3)) * (long long)sz + (long long)Y0 * (long long)sy);
+#pragma unroll
+        for (int y = 0; y < 4; y++) {
+            // (opaque again, in the step: hipcc otherwise zero-extends the offset outside the loop, into a register
+            // pair, and adds the base to it in 64 bits, where instruction selection no longer sees the scalar-base form)
+            uint32_t o = coff[y];
+            if (EXABM4D_BM_STEPADDR) asm volatile("" : "+v"(o));
+            const uint32_t* ap = EXABM4D_BM_STEPADDR
+                ? reinterpret_cast<const uint32_t*>(cbase + (size_t)o)
+                : reinterpret_cast<const uint32_t*>(vol + (size_t)(qz + (step & 3)) * sz + (size_t)(qy + y) * sy + qx);
             An[y] = u32x2{ap[0], ap[1]};
         }
     };
@@ -680,6 +731,21 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
         const int z = step & 3, pass = (step >> 2) & 1, dz = (step >> 3) - RAD;
         const int dylo = pass == 0 ? -RAD : 1;
         const int pz = min(max(Z0 + z + dz, 0), g.nz - 1);
+        if (EXABM4D_BM_STEPADDR) {
+            // row yb[pass], column X0 of plane pz
+            const int yb0 = yb[0], yb1 = yb[1];
+            const char* base = vol_b + 2 * ((long long)pz * (long long)sz +
+                                            (long long)(pass ? yb1 : yb0) * (long long)sy + X0);
+#pragma unroll
+            for (int i = 0; i < NDMA; i++) {
+                // (values, not a conditional lvalue: a select of two addresses keeps the arrays out of registers)
+                const uint32_t o0 = doff[0][i], o1 = doff[1][i];
+                __builtin_amdgcn_global_load_lds(
+                    (const __attribute__((address_space(1))) void*)(base + (size_t)(pass ? o1 : o0)),
+                    (__attribute__((address_space(3))) void*)(dst + 256 * i), 16, 0, 0);
+            }
+            return;
+        }
         const uint16_t* plane = vol + (size_t)pz * sz;
         int l = lane;
         asm volatile("" : "+v"(l));
@@ -904,6 +970,10 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
                 BM_STAMP_ADD(4, b0, b1);
                 BM_STAMP_ADD(5, b1, b2);
                 BM_STAMP_ADD(4, b2, b3);
+#ifdef EXABM4D_BM_STAMPS
+                stb[e0 ? 2 : 0] += b1 - b0;
+                stb[e0 ? 3 : 1] += b3 - b2;
+#endif
                 if (carries) {
                     // the top wave's sums are the next block's lowest layer (read there by wave 0 in
                     // this same round, i.e. before this slot is written again)
@@ -952,6 +1022,8 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     st[7] = bm_stamp() - tk0;
     if (lane == 0)
         for (int i = 0; i < 8; i++) atomicAdd(&g_bm_stamps[i], st[i]);
+    if (lane == 0)
+        for (int i = 0; i < 4; i++) atomicAdd(&g_bm_barrier_stamps[i][tid >> 6], stb[i]);
 #endif
 }
 
@@ -961,6 +1033,13 @@ extern "C" void exabm4d_debug_bm_stamps(unsigned long long* out, int reset) {
     (void)hipDeviceSynchronize();
     (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bm_stamps), sizeof(z));
     if (reset) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bm_stamps), z, sizeof(z));
+}
+// out[4][8]: cycles in each of the four barriers of a (dz, pass), per wave index
+extern "C" void exabm4d_debug_bm_barrier_stamps(unsigned long long* out, int reset) {
+    unsigned long long z[4][8] = {};
+    (void)hipDeviceSynchronize();
+    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bm_barrier_stamps), sizeof(z));
+    if (reset) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bm_barrier_stamps), z, sizeof(z));
 }
 #endif
 
@@ -1119,6 +1198,10 @@ hipError_t launch_blockmatch(const float* vol, const VolGeom& g, int batch, uint
             hipError_t e = hipMemsetAsync(carry.done, 0, (cols + 8) * sizeof(int), stream);
             if (e != hipSuccess) return e;
         }
+        // the integer kernel's lanes address a staged plane by 32-bit byte offsets from its first row (EXABM4D_BM_STEPADDR)
+        if (vol16 && EXABM4D_BM_STEPADDR &&
+            ((unsigned long long)Cube::PROWS * (unsigned long long)g.nx + 80ull) * 2ull >= (1ull << 32))
+            return hipErrorInvalidValue;
         const dim3 grid((unsigned)(p.xq ? 8 * p.xq * p.tz : p.tz * p.ty * p.tx), (unsigned)(p.xq ? 1 : batch));
         auto launch = [&](auto plan) {          // the kernel for the volume's type, in the plan's tile shape
             using Shape16 = TileShape16<decltype(plan)::TCY, decltype(plan)::TCX>;

@@ -1,6 +1,8 @@
 """Per-phase s_memtime sums of bm_tile16_kernel: python tools/dbg/bm_stamps.py LIB [SIZE] [LABEL] > stamps.json
 LIB is a library built with -DEXABM4D_BM_STAMPS (tools/dbg/build_variant.sh bmstamps -DEXABM4D_BM_STAMPS; add
--DEXABM4D_BM_HANDWAIT=0 for the form whose waits hipcc places).  One SIZE^3 uint16 launch after a warm-up launch."""
+-DEXABM4D_BM_HANDWAIT=0 for the form whose waits hipcc places, -DEXABM4D_BM_STEPADDR=0 for
+the form of before DESIGN.md 5.2r).  One SIZE^3 uint16 launch after a warm-up launch.  "barriers_by_wave": the
+exchange-barrier slot per wave index and per barrier of a (dz, pass) -- the wave that waits least arrived last."""
 import os, sys, ctypes, json, numpy as np
 os.environ["EXABM4D_LIB"] = os.path.abspath(sys.argv[1])
 R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -15,9 +17,15 @@ g = [len(nat.grid_positions(n)) for n in shape]
 k = ctx.alloc(g[0] * g[1] * g[2] * 64)
 L = ctypes.CDLL(os.environ["EXABM4D_LIB"])
 out = (ctypes.c_ulonglong * 8)()
+bar = (ctypes.c_ulonglong * 32)()
 for i in range(2):
     ctx.blockmatch_u16(d, shape, 24.0, 3.0, k); ctx.sync()
     L.exabm4d_debug_bm_stamps(out, 1)
+    L.exabm4d_debug_bm_barrier_stamps(bar, 1)
+bnames = ["round 1, in front of selection", "round 1, behind selection", "round 2, in front of selection",
+          "round 2, behind selection"]
+by_wave = {n: [round(bar[8 * b + w] / out[7], 5) for w in range(8)] for b, n in enumerate(bnames)}
+by_wave["all four"] = [round(sum(bar[8 * b + w] for b in range(4)) / out[7], 5) for w in range(8)]
 names = ["top_wait", "cell_plane_wait", "window_wait", "accumulate", "exchange_barriers", "selection", "carry_waits"]
 share = {n: round(out[i] / out[7], 4) for i, n in enumerate(names)}
 share["other"] = round(1.0 - sum(share.values()), 4)
@@ -30,4 +38,9 @@ print(json.dumps({
             "publishing sums, carry stores, prologue and table store.",
     "build": sys.argv[3] if len(sys.argv) > 3 else os.path.basename(sys.argv[1]),
     "volume": list(shape), "wave_cycles": int(out[7]), "share": share,
-    "memory_waits": round(share["top_wait"] + share["cell_plane_wait"] + share["window_wait"], 4)}, indent=1))
+    "memory_waits": round(share["top_wait"] + share["cell_plane_wait"] + share["window_wait"], 4),
+    "barriers_by_wave": {"what": "share of the summed wave lifetimes (all eight waves) spent in each barrier, by wave "
+                                 "index 0..7; a row sums to that barrier's part of exchange_barriers",
+                         **by_wave}}, indent=1))
+for n, row in by_wave.items():
+    print(f"{n:32s}" + " ".join(f"{100 * v:6.2f}" for v in row) + "   % of wave time, waves 0..7", file=sys.stderr)
