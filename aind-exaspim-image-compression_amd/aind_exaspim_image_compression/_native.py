@@ -240,6 +240,7 @@ SIGNATURES = {
                                         c_vp]),
     "exabm4d_gather_boxes_dev": (_I, [_CTX, c_vp, _SZ, c_vp, _I, c_vp, _I, c_vp, _I, _I, _I, _I, _I, _F,
                                       ctypes.c_double, c_vp]),
+    "exabm4d_scatter_boxes_dev": (_I, [_CTX, c_vp, _SZ, _I, c_vp, _I, c_vp, _SZ, _I, c_vp, _I, c_vp, _I, _F]),
 }
 
 # ``exabm4d_box_src`` (include/exabm4d.h): a decoded chunk in the pool ``Context.gather_boxes`` reads
@@ -962,6 +963,30 @@ class Context:
             self.handle, _ptr(pool), int(pool_elems), srcs.ctypes.data_as(c_vp), len(srcs),
             box_srcs.ctypes.data_as(c_vp), box_srcs.shape[1], starts.ctypes.data_as(c_vp), len(starts), bz, by, bx,
             self.DTYPES[dt], float(offset), float(fill), _ptr(out)))
+
+    # -- region writes of a chunk store -------------------------------------------
+    SCATTER_DTYPES = {np.dtype(np.uint16): 0, np.dtype(np.float32): 1, np.dtype(np.uint8): 3}
+
+    def scatter_boxes(self, src, src_elems, src_dtype, boxes, pool, pool_elems, pool_dtype, dsts, dst_boxes,
+                      offset=0.0):
+        """The gather's mirror: every voxel of every destination ``dsts[d]`` (``BOX_SRC`` records: regions of the
+        device buffer ``pool``) takes the value of the last box of ``dst_boxes[d]`` (host int32 (ndst, per_dst), -1 =
+        unused) that holds it, read from the device buffer ``src`` where ``boxes[k]`` (``BOX_SRC``) says; a voxel no
+        listed box holds stays as it is.  (``src_dtype``, ``pool_dtype``): (uint16, uint16), (uint8, uint8), or
+        (float32, uint16) = ``rint(clip(v + offset, 0, 65535))``.  The destinations must not overlap.  Checked on
+        the host (ValueError, nothing written); asynchronous on the context's stream."""
+        sdt, pdt = np.dtype(src_dtype), np.dtype(pool_dtype)
+        if sdt not in self.SCATTER_DTYPES or pdt not in self.SCATTER_DTYPES:
+            raise ValueError("scatter_boxes: elements are uint16, float32 or uint8")
+        boxes = np.ascontiguousarray(boxes, dtype=BOX_SRC).reshape(-1)
+        dsts = np.ascontiguousarray(dsts, dtype=BOX_SRC).reshape(-1)
+        dst_boxes = np.ascontiguousarray(dst_boxes, dtype=np.int32)
+        if dst_boxes.ndim != 2 or dst_boxes.shape[0] != len(dsts):
+            raise ValueError("scatter_boxes: dst_boxes must be (ndst, per_dst)")
+        self._check(lib().exabm4d_scatter_boxes_dev(
+            self.handle, _ptr(src), int(src_elems), self.SCATTER_DTYPES[sdt], boxes.ctypes.data_as(c_vp), len(boxes),
+            _ptr(pool), int(pool_elems), self.SCATTER_DTYPES[pdt], dsts.ctypes.data_as(c_vp), len(dsts),
+            dst_boxes.ctypes.data_as(c_vp), dst_boxes.shape[1], float(offset)))
 
     def close(self):
         if self.handle and os.getpid() == self.pid:

@@ -20,6 +20,7 @@ patch (scripts/precompute.py:215-228).  Three ways to run it on an 8-GPU node, s
   * ``denoise_patches(raw, sigma, devices="all")``: the whole batch split over all GPUs in one call.
 All three give the same teachers, bit for bit (every patch carries its own fixed-point unit).
 """
+import time
 from dataclasses import dataclass, asdict
 
 import numpy as np
@@ -351,3 +352,166 @@ def denoise_chunked_streamed(vol_u16, sigma=None, offset=0.0, chunk=256, halo=8,
     ctx.denoise_chunked_u16_host(vol, out, float(sigma), float(offset), chunk=int(chunk), halo=int(halo),
                                  params=prof.native(), stages=int(stages))
     return out
+
+
+def _core_runs(n, chunk, halo):
+    """Per core along an axis of ``n`` voxels: (start, extent, halo in front, halo behind), the halo cut at the
+    faces -- ``chunk_runs`` of ``csrc/api_bm4d.hip``."""
+    runs = []
+    for start in range(0, n, chunk):
+        e = min(chunk, n - start)
+        runs.append((start, e, min(halo, start), min(halo, n - (start + e))))
+    return runs
+
+
+# device bytes a core costs while its brick is in flight, per voxel of its padded window (the pipeline's scratch --
+# keys, numerator, basic estimate, corner weights, two fp32 volumes and the Wiener pair: 40 bytes -- plus the fp32 and
+# uint16 copies and the window batch in and out) and per voxel of the core (its pool and coded streams)
+_STORE_WINDOW_BYTES = 56
+_STORE_CORE_BYTES = 8
+
+
+def denoise_store(src, dst_path, sigma=None, offset=0.0, chunk=256, halo=8, profile=None, stages=2, device=None,
+                  noise=None, inverse="closed_form", codec=None, chunks=None, attributes=None, budget_bytes=4 << 30,
+                  stats=None):
+    """A stored volume in, a denoised and coded store out, without ever holding the volume: the result is
+    ``write_zarr(denoise_chunked(read_zarr(src)[0, 0], ...), dst_path, ...)``, chunk file for chunk file, for a
+    volume of any size.
+
+    ``src``: a store's path or a ``StoredArray``.  The destination is made with ``chunk_store.create_zarr``
+    (``codec``: default ``ExacCodec(2)``; ``chunks``: default the source's; ``attributes``).  The cores of the
+    chunk-local mode (``chunk``^3 voxels, read with ``halo`` voxels on each side, the window cut at
+    the volume's faces) are visited in raster order, in bricks of as many cores as fit ``budget_bytes`` of device
+    memory (at least one).  A brick's windows are read from the source per window shape
+    (``read_patches(out="device")``), every shape is denoised by one batched pipeline call -- the pipeline
+    ``denoise_chunked`` runs, on the same padded arrays -- and the cores are scattered into one pool of destination
+    chunks, coded and committed.  ``chunk`` must be a multiple of the destination's chunk shape on every axis, so that
+    every destination chunk lies in one core and none is read back.
+
+    ``sigma`` / ``offset`` / ``noise`` / ``inverse`` as in ``denoise_chunked``, except that "auto" is rejected: nothing
+    here sees the whole volume.  Measure a region instead -- ``utils.noise.estimate_sigma(arr[0, 0, z0:z1, y0:y1,
+    x0:x1])`` or ``utils.noise.estimate_poisson_gaussian`` on such a read -- and pass the result.
+
+    Returns raw bytes / stored chunk bytes, like ``write_zarr``.  ``stats`` (a dict) receives ``seconds`` per phase
+    (read, denoise, scatter, encode, files_write), ``bricks``, ``windows`` and ``largest_alloc``, the largest device
+    allocation made here (the pipeline's scratch is the context's and is not counted)."""
+    from aind_exaspim_image_compression.utils import chunk_store, store_write
+    from aind_exaspim_image_compression.utils.chunk_codec import ExacCodec
+    # -- every argument check, before a context exists
+    if isinstance(sigma, str) or isinstance(noise, str):
+        raise ValueError("denoise_store: 'auto' is not available, nothing here sees the whole volume; measure a region "
+                         "read (utils.noise.estimate_sigma / estimate_poisson_gaussian) and pass the result")
+    nz_model = _pg_noise(noise, inverse, sigma, offset)
+    chunk, halo, stages = int(chunk), int(halo), int(stages)
+    if chunk < 1 or not 0 <= halo <= 64:
+        raise ValueError("denoise_store: chunk >= 1 and 0 <= halo <= 64")
+    if stages not in (1, 2):
+        raise ValueError("denoise_store: stages must be 1 or 2")
+    if int(budget_bytes) < 1:
+        raise ValueError("denoise_store: budget_bytes must be positive")
+    arr = src if hasattr(src, "read_patches") else chunk_store.open_zarr(src, device=device)
+    shape = arr.shape[2:]
+    chunks = tuple(int(c) for c in (chunks if chunks is not None else arr.chunks))
+    if len(chunks) != 5 or chunks[:2] != (1, 1) or min(chunks) < 1:
+        raise ValueError("chunks must be (1, 1, cz, cy, cx)")
+    if any(chunk % c for c in chunks[2:]):
+        raise ValueError("denoise_store: chunk=%d is not a multiple of the destination's chunk shape %s on every "
+                         "axis" % (chunk, chunks[2:]))
+    runs = [_core_runs(n, chunk, halo) for n in shape]
+    if any(e + lo + hi < 8 for axis in runs for _, e, lo, hi in axis):
+        raise ValueError("denoise_store: a padded chunk would be thinner than one block (8)")
+    codec = codec or ExacCodec(2)
+    prof = (profile or BM4DProfile()).native()
+    sigma = None if nz_model is not None else float(np.asarray(sigma).reshape(-1)[0])
+
+    out = chunk_store.create_zarr(dst_path, shape, chunks, codec=codec, attributes=attributes, overwrite=True,
+                                  device=device)
+    # cores in raster order: (window start, window shape, core offset in the window, core start, core extent)
+    cores = []
+    for z0, ez, lz, hz in runs[0]:
+        for y0, ey, ly, hy in runs[1]:
+            for x0, ex, lx, hx in runs[2]:
+                cores.append(((z0 - lz, y0 - ly, x0 - lx), (ez + lz + hz, ey + ly + hy, ex + lx + hx), (lz, ly, lx),
+                              (z0, y0, x0), (ez, ey, ex)))
+    cost = [_STORE_WINDOW_BYTES * int(np.prod(c[1])) + _STORE_CORE_BYTES * int(np.prod(c[4])) for c in cores]
+    budget = int(budget_bytes)
+    arr_pool_cap, arr.max_pool_bytes = arr.max_pool_bytes, max(1, min(arr.max_pool_bytes, budget // 8))
+    bricks, first, held = [], 0, 0
+    for n, c in enumerate(cost):
+        if n > first and held + c > budget - budget // 8:
+            bricks.append((first, n))
+            first, held = n, 0
+        held += c
+    bricks.append((first, len(cores)))
+
+    st = store_write._new_stats()
+    seconds = {"read": 0.0, "denoise": 0.0, "scatter": 0.0, "encode": 0.0, "files_write": 0.0}
+    largest, written, windows = 0, 0, 0
+    d_table = None
+    try:
+        ctx = _native.context(device)
+        d_table = store_write.bound_table_on_device(out, ctx)
+        for b0, b1 in bricks:
+            brick = cores[b0:b1]
+            plan = store_write.plan_write(shape, chunks[2:], [c[3] for c in brick], [c[4] for c in brick],
+                                          out._nominal, exists=lambda *idx: False, max_pool_bytes=1 << 62)
+            (g,) = plan
+            if any(s != store_write.COVERED for s in g.states):
+                raise RuntimeError("denoise_store: a destination chunk is not covered by one core")
+            classes = {}
+            for k, c in enumerate(brick):
+                classes.setdefault(c[1], []).append(k)
+            pool = store_write.open_pool(out, ctx, g, st)
+            largest = max(largest, 2 * g.pool_elems)
+            try:
+                for win, members in classes.items():
+                    nvox = int(np.prod(win))
+                    t0 = time.perf_counter()
+                    d_in = arr.read_patches([brick[k][0] for k in members], win, is_center=False, out="device")
+                    d_res = None
+                    try:
+                        d_res = ctx.alloc(2 * nvox * len(members))
+                        largest = max(largest, 2 * nvox * len(members))
+                        t1 = time.perf_counter()
+                        if nz_model is not None:
+                            ctx.denoise_pg_u16(d_in, d_res, win, nz_model, params=prof, stages=stages,
+                                               batch=len(members))
+                        else:
+                            ctx.denoise_u16(d_in, d_res, win, sigma, float(offset), params=prof, stages=stages,
+                                            batch=len(members))
+                        ctx.sync()
+                        t2 = time.perf_counter()
+                        # the cores: the inner part of each window, its front offset its own
+                        rec = np.zeros(len(members), dtype=_native.BOX_SRC)
+                        remap = np.full(len(brick) + 1, -1, dtype=np.int32)      # [-1] stays -1
+                        for j, k in enumerate(members):
+                            _, _, (lz, ly, lx), org, ext = brick[k]
+                            rec[j]["base"] = j * nvox + (lz * win[1] + ly) * win[2] + lx
+                            rec[j]["stride_z"], rec[j]["stride_y"] = win[1] * win[2], win[2]
+                            rec[j]["z0"], rec[j]["y0"], rec[j]["x0"] = org
+                            rec[j]["ez"], rec[j]["ey"], rec[j]["ex"] = ext
+                            remap[k] = j
+                        store_write.scatter(ctx, g, pool, d_res, nvox * len(members), np.uint16, rec,
+                                            dst_boxes=remap[g.dst_boxes])
+                        ctx.sync()
+                        t3 = time.perf_counter()
+                    finally:
+                        d_in.free()
+                        if d_res is not None:
+                            d_res.free()
+                    seconds["read"] += t1 - t0
+                    seconds["denoise"] += t2 - t1
+                    seconds["scatter"] += t3 - t2
+                    windows += len(members)
+                written += store_write.encode_commit(out, ctx, g, pool, st, d_table)
+            finally:
+                pool.free()
+    finally:
+        arr.max_pool_bytes = arr_pool_cap
+        if d_table is not None:
+            d_table.free()
+    seconds["encode"], seconds["files_write"] = st["seconds"]["encode"], st["seconds"]["files_write"]
+    if stats is not None:
+        stats.update(seconds=seconds, bricks=len(bricks), windows=windows, largest_alloc=largest,
+                     chunks=st["chunks"], encode_calls=st["encode_calls"])
+    return 2 * int(np.prod(shape)) / written

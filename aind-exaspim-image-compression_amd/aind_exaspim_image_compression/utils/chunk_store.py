@@ -203,15 +203,50 @@ def read_chunk(path, iz, iy, ix, codec=None):
     return codec.decode(blob).reshape(ext)
 
 
-def open_zarr(path, device=None, max_pool_bytes=1 << 30):
+def open_zarr(path, device=None, max_pool_bytes=1 << 30, mode="r", codec=None):
     """Chunk store -> ``StoredArray`` (``utils/store_read.py``): the (1, 1, z, y, x) array behind
     numpy basic indexing and ``read_patches``, which decode only the chunks a read touches.  Reads ``zarr.json``
-    only.  ``max_pool_bytes``: the most decoded chunks a read keeps on the device at a time."""
+    only.  ``max_pool_bytes``: the most decoded chunks a read or a write keeps on the device at a time.
+    ``mode="r+"`` opens the array writable (``write_patches`` and item assignment); with the default
+    ``"r"`` writes raise.  ``codec``: needed only to write a block-bounded store with a bound table, which the file
+    does not hold; a codec whose ``config_entry()`` differs from the stored one raises ``ValueError``."""
     from aind_exaspim_image_compression.utils.store_read import StoredArray
-    return StoredArray(path, device=device, max_pool_bytes=max_pool_bytes)
+    return StoredArray(path, device=device, max_pool_bytes=max_pool_bytes, mode=mode, codec=codec)
+
+
+def create_zarr(path, shape, chunks=(1, 1, 64, 64, 64), codec=None, attributes=None, overwrite=False, device=None,
+                max_pool_bytes=1 << 30):
+    """An empty store -> writable ``StoredArray``: writes ``zarr.json`` only (the document ``write_zarr`` would write
+    for an array of ``shape``: (z, y, x) or (1, 1, z, y, x)) and no chunk.  Region writes fill it; a chunk without a
+    file counts as zeros for them, while reads of one keep raising.  A store built by aligned writes of a whole
+    volume is byte for byte what ``write_zarr`` makes of that volume."""
+    shape = tuple(int(s) for s in shape)
+    shape = (1,) * (5 - len(shape)) + shape
+    if len(shape) != 5 or shape[:2] != (1, 1) or min(shape) < 1:
+        raise ValueError("create_zarr stores (1, 1, z, y, x) arrays")
+    if len(chunks) != 5 or tuple(chunks[:2]) != (1, 1) or min(int(c) for c in chunks) < 1:
+        raise ValueError("chunks must be (1, 1, cz, cy, cx)")
+    codec = codec or ExacCodec(2)
+    if codec.typesize != 2:
+        raise NotImplementedError("region writes of int32 (index) stores are not implemented")
+    if os.path.exists(os.path.join(path, "zarr.json")) and not overwrite:
+        raise FileExistsError(path)
+    os.makedirs(path, exist_ok=True)
+    chunk3 = codec._chunk(shape[2:], chunks[2:])      # as an EncodedVolume states it: clamped unless nominal
+    with open(os.path.join(path, "zarr.json"), "w") as f:
+        json.dump(metadata(shape[2:], chunk3, attributes=attributes, codec=codec), f, indent=1)
+    return open_zarr(path, device=device, max_pool_bytes=max_pool_bytes, mode="r+", codec=codec)
 
 
 def _codec_of(meta):
     """The decoder a store's ``zarr.json`` names."""
     entry = meta["codecs"][0]
     return CODECS[entry["name"]].from_config(entry["configuration"])
+
+
+def _encoder_of(meta):
+    """The coder of a store's ``zarr.json``: its decoder, at the stored format version."""
+    codec = _codec_of(meta)
+    if isinstance(codec, ExacCodec):
+        codec = ExacCodec(codec.typesize, version=int(meta["codecs"][0]["configuration"].get("version", 2)))
+    return codec

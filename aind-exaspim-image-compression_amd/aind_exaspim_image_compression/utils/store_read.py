@@ -185,28 +185,69 @@ def normalize_key(key, shape):
 
 
 class StoredArray:
-    """A stored (1, 1, z, y, x) uint16 volume read by regions (``chunk_store.open_zarr``)."""
+    """A stored (1, 1, z, y, x) uint16 volume read by regions (``chunk_store.open_zarr``) and, opened with
+    ``mode="r+"`` (or made by ``chunk_store.create_zarr``), written by regions (``utils/store_write.py``)."""
 
     ndim = 5
     dtype = np.dtype(np.uint16)
 
-    def __init__(self, path, device=None, max_pool_bytes=1 << 30):
+    def __init__(self, path, device=None, max_pool_bytes=1 << 30, mode="r", codec=None):
+        if mode not in ("r", "r+"):
+            raise ValueError("StoredArray: mode is 'r' or 'r+'")
         with open(os.path.join(path, "zarr.json")) as f:
             self.meta = json.load(f)
         shape3, chunk3, typesize, self._nominal = chunk_store.check_metadata(self.meta)
         if typesize != 2:
             raise NotImplementedError("region reads of int32 (index) stores are not implemented")
+        entry = self.meta["codecs"][0]
+        if codec is not None and (not isinstance(codec, chunk_store.CODECS[entry["name"]]) or
+                                  codec.config_entry() != entry["configuration"]):
+            raise ValueError("open_zarr: the codec passed is not the one the store was written with")
         self.path = path
         self.shape = (1, 1) + shape3
         self.chunks = (1, 1) + chunk3
         self.device = device
         self.max_pool_bytes = int(max_pool_bytes)
+        self.mode = mode
         self._codec = chunk_store._codec_of(self.meta)
         self._codec.device = device
+        # the coder of a write: the stored entry's (an exac store keeps its format version), or the one passed --
+        # a block-bounded store with a bound table does not hold the table
+        self._write_codec = codec if codec is not None else chunk_store._encoder_of(self.meta)
+        if mode == "r+" and codec is None and "bound" in entry["configuration"]:
+            raise ValueError("open_zarr: a block-bounded store with a bound table is written with codec=, the "
+                             "codec that holds the table")
         self.last_read = None
+        self.last_write = None
 
     def __len__(self):
         return 1
+
+    def __setitem__(self, key, value):
+        """``arr[0, 0, z0:z1, y0:y1, x0:x1] = value`` (the indexing rules of ``normalize_key``): ``value`` is an
+        array of exactly the result shape, or a scalar; integers in 0..65535 are stored as they are, floats are
+        clipped and rounded like ``write_patches``' float32 patches."""
+        from aind_exaspim_image_compression.utils import store_write
+        store_write.setitem(self, key, value)
+
+    def write_patches(self, voxels, patches, is_center=True, offset=0.0, mask=None):
+        """Writes (N, z, y, x) ``patches`` at ``voxels`` (N, 3), placed as ``read_patches`` places them, in order:
+        where patches overlap the later one wins, as in ``for n: arr[box n] = patches[n]``; parts outside the array
+        are dropped.  ``patches``: a host uint16 array, a host float32 array (stored as ``rint(clip(v + offset, 0,
+        65535))``, computed on the device) or a ``DevicePatches`` of either type, which never visits the host.
+        ``mask`` (block-bounded stores only; the patches' shape) marks the voxels held to the codec's
+        ``fg_max_error``; without one every voxel is background.
+
+        Only the touched chunks are decoded, changed and coded again; a chunk without a file counts
+        as zeros (the fill value), and a chunk file is replaced atomically.  Boxes go into groups under
+        ``max_pool_bytes`` and nothing of a group is written before all of it has been coded.  A lossy store
+        (``exac-dctq``, ``exac-dctq-block``) takes only writes that cover every touched chunk whole -- aligned to the
+        chunk grid or the array's edge -- and raises ``ValueError`` otherwise, before anything is written.
+        ``last_write`` describes the last write that succeeded (chunks, chunk_bytes, decoded, encode_calls, groups,
+        seconds per phase) and is ``None`` after one that failed.  Concurrent writers to one chunk are undefined:
+        each reads, changes and replaces the whole chunk."""
+        from aind_exaspim_image_compression.utils import store_write
+        store_write.write_patches(self, voxels, patches, is_center=is_center, offset=offset, mask=mask)
 
     def __getitem__(self, key):
         starts, stops, shape = normalize_key(key, self.shape)

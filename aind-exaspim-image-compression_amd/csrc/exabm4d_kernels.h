@@ -384,4 +384,16 @@ hipError_t launch_gather_boxes(const uint16_t* pool, const BoxSrc* srcs, const i
                                const int32_t* starts, int nbox, int bz, int by, int bx, int out_f32, float offset,
                                float fill_f32, uint16_t fill_u16, void* out, hipStream_t s);
 
+// ---- region writes of a chunk store (region_kernels.hip) ----
+// The gather's mirror: every voxel of every destination dsts[d] (a region of `pool`) takes the value of the LAST box
+// of lists[d][0..per_dst) (-1: unused) that holds it, read from `src` where boxes[k] says; a voxel no listed box
+// holds is not written.  kind: SCATTER_U16 (uint16 -> uint16), SCATTER_F32 (fp32 -> uint16 as rint(clamp(v + offset,
+// 0, 65535))), SCATTER_U8 (bytes -> bytes).  row0[d] = the rows (ez * ey) of the destinations before d, row0[ndst] =
+// rows.  boxes, dsts, row0 and lists are device arrays; the caller has checked that every record lies inside its
+// buffer and that the destinations do not overlap.
+enum { SCATTER_U16 = 0, SCATTER_F32 = 1, SCATTER_U8 = 2 };
+hipError_t launch_scatter_boxes(const void* src, int kind, const BoxSrc* boxes, const BoxSrc* dsts,
+                                const unsigned long long* row0, int ndst, const int32_t* lists, int per_dst,
+                                unsigned long long rows, float offset, void* pool, hipStream_t s);
+
 }  // namespace exabm4d

@@ -1,5 +1,6 @@
-// region_kernels.hip -- boxes gathered from a pool of decoded chunks: the read side of the chunk
-// store.  A copy kernel: every output element is written once, every pool element a box covers is read once.
+// region_kernels.hip -- boxes gathered from a pool of decoded chunks, the read side of the chunk
+// store, and boxes scattered into such a pool, its write side.  Copy kernels: every output element
+// is written at most once, every element a box covers is read once.
 #include "exabm4d_kernels.h"
 
 namespace exabm4d {
@@ -99,7 +100,134 @@ __global__ __launch_bounds__(RG_THREADS) void gather_boxes_kernel(
     }
 }
 
+// ---- the write side: boxes scattered into the pool -------------------------------------------
+// One element pairing of the scatter: source element S, pool element T, how one becomes the other.
+struct CopyU16 {
+    using S = uint16_t;
+    using T = uint16_t;
+    __device__ T conv(S v) const { return v; }
+};
+struct CopyU8 {
+    using S = uint8_t;
+    using T = uint8_t;
+    __device__ T conv(S v) const { return v; }
+};
+struct CountsF32 {
+    using S = float;
+    using T = uint16_t;
+    float offset;
+    // one IEEE addition, np.clip, np.rint (ties to even), astype(uint16): exabm4d_normalize_u16_dev's tail.  fmaxf
+    // returns its other operand for a NaN, so a NaN becomes 0.
+    __device__ T conv(S v) const { return (uint16_t)rintf(fminf(fmaxf(v + offset, 0.0f), 65535.0f)); }
+};
+
+// Two neighbouring elements as one load or store of twice the width.
+template <typename E>
+struct alignas(2 * sizeof(E)) Two {
+    E a, b;
+};
+
+// `len` elements of a row segment, lanes along x; `o` and `s` are wave-uniform, so every branch on their alignment
+// is too.  Elements go out in pairs where the pool address allows a store of twice the width; a source pair is
+// one load of twice the width where the source address allows that, else two loads.  Every element of
+// [o, o + len) is written by exactly one lane and nothing else is.
+template <typename C>
+__device__ inline void copy_segment(const C& c, typename C::T* o, const typename C::S* s, int len, int lane) {
+    using S = typename C::S;
+    using T = typename C::T;
+    const int head = (int)(((uintptr_t)o / sizeof(T)) & 1);           // o is aligned to sizeof(T)
+    if (head && lane == 0) o[0] = c.conv(s[0]);
+    const int pairs = (len - head) >> 1;
+    Two<T>* o2 = reinterpret_cast<Two<T>*>(o + head);
+    const S* s1 = s + head;
+    if ((((uintptr_t)s1 / sizeof(S)) & 1) == 0) {
+        const Two<S>* s2 = reinterpret_cast<const Two<S>*>(s1);
+        for (int i = lane; i < pairs; i += 64) {
+            const Two<S> v = s2[i];
+            o2[i] = Two<T>{c.conv(v.a), c.conv(v.b)};
+        }
+    } else {
+        for (int i = lane; i < pairs; i += 64) o2[i] = Two<T>{c.conv(s1[2 * i]), c.conv(s1[2 * i + 1])};
+    }
+    const int done = head + 2 * pairs;
+    if (done < len && lane == 63) o[done] = c.conv(s[done]);
+}
+
+// One wave per destination row (destination d, plane z, row y); d is found in row0 by bisection.  The wave walks the
+// row in segments: at x it scans the destination's box list from the last entry to the first for the first box that
+// holds the voxel; the segment ends where that box ends, where a box scanned before it begins (it wins there), or
+// -- with no box, when nothing is written -- where the next one begins.  All of that is wave-uniform (scalar loads
+// and branches); only copy_segment() uses the lanes.
+template <typename C>
+__global__ __launch_bounds__(RG_THREADS) void scatter_boxes_kernel(
+        const typename C::S* __restrict__ src, const BoxSrc* __restrict__ boxes, const BoxSrc* __restrict__ dsts,
+        const unsigned long long* __restrict__ row0, int ndst, const int32_t* __restrict__ lists, int per_dst,
+        unsigned long long rows, C c, typename C::T* __restrict__ pool) {
+    const int lane = threadIdx.x & 63;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const unsigned long long stride = (unsigned long long)gridDim.x * RG_WAVES;
+    for (unsigned long long r = (unsigned long long)blockIdx.x * RG_WAVES + wave; r < rows; r += stride) {
+        int lo = 0, hi = ndst - 1;                                    // the last d with row0[d] <= r
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (row0[mid] <= r) lo = mid; else hi = mid - 1;
+        }
+        const BoxSrc& d = dsts[lo];
+        const unsigned rem = (unsigned)(r - row0[lo]);
+        const unsigned z = rem / (unsigned)d.ey, y = rem % (unsigned)d.ey;
+        const long long pz = (long long)d.z0 + z, py = (long long)d.y0 + y;
+        const int32_t* list = lists + (unsigned long long)lo * per_dst;
+        typename C::T* orow = pool + d.base + (unsigned long long)z * d.stride_z + (unsigned long long)y * d.stride_y;
+        const int ex = d.ex;
+        int x = 0;
+        while (x < ex) {
+            const long long px = (long long)d.x0 + x;
+            int len = ex - x;
+            const typename C::S* s = nullptr;
+            for (int j = per_dst - 1; j >= 0; j--) {
+                const int k = list[j];
+                if (k < 0) continue;
+                const BoxSrc& b = boxes[k];
+                if (pz < b.z0 || pz >= (long long)b.z0 + b.ez || py < b.y0 || py >= (long long)b.y0 + b.ey) continue;
+                const long long x0 = b.x0, x1 = x0 + b.ex;
+                if (px >= x0 && px < x1) {
+                    if (x1 - px < len) len = (int)(x1 - px);
+                    s = src + b.base + (unsigned long long)(pz - b.z0) * b.stride_z +
+                        (unsigned long long)(py - b.y0) * b.stride_y + (unsigned long long)(px - x0);
+                    break;
+                }
+                if (x0 > px && x0 - px < len) len = (int)(x0 - px);
+            }
+            if (s) copy_segment(c, orow + x, s, len, lane);
+            x += len;
+        }
+    }
+}
+
+template <typename C>
+static hipError_t scatter_launch(const void* src, const BoxSrc* boxes, const BoxSrc* dsts,
+                                 const unsigned long long* row0, int ndst, const int32_t* lists, int per_dst,
+                                 unsigned long long rows, C c, void* pool, hipStream_t s) {
+    const unsigned long long want = (rows + RG_WAVES - 1) / RG_WAVES;
+    const unsigned grid = (unsigned)(want < 8192 ? want : 8192);
+    hipLaunchKernelGGL(scatter_boxes_kernel<C>, dim3(grid), dim3(RG_THREADS), 0, s,
+                       static_cast<const typename C::S*>(src), boxes, dsts, row0, ndst, lists, per_dst, rows, c,
+                       static_cast<typename C::T*>(pool));
+    return hipGetLastError();
+}
+
 }  // namespace
+
+hipError_t launch_scatter_boxes(const void* src, int kind, const BoxSrc* boxes, const BoxSrc* dsts,
+                                const unsigned long long* row0, int ndst, const int32_t* lists, int per_dst,
+                                unsigned long long rows, float offset, void* pool, hipStream_t s) {
+    if (rows == 0 || ndst == 0) return hipSuccess;
+    if (kind == SCATTER_F32)
+        return scatter_launch(src, boxes, dsts, row0, ndst, lists, per_dst, rows, CountsF32{offset}, pool, s);
+    if (kind == SCATTER_U8)
+        return scatter_launch(src, boxes, dsts, row0, ndst, lists, per_dst, rows, CopyU8{}, pool, s);
+    return scatter_launch(src, boxes, dsts, row0, ndst, lists, per_dst, rows, CopyU16{}, pool, s);
+}
 
 hipError_t launch_gather_boxes(const uint16_t* pool, const BoxSrc* srcs, const int32_t* lists, int per_box,
                                const int32_t* starts, int nbox, int bz, int by, int bx, int out_f32, float offset,

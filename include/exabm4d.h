@@ -916,6 +916,38 @@ int exabm4d_gather_boxes_dev(exabm4d_ctx* ctx, const uint16_t* pool, size_t pool
                              const int32_t* starts_host, int nbox, int bz, int by, int bx, int out_dtype,
                              float offset, double fill, void* out);
 
+/* ---- region writes of a chunk store: boxes scattered into decoded chunks -------------
+ * The mirror of exabm4d_gather_boxes_dev; both sides are exabm4d_box_src records.  boxes_host[nbox] say where each
+ * source box lies in src (device, src_elems elements of src_dtype, only read: base and strides in elements of src)
+ * and where it belongs in the array (origin, extent).  A record describes the written part only: the core of a
+ * padded window is a record whose base points inside the window and whose strides are the window's.
+ * dsts_host[ndst] are regions of pool (device, pool_elems elements of pool_dtype) -- the decoded chunks of a
+ * store, as the read planner lays them out -- and dst_boxes_host[d][0 .. per_dst) lists, per destination, the boxes
+ * that may touch it (indices into boxes_host, -1 = unused).  For every destination d and every voxel p of its
+ * extent the listed boxes are scanned from the last entry to the first, and the first box that contains p supplies
+ * the value: pool[d.base + (pz - d.z0) d.stride_z + (py - d.y0) d.stride_y + (px - d.x0)] <- src[b.base + (pz -
+ * b.z0) b.stride_z + (py - b.y0) b.stride_y + (px - b.x0)].  Where no listed box contains p the pool element is not
+ * written.  With lists in ascending box order this is numpy's `for n: arr[box n] = v[n]`.
+ * (src_dtype, pool_dtype) is one of: (EXABM4D_DT_U16, EXABM4D_DT_U16), a copy; (EXABM4D_DT_F32, EXABM4D_DT_U16),
+ * uint16(rint(clamp((float)v + offset, 0, 65535))) -- one IEEE addition, ties to even, NaN gives 0: the tail of
+ * exabm4d_normalize_u16_dev and the inverse of the gather's fp32 output; (EXABM4D_DT_U8, EXABM4D_DT_U8), a copy
+ * (a mask pool).  offset is used by the fp32 form only.
+ * The destinations must not overlap in the pool: that is the caller's contract (the store planner's chunks never
+ * do) and it is not checked.  Then every pool element is written at most once, by one thread, so overlapping boxes
+ * need no atomics and the result is deterministic.  src and pool must not overlap.
+ * The tables are host arrays.  Everything else is checked on the host before anything is launched -- every box
+ * inside [0, src_elems), every destination inside [0, pool_elems), extents >= 1, list entries in [-1, nbox), nbox,
+ * ndst, per_dst >= 0, ez * ey < 2^31 per destination, ndst * per_dst <= 2^31, src and pool at multiples of their
+ * element sizes, the dtype pair one of the three -- and a failure gives EXABM4D_ERR_INVALID with nothing written.
+ * The tables are copied into the context's memory, the kernel is launched on the context's stream, and the call
+ * does not synchronise (the host tables may be released on return); ndst == 0 or nbox == 0 succeeds without a
+ * launch. */
+#define EXABM4D_DT_U8 3               /* bytes: the scatter's mask form only */
+int exabm4d_scatter_boxes_dev(exabm4d_ctx* ctx, const void* src, size_t src_elems, int src_dtype,
+                              const exabm4d_box_src* boxes_host, int nbox, void* pool, size_t pool_elems,
+                              int pool_dtype, const exabm4d_box_src* dsts_host, int ndst,
+                              const int32_t* dst_boxes_host, int per_dst, float offset);
+
 #ifdef __cplusplus
 }
 #endif
