@@ -10,15 +10,12 @@
 // bm_tile_kernel exploits: one lane owns one cell, cell sums go through LDS, one lane owns one
 // reference block's running top-16 list.
 #include "exabm4d_kernels.h"
+#ifdef EXABM4D_BM_STAMPS
+#define KERNEL_STAMPS
+#endif
+#include "kernel_stamps.h"
 #include <type_traits>
 #include <utility>
-
-#ifndef EXABM4D_BM_HANDWAIT
-#define EXABM4D_BM_HANDWAIT 1    // A/B build: 0 = the integer kernel's window rows and cell plane by plain loads (hipcc's waits)
-#endif
-#ifndef EXABM4D_BM_STEPADDR
-#define EXABM4D_BM_STEPADDR 1    // A/B build: 0 = the integer kernel forms every lane's 64-bit addresses anew in each step
-#endif
 
 namespace exabm4d {
 
@@ -30,18 +27,6 @@ __device__ unsigned long long g_bm_stamps[8];
 // Slot 4 again, kept apart: [barrier of the (dz, pass): 2 round + (0 in front of / 1 behind the selection)][wave cz].
 // The wave that arrives last at a barrier waits least in it.
 __device__ unsigned long long g_bm_barrier_stamps[4][8];
-__device__ __forceinline__ unsigned long long bm_stamp() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define BM_STAMP(var) const unsigned long long var = bm_stamp()
-#define BM_STAMP_ADD(i, a, b) st[i] += (b) - (a)
-#else
-#define BM_STAMP(var)
-#define BM_STAMP_ADD(i, a, b)
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -578,7 +563,6 @@ __global__ __launch_bounds__(512) void bm_tile_kernel(const float* __restrict__ 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef u32x4 u32x4a8 __attribute__((aligned(8)));
 template <int TCY_, int TCX_>
 struct TileShape16 : TilePlan<TCY_, TCX_> {
     using Plan = TilePlan<TCY_, TCX_>;
@@ -616,7 +600,7 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     const size_t sy = (size_t)g.nx, sz = (size_t)g.nx * (size_t)g.ny;
 #ifdef EXABM4D_BM_STAMPS
     unsigned long long st[8] = {}, stb[4] = {};
-    const unsigned long long tk0 = bm_stamp();
+    const unsigned long long tk0 = stamp();
 #endif
 
     // cell layers a tile advances by (CARRY above); this tile's column and its two carry slots
@@ -637,7 +621,6 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
 #pragma unroll
     for (int d = 0; d < SWIN; d++)
         xmask |= ((rx + d - RAD >= 0) && (rx + d - RAD <= g.nx - BLK)) ? (1u << d) : 0u;
-    const bool yin = (Y0 - RAD >= 0) && (Y0 + 1 + PROWS - 1 <= g.ny - 1);
 
     do {   // once; `break` = an idle wave skips the tile's work, not the barriers and the tail below
     const int L = Ls + cz;                             // this wave's cell layer
@@ -649,10 +632,10 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     const bool carries = carry.on && cz == TCZ - 1 && L + 1 <= g.az;   // ... and this wave's sums are the next tile's
     const bool ref_ok = ref_yx && active && (cz > 0 || lower_carried);
     {
-        BM_STAMP(c0);
+        STAMP(c0);
         if ((lower_carried || carries) && tz > 0) carry_wait_for(done_col, tz, lane, carry);
-        BM_STAMP(c1);
-        BM_STAMP_ADD(6, c0, c1);
+        STAMP(c1);
+        STAMP_ADD(6, c0, c1);
     }
     const int rz = STEP * iz;
 
@@ -668,7 +651,7 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     // the statement ends: built that way, it copied the destination registers to those of `A` ABOVE the
     // hand-placed wait, "=v" and "+v" operands alike, i.e. before the data had landed.)
     //
-    // Step addresses (EXABM4D_BM_STEPADDR).  Which row and column a lane fetches depends on the
+    // Step addresses.  Which row and column a lane fetches depends on the
     // lane, the tile and -- where staged rows clamp at a y edge -- the pass; what changes from step to step is the
     // plane, and that is wave-uniform.  So a lane keeps 32-bit byte offsets, computed once per tile: `doff[pass][i]`
     // for LDS-DMA chunk i, from the pass's first staged row at column X0, and `coff[y]` for its cell's four rows,
@@ -681,7 +664,7 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     // The offsets are made opaque: hipcc otherwise re-derives them from the lane id inside the step loops.
     uint32_t doff[2][NDMA], coff[4];
     int yb[2];                                         // a pass's first staged row, clamped
-    if (EXABM4D_BM_STEPADDR) {
+    {
         int l = lane;
         asm volatile("" : "+v"(l));
 #pragma unroll
@@ -714,10 +697,8 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
             // (opaque again, in the step: hipcc otherwise zero-extends the offset outside the loop, into a register
             // pair, and adds the base to it in 64 bits, where instruction selection no longer sees the scalar-base form)
             uint32_t o = coff[y];
-            if (EXABM4D_BM_STEPADDR) asm volatile("" : "+v"(o));
-            const uint32_t* ap = EXABM4D_BM_STEPADDR
-                ? reinterpret_cast<const uint32_t*>(cbase + (size_t)o)
-                : reinterpret_cast<const uint32_t*>(vol + (size_t)(qz + (step & 3)) * sz + (size_t)(qy + y) * sy + qx);
+            asm volatile("" : "+v"(o));
+            const uint32_t* ap = reinterpret_cast<const uint32_t*>(cbase + (size_t)o);
             An[y] = u32x2{ap[0], ap[1]};
         }
     };
@@ -729,36 +710,17 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     auto pbuf = [&](int w, int b) { return (lds_u32*)&pbuf_all[w][b][0]; };
     auto issue_dma = [&](int step, lds_u32* dst) {
         const int z = step & 3, pass = (step >> 2) & 1, dz = (step >> 3) - RAD;
-        const int dylo = pass == 0 ? -RAD : 1;
         const int pz = min(max(Z0 + z + dz, 0), g.nz - 1);
-        if (EXABM4D_BM_STEPADDR) {
-            // row yb[pass], column X0 of plane pz
-            const int yb0 = yb[0], yb1 = yb[1];
-            const char* base = vol_b + 2 * ((long long)pz * (long long)sz +
-                                            (long long)(pass ? yb1 : yb0) * (long long)sy + X0);
-#pragma unroll
-            for (int i = 0; i < NDMA; i++) {
-                // (values, not a conditional lvalue: a select of two addresses keeps the arrays out of registers)
-                const uint32_t o0 = doff[0][i], o1 = doff[1][i];
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) void*)(base + (size_t)(pass ? o1 : o0)),
-                    (__attribute__((address_space(3))) void*)(dst + 256 * i), 16, 0, 0);
-            }
-            return;
-        }
-        const uint16_t* plane = vol + (size_t)pz * sz;
-        int l = lane;
-        asm volatile("" : "+v"(l));
+        // row yb[pass], column X0 of plane pz
+        const int yb0 = yb[0], yb1 = yb[1];
+        const char* base = vol_b + 2 * ((long long)pz * (long long)sz +
+                                        (long long)(pass ? yb1 : yb0) * (long long)sy + X0);
 #pragma unroll
         for (int i = 0; i < NDMA; i++) {
-            const unsigned p = 64u * i + (unsigned)l;
-            const unsigned r0 = (p * (65536u / PCH + 1u)) >> 16;          // p / PCH for p < 2^12
-            const unsigned r = min(r0, (unsigned)(PROWS - 1));
-            const unsigned q = min(p - r0 * PCH, (unsigned)(PCOLS / 8 - 1));
-            const int yy = yin ? Y0 + dylo + (int)r : min(max(Y0 + dylo + (int)r, 0), g.ny - 1);
-            const uint16_t* src = plane + (ptrdiff_t)yy * (ptrdiff_t)sy + (X0 + 8 * (int)q);
+            // (values, not a conditional lvalue: a select of two addresses keeps the arrays out of registers)
+            const uint32_t o0 = doff[0][i], o1 = doff[1][i];
             __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void*)src,
+                (const __attribute__((address_space(1))) void*)(base + (size_t)(pass ? o1 : o0)),
                 (__attribute__((address_space(3))) void*)(dst + 256 * i), 16, 0, 0);
         }
     };
@@ -770,12 +732,10 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
         break;
     }
     issue_dma(0, pbuf(cz, 0));
-    if (EXABM4D_BM_HANDWAIT) {
-        // the first step's cell plane, used (= waited for by hipcc) here: left pending into the loop, it would make
-        // hipcc wait vmcnt(0) at the first use of `An` in every step, behind the DMA of the next plane
-        load_cell_plane(0);
-        asm volatile("" ::"v"(An[0]), "v"(An[1]), "v"(An[2]), "v"(An[3]));
-    }
+    // the first step's cell plane, used (= waited for by hipcc) here: left pending into the loop, it would make
+    // hipcc wait vmcnt(0) at the first use of `An` in every step, behind the DMA of the next plane
+    load_cell_plane(0);
+    asm volatile("" ::"v"(An[0]), "v"(An[1]), "v"(An[2]), "v"(An[3]));
 
     int acc[NE][SWIN];
 #pragma unroll
@@ -794,7 +754,7 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
         lds_u32* cur = pbuf(cz, step & 1);
         lds_u32* nxt = pbuf(cz, (step + 1) & 1);
 
-        // The waits of a step (EXABM4D_BM_HANDWAIT).  The window rows are read by inline asm, which hipcc leaves
+        // The waits of a step.  The window rows are read by inline asm, which hipcc leaves
         // out of its wait counts; so none of its own waits falls between the issue of plane step + 1 and the end
         // of the accumulate block.  With plain window reads it waited vmcnt(0) in front of the first one -- an
         // LDS-DMA is a pending LDS write to it, `cur` or `nxt` alike -- i.e. for the plane it had just requested,
@@ -809,58 +769,44 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
         // step - 1's last barrier.  The z == 3 exchange needs no change: it aliases `cur` and reads the
         // neighbour's `cur` behind its own barriers, with plain LDS accesses, in front of which hipcc (and
         // __syncthreads()) still drains the DMA into `nxt` -- by then it has had the accumulate block to land.
-        BM_STAMP(t0);
+        STAMP(t0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        BM_STAMP(t1);
-        if (!EXABM4D_BM_HANDWAIT) {
-            load_cell_plane(step);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        STAMP(t1);
+        // (no code: names `load_cell_plane` ahead of `An`.  This lambda's captures are laid out in the order of their
+        // first use, and the order of hipcc's four register copies of `An` at the loop boundaries follows the layout.)
+        (void)load_cell_plane;
         const u32x2 A[4] = {An[0], An[1], An[2], An[3]};
-#ifdef EXABM4D_BM_STAMPS
-        if (!EXABM4D_BM_HANDWAIT) asm volatile("" ::"v"(A[0]), "v"(A[1]), "v"(A[2]), "v"(A[3]));
-#endif
-        BM_STAMP(t2);
+        STAMP(t2);
         if (step + 1 < NSTEP) issue_dma(step + 1, nxt);
         if (lower_carried && z == 2)
             carry_prefetch(carry_rd + (size_t)(step >> 2) * 2 * CARRY_ROUND, (lds_u32*)&lower0[0], lane);
-        if (EXABM4D_BM_HANDWAIT) {
-            // the next step's cell plane, behind the DMA: retired with it at the top of the next step
-            if (step + 1 < NSTEP) load_cell_plane(step + 1);
-            asm volatile("" ::: "memory");
-        }
-        BM_STAMP(t3);
+        // the next step's cell plane, behind the DMA: retired with it at the top of the next step
+        if (step + 1 < NSTEP) load_cell_plane(step + 1);
+        asm volatile("" ::: "memory");
+        STAMP(t3);
 
         {
             const lds_u32* wrow_l = cur + ((4 * cy) * PSTR + 4 * cx) / 2;      // dword index
             const uint32_t wrow_lds = (uint32_t)(uintptr_t)wrow_l;
-            [[maybe_unused]] const uint32_t* wrow = (const uint32_t*)wrow_l;
             // staged columns 0..7 / 8..15 of window row r (32 bytes, 8-byte aligned): two ds_read2_b64
             auto read_row = [&](auto rc, u32x4& lo, u32x4& hi) {
                 constexpr int r = decltype(rc)::value;
                 constexpr int O = r * (PSTR / 4);                                  // in units of 8 bytes
                 static_assert(O + 3 < 256, "ds_read2_b64 offsets are 8 bits");
-                if (EXABM4D_BM_HANDWAIT) {
-                    asm volatile("ds_read2_b64 %0, %2 offset0:%3 offset1:%4\n\t"
-                                 "ds_read2_b64 %1, %2 offset0:%5 offset1:%6"
-                                 : "=&v"(lo), "=&v"(hi)
-                                 : "v"(wrow_lds), "n"(O), "n"(O + 1), "n"(O + 2), "n"(O + 3));
-                } else {
-                    lo = *reinterpret_cast<const u32x4a8*>(wrow + r * (PSTR / 2));
-                    hi = *reinterpret_cast<const u32x4a8*>(wrow + r * (PSTR / 2) + 4);
-                }
+                // (a copy: hipcc does not capture a variable for a generic lambda that names it in an asm operand only)
+                const uint32_t row0 = wrow_lds;
+                asm volatile("ds_read2_b64 %0, %2 offset0:%3 offset1:%4\n\t"
+                             "ds_read2_b64 %1, %2 offset0:%5 offset1:%6"
+                             : "=&v"(lo), "=&v"(hi)
+                             : "v"(row0), "n"(O), "n"(O + 1), "n"(O + 2), "n"(O + 3));
             };
             auto await_row = [&](u32x4& lo, u32x4& hi) {
-                if (EXABM4D_BM_HANDWAIT) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo), "+v"(hi));
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo), "+v"(hi));
             };
             u32x4 q0, q1;
             read_row(std::integral_constant<int, 0>{}, q0, q1);
             await_row(q0, q1);
-#ifdef EXABM4D_BM_STAMPS
-            // (a plain read has landed when something uses it)
-            if (!EXABM4D_BM_HANDWAIT) asm volatile("" : "+v"(q0), "+v"(q1));
-#endif
-            BM_STAMP(t4);
+            STAMP(t4);
             static_for([&](auto rc) {
                 constexpr int rp = decltype(rc)::value;
                 u32x4 n0, n1;
@@ -895,11 +841,11 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
                 }
             }, std::make_integer_sequence<int, 3 + NEP>{});
             asm volatile("" ::: "memory");
-            BM_STAMP(t5);
-            BM_STAMP_ADD(0, t0, t1);
-            BM_STAMP_ADD(1, t1, t2);
-            BM_STAMP_ADD(2, t3, t4);
-            BM_STAMP_ADD(3, t4, t5);
+            STAMP(t5);
+            STAMP_ADD(0, t0, t1);
+            STAMP_ADD(1, t1, t2);
+            STAMP_ADD(2, t3, t4);
+            STAMP_ADD(3, t4, t5);
         }
     };
     // The end of a pass, behind the accumulate block of its last step (z == 3): publish the sums, select, carry.
@@ -930,9 +876,9 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
                 for (int e = e0; e < (e0 + NR0 < NEP ? e0 + NR0 : NEP); e++)
 #pragma unroll
                     for (int d = 0; d < SWIN; d++) mine[64 * ((e - e0) * SWIN + d)] = pair_sum(e, d);
-                BM_STAMP(b0);
+                STAMP(b0);
                 __syncthreads();
-                BM_STAMP(b1);
+                STAMP(b1);
                 if (ref_ok) {
                     // a dy row's block sums first (its 22 LDS reads in flight together), then its
                     // candidates one by one: read-add-compare-branch per candidate exposed an LDS round
@@ -964,12 +910,12 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
                         }
                     }
                 }
-                BM_STAMP(b2);
+                STAMP(b2);
                 __syncthreads();
-                BM_STAMP(b3);
-                BM_STAMP_ADD(4, b0, b1);
-                BM_STAMP_ADD(5, b1, b2);
-                BM_STAMP_ADD(4, b2, b3);
+                STAMP(b3);
+                STAMP_ADD(4, b0, b1);
+                STAMP_ADD(5, b1, b2);
+                STAMP_ADD(4, b2, b3);
 #ifdef EXABM4D_BM_STAMPS
                 stb[e0 ? 2 : 0] += b1 - b0;
                 stb[e0 ? 3 : 1] += b3 - b2;
@@ -1011,15 +957,15 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
 
     if (carry.on) {
         // the tile is finished when wave 7's stores have been acknowledged and wave 0's last prefetch has landed
-        BM_STAMP(c0);
+        STAMP(c0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        BM_STAMP(c1);
-        BM_STAMP_ADD(6, c0, c1);
+        STAMP(c1);
+        STAMP_ADD(6, c0, c1);
         if (threadIdx.x == 0) __hip_atomic_store(done_col, tz + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 #ifdef EXABM4D_BM_STAMPS
-    st[7] = bm_stamp() - tk0;
+    st[7] = stamp() - tk0;
     if (lane == 0)
         for (int i = 0; i < 8; i++) atomicAdd(&g_bm_stamps[i], st[i]);
     if (lane == 0)
@@ -1198,8 +1144,8 @@ hipError_t launch_blockmatch(const float* vol, const VolGeom& g, int batch, uint
             hipError_t e = hipMemsetAsync(carry.done, 0, (cols + 8) * sizeof(int), stream);
             if (e != hipSuccess) return e;
         }
-        // the integer kernel's lanes address a staged plane by 32-bit byte offsets from its first row (EXABM4D_BM_STEPADDR)
-        if (vol16 && EXABM4D_BM_STEPADDR &&
+        // the integer kernel's lanes address a staged plane by 32-bit byte offsets from its first row
+        if (vol16 &&
             ((unsigned long long)Cube::PROWS * (unsigned long long)g.nx + 80ull) * 2ull >= (1ull << 32))
             return hipErrorInvalidValue;
         const dim3 grid((unsigned)(p.xq ? 8 * p.xq * p.tz : p.tz * p.ty * p.tx), (unsigned)(p.xq ? 1 : batch));

@@ -26,9 +26,6 @@ __device__ __forceinline__ f2 mk2(float a, float b) {
     return r;
 }
 
-#ifndef EXABM4D_TR_SWAP
-#define EXABM4D_TR_SWAP 1                 // 0 (A/B builds): the transposes of rounds 1-3, whose [hi][r][lo] writes conflict 2-way
-#endif
 // Bank conflicts of the transposes (round 4).  ds_write_b64 is served in groups of 16
 // consecutive lanes with bank = dword address mod 32 (MI355X_MICROARCH.md, LDS): a [hi][r][lo] write puts the
 // lanes of hi = 2g and 2g + 1 of a group 160 dwords = 0 (mod 32) apart -- every such instruction 2-way
@@ -44,7 +41,7 @@ __device__ __forceinline__ f2 mk2(float a, float b) {
 // gate, not for the LDS, and the two more address registers per lane cost it more than the conflicts did) and
 // the transform quantiser is HBM-bound -- so only the Wiener kernel instantiates it.
 template <bool SWAP>
-__device__ __forceinline__ int tr_swap(int hi) { return (SWAP && EXABM4D_TR_SWAP) ? 4 * (hi & 1) : 0; }
+__device__ __forceinline__ int tr_swap(int hi) { return SWAP ? 4 * (hi & 1) : 0; }
 // x coordinate held by lane (hi, lo) after pair_inv / pair_inv_x2 (layout L1 up to that permutation)
 template <bool SWAP>
 __device__ __forceinline__ int tr_x(int hi, int lo) { return lo ^ tr_swap<SWAP>(hi); }

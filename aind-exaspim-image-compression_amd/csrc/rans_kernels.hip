@@ -237,9 +237,6 @@ __global__ __launch_bounds__(64 * TS / PP) void rans_encode_kernel(const void* _
         out[q] = reinterpret_cast<uint16_t*>(slot + g.slot_hdr + (size_t)(p0 + q) * g.slot_plane);
         any_coded = any_coded || nsym[q] > 1;
     }
-#ifdef EXABM4D_ENC_SKIP2
-    any_coded = false;      // timing probe: histogram + tables only
-#endif
     if (any_coded) {
         constexpr int RB = 8;
         if (fast && rows) rc.seek(rows - 1);

@@ -23,6 +23,10 @@
 
 #include "exabm4d_kernels.h"
 #include "dct_pairs.h"
+#ifdef EXABM4D_STAMPS
+#define KERNEL_STAMPS
+#endif
+#include "kernel_stamps.h"
 
 namespace exabm4d {
 
@@ -31,27 +35,10 @@ typedef float f16v __attribute__((ext_vector_type(16)));
 #ifdef EXABM4D_STAMPS
 // Diagnostic build only: per-phase cycle sums (s_memtime) accumulated over all waves.
 __device__ unsigned long long g_stamps[18];        // nine slots per kernel: hard threshold, Wiener
-__device__ __forceinline__ unsigned long long stamp() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define STAMP(var) const unsigned long long var = stamp()
-#define STAMP_ADD(i, a, b) st[i] += (b) - (a)
-#define STAMP_MOVE(i, j, a, b) (st[i] += (b) - (a), st[j] -= (b) - (a))
-#else
-#define STAMP(var)
-#define STAMP_ADD(i, a, b)
-#define STAMP_MOVE(i, j, a, b) (void)0
 #endif
 
 constexpr float HAAR_C = 0.70710678118654752440f;
 
-#ifndef EXABM4D_GATHER_AUX
-#define EXABM4D_GATHER_AUX 0     // cache-policy bits of the gathers' buffer loads (A/B builds: 1 = sc0, 2 = nt, 3 = both)
-#endif
 // Gather of one block in layout L1 (hi = z, lo = x, regs y), the lane's eight row offsets
 // (hi * sz + y * sy + lo, constant for the whole kernel) precomputed in registers: one uniform base
 // per block (the corner) in an SGPR pair and no scalar address arithmetic per row.
@@ -63,7 +50,7 @@ __device__ __forceinline__ void gather8v(__amdgpu_buffer_rsrc_t rsrc, int corner
                                          float (&v)[8]) {
 #pragma unroll
     for (int y = 0; y < 8; y++)
-        v[y] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)voff[y], corner, EXABM4D_GATHER_AUX));
+        v[y] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)voff[y], corner, 0));
 }
 
 // Packed Haar along the group axis: v[k] holds two independent sequences in .x / .y.
@@ -105,7 +92,7 @@ __device__ __forceinline__ void gather8v2(__amdgpu_buffer_rsrc_t rsrc, int corne
                                           float (&a)[8], float (&b)[8]) {
 #pragma unroll
     for (int y = 0; y < 8; y++) {
-        const u2v t = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)(2u * voff[y]), corner2, EXABM4D_GATHER_AUX);
+        const u2v t = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)(2u * voff[y]), corner2, 0);
         a[y] = __uint_as_float(t.x);
         b[y] = __uint_as_float(t.y);
     }
@@ -142,15 +129,6 @@ struct TileGeom {
 // weights depended on arrival order, and stage 2's match tables are discontinuous in the last bits of
 // the basic estimate: uint16 results moved by up to 4 counts between launches.)
 // =================================================================================================
-#ifndef EXABM4D_PRIO
-#define EXABM4D_PRIO 1                         // 0: no wave priorities (A/B builds)
-#endif
-#ifndef EXABM4D_X2
-#define EXABM4D_X2 1                           // 0: one block pair per transform everywhere (A/B builds)
-#endif
-#ifndef EXABM4D_X2INV
-#define EXABM4D_X2INV 1                        // inverse transforms of four blocks as two interleaved pairs
-#endif
 // Per-kernel geometry of the two-waves-per-group kernels.  The hard-threshold kernel needs 133
 // registers and runs THREE waves per SIMD (12 per workgroup, six pairs); the Wiener kernel holds
 // two spectra (245 registers) and stays at two (8 per workgroup).  LDS = ring (NPL planes of
@@ -179,17 +157,9 @@ struct TileGeom {
 #ifndef EXABM4D_WIE_NPL
 #define EXABM4D_WIE_NPL 22
 #endif
-#ifndef EXABM4D_WIE_PAIR_SAME_SIMD
-#define EXABM4D_WIE_PAIR_SAME_SIMD 0           // 1 (A/B builds): the two waves of a Wiener pair share a SIMD (waves w, w + 4)
-#endif
-// Which waves form a pair.  Default: neighbours (w, w ^ 1) -- consecutive wave ids go to different SIMDs.
-// SAME_SIMD (8-wave workgroups only): w and w + 4 land on the same SIMD.
-template <bool SAME>
-struct PairMap {
-    static __device__ __forceinline__ int half(int w) { return SAME ? (w >> 2) & 1 : w & 1; }
-    static __device__ __forceinline__ int partner(int w) { return SAME ? w ^ 4 : w ^ 1; }
-    static __device__ __forceinline__ int pair(int w) { return SAME ? (w & 3) : w >> 1; }
-};
+// The waves of a pair are neighbours (w, w ^ 1): which half of its pair wave w is.  (A function, and `leader` below
+// goes through it: written out there, hipcc orders the stage kernels' scalar prologue differently.)
+__device__ __forceinline__ int pair_half(int w) { return w & 1; }
 template <int NW_, int TY_, int TX_, int NPL_>
 struct HalfGeom {
     static constexpr int TBW = 2 * TBUF;                // floats of LDS per wave buffer
@@ -228,13 +198,7 @@ __device__ __forceinline__ long long magic_bits(double m) {
 #ifndef EXABM4D_WIE_ILV
 #define EXABM4D_WIE_ILV 2                      // Newton chains interleaved per scheduling region (0: no limit)
 #endif
-#ifndef EXABM4D_WIE_RCP
-#define EXABM4D_WIE_RCP 0                      // 1 (timing probe, wrong bits): v_rcp_f32 as in rounds 1-3
-#endif
 __device__ __forceinline__ f2 rcp_nr2(f2 d) {
-#if EXABM4D_WIE_RCP == 1
-    return mk2(__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y));
-#endif
     f2 r = mk2(__uint_as_float(0x7EF311C7u - __float_as_uint(d.x)), __uint_as_float(0x7EF311C7u - __float_as_uint(d.y)));
 #pragma unroll
     for (int i = 0; i < 3; i++) r = __builtin_elementwise_fma(__builtin_elementwise_fma(-d, r, (f2)(1.0f)), r, r);
@@ -384,9 +348,6 @@ __device__ __forceinline__ void flush_num_plane(ring_t* ring, long long* __restr
 // at most one void draw per wave lands on a closed word -- far from its 16 bits).  The closer waits
 // for lock[3] to reach the plane count, closes the word and retires the layer.  Returns whether a
 // plane was flushed.
-#ifndef EXABM4D_HELP_FLUSH
-#define EXABM4D_HELP_FLUSH 1
-#endif
 template <class C>
 __device__ __forceinline__ bool flush_take(int* lock, ring_t* ring, long long* __restrict__ num, const TileGeom& tg,
                                            const VolGeom& g, int izb, int lane) {
@@ -476,14 +437,13 @@ __device__ __forceinline__ bool process_half_group(
     ) {
     using C = HalfCfg<WIENER>;
     constexpr int HNW = C::NW, HNPL = C::NPL, HPS = C::PS, REG = C::COLS;
-    constexpr bool HELP_FLUSH = !WIENER && EXABM4D_HELP_FLUSH;   // (the Wiener kernel has no registers for it
-                                                                 //  and waits 1.5 % of its time at the gate)
+    constexpr bool HELP_FLUSH = !WIENER;       // (the Wiener kernel has no registers for it
+                                               //  and waits 1.5 % of its time at the gate)
     constexpr int NP = WIENER ? 8 : 4;         // f2 values per lane swapped with the partner
     const int hi = lane >> 3, lo = lane & 7;
     const int xl = tr_x<WIENER>(hi, lo);               // the block column this lane holds after the inverse transforms (dct_pairs.h)
     STAMP(t0);
-    using PM = PairMap<WIENER && EXABM4D_WIE_PAIR_SAME_SIMD && HalfCfg<WIENER>::NW == 8>;
-    const int half = PM::half(wave), partner = PM::partner(wave);
+    const int half = pair_half(wave), partner = wave ^ 1;
     const uint32_t mykey = lane < MAXG ? kk[lane] : KEY_EMPTY;
     const int count = __popcll(__ballot(mykey != KEY_EMPTY));
     int K = 1;
@@ -540,7 +500,7 @@ __device__ __forceinline__ bool process_half_group(
 #pragma unroll
         for (int y = 0; y < 8; y++)
             voff[y] = 4u * ((unsigned)hi * (unsigned)sz + (unsigned)y * (unsigned)sy + (unsigned)lo);
-        if constexpr (!WIENER && KH >= 4 && EXABM4D_X2) {
+        if constexpr (!WIENER && KH >= 4) {
             float c[8], d[8];
             f2 w2[8];
             gather8v(noisy_r, corner_of(kb), voff, a);
@@ -825,7 +785,7 @@ __device__ __forceinline__ bool process_half_group(
                                        (unsigned long long)magic_bits(__builtin_fma((double)(comp ? v[y].y : v[y].x), ww[y], RINT_MAGIC)),
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         };
-        if constexpr (KH >= 4 && EXABM4D_X2INV) {
+        if constexpr (KH >= 4) {
             f2 w2[8];
 #pragma unroll
             for (int kl = 0; kl < KH; kl += 4) {
@@ -910,8 +870,7 @@ __global__ __launch_bounds__(HalfCfg<WIENER>::NW * 64) void stage_half_kernel(
     // readfirstlane: the wave index steers register indexing below and must be provably uniform
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     f2* tb = reinterpret_cast<f2*>(lds + 2 * HNPL * HPS + wave * C::TBW);
-    using PM = PairMap<WIENER && EXABM4D_WIE_PAIR_SAME_SIMD && C::NW == 8>;
-    f2* partner_tb = reinterpret_cast<f2*>(lds + 2 * HNPL * HPS + PM::partner(wave) * C::TBW);
+    f2* partner_tb = reinterpret_cast<f2*>(lds + 2 * HNPL * HPS + (wave ^ 1) * C::TBW);
     int* lock = reinterpret_cast<int*>(lds + 2 * HNPL * HPS + HNW * C::TBW);
     int* sync = lock + 4;                                  // ready[HNW], ack[HNW]
     int* cnt = sync + 2 * HNW;                             // reports per layer (slot = layer & 7)
@@ -963,8 +922,8 @@ __global__ __launch_bounds__(HalfCfg<WIENER>::NW * 64) void stage_half_kernel(
     }
     __syncthreads();
 
-    const int pairid = PM::pair(wave);
-    const bool leader = PM::half(wave) == 0;
+    const int pairid = wave >> 1;
+    const bool leader = pair_half(wave) == 0;
     int seq = 0;
     int seen = 0;           // last value read of lock[1] (layers retired), see the per-block gate
     const Dct7& tab = T;
@@ -1018,7 +977,6 @@ __global__ __launch_bounds__(HalfCfg<WIENER>::NW * 64) void stage_half_kernel(
         const int iy = iy0 + jy, ix = ix0 + jx;
         const int ry = grid_pos(iy, g.ay, g.ny), rx = grid_pos(ix, g.ax, g.nx);
         const uint32_t* kk = keys + ((size_t)((size_t)iz * g.gy + iy) * g.gx + ix) * MAXG;
-#if EXABM4D_PRIO
         {
             // A wave that starts a group of the oldest open layer holds up everybody at the
             // gate: it gets issue priority (s_setprio) over a SIMD neighbour that started its
@@ -1032,7 +990,6 @@ __global__ __launch_bounds__(HalfCfg<WIENER>::NW * 64) void stage_half_kernel(
             else
                 __builtin_amdgcn_s_setprio(0);
         }
-#endif
         const bool closer = process_half_group<WIENER>(
             noisy, basic, kk, z0, ry, rx, tg, sy, sz, tab, win, win_g, thr, sigma2, up, ring, cvol, tb,
             partner_tb, lock, sync, cnt, wave, seq, seen, layer, 2 * nrefs, lane, g.nvox, num, g, izb, pair
@@ -1056,7 +1013,7 @@ __global__ __launch_bounds__(HalfCfg<WIENER>::NW * 64) void stage_half_kernel(
             cbar();
             if (iz + 1 < ize) {
                 const int zn = grid_pos(iz + 1, g.az, g.nz);
-                if constexpr (!WIENER && EXABM4D_HELP_FLUSH) {
+                if constexpr (!WIENER) {
                     if (lane == 0) {
                         __hip_atomic_store(lock + 3, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         __hip_atomic_store(lock + 2, (layer + 1) << 16, __ATOMIC_RELAXED,

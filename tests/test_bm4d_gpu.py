@@ -9,7 +9,7 @@ order in which waves, workgroups and launches add (rounds 1-3: fp32 tolerance, u
 import numpy as np
 import pytest
 
-from util import psnr, synth_volume
+from util import ctx_options, match_tables, psnr, synth_volume
 
 from aind_exaspim_image_compression import _native
 
@@ -19,13 +19,7 @@ SIGMA = 24.0
 
 
 def _keys_gpu(ctx, vol, sigma, c_match):
-    from aind_exaspim_image_compression import _native as nat
-    g = [len(nat.grid_positions(n)) for n in vol.shape]
-    d_vol = ctx.to_device(vol)
-    d_keys = ctx.alloc(g[0] * g[1] * g[2] * 16 * 4)
-    ctx.blockmatch(d_vol, vol.shape, sigma, c_match, d_keys)
-    ctx.sync()
-    return d_keys.download((g[0], g[1], g[2], 16), np.uint32)
+    return match_tables(ctx, vol, sigma, c_match, u16=False)
 
 
 @pytest.mark.parametrize("shape", [(64, 64, 64), (40, 44, 48), (8, 8, 8), (16, 12, 36),
@@ -45,18 +39,10 @@ def test_blockmatch_on_guarded_copy_bit_exact(ctx, oracle, shape):
     clamping and read past the row ends (poisoned with NaN patterns here): same match tables."""
     vol, _ = synth_volume(shape, seed=sum(shape) + 1)
     want = oracle.blockmatch(vol, SIGMA, 3.0)
-    ctx.set_option("bm_guarded_copy", 1)
-    try:
+    with ctx_options(ctx, bm_guarded_copy=1):
         got = _keys_gpu(ctx, vol, SIGMA, 3.0)
         batch = np.stack([vol, vol[::-1].copy()])
-        g = got.shape[:3]
-        d_vol = ctx.to_device(batch)
-        d_keys = ctx.alloc(2 * g[0] * g[1] * g[2] * 16 * 4)
-        ctx.blockmatch(d_vol, vol.shape, SIGMA, 3.0, d_keys, batch=2)
-        ctx.sync()
-        both = d_keys.download((2,) + got.shape, np.uint32)
-    finally:
-        ctx.set_option("bm_guarded_copy", 0)
+        both = _keys_gpu(ctx, batch, SIGMA, 3.0)
     np.testing.assert_array_equal(got, want)
     np.testing.assert_array_equal(both[0], want)
     np.testing.assert_array_equal(both[1], oracle.blockmatch(batch[1], SIGMA, 3.0))
@@ -66,11 +52,8 @@ def test_blockmatch_generic_kernel_matches(ctx, oracle):
     """The one-wave-per-block kernel alone must also reproduce the oracle bit for bit."""
     vol, _ = synth_volume((36, 40, 44), seed=5)
     want = oracle.blockmatch(vol, SIGMA, 3.0)
-    ctx.set_option("force_generic_bm", 1)
-    try:
+    with ctx_options(ctx, force_generic_bm=1):
         got = _keys_gpu(ctx, vol, SIGMA, 3.0)
-    finally:
-        ctx.set_option("force_generic_bm", 0)
     np.testing.assert_array_equal(got, want)
 
 
@@ -84,11 +67,8 @@ def test_blockmatch_tables_are_never_empty(ctx, oracle):
     want = oracle.blockmatch(vol, SIGMA, 3.0)
     assert (want[..., 0] == 0).all() and (want[1, 1, 1, 1:] == 0xFFFFFFFF).all()
     np.testing.assert_array_equal(_keys_gpu(ctx, vol, SIGMA, 3.0), want)
-    ctx.set_option("force_generic_bm", 1)
-    try:
+    with ctx_options(ctx, force_generic_bm=1):
         np.testing.assert_array_equal(_keys_gpu(ctx, vol, SIGMA, 3.0), want)
-    finally:
-        ctx.set_option("force_generic_bm", 0)
 
 
 def test_blockmatch_constant_volume_self_first(ctx, oracle):
@@ -185,12 +165,11 @@ def test_tall_ragged_volume_every_launch_shape_gives_the_oracles_result(ctx, ora
     d_out = ctx.alloc(vol.nbytes)
     try:
         for chunks in (1, 0, 9):
-            ctx.set_option("stage_chunks", chunks)
-            ctx.denoise_u16(d_in, d_out, shape, SIGMA, 37.0)
-            ctx.sync()
+            with ctx_options(ctx, stage_chunks=chunks):
+                ctx.denoise_u16(d_in, d_out, shape, SIGMA, 37.0)
+                ctx.sync()
             np.testing.assert_array_equal(d_out.download(shape, np.uint16), want, err_msg=f"stage_chunks {chunks}")
     finally:
-        ctx.set_option("stage_chunks", 0)
         d_in.free()
         d_out.free()
 
@@ -265,11 +244,8 @@ def test_large_host_batch_in_overlapped_sub_batches(ctx, oracle):
     raw = np.concatenate([base + np.float32(3 * k) for k in range(65)])
     assert raw.shape[0] == 520
     got = ctx.denoise_f32_host(raw, SIGMA, clip=(0.0, 65535.0))
-    ctx.set_option("host_pipeline", 0)
-    try:
+    with ctx_options(ctx, host_pipeline=0):
         one = ctx.denoise_f32_host(raw, SIGMA, clip=(0.0, 65535.0))
-    finally:
-        ctx.set_option("host_pipeline", 1)
     np.testing.assert_array_equal(got, one)
     for i in (0, 300, 519):
         np.testing.assert_array_equal(got[i], np.clip(oracle.bm4d(raw[i], SIGMA), 0, 65535))
@@ -291,15 +267,12 @@ def test_calls_queued_back_to_back_and_the_zeroing_stream(ctx, oracle):
     d_out = [ctx.alloc(v.nbytes) for v in vols]
     got = {}
     for overlap in (1, 0):
-        ctx.set_option("zero_overlap", overlap)
-        try:
+        with ctx_options(ctx, zero_overlap=overlap):
             for d in d_out:
                 d.fill(0xEE)
             for i in range(3):
                 ctx.denoise_u16(d_in[i], d_out[i], vols[i].shape, SIGMA, 37.0)
             ctx.sync()
-        finally:
-            ctx.set_option("zero_overlap", 1)
         got[overlap] = [d_out[i].download(vols[i].shape, np.uint16) for i in range(3)]
     for i in range(3):
         np.testing.assert_array_equal(got[1][i], got[0][i])
@@ -322,16 +295,11 @@ def test_pipeline_u16_stage2_matches_on_counts_in_every_kernel(ctx, oracle, shap
     want = oracle.bm4d_u16(vol, SIGMA, offset)
     d_in, d_out = ctx.to_device(vol), ctx.alloc(vol.nbytes)
     try:
-        for option, value in ((None, 0), ("bm_int", 0), ("force_generic_bm", 1)):
-            if option:
-                ctx.set_option(option, value)
-            try:
+        for options in ({}, {"bm_int": 0}, {"force_generic_bm": 1}):
+            with ctx_options(ctx, **options):
                 d_out.fill(0xEE)
                 ctx.denoise_u16(d_in, d_out, shape, SIGMA, offset)
                 ctx.sync()
-            finally:
-                if option:
-                    ctx.set_option(option, 1 - value)
             np.testing.assert_array_equal(d_out.download(shape, np.uint16), want)
     finally:
         d_in.free()
@@ -438,19 +406,8 @@ def test_fp32_input_outside_the_working_range_is_refused(ctx, oracle):
     np.testing.assert_array_equal(ctx.denoise_f32_host(vol, SIGMA), oracle.bm4d(vol, SIGMA))
 
 
-def _keys_u16(ctx, vol, sigma, c_match, batch=1):
-    shape = vol.shape[-3:]
-    g = [len(_native.grid_positions(n)) for n in shape]
-    d_vol = ctx.to_device(vol)
-    d_keys = ctx.alloc(batch * g[0] * g[1] * g[2] * 16 * 4)
-    try:
-        ctx.blockmatch_u16(d_vol, shape, sigma, c_match, d_keys, batch=batch)
-        ctx.sync()
-        return d_keys.download((batch, g[0], g[1], g[2], 16) if batch > 1 else (g[0], g[1], g[2], 16),
-                               np.uint32)
-    finally:
-        d_vol.free()
-        d_keys.free()
+def _keys_u16(ctx, vol, sigma, c_match):
+    return match_tables(ctx, vol, sigma, c_match)
 
 
 @pytest.mark.parametrize("shape", [(24, 28, 32), (40, 44, 64), (26, 31, 22), (64, 64, 64), (33, 72, 130),
@@ -468,17 +425,14 @@ def test_integer_block_matching_equals_the_oracle(ctx, oracle, shape):
     for sigma, c_match in ((SIGMA, 3.0), (SIGMA, 0.6), (90.0, 3.0), (120.0, 3.0)):   # 120: bound > 2^24 -> float kernel
         want = oracle.blockmatch(f, sigma, c_match)
         np.testing.assert_array_equal(_keys_u16(ctx, vol, sigma, c_match), want)
-    ctx.set_option("bm_int", 0)
-    try:
+    with ctx_options(ctx, bm_int=0):
         np.testing.assert_array_equal(_keys_u16(ctx, vol, SIGMA, 3.0), oracle.blockmatch(f, SIGMA, 3.0))
-    finally:
-        ctx.set_option("bm_int", 1)
 
 
 def test_integer_block_matching_batch_of_patches(ctx, oracle):
     """A batch of 64^3 patches (the 4 x 16 tile shape) through the integer kernel."""
     vols = np.stack([synth_volume((64, 64, 64), seed=50 + i, as_u16=True)[0] for i in range(3)])
-    got = _keys_u16(ctx, vols, SIGMA, 3.0, batch=3)
+    got = _keys_u16(ctx, vols, SIGMA, 3.0)
     for i in range(3):
         np.testing.assert_array_equal(got[i], oracle.blockmatch(vols[i].astype(np.float32) - 37.0, SIGMA, 3.0))
 
@@ -493,13 +447,12 @@ def test_non_dyadic_offset_takes_the_float_kernel(ctx, oracle):
     vol = synth_volume((40, 48, 64), seed=77, as_u16=True)[0]
 
     def run(offset, bm_int):
-        ctx.set_option("bm_int", bm_int)
         d_in, d_out = ctx.to_device(vol), ctx.alloc(vol.nbytes)
         try:
-            ctx.denoise_u16(d_in, d_out, vol.shape, SIGMA, offset)
-            return d_out.download(vol.shape, np.uint16)
+            with ctx_options(ctx, bm_int=bm_int):
+                ctx.denoise_u16(d_in, d_out, vol.shape, SIGMA, offset)
+                return d_out.download(vol.shape, np.uint16)
         finally:
-            ctx.set_option("bm_int", 1)
             d_in.free()
             d_out.free()
 
@@ -528,12 +481,9 @@ def test_wiener_gathers_from_the_interleaved_volume(ctx, oracle):
     keys[np.arange(16)[None, None, None, :] >= cut[..., None]] = 0xFFFFFFFF
     assert np.unique((keys != 0xFFFFFFFF).sum(axis=-1)).size > 4
     res = {}
-    try:
-        for pv in (1, 0):
-            ctx.set_option("stage_pairvol", pv)
+    for pv in (1, 0):
+        with ctx_options(ctx, stage_pairvol=pv):
             res[pv] = _stage_gpu(ctx, noisy, keys, SIGMA, basic=basic)
-    finally:
-        ctx.set_option("stage_pairvol", 1)
     np.testing.assert_array_equal(res[1][0], res[0][0])
     np.testing.assert_array_equal(res[1][1], res[0][1])
     num_w, den_w = oracle.stage(noisy, keys, SIGMA, basic=basic, port=True)
@@ -551,20 +501,20 @@ def test_block_matching_workgroup_orders_give_identical_tables(ctx):
     vol[20:40, 100:300, 200:420] += 500
     f = vol.astype(np.float32) - np.float32(37.0)
     g = [len(_native.grid_positions(n)) for n in vol.shape]
-    d_u16, d_f32 = ctx.to_device(vol), ctx.to_device(f)
+    d_u16, d_f32 = ctx.to_device(vol), ctx.to_device(f)            # (large: uploaded once for the five modes)
     d_keys = ctx.alloc(g[0] * g[1] * g[2] * 16 * 4)
     got = {}
     try:
-        for mode in (0, 1, 2, 3, 5):
-            ctx.set_option("bm_xcd_mode", mode)
-            ctx.blockmatch_u16(d_u16, vol.shape, SIGMA, 3.0, d_keys)
-            ctx.sync()
-            a = d_keys.download((*g, 16), np.uint32)
-            ctx.blockmatch(d_f32, vol.shape, SIGMA, 0.6, d_keys)
-            ctx.sync()
-            got[mode] = (a, d_keys.download((*g, 16), np.uint32))
+        with ctx_options(ctx) as set_options:
+            for mode in (0, 1, 2, 3, 5):
+                set_options(bm_xcd_mode=mode)
+                ctx.blockmatch_u16(d_u16, vol.shape, SIGMA, 3.0, d_keys)
+                ctx.sync()
+                a = d_keys.download((*g, 16), np.uint32)
+                ctx.blockmatch(d_f32, vol.shape, SIGMA, 0.6, d_keys)
+                ctx.sync()
+                got[mode] = (a, d_keys.download((*g, 16), np.uint32))
     finally:
-        ctx.set_option("bm_xcd_mode", 2)
         for b in (d_u16, d_f32, d_keys):
             b.free()
     for mode in (1, 2, 3, 5):
@@ -578,14 +528,11 @@ def test_stage_tile_order_option_changes_nothing_but_the_order(ctx):
     1024^3), 0 in raster order.  Same groups, same arithmetic, integer sums: the same uint16 volume."""
     from aind_exaspim_image_compression.bm4d import denoise_volume
     vol = synth_volume((40, 150, 170), seed=17, as_u16=True)[0]
-    ctx.set_option("stage_strip", 0)
-    want = denoise_volume(vol, SIGMA, 37.0)
-    try:
+    with ctx_options(ctx, stage_strip=0) as set_options:
+        want = denoise_volume(vol, SIGMA, 37.0)
         for n in (2, 3, 7):
-            ctx.set_option("stage_strip", n)
+            set_options(stage_strip=n)
             np.testing.assert_array_equal(denoise_volume(vol, SIGMA, 37.0), want, err_msg=f"stage_strip {n}")
-    finally:
-        ctx.set_option("stage_strip", 3)
 
 
 def test_staged_entry_points_accept_views_offset_by_one_element(ctx, oracle):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import bm_adversarial_inputs as adv
+from util import ctx_options
 
 from aind_exaspim_image_compression import _native
 
@@ -44,33 +45,28 @@ class _Matcher:
         self.g = _grid(self.shape)
         self.d_keys = ctx.alloc(self.batch * int(np.prod(self.g)) * 16 * 4)
 
-    def tables(self, u16, sigma, c_match, option=None, value=0, restore=0):
+    def tables(self, u16, sigma, c_match, **options):
         ctx = self.ctx
-        if option:
-            ctx.set_option(option, value)
-        try:
+        with ctx_options(ctx, **options):
             self.d_keys.fill(0x5A)
             call, vol = (ctx.blockmatch_u16, self.d_u16) if u16 else (ctx.blockmatch, self.d_f32)
             call(vol, self.shape, sigma, c_match, self.d_keys, batch=self.batch)
             ctx.sync()
             return self.d_keys.download((self.batch, *self.g, 16), np.uint32)
-        finally:
-            if option:
-                ctx.set_option(option, restore)
 
     def free(self):
         for b in (self.d_f32, self.d_u16, self.d_keys):
             b.free()
 
 
-# (name of the path, uint16 entry point?, option, value, value to restore)
-PATHS = [("blockmatch", False, None, 0, 0),
-         ("blockmatch on a guarded copy", False, "bm_guarded_copy", 1, 0),
-         ("blockmatch, one-wave kernel", False, "force_generic_bm", 1, 0),
-         ("blockmatch_u16, integer kernel", True, "bm_int", 1, 1),
-         ("blockmatch_u16, float kernel", True, "bm_int", 0, 1)]
-CARRY_PATHS = [("blockmatch with the carry", False, "bm_carry", 2, 1),
-               ("blockmatch_u16 with the carry", True, "bm_carry", 2, 1)]
+# (name of the path, uint16 entry point?, options)
+PATHS = [("blockmatch", False, {}),
+         ("blockmatch on a guarded copy", False, {"bm_guarded_copy": 1}),
+         ("blockmatch, one-wave kernel", False, {"force_generic_bm": 1}),
+         ("blockmatch_u16, integer kernel", True, {"bm_int": 1}),
+         ("blockmatch_u16, float kernel", True, {"bm_int": 0})]
+CARRY_PATHS = [("blockmatch with the carry", False, {"bm_carry": 2}),
+               ("blockmatch_u16 with the carry", True, {"bm_carry": 2})]
 
 
 @pytest.mark.parametrize("name", [n for n, _, _ in adv.CASES])
@@ -80,8 +76,8 @@ def test_match_tables_equal_the_oracle_on_every_path(ctx, oracle, shape, name):
     try:
         for sigma, c_match in adv.BY_NAME[name][1]:
             want = _oracle_tables(oracle, name, shape, sigma, c_match)
-            for what, u16, option, value, restore in PATHS:
-                got = m.tables(u16, sigma, c_match, option, value, restore)[0]
+            for what, u16, options in PATHS:
+                got = m.tables(u16, sigma, c_match, **options)[0]
                 np.testing.assert_array_equal(got, want, err_msg=f"{what}: {name} {shape} sigma {sigma} c {c_match}")
     finally:
         m.free()
@@ -92,15 +88,12 @@ def test_match_tables_of_a_patch_with_and_without_the_carry(ctx, oracle, name):
     m = _Matcher(ctx, [adv.volume(name, TALL)])
     try:
         assert not _native.blockmatch_plan(TALL, ctx=ctx)["carry"]            # a small launch: off unless forced
-        ctx.set_option("bm_carry", 2)
-        try:
+        with ctx_options(ctx, bm_carry=2):
             assert _native.blockmatch_plan(TALL, ctx=ctx)["carry"]
-        finally:
-            ctx.set_option("bm_carry", 1)
         for sigma, c_match in adv.BY_NAME[name][1]:
             want = _oracle_tables(oracle, name, TALL, sigma, c_match)
-            for what, u16, option, value, restore in PATHS + CARRY_PATHS:
-                got = m.tables(u16, sigma, c_match, option, value, restore)[0]
+            for what, u16, options in PATHS + CARRY_PATHS:
+                got = m.tables(u16, sigma, c_match, **options)[0]
                 np.testing.assert_array_equal(got, want, err_msg=f"{what}: {name} sigma {sigma} c {c_match}")
     finally:
         m.free()

@@ -6,7 +6,7 @@ waves, both tile shapes, the float and the integer kernel, batches."""
 import numpy as np
 import pytest
 
-from util import synth_volume
+from util import ctx_options, match_tables, synth_volume
 
 from aind_exaspim_image_compression import _native
 
@@ -14,30 +14,15 @@ pytestmark = pytest.mark.gpu
 SIGMA = 24.0
 
 
-def _keys(ctx, vol, c_match, integer, batch=1):
-    shape = vol.shape[-3:]
-    g = [len(_native.grid_positions(n)) for n in shape]
+def _keys(ctx, vol, c_match, integer):
     src = vol if integer else (vol.astype(np.float32) - np.float32(37.0))
-    d_vol = ctx.to_device(np.ascontiguousarray(src))
-    d_keys = ctx.alloc(batch * g[0] * g[1] * g[2] * 16 * 4)
-    try:
-        if integer:
-            ctx.blockmatch_u16(d_vol, shape, SIGMA, c_match, d_keys, batch=batch)
-        else:
-            ctx.blockmatch(d_vol, shape, SIGMA, c_match, d_keys, batch=batch)
-        ctx.sync()
-        return d_keys.download((batch, *g, 16) if batch > 1 else (*g, 16), np.uint32)
-    finally:
-        d_vol.free()
-        d_keys.free()
+    return match_tables(ctx, src, SIGMA, c_match, u16=integer)
 
 
 @pytest.fixture
 def carry(ctx):
-    def set_carry(n):
-        ctx.set_option("bm_carry", n)      # 0 off, 1 automatic (large launches), 2 forced
-    yield set_carry
-    ctx.set_option("bm_carry", 1)
+    with ctx_options(ctx) as set_options:
+        yield lambda n: set_options(bm_carry=n)      # 0 off, 1 automatic (large launches), 2 forced
 
 
 @pytest.mark.parametrize("integer", [False, True])
@@ -68,7 +53,7 @@ def test_carry_with_patches_batches_and_unaligned_planes(ctx, oracle, carry, int
     carry(2)
     f0 = vols[0].astype(np.float32) - (np.float32(0.0) if integer else np.float32(37.0))
     np.testing.assert_array_equal(_keys(ctx, vols[0], 3.0, integer), oracle.blockmatch(f0, SIGMA, 3.0))
-    got = _keys(ctx, vols, 3.0, integer, batch=3)
+    got = _keys(ctx, vols, 3.0, integer)
     for i in range(3):
         f = vols[i].astype(np.float32) - (np.float32(0.0) if integer else np.float32(37.0))
         np.testing.assert_array_equal(got[i], oracle.blockmatch(f, SIGMA, 3.0))
@@ -112,9 +97,9 @@ def test_large_batch_of_patches_takes_the_carry_by_default(ctx, carry, integer):
     vols = np.ascontiguousarray(base[rng.integers(0, 6, 120)])
     vols += rng.integers(0, 3, vols.shape, dtype=np.uint16)            # 120 different patches
     carry(0)
-    want = _keys(ctx, vols, 3.0, integer, batch=120)
+    want = _keys(ctx, vols, 3.0, integer)
     carry(1)
-    np.testing.assert_array_equal(_keys(ctx, vols, 3.0, integer, batch=120), want)
+    np.testing.assert_array_equal(_keys(ctx, vols, 3.0, integer), want)
 
 
 def test_chunk_local_mode_with_and_without_the_carry(ctx, carry):
@@ -206,14 +191,12 @@ def test_options_belong_to_their_context(ctx):
     setter.  A second context on the same device keeps the defaults whatever the first one sets."""
     other = _native.Context(0)
     try:
-        ctx.set_option("bm_carry", 0)
-        assert not _native.blockmatch_plan((1024, 1024, 1024), ctx=ctx)["carry"]
-        assert _native.blockmatch_plan((1024, 1024, 1024), ctx=other)["carry"]
-        assert _native.blockmatch_plan((1024, 1024, 1024))["carry"]
-        ctx.set_option("bm_xcd_mode", 0)
-        assert _native.blockmatch_plan((64, 640, 640), ctx=ctx)["slab_order_q"] == 0
-        assert _native.blockmatch_plan((64, 640, 640), ctx=other)["slab_order_q"] > 0
+        with ctx_options(ctx, bm_carry=0) as set_options:
+            assert not _native.blockmatch_plan((1024, 1024, 1024), ctx=ctx)["carry"]
+            assert _native.blockmatch_plan((1024, 1024, 1024), ctx=other)["carry"]
+            assert _native.blockmatch_plan((1024, 1024, 1024))["carry"]
+            set_options(bm_xcd_mode=0)
+            assert _native.blockmatch_plan((64, 640, 640), ctx=ctx)["slab_order_q"] == 0
+            assert _native.blockmatch_plan((64, 640, 640), ctx=other)["slab_order_q"] > 0
     finally:
-        ctx.set_option("bm_carry", 1)
-        ctx.set_option("bm_xcd_mode", 2)
         other.close()

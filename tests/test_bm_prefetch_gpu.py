@@ -18,7 +18,7 @@ change under the shift."""
 import numpy as np
 import pytest
 
-from util import synth_volume
+from util import ctx_options, match_tables, synth_volume
 
 from aind_exaspim_image_compression import _native
 
@@ -58,26 +58,10 @@ def _reference(oracle, case, bound):
     return _cache[(case, bound)]
 
 
-def _keys(ctx, vols, sigma, c_match):
-    batch, shape = vols.shape[0], vols.shape[1:]
-    g = [len(_native.grid_positions(n)) for n in shape]
-    d_vol = ctx.to_device(np.ascontiguousarray(vols))
-    d_keys = ctx.alloc(batch * g[0] * g[1] * g[2] * 16 * 4)
-    try:
-        ctx.blockmatch_u16(d_vol, shape, sigma, c_match, d_keys, batch=batch)
-        ctx.sync()
-        return d_keys.download((batch, *g, 16), np.uint32)
-    finally:
-        d_vol.free()
-        d_keys.free()
-
-
 @pytest.fixture
 def carry(ctx):
-    def set_carry(n):
-        ctx.set_option("bm_carry", n)      # 0 off, 1 automatic (large launches), 2 forced
-    yield set_carry
-    ctx.set_option("bm_carry", 1)
+    with ctx_options(ctx) as set_options:
+        yield lambda n: set_options(bm_carry=n)      # 0 off, 1 automatic (large launches), 2 forced
 
 
 @pytest.mark.parametrize("carry_mode", [0, 2], ids=["carry_off", "carry_forced"])
@@ -90,7 +74,7 @@ def test_tables_equal_the_oracle_launch_after_launch(ctx, oracle, carry, case, b
     if carry_mode == 2:
         assert _native.blockmatch_plan(vols.shape[1:], batch=vols.shape[0], ctx=ctx)["carry"]
     for rep in range(3):       # the plane buffers and the carry slots are reused by every step, tile and launch
-        np.testing.assert_array_equal(_keys(ctx, vols, sigma, c_match), want, err_msg=f"launch {rep}")
+        np.testing.assert_array_equal(match_tables(ctx, vols, sigma, c_match), want, err_msg=f"launch {rep}")
 
 
 def test_pipeline_equals_the_oracle(ctx, oracle):

@@ -7,6 +7,8 @@ at all, high, and on both sides at once; the first tile column (the base lies be
 import numpy as np
 import pytest
 
+from util import ctx_options, match_tables
+
 from aind_exaspim_image_compression import _native
 
 pytestmark = pytest.mark.gpu
@@ -30,28 +32,13 @@ def _volume(shape, seed):
 
 
 def _keys(ctx, vols):
-    batch = vols.shape[0] if vols.ndim == 4 else 1
-    shape = vols.shape[-3:]
-    g = [len(_native.grid_positions(n)) for n in shape]
-    d_vol = ctx.to_device(np.ascontiguousarray(vols))
-    d_keys = ctx.alloc(batch * g[0] * g[1] * g[2] * 16 * 4)
-    try:
-        ctx.blockmatch_u16(d_vol, shape, SIGMA, C_MATCH, d_keys, batch=batch)
-        ctx.sync()
-        return d_keys.download((batch, *g, 16) if batch > 1 else (*g, 16), np.uint32)
-    finally:
-        d_vol.free()
-        d_keys.free()
+    return match_tables(ctx, vols, SIGMA, C_MATCH)
 
 
 @pytest.fixture
 def options(ctx):
-    def set_options(carry, xcd_mode=2):
-        ctx.set_option("bm_carry", carry)      # 0 off, 1 automatic, 2 forced
-        ctx.set_option("bm_xcd_mode", xcd_mode)
-    yield set_options
-    ctx.set_option("bm_carry", 1)
-    ctx.set_option("bm_xcd_mode", 2)
+    with ctx_options(ctx) as set_options:       # bm_carry: 0 off, 1 automatic, 2 forced
+        yield lambda carry, xcd_mode=2: set_options(bm_carry=carry, bm_xcd_mode=xcd_mode)
 
 
 @pytest.fixture(scope="module")

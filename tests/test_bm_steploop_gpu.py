@@ -16,7 +16,7 @@ Inputs (util.synth_volume, uint16) and bounds as in test_bm_prefetch_gpu.py:
 import numpy as np
 import pytest
 
-from util import synth_volume
+from util import ctx_options, match_tables, synth_volume
 
 from aind_exaspim_image_compression import _native
 
@@ -65,26 +65,10 @@ def test_oracle_tables_draw_on_every_dz_and_pass(oracle, case, bound):
     _reference(oracle, case, bound)
 
 
-def _keys(ctx, vols, sigma, c_match):
-    batch, shape = vols.shape[0], vols.shape[1:]
-    g = [len(_native.grid_positions(n)) for n in shape]
-    d_vol = ctx.to_device(np.ascontiguousarray(vols))
-    d_keys = ctx.alloc(batch * g[0] * g[1] * g[2] * 16 * 4)
-    try:
-        ctx.blockmatch_u16(d_vol, shape, sigma, c_match, d_keys, batch=batch)
-        ctx.sync()
-        return d_keys.download((batch, *g, 16), np.uint32)
-    finally:
-        d_vol.free()
-        d_keys.free()
-
-
 @pytest.fixture
 def carry(ctx):
-    def set_carry(n):
-        ctx.set_option("bm_carry", n)      # 0 off, 1 automatic (large launches), 2 forced
-    yield set_carry
-    ctx.set_option("bm_carry", 1)
+    with ctx_options(ctx) as set_options:
+        yield lambda n: set_options(bm_carry=n)      # 0 off, 1 automatic (large launches), 2 forced
 
 
 @pytest.mark.gpu
@@ -98,7 +82,7 @@ def test_tables_equal_the_oracle_twice(ctx, oracle, carry, case, bound, carry_mo
     if carry_mode == 2:
         assert _native.blockmatch_plan(vols.shape[1:], batch=vols.shape[0], ctx=ctx)["carry"]
     for rep in range(2):
-        got = _keys(ctx, vols, sigma, c_match)
+        got = match_tables(ctx, vols, sigma, c_match)
         if not np.array_equal(got, want):
             diff = class_counts(got) - class_counts(want)
             np.testing.assert_array_equal(got, want, err_msg=f"launch {rep}; entries per (dz, pass) class, got - "

@@ -16,22 +16,14 @@ import os
 import numpy as np
 import pytest
 
-from aind_exaspim_image_compression import _native
+from util import match_tables
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def _keys(ctx, vol, sigma, c_match):
-    g = [len(_native.grid_positions(n)) for n in vol.shape]
-    d_vol, d_keys = ctx.to_device(vol), ctx.alloc(g[0] * g[1] * g[2] * 64)
-    try:
-        ctx.blockmatch(d_vol, vol.shape, sigma, c_match, d_keys)
-        ctx.sync()
-        return d_keys.download((g[0], g[1], g[2], 16), np.uint32)
-    finally:
-        d_vol.free()
-        d_keys.free()
+    return match_tables(ctx, vol, sigma, c_match, u16=False)
 
 
 @pytest.mark.parametrize("name,sigma,offset", [("fuzz_tie_volume.npz", 24.0, 100.5),

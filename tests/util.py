@@ -94,6 +94,53 @@ class GuardedView:
         self.buf.free()
 
 
+def match_tables(ctx, vols, sigma, c_match, u16=True):
+    """Block matching's tables of a volume (3-D: `(gz, gy, gx, 16)`) or of a batch of volumes (4-D:
+    `(batch, gz, gy, gx, 16)`), through `blockmatch_u16` (`u16`: biased uint16 counts) or `blockmatch` (fp32):
+    upload, launch, sync, download; both device buffers are freed whatever happens."""
+    from aind_exaspim_image_compression import _native
+    shape = vols.shape[-3:]
+    batch = vols.shape[0] if vols.ndim == 4 else 1
+    g = [len(_native.grid_positions(n)) for n in shape]
+    d_vol = ctx.to_device(np.ascontiguousarray(vols))
+    d_keys = ctx.alloc(batch * g[0] * g[1] * g[2] * 16 * 4)
+    try:
+        (ctx.blockmatch_u16 if u16 else ctx.blockmatch)(d_vol, shape, sigma, c_match, d_keys, batch=batch)
+        ctx.sync()
+        return d_keys.download((batch, *g, 16) if vols.ndim == 4 else (*g, 16), np.uint32)
+    finally:
+        d_vol.free()
+        d_keys.free()
+
+
+# The library's defaults of the options the tests change (exabm4d_set_option).
+OPTION_DEFAULTS = {
+    "bm_carry": 1, "bm_xcd_mode": 2, "force_generic_bm": 0, "bm_guarded_copy": 0, "bm_int": 1,
+    "zero_overlap": 1, "host_pipeline": 1, "stage_chunks": 0, "stage_strip": 3, "stage_pairvol": 1,
+}
+
+
+@contextlib.contextmanager
+def ctx_options(ctx, **values):
+    """Sets the context's options `values`; on exit every option set is back at the library's default.  Yields a
+    function that sets further options under the same promise (a test that goes through several settings)."""
+    touched = []
+
+    def set_options(**more):
+        for name, value in more.items():
+            assert name in OPTION_DEFAULTS, f"{name}: name its default in OPTION_DEFAULTS"
+            if name not in touched:
+                touched.append(name)
+            ctx.set_option(name, value)
+
+    try:
+        set_options(**values)
+        yield set_options
+    finally:
+        for name in touched:
+            ctx.set_option(name, OPTION_DEFAULTS[name])
+
+
 @contextlib.contextmanager
 def socket_dir(tmp_path, room=0):
     """A directory for the broker's AF_UNIX socket (plus `room` bytes of sub-directories): tmp_path when the

@@ -1,7 +1,7 @@
 """Per-phase s_memtime sums of bm_tile16_kernel: python tools/dbg/bm_stamps.py LIB [SIZE] [LABEL] > stamps.json
-LIB is a library built with -DEXABM4D_BM_STAMPS (tools/dbg/build_variant.sh bmstamps -DEXABM4D_BM_STAMPS; add
--DEXABM4D_BM_HANDWAIT=0 for the form whose waits hipcc places, -DEXABM4D_BM_STEPADDR=0 for
-the form of before DESIGN.md 5.2r).  One SIZE^3 uint16 launch after a warm-up launch.  "barriers_by_wave": the
+LIB is a library built with -DEXABM4D_BM_STAMPS (tools/dbg/build_variant.sh bmstamps -DEXABM4D_BM_STAMPS; the
+stamp function itself is csrc/kernel_stamps.h.  The forms of before DESIGN.md 5.2o and 5.2r, whose stamps are
+profiles/*/bm_stamps_parent.json, are in the history: docs/DESIGN_HISTORY.md, "Retired A/B switches").  One SIZE^3 uint16 launch after a warm-up launch.  "barriers_by_wave": the
 exchange-barrier slot per wave index and per barrier of a (dz, pass) -- the wave that waits least arrived last."""
 import os, sys, ctypes, json, numpy as np
 os.environ["EXABM4D_LIB"] = os.path.abspath(sys.argv[1])

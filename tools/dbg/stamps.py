@@ -1,6 +1,6 @@
 """Per-phase s_memtime sums of the stage kernels: python tools/dbg/stamps.py [LABEL] > stamps.json
-Needs tools/dbg/libexabm4d_stamps.so, a library built with -DEXABM4D_STAMPS (tools/dbg/build_variant.sh), or
-the library EXABM4D_STAMPS_LIB names.  SIZE (default 512) is the cube's edge.  Nine slots per kernel."""
+Needs tools/dbg/libexabm4d_stamps.so, a library built with -DEXABM4D_STAMPS (tools/dbg/build_variant.sh; the
+stamp function itself is csrc/kernel_stamps.h), or the library EXABM4D_STAMPS_LIB names.  SIZE (default 512) is the cube's edge.  Nine slots per kernel."""
 import os, sys, ctypes, json
 os.environ["EXABM4D_LIB"] = os.environ.get("EXABM4D_STAMPS_LIB") or os.path.join(
     os.path.dirname(os.path.abspath(__file__)), "libexabm4d_stamps.so")
