@@ -28,6 +28,7 @@ c_vp = ctypes.c_void_p
 
 KEY_EMPTY = 0xFFFFFFFF
 LABEL_SET_MAX = 1024        # exabm4d.h EXABM4D_LABEL_SET_MAX: distinct labels one patch's device set holds
+RASTER_BOXES = 256          # exabm4d.h EXABM4D_RASTER_BOXES: box origins one rasteriser launch keeps in LDS
 SEG_STATS_K = 23            # exabm4d.h EXABM4D_SEG_STATS_K
 GAUSS_MAX_RADIUS = 64       # exabm4d.h EXABM4D_GAUSS_MAX_RADIUS
 NOISE_LEVELS = 49           # exabm4d.h EXABM4D_NOISE_LEVELS
@@ -236,6 +237,8 @@ SIGNATURES = {
     "exabm4d_label_set_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp]),
     "exabm4d_segment_stats_dev": (_I, [_CTX, c_vp, _I, c_vp, _I, c_vp, _I, _I, _I, _I, _I, c_vp, c_vp, _I,
                                        c_vp]),
+    "exabm4d_foreground_counts_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, _F, _I, c_vp, c_vp]),
+    "exabm4d_annotation_masks_dev": (_I, [_CTX, c_vp, _I, _I, c_vp, _SZ, c_vp, _I, _I, _I, _I, _I, c_vp]),
     "exabm4d_evaluate_batch_dev": (_I, [_CTX, c_vp, _I, c_vp, _I, c_vp, _I, c_vp, _I, _SZ, ctypes.c_double, c_u32p,
                                         c_vp]),
     "exabm4d_gather_boxes_dev": (_I, [_CTX, c_vp, _SZ, c_vp, _I, c_vp, _I, c_vp, _I, _I, _I, _I, _I, _F,
@@ -929,6 +932,28 @@ class Context:
             self.DTYPES[np.dtype(raw_dtype)], _ptr(smooth), int(batch), nz, ny, nx, int(lag),
             ip.ctypes.data_as(c_vp), ik.ctypes.data_as(c_vp), len(ip), out.ctypes.data_as(c_vp)))
         return out
+
+    # -- patch samplers ------------------------------------------------------------
+    def foreground_counts(self, raw, dtype, batch, shape, k=6.0, dilate=1):
+        """``int(make_foreground_mask(raw[b], k, dilate).sum())`` of ``batch`` uint16 or float32 patches on the
+        device, as a (batch,) uint32 array; no mask is written for ``dilate`` 0 or 1."""
+        counts = np.empty(int(batch), dtype=np.uint32)
+        nz, ny, nx = shape
+        self._check(lib().exabm4d_foreground_counts_dev(
+            self.handle, _ptr(raw), self.DTYPES[np.dtype(dtype)], int(batch), int(nz), int(ny), int(nx), float(k),
+            int(dilate), counts.ctypes.data_as(c_vp), None))
+        return counts
+
+    def annotation_masks(self, labels, label_dtype, seg_dilate, points, npoints, starts, skel_dilate, shape, mask):
+        """``make_segmentation_mask(labels[b], seg_dilate) | make_skeleton_mask(points, starts[b], shape,
+        skel_dilate)`` of every box into the device bytes ``mask``.  ``labels``: None or (batch, *shape) labels on
+        the device; ``points``: None or ``npoints`` int32 zyx triples on the device; ``starts``: host (batch, 3)."""
+        starts = np.ascontiguousarray(starts, dtype=np.int32).reshape(-1, 3)
+        nz, ny, nx = shape
+        self._check(lib().exabm4d_annotation_masks_dev(
+            self.handle, _ptr(labels), LABEL_DTYPES[np.dtype(label_dtype)] if labels is not None else 0,
+            int(seg_dilate), _ptr(points), int(npoints), starts.ctypes.data_as(c_vp), int(skel_dilate), len(starts),
+            int(nz), int(ny), int(nx), _ptr(mask)))
 
     # -- validation scoring (DESIGN.md 5.12) ------------------------------------------------------
     def evaluate_batch(self, pred, pred_dtype, raw, raw_dtype, target, target_dtype, mask, batch, n, k, ranks):

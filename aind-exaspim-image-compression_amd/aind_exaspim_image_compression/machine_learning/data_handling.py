@@ -16,8 +16,9 @@ by the reference.
 Provided with the reference's names and behaviour: ``build_training_example`` (:44-82),
 ``CachedPatchDataset`` (:1015-1187), ``CachedValidateDataset`` (:1190-1217); plus
 ``PatchCacheWriter`` / ``write_patch_cache`` (the file-writing half of ``precompute()``) and
-``load_cached_transform`` (``scripts/train_bm4dnet.py:42-79``).  The cloud datasets, samplers and
-the resample loop of the reference module are out of scope: the writer takes
+``load_cached_transform`` (``scripts/train_bm4dnet.py:42-79``).  The cloud datasets are out of scope
+(SURVEY.md section 8); the samplers and the resample loop over local stores are
+``machine_learning/sampling.py``, whose ``precompute_cache`` feeds this writer.  The writer itself takes
 the patches from the caller.  The masks it may take too; without them it builds the reference's
 ``sample_counts`` fallback (``data_handling.py:929-930``), ``make_foreground_mask`` of each raw
 patch, on the device (``metrics.foreground_masks``).  The mask builders and the coherence gate the

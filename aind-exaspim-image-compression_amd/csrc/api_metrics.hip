@@ -107,13 +107,7 @@ int exabm4d_noise_table_dev(exabm4d_ctx* ctx, const void* vol, int dtype, int nz
 }
 
 // ---- patch-cache foreground masks and coherence gate ---------------------------------
-static int check_patches(exabm4d_ctx* ctx, int batch, int nz, int ny, int nx) {
-    if (batch < 1 || nz < 1 || ny < 1 || nx < 1) return fail(ctx, EXABM4D_ERR_INVALID, "bad batch / sizes");
-    if ((long long)nz * ny * nx >= (1ll << 32) || (long long)nz * ny * nx * batch > (1ll << 40))
-        return fail(ctx, EXABM4D_ERR_INVALID, "patch or batch too large");
-    return EXABM4D_OK;
-}
-
+// check_patches and bad_label_dtype are shared with api_sampler.hip (exabm4d_api.h)
 static_assert(LS_MAX == EXABM4D_LABEL_SET_MAX && SEG_STATS_K == EXABM4D_SEG_STATS_K &&
               GF_MAXR == EXABM4D_GAUSS_MAX_RADIUS && LBL_I64 == EXABM4D_LBL_I64, "exabm4d.h and exabm4d_kernels.h differ");
 
@@ -174,8 +168,6 @@ int exabm4d_gaussian_filter3d_dev(exabm4d_ctx* ctx, const void* src, int dtype, 
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return EXABM4D_OK;
 }
-
-static bool bad_label_dtype(int d) { return d < EXABM4D_LBL_U8 || d > EXABM4D_LBL_I64; }
 
 int exabm4d_label_set_dev(exabm4d_ctx* ctx, const void* labels, int label_dtype, int batch, int nz, int ny,
                           int nx, uint64_t* keys_host, uint32_t* counts_host, uint32_t* n_host,

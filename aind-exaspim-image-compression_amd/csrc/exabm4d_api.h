@@ -75,6 +75,15 @@ int carve(exabm4d_ctx* ctx, DevBuf& buf, size_t guard, Layout& out, F&& layout) 
     return EXABM4D_OK;
 }
 
+// batches of patches (the mask, coherence-gate and sampler entries): sizes the kernels' 32-bit voxel indices hold
+inline int check_patches(exabm4d_ctx* ctx, int batch, int nz, int ny, int nx) {
+    if (batch < 1 || nz < 1 || ny < 1 || nx < 1) return fail(ctx, EXABM4D_ERR_INVALID, "bad batch / sizes");
+    if ((long long)nz * ny * nx >= (1ll << 32) || (long long)nz * ny * nx * batch > (1ll << 40))
+        return fail(ctx, EXABM4D_ERR_INVALID, "patch or batch too large");
+    return EXABM4D_OK;
+}
+inline bool bad_label_dtype(int d) { return d < EXABM4D_LBL_U8 || d > EXABM4D_LBL_I64; }
+
 }  // namespace exabm4d
 
 struct exabm4d_ctx {

@@ -345,6 +345,9 @@ hipError_t launch_fg_threshold(const void* raw, int dtype, int batch, size_t n, 
 hipError_t launch_dilate(const uint8_t* in, const void* raw, int raw_dtype, const float* thr, int batch,
                          int nz, int ny, int nx, int iterations, uint8_t* tmp, uint8_t* out,
                          hipStream_t s);
+// the source is labels > 0 (ldtype: LBL_*)
+hipError_t launch_dilate_labels(const void* labels, int ldtype, int batch, int nz, int ny, int nx, int iterations,
+                                uint8_t* tmp, uint8_t* out, hipStream_t s);
 // src: dtype 1 float32, 2 float64
 hipError_t launch_gaussian3d(const void* src, int dtype, int batch, int nz, int ny, int nx,
                              const GaussWeights& w, double* tmp, double* out, hipStream_t s);
@@ -354,6 +357,24 @@ hipError_t launch_label_set(const void* labels, int ldtype, int batch, size_t n,
 hipError_t launch_segment_stats(const void* labels, int ldtype, const void* raw, int rdtype, const double* smooth,
                                 int nz, int ny, int nx, int lag, const int32_t* item_patch,
                                 const unsigned long long* item_key, int items, double* out, hipStream_t s);
+
+// ---- patch samplers (sampler_kernels.hip) ------------------------------------------------
+constexpr int RASTER_BOXES = 256;   // box origins one rasteriser launch keeps in LDS (3 KiB)
+struct RasterBounds {
+    long long lo[3], hi[3];         // the bounding box of a launch's boxes, zyx, hi exclusive
+};
+// counts[b] = voxels of patch b that are set, or (iterate) have a face neighbour inside the patch that is; counts
+// are zeroed on the stream first.  The source is raw > thr[b] (dtype 0 uint16, 1 float32) or a mask.
+long long count_workgroups(int batch, int nz, int ny, int nx);   // the grid of the two launchers: keep below 2^31
+hipError_t launch_count_above(const void* raw, int dtype, const float* thr, int batch, int nz, int ny, int nx,
+                              int iterate, uint32_t* counts, hipStream_t s);
+hipError_t launch_count_mask(const uint8_t* mask, int batch, int nz, int ny, int nx, int iterate, uint32_t* counts,
+                             hipStream_t s);
+// out[b][p - starts[b]] = 1 for every point p (int32 zyx triples) inside box b of nbox <= RASTER_BOXES boxes;
+// pts, starts and out are device arrays, out is not cleared
+hipError_t launch_raster_points(const int32_t* pts, size_t npts, const int32_t* starts, int nbox, int nz, int ny,
+                                int nx, const RasterBounds& bb, uint8_t* out, hipStream_t s);
+hipError_t launch_or_bytes(const uint8_t* in, size_t total, uint8_t* out, hipStream_t s);   // out |= in, 0 / 1 bytes
 
 // ---- validation scoring (validate_kernels.hip) -------------------------------------------
 constexpr int VAL_K = 16;           // doubles per patch (exabm4d.h EXABM4D_EVAL_K)

@@ -8,7 +8,7 @@
 //                         NaN (a NaN voxel, an infinite median).  One workgroup per patch.
 //   dilate_kernel         one iteration of scipy.ndimage.binary_dilation with the 6-neighbour cross
 //                         and border_value 0; the first iteration can read raw > thr[b] instead of
-//                         a mask (the threshold fused into the first pass).
+//                         a mask (the threshold fused into the first pass), or labels > 0.
 //   gauss1d_kernel        one axis of scipy.ndimage.gaussian_filter in fp64 with scipy's "reflect"
 //                         boundary (period 2n, so axes shorter than the radius reflect again) and
 //                         scipy's symmetric accumulation order (ni_filters.c NI_Correlate1D).
@@ -22,6 +22,7 @@
 // Every floating-point result is deterministic: fixed thread-to-voxel mappings and fixed-order
 // workgroup reductions, no floating-point atomics (the LDS atomics are integer counters).
 #include "exabm4d_kernels.h"
+#include "mask_src.h"
 
 namespace exabm4d {
 
@@ -161,17 +162,7 @@ hipError_t launch_fg_threshold(const void* raw, int dtype, int batch, size_t n, 
 // ---- binary dilation, 6-neighbour cross, border_value 0 ---------------------------------------------
 constexpr int DIL_T = 256;
 
-template <class T>
-struct AboveThr {
-    const T* p;
-    const float* thr;
-    size_t n;
-    __device__ bool operator()(size_t i) const { return (float)p[i] > thr[i / n]; }
-};
-struct MaskSrc {
-    const uint8_t* p;
-    __device__ bool operator()(size_t i) const { return p[i] != 0; }
-};
+// the sources (AboveThr, MaskSrc, LabelSrc) are in mask_src.h
 
 // out[v] = src(v) or src of a face neighbour inside the patch; iterate == 0 only copies src
 template <class Src>
@@ -197,28 +188,21 @@ static unsigned grid_for(size_t total, int threads) {
     return (unsigned)(b ? b : 1);
 }
 
-// iterations of the cross on a batch of masks (or of raw > thr when thr != NULL): `iterations`
-// passes ping-ponging between out and tmp, arranged so that the last one writes out.
-hipError_t launch_dilate(const uint8_t* in, const void* raw, int raw_dtype, const float* thr, int batch,
-                         int nz, int ny, int nx, int iterations, uint8_t* tmp, uint8_t* out,
-                         hipStream_t s) {
+// `iterations` passes of the cross ping-ponging between out and tmp, arranged so that the last one writes out;
+// first(grid, iterate, dst) launches pass 0 from the caller's source, the later passes read the mask before them.
+template <class First>
+static hipError_t dilate_passes(First&& first, int batch, int nz, int ny, int nx, int iterations, uint8_t* tmp,
+                                uint8_t* out, hipStream_t s) {
     const size_t n = (size_t)nz * ny * nx, total = n * batch;
     const unsigned g = grid_for(total, DIL_T);
     const int passes = iterations > 0 ? iterations : 1;
+    const int iterate = iterations > 0 ? 1 : 0;
     for (int it = 0; it < passes; it++) {
         uint8_t* dst = ((passes - 1 - it) % 2 == 0) ? out : tmp;
-        const int iterate = iterations > 0 ? 1 : 0;
-        if (it == 0 && thr) {
-            if (raw_dtype == 0)
-                hipLaunchKernelGGL(dilate_kernel<AboveThr<uint16_t>>, dim3(g), dim3(DIL_T), 0, s,
-                                   AboveThr<uint16_t>{(const uint16_t*)raw, thr, n}, nz, ny, nx, total,
-                                   iterate, dst);
-            else
-                hipLaunchKernelGGL(dilate_kernel<AboveThr<float>>, dim3(g), dim3(DIL_T), 0, s,
-                                   AboveThr<float>{(const float*)raw, thr, n}, nz, ny, nx, total, iterate,
-                                   dst);
+        if (it == 0) {
+            first(g, iterate, dst);
         } else {
-            const uint8_t* srcp = it == 0 ? in : (((passes - it) % 2 == 0) ? out : tmp);
+            const uint8_t* srcp = ((passes - it) % 2 == 0) ? out : tmp;
             hipLaunchKernelGGL(dilate_kernel<MaskSrc>, dim3(g), dim3(DIL_T), 0, s, MaskSrc{srcp}, nz, ny, nx,
                                total, iterate, dst);
         }
@@ -226,6 +210,46 @@ hipError_t launch_dilate(const uint8_t* in, const void* raw, int raw_dtype, cons
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+template <class Src>
+static void dilate_from(Src src, unsigned g, int nz, int ny, int nx, size_t total, int iterate, uint8_t* dst,
+                        hipStream_t s) {
+    hipLaunchKernelGGL(dilate_kernel<Src>, dim3(g), dim3(DIL_T), 0, s, src, nz, ny, nx, total, iterate, dst);
+}
+
+// iterations of the cross on a batch of masks (or of raw > thr when thr != NULL)
+hipError_t launch_dilate(const uint8_t* in, const void* raw, int raw_dtype, const float* thr, int batch,
+                         int nz, int ny, int nx, int iterations, uint8_t* tmp, uint8_t* out,
+                         hipStream_t s) {
+    const size_t n = (size_t)nz * ny * nx, total = n * batch;
+    return dilate_passes(
+        [&](unsigned g, int iterate, uint8_t* dst) {
+            if (thr && raw_dtype == 0)
+                dilate_from(AboveThr<uint16_t>{(const uint16_t*)raw, thr, n}, g, nz, ny, nx, total, iterate, dst, s);
+            else if (thr)
+                dilate_from(AboveThr<float>{(const float*)raw, thr, n}, g, nz, ny, nx, total, iterate, dst, s);
+            else
+                dilate_from(MaskSrc{in}, g, nz, ny, nx, total, iterate, dst, s);
+        },
+        batch, nz, ny, nx, iterations, tmp, out, s);
+}
+
+// the same on labels > 0 (make_segmentation_mask): the comparison is fused into the first pass
+hipError_t launch_dilate_labels(const void* labels, int ldtype, int batch, int nz, int ny, int nx, int iterations,
+                                uint8_t* tmp, uint8_t* out, hipStream_t s) {
+    const size_t total = (size_t)nz * ny * nx * batch;
+    return dilate_passes(
+        [&](unsigned g, int iterate, uint8_t* dst) {
+            switch (ldtype) {
+                case LBL_U8: dilate_from(LabelSrc<uint8_t>{(const uint8_t*)labels}, g, nz, ny, nx, total, iterate, dst, s); break;
+                case LBL_U32: dilate_from(LabelSrc<uint32_t>{(const uint32_t*)labels}, g, nz, ny, nx, total, iterate, dst, s); break;
+                case LBL_U64: dilate_from(LabelSrc<uint64_t>{(const uint64_t*)labels}, g, nz, ny, nx, total, iterate, dst, s); break;
+                case LBL_I32: dilate_from(LabelSrc<int32_t>{(const int32_t*)labels}, g, nz, ny, nx, total, iterate, dst, s); break;
+                default: dilate_from(LabelSrc<int64_t>{(const int64_t*)labels}, g, nz, ny, nx, total, iterate, dst, s); break;
+            }
+        },
+        batch, nz, ny, nx, iterations, tmp, out, s);
 }
 
 // ---- Gaussian smoothing, one axis, fp64 ---------------------------------------------------------------

@@ -857,6 +857,38 @@ int exabm4d_segment_stats_dev(exabm4d_ctx* ctx, const void* labels, int label_dt
                               const int32_t* item_patch_host, const uint64_t* item_key_host, int n_items,
                               double* out_host);
 
+/* ---- patch samplers (data_handling.py:446-702) ---------------------------------------
+ * int(make_foreground_mask(raw, k, dilate).sum()) of every patch, as sample_bright_voxel scores its candidates
+ * (data_handling.py:693): counts_host[batch] uint32.  The threshold is that of exabm4d_foreground_masks_dev, its
+ * NaN rule included: a patch with a NaN threshold counts 0 and does not affect the others.  For dilate 0 or 1 no
+ * mask is written to memory: a voxel counts when it is above the threshold or (dilate 1) has a face neighbour
+ * inside the patch that is -- one iteration of the 6-neighbour cross with border 0.  dilate >= 2 makes the first
+ * dilate - 1 iterations through the mask path into the context's memory and the last one while counting.  The
+ * counts are integer sums (per wave by ballot and population count, one integer add per workgroup), so they do
+ * not depend on the launch shape or on the batch size.  Checked on the host: non-NULL raw and counts_host, raw
+ * EXABM4D_DT_U16 or EXABM4D_DT_F32, dilate >= 0, the sizes as for the mask entries.  thr_host: NULL or `batch`
+ * floats.  One synchronisation of the context's stream, at the end. */
+int exabm4d_foreground_counts_dev(exabm4d_ctx* ctx, const void* raw, int dtype, int batch, int nz, int ny, int nx,
+                                  float k, int dilate, uint32_t* counts_host, float* thr_host);
+
+/* annotation_mask of a batch of boxes (data_handling.py:446-481): mask[b] (device, batch * nz * ny * nx bytes,
+ * 0 / 1) = make_segmentation_mask(labels[b], seg_dilate) | make_skeleton_mask(points, starts_host[b], (nz, ny,
+ * nx), skel_dilate).  labels: NULL, or `batch` label patches on the device of label_dtype EXABM4D_LBL_*; they give
+ * labels > 0, dilated seg_dilate times.  points: NULL, or npoints int32 (z, y, x) voxel triples on the device (one
+ * upload per brain serves every call; with npoints == 0 the pointer is not read and the contribution is empty); a
+ * point sets its voxel in every box that contains it -- box b covers starts_host[b] + [0, nz) x [0, ny) x [0, nx),
+ * starts_host[batch][3] a host array -- and that mask is dilated skel_dilate times.  Duplicate points, overlapping
+ * boxes and boxes away from every point are fine.  Both NULL gives EXABM4D_ERR_INVALID: the reference's None is
+ * the caller's case.  Checked on the host: the pointers, the label type, dilations >= 0, the sizes as for the
+ * mask entries, npoints <= 2^40.  The mask is cleared and everything launched on the context's stream: the boxes'
+ * origins are kept in LDS, EXABM4D_RASTER_BOXES per launch, so a larger batch takes several launches; the stores
+ * are plain bytes of 1 (equal concurrent stores, no atomics), which makes the mask deterministic.  One
+ * synchronisation of the context's stream, at the end; the context's memory is used for the intermediate masks. */
+#define EXABM4D_RASTER_BOXES 256
+int exabm4d_annotation_masks_dev(exabm4d_ctx* ctx, const void* labels, int label_dtype, int seg_dilate,
+                                 const int32_t* points, size_t npoints, const int32_t* starts_host, int skel_dilate,
+                                 int batch, int nz, int ny, int nx, uint8_t* mask);
+
 /* ---- validation scoring: evaluate_example of every patch of a batch ----------------
  * The count-space metrics behind the reference's Trainer.validate (machine_learning/metrics.py:352-424) for
  * `batch` patches of n voxels, contiguous in HBM: pred, raw and target are EXABM4D_DT_U16 or EXABM4D_DT_F32
