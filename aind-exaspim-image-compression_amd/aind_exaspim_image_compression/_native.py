@@ -95,6 +95,26 @@ class PgNoise(ctypes.Structure):
     ]
 
 
+class PatchGrid(ctypes.Structure):
+    """``exabm4d_patch_grid`` (include/exabm4d.h): a brick's patches as a regular grid."""
+
+    _fields_ = [
+        ("first", ctypes.c_int32 * 3),
+        ("count", ctypes.c_int32 * 3),
+        ("stride", ctypes.c_int32),
+        ("patch", ctypes.c_int32),
+    ]
+
+
+def patch_grid(first, count, stride, patch):
+    """A filled ``PatchGrid``: per axis (z, y, x) the first patch index and the number of patches."""
+    g = PatchGrid()
+    g.first[:] = [int(v) for v in first]
+    g.count[:] = [int(v) for v in count]
+    g.stride, g.patch = int(stride), int(patch)
+    return g
+
+
 PG_INVERSES = {"algebraic": 0, "asymptotic": 1, "closed_form": 2}    # exabm4d.h EXABM4D_PG_INVERSE_*
 
 
@@ -112,6 +132,7 @@ _CTX = c_vp
 _PP = ctypes.POINTER(Params)
 _NP = ctypes.POINTER(PgNoise)
 _TP = ctypes.POINTER(Transform)
+_GP = ctypes.POINTER(PatchGrid)
 _I, _F, _SZ = ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 SIGNATURES = {
     "exabm4d_version": (_I, []),
@@ -196,6 +217,8 @@ SIGNATURES = {
     "exabm4d_tile_gather_dev": (_I, [_CTX, c_vp, _I, _I, _I, c_i32p, _I, _I, c_vp]),
     "exabm4d_tile_accumulate_dev": (_I, [_CTX, c_vp, c_i32p, _I, _I, _I, c_vp, c_vp, _I, _I, _I]),
     "exabm4d_tile_finalize_u16_dev": (_I, [_CTX, _TP, c_vp, c_vp, c_vp, _SZ]),
+    "exabm4d_tile_gather_u16_dev": (_I, [_CTX, c_vp, c_i32p, c_i32p, c_i32p, _TP, _GP, ctypes.c_longlong, _I, c_vp]),
+    "exabm4d_tile_stitch_u16_dev": (_I, [_CTX, c_vp, ctypes.c_longlong, _GP, _I, c_i32p, c_i32p, c_i32p, _TP, c_vp]),
     "exabm4d_chunk_byte_histograms_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, _I, c_vp]),
     "exabm4d_dctq_forward_dev": (_I, [_CTX, c_vp, _I, _I, _I, ctypes.c_float, c_vp]),
     "exabm4d_dctq_inverse_dev": (_I, [_CTX, c_vp, _I, _I, _I, ctypes.c_float, c_vp]),
@@ -719,6 +742,23 @@ class Context:
     def tile_finalize(self, tf, acc, wgt, out, n):
         self._check(lib().exabm4d_tile_finalize_u16_dev(self.handle, ctypes.byref(tf), _ptr(acc),
                                                         _ptr(wgt), _ptr(out), n))
+
+    def tile_gather_u16(self, tf, win, win_origin, win_dims, vol_dims, grid, k0, nb, out):
+        """Patches ``[k0, k0 + nb)`` of ``grid`` (a ``PatchGrid``) from the uint16 window ``win`` -> ``out``
+        (nb, patch, patch, patch) fp32: transformed inside the volume, 0.0 beyond it.  ValueError for a window that
+        does not hold the grid's patches or a batch past the grid."""
+        tri = [(ctypes.c_int32 * 3)(*(int(v) for v in t)) for t in (win_origin, win_dims, vol_dims)]
+        self._check(lib().exabm4d_tile_gather_u16_dev(self.handle, _ptr(win), tri[0], tri[1], tri[2],
+                                                      ctypes.byref(tf), ctypes.byref(grid), int(k0), int(nb),
+                                                      _ptr(out)))
+
+    def tile_stitch_u16(self, tf, preds, n_patches, grid, trim, box_origin, box_dims, vol_dims, out):
+        """All predictions of ``grid`` (``preds``: (n_patches, patch, patch, patch) fp32, raster order) -> the
+        uint16 counts of the box, dense in ``out``."""
+        tri = [(ctypes.c_int32 * 3)(*(int(v) for v in t)) for t in (box_origin, box_dims, vol_dims)]
+        self._check(lib().exabm4d_tile_stitch_u16_dev(self.handle, _ptr(preds), int(n_patches), ctypes.byref(grid),
+                                                      int(trim), tri[0], tri[1], tri[2], ctypes.byref(tf),
+                                                      _ptr(out)))
 
     def chunk_byte_histograms(self, vol, shape, chunk, hist):
         nz, ny, nx = shape

@@ -16,6 +16,7 @@ voxels along every axis receive zero weight and come out as ``transform.inverse(
 import contextlib
 import itertools
 import os
+import time
 
 import numpy as np
 import torch
@@ -416,6 +417,23 @@ def quick_start(model):
     return model
 
 
+def _forward_plan(model, fast, amp_dtype):
+    """How ``predict`` and ``predict_store`` run their forward passes: ``(run, loop_amp, call_amp)`` -- what to call
+    on a batch, the context around the whole loop and the one around each call.  ``run`` is an NDHWC shadow of an
+    eval-mode fp32 module under ``fast``, else ``model`` itself."""
+    run = model
+    shadowed = False
+    if fast and isinstance(model, torch.nn.Module) and not model.training and \
+            all(p.dtype == torch.float32 for p in model.parameters()) and any(True for _ in model.parameters()):
+        run = _ndhwc_shadow(model, half=amp_dtype is not None)
+        shadowed = True
+    # the shadow's forward passes share one autocast region (its weights are cast once per call, not per batch);
+    # a caller's module or callable gets autocast around each call
+    amp = (lambda: torch.autocast("cuda", dtype=amp_dtype)) if amp_dtype is not None else contextlib.nullcontext
+    loop_amp, call_amp = (amp, contextlib.nullcontext) if shadowed else (contextlib.nullcontext, amp)
+    return run, loop_amp, call_amp
+
+
 def predict(img, model, transform, batch_size=32, patch_size=64, overlap=12, trim=5,
             verbose=True, fast=True, precision="fp32"):
     """Denoise a 3-D image by overlapping-patch inference; returns uint16 counts.
@@ -449,16 +467,7 @@ def predict(img, model, transform, batch_size=32, patch_size=64, overlap=12, tri
     n = int(np.prod(shape))
     dev = _model_device(model)
     ctx = _native.context(dev.index or 0)
-    run = model
-    shadowed = False
-    if fast and isinstance(model, torch.nn.Module) and not model.training and \
-            all(p.dtype == torch.float32 for p in model.parameters()) and any(True for _ in model.parameters()):
-        run = _ndhwc_shadow(model, half=amp_dtype is not None)
-        shadowed = True
-    # the shadow's forward passes share one autocast region (its weights are cast once per call, not per batch);
-    # a caller's module or callable gets autocast around each call
-    amp = (lambda: torch.autocast("cuda", dtype=amp_dtype)) if amp_dtype is not None else contextlib.nullcontext
-    loop_amp, call_amp = (amp, contextlib.nullcontext) if shadowed else (contextlib.nullcontext, amp)
+    run, loop_amp, call_amp = _forward_plan(model, fast, amp_dtype)
 
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
@@ -505,6 +514,202 @@ def predict(img, model, transform, batch_size=32, patch_size=64, overlap=12, tri
     if pbar is not None:
         pbar.close()
     return out
+
+
+def predict_store(src, dst_path, model, transform, batch_size=32, patch_size=64, overlap=12, trim=5,
+                  verbose=True, fast=True, precision="fp32", codec=None, chunks=None, attributes=None,
+                  budget_bytes=16 << 30, device=None, stats=None):
+    """A stored volume in, the network's denoised and coded store out, without ever holding the volume: the result is
+    ``write_zarr(predict(read_zarr(src)[0, 0], model, transform, ...), dst_path, ...)`` for a volume of any size
+    (DESIGN.md 5.16).
+
+    ``src``: a store's path or a ``StoredArray`` of uint16 (opened for the device used here).  The destination is
+    made with ``chunk_store.create_zarr`` (``codec``: default ``ExacCodec(2)``; ``chunks``: default the source's;
+    ``attributes``).  ``model``, ``transform``, ``batch_size``, ``patch_size``, ``overlap``, ``trim``, ``fast`` and
+    ``precision`` mean what they mean in ``predict``.  ``device``: default the model's.
+
+    The volume is cut into bricks of whole destination chunks that cost at most ``budget_bytes`` of device memory each
+    (``utils.store_predict.plan_predict``; a single chunk is taken whatever it costs).  Per brick: the window its
+    patches read comes from the source by a region read that stays on the device, every patch of ``predict``'s tiling
+    whose core meets the brick is cut from it, transformed and run -- the same input values, zero padding included --
+    and all predictions of the brick are stitched in one launch that adds them per voxel in ``predict``'s order (raster
+    order of patch starts) and applies the same normalisation, inverse transform and rounding; the counts are
+    scattered into a pool of destination chunks, coded and committed.  For a model whose output rows do not depend on
+    the rest of the batch the store is therefore chunk file for chunk file what the whole-volume call gives.  Nothing
+    is carried between bricks: a patch whose core meets several bricks runs once for each.
+
+    ``transform`` is used as given: no per-volume offset is estimated, nothing here sees the whole volume.  Measure a
+    region read instead -- ``estimate_offset(arr[0, 0, z0:z1, y0:y1, x0:x1])`` -- and pass
+    ``build_volume_transform(base, offset=...)``.
+
+    Returns raw bytes / stored chunk bytes, like ``write_zarr``.  ``stats`` (a dict) receives ``seconds`` per phase
+    (read, gather, forward, stitch, scatter, encode, files_write; the stream is synchronised around the phases, per
+    batch for gather and forward, only when ``stats`` is given -- otherwise only a read, an encode or freeing a buffer
+    waits for it), ``bricks``, ``patches_run``, ``patches_unique`` (``count_patches`` of
+    the volume) and ``largest_alloc``, the most device bytes held here at one time (the model's activations are the
+    framework's and are not counted)."""
+    from aind_exaspim_image_compression.utils import chunk_store, store_predict, store_write
+    from aind_exaspim_image_compression.utils.chunk_codec import ExacCodec
+    # -- every argument check, before a context exists
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {sorted(PRECISIONS)}, not {precision!r}")
+    amp_dtype = PRECISIONS[precision]
+    batch_size, patch_size, overlap, trim = int(batch_size), int(patch_size), int(overlap), int(trim)
+    if batch_size < 1:
+        raise ValueError("predict_store: batch_size >= 1")
+    if patch_size < 1 or not overlap < patch_size:
+        raise ValueError("predict_store: patch_size >= 1 and overlap < patch_size")
+    if trim < 0 or patch_size - 2 * trim < 1:
+        raise ValueError("predict_store: 0 <= trim and patch_size - 2 * trim >= 1")
+    budget = int(budget_bytes)
+    if budget < 1:
+        raise ValueError("predict_store: budget_bytes must be positive")
+    if chunks is not None:
+        chunks = tuple(int(c) for c in chunks)
+        if len(chunks) != 5 or chunks[:2] != (1, 1) or min(chunks) < 1:
+            raise ValueError("chunks must be (1, 1, cz, cy, cx)")
+    # the device: the caller's, else the model's (no context is needed to tell); a path is opened for it
+    dev = torch.device("cuda", int(device)) if device is not None else _model_device(model)
+    index = dev.index or 0
+    try:
+        arr = src if hasattr(src, "read_patches") else chunk_store.open_zarr(src, device=index)
+    except NotImplementedError as e:
+        raise ValueError("predict_store: the source must hold uint16 (%s)" % e) from None
+    if np.dtype(arr.dtype) != np.uint16:
+        raise ValueError("predict_store: the source must hold uint16")
+    if int(arr.device if arr.device is not None else _native.default_device()) != index:
+        raise ValueError("predict_store: the source was opened for another device than cuda:%d, the one used here"
+                         % index)
+    shape = tuple(int(s) for s in arr.shape[2:])
+    chunks = chunks if chunks is not None else tuple(int(c) for c in arr.chunks)
+    codec = codec or ExacCodec(2)
+    bricks = store_predict.plan_predict(shape, chunks[2:], patch_size, overlap, trim, batch_size, budget)
+    most = max(b.n_patches for b in bricks)
+    unique = count_patches(_ShapeOnly((1, 1) + shape), patch_size, overlap)
+
+    _miopen_defaults()
+    ctx = _native.context(index)
+    out = chunk_store.create_zarr(dst_path, shape, chunks, codec=codec, attributes=attributes, overwrite=True,
+                                  device=index)
+    run, loop_amp, call_amp = _forward_plan(model, fast, amp_dtype)
+    tf = transform.native_struct()
+    pv = patch_size ** 3
+    st = store_write._new_stats()
+    seconds = dict.fromkeys(("read", "gather", "forward", "stitch", "scatter", "encode", "files_write"), 0.0)
+    timed = stats is not None
+    held = {"now": 0, "most": 0}
+
+    def hold(nbytes):
+        held["now"] += nbytes
+        held["most"] = max(held["most"], held["now"])
+
+    pbar = None
+    if verbose:
+        from tqdm import tqdm
+        pbar = tqdm(total=sum(b.n_patches for b in bricks), desc="Denoise")
+    arr_pool_cap, arr.max_pool_bytes = arr.max_pool_bytes, max(1, min(arr.max_pool_bytes,
+                                                                    budget // store_predict.READER_SHARE))
+    written, patches_run, seen_batch = 0, 0, False
+    d_table = None
+    try:
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            ctx.set_stream(stream.cuda_stream)       # kernels, the codecs and the model share one stream
+
+            def clock(sync):
+                if sync:
+                    stream.synchronize()
+                return time.perf_counter()
+
+            # one input batch and one buffer of predictions, sized for the largest brick, for the whole call
+            batch = torch.zeros((batch_size, 1, patch_size, patch_size, patch_size), dtype=torch.float32, device=dev)
+            preds = torch.empty((max(most, 1), 1, patch_size, patch_size, patch_size), dtype=torch.float32,
+                                device=dev)
+            hold(4 * pv * (batch_size + max(most, 1)))
+            d_table = store_write.bound_table_on_device(out, ctx)
+            for brick in bricks:
+                n_patches = brick.n_patches
+                grid = _native.patch_grid(brick.first, brick.count, patch_size - overlap, patch_size)
+                if n_patches:
+                    # the window in z slabs, so that the reader's pool stays under its cap; the slabs lie one after
+                    # another: one window, as tall as the plan priced it
+                    wz, wy, wx = brick.win_extent
+                    slabs, slab = store_predict.window_slabs(wz, chunks[2])
+                    win_dims = (slabs * slab, wy, wx)
+                    t0 = time.perf_counter()
+                    d_win = arr.read_patches([(brick.win_origin[0] + j * slab,) + tuple(brick.win_origin[1:])
+                                              for j in range(slabs)], (slab, wy, wx), is_center=False, out="device")
+                    hold(2 * int(np.prod(win_dims)))
+                    seconds["read"] += time.perf_counter() - t0
+                    try:
+                        with loop_amp():
+                            for k0 in range(0, n_patches, batch_size):
+                                nb = min(batch_size, n_patches - k0)
+                                t0 = clock(timed)
+                                ctx.tile_gather_u16(tf, d_win, brick.win_origin, win_dims, shape, grid, k0, nb, batch)
+                                t1 = clock(timed)
+                                # predict's rule for a short batch: at full size once the tensor holds earlier rows
+                                # (MIOpen sees ONE shape), for eval-mode modules only; the call's first batch as it is
+                                full = nb < batch_size and seen_batch and not getattr(model, "training", True)
+                                with torch.no_grad(), call_amp():
+                                    res = run(batch if full else batch[:nb])[:nb]
+                                preds[k0:k0 + nb].copy_(res)
+                                del res
+                                t2 = clock(timed)
+                                seconds["gather"] += t1 - t0
+                                seconds["forward"] += t2 - t1
+                                seen_batch = True
+                                patches_run += nb
+                                if pbar is not None:
+                                    pbar.update(nb)
+                    finally:                                 # (freeing a buffer waits for the stream)
+                        d_win.free()
+                        hold(-2 * int(np.prod(win_dims)))
+                nvox = int(np.prod(brick.extent))
+                (g,) = store_write.plan_write(shape, chunks[2:], [brick.origin], [brick.extent], out._nominal,
+                                              exists=lambda *idx: False, max_pool_bytes=1 << 62)
+                if any(s != store_write.COVERED for s in g.states):
+                    raise RuntimeError("predict_store: a destination chunk is not covered by one brick")
+                d_res = pool = None
+                try:
+                    t0 = clock(timed)
+                    d_res = ctx.alloc(2 * nvox)
+                    hold(2 * nvox)
+                    ctx.tile_stitch_u16(tf, preds if n_patches else None, n_patches, grid, trim, brick.origin,
+                                        brick.extent, shape, d_res)
+                    t1 = clock(timed)
+                    pool = store_write.open_pool(out, ctx, g, st)
+                    hold(2 * g.pool_elems)
+                    store_write.scatter(ctx, g, pool, d_res, nvox, np.uint16,
+                                        store_write.box_records([brick.origin], brick.extent))
+                    t2 = clock(timed)
+                    d_res.free()
+                    d_res = None
+                    hold(-2 * nvox)
+                    seconds["stitch"] += t1 - t0
+                    seconds["scatter"] += t2 - t1
+                    written += store_write.encode_commit(out, ctx, g, pool, st, d_table)
+                finally:
+                    if d_res is not None:
+                        d_res.free()
+                        hold(-2 * nvox)
+                    if pool is not None:
+                        pool.free()
+                        hold(-2 * g.pool_elems)
+            del batch, preds
+    finally:
+        ctx.reset_stream()
+        arr.max_pool_bytes = arr_pool_cap
+        if d_table is not None:
+            d_table.free()
+        if pbar is not None:
+            pbar.close()
+    del run
+    seconds["encode"], seconds["files_write"] = st["seconds"]["encode"], st["seconds"]["files_write"]
+    if stats is not None:
+        stats.update(seconds=seconds, bricks=len(bricks), patches_run=patches_run, patches_unique=unique,
+                     largest_alloc=held["most"], chunks=st["chunks"], encode_calls=st["encode_calls"])
+    return 2 * int(np.prod(shape)) / written
 
 
 def predict_patch(patch, model, transform):

@@ -375,4 +375,71 @@ int exabm4d_tile_finalize_u16_dev(exabm4d_ctx* ctx, const exabm4d_transform* t,
     return EXABM4D_OK;
 }
 
+// ---- overlap tiling of one brick -----------------------------------------------------------------
+// The grid as the kernels take it, or false: sizes in range and every patch's far end inside int.
+static bool tile_grid(const exabm4d_patch_grid* grid, TileGrid& g, long long& patches) {
+    if (!grid || grid->stride < 1 || grid->patch < 1 || grid->patch > 1024) return false;
+    patches = 1;
+    for (int a = 0; a < 3; a++) {
+        if (grid->first[a] < 0 || grid->count[a] < 0) return false;
+        const long long end = ((long long)grid->first[a] + grid->count[a]) * grid->stride + grid->patch;
+        if (end > 0x7fffffffLL) return false;
+        g.first[a] = grid->first[a];
+        g.count[a] = grid->count[a];
+        patches *= grid->count[a];
+        if (patches > (1LL << 40)) return false;                 // checked per factor: the product cannot wrap
+    }
+    g.stride = grid->stride;
+    g.patch = grid->patch;
+    return true;
+}
+int exabm4d_tile_gather_u16_dev(exabm4d_ctx* ctx, const uint16_t* win, const int32_t* win_origin_zyx,
+                                const int32_t* win_dims_zyx, const int32_t* vol_dims_zyx,
+                                const exabm4d_transform* t, const exabm4d_patch_grid* grid, long long k0, int nb,
+                                float* out) {
+    TfDev d;
+    if (int rc = tf_entry(ctx, win && win_origin_zyx && win_dims_zyx && vol_dims_zyx && grid && out, t, d)) return rc;
+    TileGrid g;
+    long long patches = 0;
+    if (!tile_grid(grid, g, patches)) return fail(ctx, EXABM4D_ERR_INVALID, "tile_gather_u16: bad patch grid");
+    if (k0 < 0 || nb < 0 || k0 + nb > patches)
+        return fail(ctx, EXABM4D_ERR_INVALID, "tile_gather_u16: the batch runs past the patch grid");
+    Int3 w0, wd, vol;
+    for (int a = 0; a < 3; a++) {
+        w0.v[a] = win_origin_zyx[a];
+        wd.v[a] = win_dims_zyx[a];
+        vol.v[a] = vol_dims_zyx[a];
+        if (w0.v[a] < 0 || wd.v[a] < 1 || vol.v[a] < 1) return fail(ctx, EXABM4D_ERR_INVALID, "tile_gather_u16: bad sizes");
+        if (g.count[a] == 0) continue;
+        const long long lo = (long long)g.first[a] * g.stride;
+        const long long hi = std::min<long long>(((long long)g.first[a] + g.count[a] - 1) * g.stride + g.patch, vol.v[a]);
+        if (lo < hi && (w0.v[a] > lo || hi > (long long)w0.v[a] + wd.v[a]))
+            return fail(ctx, EXABM4D_ERR_INVALID, "tile_gather_u16: the window does not hold the grid's patches");
+    }
+    HIP_TRY(ctx, launch_tile_gather_u16(win, w0, wd, vol, d, g, k0, nb, out, ctx->stream));
+    return EXABM4D_OK;
+}
+int exabm4d_tile_stitch_u16_dev(exabm4d_ctx* ctx, const float* preds, long long n_patches,
+                                const exabm4d_patch_grid* grid, int trim, const int32_t* box_origin_zyx,
+                                const int32_t* box_dims_zyx, const int32_t* vol_dims_zyx,
+                                const exabm4d_transform* t, uint16_t* out) {
+    TfDev d;
+    if (int rc = tf_entry(ctx, grid && box_origin_zyx && box_dims_zyx && vol_dims_zyx && out, t, d)) return rc;
+    TileGrid g;
+    long long patches = 0;
+    if (!tile_grid(grid, g, patches)) return fail(ctx, EXABM4D_ERR_INVALID, "tile_stitch_u16: bad patch grid");
+    if (n_patches != patches || (patches > 0 && !preds))
+        return fail(ctx, EXABM4D_ERR_INVALID, "tile_stitch_u16: preds does not hold the grid's patches");
+    if (trim < 0 || 2 * trim >= g.patch) return fail(ctx, EXABM4D_ERR_INVALID, "tile_stitch_u16: 0 <= 2 trim < patch");
+    Int3 o0, oe;
+    for (int a = 0; a < 3; a++) {
+        o0.v[a] = box_origin_zyx[a];
+        oe.v[a] = box_dims_zyx[a];
+        if (o0.v[a] < 0 || oe.v[a] < 1 || (long long)o0.v[a] + oe.v[a] > vol_dims_zyx[a])
+            return fail(ctx, EXABM4D_ERR_INVALID, "tile_stitch_u16: the box is not inside the volume");
+    }
+    HIP_TRY(ctx, launch_tile_stitch_u16(preds, g, trim, o0, oe, d, out, ctx->stream));
+    return EXABM4D_OK;
+}
+
 }  // extern "C"

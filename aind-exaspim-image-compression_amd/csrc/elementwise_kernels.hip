@@ -268,15 +268,17 @@ struct OpPgInverseU16 {
         st8(out + i, q);
     }
 };
+// what an accumulated prediction `a` of weight `w` becomes (OpTileFinalize, tile_stitch_u16_kernel)
+__device__ __forceinline__ uint16_t tile_finalize_value(const TfDev& t, float a, float w) {
+    const float y = a / (w + 1e-8f);         // accum_wgt += 1e-8 ; accum_pred /= accum_wgt
+    return quantise_u16(tf_inverse_float(t, y), t.maxc);
+}
 struct OpTileFinalize {
     TfDev t;
     const float* acc;
     const float* wgt;
     uint16_t* out;
-    __device__ uint16_t f(float a, float w) const {
-        const float y = a / (w + 1e-8f);     // accum_wgt += 1e-8 ; accum_pred /= accum_wgt
-        return quantise_u16(tf_inverse_float(t, y), t.maxc);
-    }
+    __device__ uint16_t f(float a, float w) const { return tile_finalize_value(t, a, w); }
     __device__ void one(size_t i) const { out[i] = f(acc[i], wgt[i]); }
     __device__ void eight(size_t i) const {
         float a[8], w[8];
@@ -400,6 +402,74 @@ __global__ __launch_bounds__(EW_THREADS) void tile_accumulate_kernel(const float
             acc[o] = acc[o] + p;
             wgt[o] = wgt[o] + 1.0f;
         }
+    }
+}
+
+// ---- overlap tiling of one brick of a stored volume ------------------------------
+// The brick's patches are a regular grid (TileGrid): patch (iz, iy, ix) starts at index * stride, its linear index
+// is raster order over the grid's counts.  One lane per output element, x fastest.
+//
+// Patches [k0, k0 + nb) of the grid, cut from the uint16 window `win` (origin w0, extent wd, inside a volume of
+// `vol`): tf_forward of the count inside the volume, 0.0f beyond it (add_padding pads the transformed image).
+// The entry has checked that the window holds every voxel of the grid's patches that lies inside the volume.
+__global__ __launch_bounds__(EW_THREADS) void tile_gather_u16_kernel(const uint16_t* __restrict__ win, Int3 w0,
+                                                                     Int3 wd, Int3 vol, TfDev t, TileGrid g,
+                                                                     long long k0, size_t total,
+                                                                     float* __restrict__ out) {
+    const size_t pv = (size_t)g.patch * g.patch * g.patch;
+    const size_t plane = (size_t)g.count[1] * g.count[2];
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (size_t)gridDim.x * blockDim.x) {
+        const size_t k = (size_t)k0 + i / pv;
+        const unsigned r = (unsigned)(i % pv), pe = (unsigned)g.patch;       // patch <= 1024: r < 2^30
+        const int x = (int)(r % pe), y = (int)((r / pe) % pe), z = (int)(r / (pe * pe));
+        const int gz = (g.first[0] + (int)(k / plane)) * g.stride + z;
+        const int gy = (g.first[1] + (int)((k % plane) / g.count[2])) * g.stride + y;
+        const int gx = (g.first[2] + (int)(k % g.count[2])) * g.stride + x;
+        float v = 0.0f;
+        if (gz < vol.v[0] && gy < vol.v[1] && gx < vol.v[2]) {
+            const size_t o = ((size_t)(gz - w0.v[0]) * wd.v[1] + (size_t)(gy - w0.v[1])) * wd.v[2] +
+                             (size_t)(gx - w0.v[2]);
+            v = tf_forward(t, (float)win[o]);
+        }
+        out[i] = v;
+    }
+}
+
+// Every voxel of the output box [o0, o0 + oe): the predictions of the grid's patches whose cores hold it, added
+// z outermost in increasing patch index -- the order tile_accumulate_kernel's launches give -- then
+// tile_finalize_value.  preds: (count_z * count_y * count_x, patch^3) in the grid's raster order.
+__global__ __launch_bounds__(EW_THREADS) void tile_stitch_u16_kernel(const float* __restrict__ preds, TileGrid g,
+                                                                     int trim, Int3 o0, Int3 oe, TfDev t,
+                                                                     uint16_t* __restrict__ out) {
+    const int core = g.patch - 2 * trim;
+    const size_t pv = (size_t)g.patch * g.patch * g.patch;
+    const size_t total = (size_t)oe.v[0] * oe.v[1] * oe.v[2];
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (size_t)gridDim.x * blockDim.x) {
+        const int p[3] = {o0.v[0] + (int)(i / ((size_t)oe.v[1] * oe.v[2])), o0.v[1] + (int)((i / oe.v[2]) % oe.v[1]),
+                          o0.v[2] + (int)(i % oe.v[2])};
+        int lo[3], hi[3];                    // patch indices i with i * stride + trim <= p < i * stride + trim + core
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            const int d = p[a] - trim, u = d - core + 1;
+            lo[a] = u <= 0 ? 0 : (u + g.stride - 1) / g.stride;
+            hi[a] = d < 0 ? -1 : d / g.stride;
+            lo[a] = lo[a] > g.first[a] ? lo[a] : g.first[a];
+            hi[a] = hi[a] < g.first[a] + g.count[a] - 1 ? hi[a] : g.first[a] + g.count[a] - 1;
+        }
+        float s = 0.0f, w = 0.0f;
+        for (int iz = lo[0]; iz <= hi[0]; iz++)
+            for (int iy = lo[1]; iy <= hi[1]; iy++)
+                for (int ix = lo[2]; ix <= hi[2]; ix++) {
+                    const size_t k = ((size_t)(iz - g.first[0]) * g.count[1] + (size_t)(iy - g.first[1])) *
+                                         g.count[2] + (size_t)(ix - g.first[2]);
+                    const size_t r = ((size_t)(p[0] - iz * g.stride) * g.patch + (size_t)(p[1] - iy * g.stride)) *
+                                         g.patch + (size_t)(p[2] - ix * g.stride);
+                    s = s + preds[k * pv + r];
+                    w = w + 1.0f;
+                }
+        out[i] = tile_finalize_value(t, s, w);
     }
 }
 
@@ -965,6 +1035,22 @@ hipError_t launch_tile_accumulate(const float* preds, const int* starts, int nb,
 hipError_t launch_tile_finalize(const TfDev& t, const float* acc, const float* wgt, uint16_t* out,
                                 size_t n, hipStream_t s) {
     return launch_stream(OpTileFinalize{t, acc, wgt, out}, n, aligned16(acc, wgt, out), s);
+}
+hipError_t launch_tile_gather_u16(const uint16_t* win, const Int3& w0, const Int3& wd, const Int3& vol,
+                                  const TfDev& t, const TileGrid& g, long long k0, int nb, float* out,
+                                  hipStream_t s) {
+    const size_t total = (size_t)nb * g.patch * g.patch * g.patch;
+    if (!total) return hipSuccess;
+    hipLaunchKernelGGL(tile_gather_u16_kernel, dim3(ew_blocks(total)), dim3(EW_THREADS), 0, s, win, w0, wd, vol, t,
+                       g, k0, total, out);
+    return hipGetLastError();
+}
+hipError_t launch_tile_stitch_u16(const float* preds, const TileGrid& g, int trim, const Int3& o0, const Int3& oe,
+                                  const TfDev& t, uint16_t* out, hipStream_t s) {
+    const size_t total = (size_t)oe.v[0] * oe.v[1] * oe.v[2];
+    hipLaunchKernelGGL(tile_stitch_u16_kernel, dim3(ew_blocks(total)), dim3(EW_THREADS), 0, s, preds, g, trim, o0,
+                       oe, t, out);
+    return hipGetLastError();
 }
 
 }  // namespace exabm4d

@@ -52,6 +52,23 @@ hipError_t launch_tile_accumulate(const float* preds, const int* starts, int nb,
                                   float* acc, float* wgt, int nz, int ny, int nx, hipStream_t s);
 hipError_t launch_tile_finalize(const TfDev& t, const float* acc, const float* wgt, uint16_t* out,
                                 size_t n, hipStream_t s);
+// Overlap tiling of one brick.  TileGrid: the brick's patches as a regular grid -- per axis (z, y, x)
+// the first patch index and the number of patches; patch i starts at i * stride and is `patch` voxels wide.
+struct Int3 {
+    int v[3];
+};
+struct TileGrid {
+    int first[3], count[3];
+    int stride, patch;
+};
+// patches [k0, k0 + nb) of the grid (raster order) from the uint16 window `win` (origin w0, extent wd) of a volume
+// of `vol` voxels -> out[nb][patch^3] = tf_forward(count), 0.0f beyond the volume; the caller has checked the window
+hipError_t launch_tile_gather_u16(const uint16_t* win, const Int3& w0, const Int3& wd, const Int3& vol,
+                                  const TfDev& t, const TileGrid& g, long long k0, int nb, float* out,
+                                  hipStream_t s);
+// preds[count_z * count_y * count_x][patch^3] -> the counts of the box [o0, o0 + oe), dense, x fastest
+hipError_t launch_tile_stitch_u16(const float* preds, const TileGrid& g, int trim, const Int3& o0, const Int3& oe,
+                                  const TfDev& t, uint16_t* out, hipStream_t s);
 hipError_t launch_chunk_hist(const uint16_t* vol, int nz, int ny, int nx, int cz, int cy, int cx,
                              uint32_t* hist, hipStream_t s);
 hipError_t launch_dctq_forward(const uint16_t* vol, int nz, int ny, int nx, const float* dct64, float q,

@@ -543,6 +543,45 @@ int exabm4d_tile_finalize_u16_dev(exabm4d_ctx* ctx, const exabm4d_transform* t,
                                   const float* accum_pred, const float* accum_wgt, uint16_t* out,
                                   size_t n);
 
+/* ---- the same tiling for one brick of a stored volume (inference.predict_store) ----
+ * A brick's patches are a regular grid, so no list of starts is passed and no count of patches is too many: per
+ * axis (z, y, x) the index of the first patch and the number of patches; patch i starts at voxel i * stride and
+ * is `patch` voxels wide (stride >= 1, 1 <= patch <= 1024, first >= 0, count >= 0).  A patch's linear index is
+ * raster order over the counts, z outermost. */
+typedef struct exabm4d_patch_grid {
+    int32_t first[3];
+    int32_t count[3];
+    int32_t stride;
+    int32_t patch;
+} exabm4d_patch_grid;
+/* out[nb][patch^3] (device fp32) = patches [k0, k0 + nb) of the grid, cut from `win`: a device uint16 array
+ * [win_dims_zyx] that holds the voxels from win_origin_zyx on of a volume of vol_dims_zyx voxels.  A voxel inside
+ * the volume is written as transform.forward((float)count) -- the operation exabm4d_transform_forward_u16_dev
+ * applies, same bits -- and a voxel beyond the volume as 0.0f: add_padding pads the transformed image
+ * (inference.py:153-199), so the pad is zero, not forward(0).  One pass: no fp32 copy of the volume exists.
+ * The three triples and the grid are host arrays.  Checked before anything is launched, EXABM4D_ERR_INVALID with
+ * nothing written otherwise: 0 <= k0, 0 <= nb, k0 + nb <= count_z * count_y * count_x, and per axis
+ * win_origin <= first * stride and min((first + count - 1) * stride + patch, vol_dim) <= win_origin + win_dim,
+ * i.e. the window holds every voxel of the grid's patches that lies inside the volume.  nb == 0 does nothing. */
+int exabm4d_tile_gather_u16_dev(exabm4d_ctx* ctx, const uint16_t* win, const int32_t* win_origin_zyx,
+                                const int32_t* win_dims_zyx, const int32_t* vol_dims_zyx,
+                                const exabm4d_transform* t, const exabm4d_patch_grid* grid, long long k0, int nb,
+                                float* out);
+/* out (device uint16, dense [box_dims_zyx], x fastest) = the denoised counts of the box that starts at
+ * box_origin_zyx of the volume, from preds[n_patches][patch^3] (device fp32, the grid's raster order; n_patches
+ * must equal the product of the counts and may be 0, preds then unused).  Per voxel p: along each axis the patch
+ * indices i of the grid with i * stride + trim <= p < i * stride + trim + (patch - 2 trim) -- however many the
+ * overlap makes it -- visited z outermost in increasing index with s = 0.0f; s = s + pred; w = w + 1.0f, then
+ * the expression of exabm4d_tile_finalize_u16_dev.  These are the fp32 operations of exabm4d_tile_accumulate_dev
+ * over the same patches in raster order followed by exabm4d_tile_finalize_u16_dev, in the same order, so the
+ * counts are the same bits; a voxel no core holds comes out as transform.inverse(0).
+ * Checked on the host (EXABM4D_ERR_INVALID, nothing written): 0 <= trim, 2 trim < patch, the box inside the
+ * volume with extents >= 1, n_patches. */
+int exabm4d_tile_stitch_u16_dev(exabm4d_ctx* ctx, const float* preds, long long n_patches,
+                                const exabm4d_patch_grid* grid, int trim, const int32_t* box_origin_zyx,
+                                const int32_t* box_dims_zyx, const int32_t* vol_dims_zyx,
+                                const exabm4d_transform* t, uint16_t* out);
+
 /* ---- encode half of the metric (SURVEY.md section 8 "next" row f-1) ---------------------------- */
 /* Per-chunk byte-plane histograms of a uint16 volume: the front end of the reference's
  * chunked compression ratio, compute_cratio(img, Blosc(zstd, SHUFFLE), patch_shape=(64,64,64))
