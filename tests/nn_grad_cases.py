@@ -8,6 +8,51 @@ GN_CASES = [((2, 3, 5, 7, 32), 8), ((1, 1, 1, 1, 4), 1), ((3, 4, 4, 4, 1024), 32
 POOL_SHAPES = [(1, 7, 5, 9, 4), (3, 2, 3, 2, 8), (2, 4, 4, 4, 1024), (1, 65, 3, 33, 12)]
 UP_SHAPES = [(1, 1, 1, 1, 4), (2, 1, 3, 2, 4), (1, 5, 7, 3, 8), (3, 4, 4, 4, 1024), (1, 32, 32, 32, 32)]
 KINK = 1e-3
+U = 2.0 ** -24                         # fp32 unit round-off
+
+# The U-Net's layers at a 64^3 patch as (channels, extent), checked against unet3d.UNet by
+# test_nn_kernels_gpu.test_layer_table.
+GN_LAYERS = [(32, 64), (64, 32), (128, 16), (256, 8), (256, 4), (128, 8), (64, 16), (32, 32)]
+POOL_LAYERS = [(32, 64), (64, 32), (128, 16), (256, 8)]
+UP_LAYERS = [(256, 4), (128, 8), (64, 16), (32, 32)]
+GN_KINDS = ["today", "mean10", "mean100", "mean1000", "std1e-2", "std1e-3", "constant", "spread"]
+
+
+def gn_inputs(kind, shape, groups, seed):
+    """Channels-last fp32 data [b, d, h, w, c] of one named distribution (per channel unless said)."""
+    rng = np.random.default_rng(seed)
+    b, c = shape[0], shape[-1]
+    n = rng.standard_normal(shape, dtype=np.float32)
+    if kind == "today":
+        return n * 3 + 1.5
+    if kind.startswith("mean"):                               # mean<m>: m + N(0, 1), mean/std = m
+        return n + np.float32(float(kind[4:]))
+    if kind.startswith("std"):                                # std<s>: 1 + s N(0, 1)
+        return 1 + np.float32(float(kind[3:])) * n
+    if kind == "constant":
+        return np.full(shape, 5.3, np.float32)
+    if kind == "spread":                                      # the channels of a group far apart, each narrow
+        return n * 0.5 + (rng.standard_normal(c) * 300).astype(np.float32)
+    raise ValueError(kind)
+
+
+def gn_preact_bound(x, groups, gamma, beta, eps=1e-5, cbias=None):
+    """``(z, E)``: the fp64 pre-activation of GroupNorm(x + cbias) and the bound E on the error of the fused fp32
+    forward's pre-activation, E = u (4|a mu| + 4|a cb| + 16 (|z| + |beta| + |gamma|)) -- derived in
+    ``test_nn_kernels_gpu.gn_bound``, which applies the activation to it."""
+    return _preact_parts(x, groups, gamma, beta, eps, cbias)[:2]
+
+
+def _preact_parts(x, groups, gamma, beta, eps=1e-5, cbias=None):
+    """``(z, E, var)`` of ``gn_preact_bound``, var[b, g] the groups' fp64 variance."""
+    c = x.shape[-1]
+    mean, var, a, z = nn_pyref.group_norm_parts(x, groups, gamma, beta, eps, cbias)
+    mu = np.repeat(mean, c // groups, axis=1)                                # [b, c]
+    cb = np.zeros(c) if cbias is None else np.abs(np.asarray(cbias, np.float64))
+    ga = np.ones(c) if gamma is None else np.abs(np.asarray(gamma, np.float64))
+    be = np.zeros(c) if beta is None else np.abs(np.asarray(beta, np.float64))
+    lead = (4 * np.abs(a * mu) + 4 * np.abs(a) * cb + 16 * (be + ga)).reshape(x.shape[0], *(1,) * (x.ndim - 2), c)
+    return z, U * (lead + 16 * np.abs(z)), var
 
 
 def gn_case(shape, groups, slope, seed, affine=True, negative_gamma=False):
@@ -39,6 +84,62 @@ def gn_case(shape, groups, slope, seed, affine=True, negative_gamma=False):
 
 def kink_free(x, groups, gamma, beta):
     return bool((np.abs(nn_pyref.group_norm_parts(x, groups, gamma, beta, 1e-5)[3]) >= KINK).all())
+
+
+def gn_case_kind(kind, shape, groups, slope, seed, gamma=None, beta=None, exact_zero=(), storage=None):
+    """``gn_case`` on a named distribution of ``gn_inputs``: ``(x, dy, gamma, beta)`` in fp32, gamma of mixed
+    sign.  ``kind``: one name, or one name per sample.  ``gamma``, ``beta``: given instead of drawn.
+
+    The elements of x are nudged until every fp64 pre-activation has |z| >= KINK, for every slope (so the
+    slopes of a case share their x).  A nudge is 1/32 of the standard deviation of the element's group -- in
+    units of z that is |gamma| / 32 whatever the scale of the data, where a fixed step of 0.03125 is 30 sigma
+    for ``std1e-3``.  A constant group (deviation 0) cannot be nudged and does not need it: its z is beta.
+
+    Asserted before returning, so before any GPU call: every element has |z| >= KINK and |z| >= 2 E, E the
+    bound on the fp32 forward's pre-activation error at that element (``gn_preact_bound``) -- the forward's y and
+    the fp64 z then lie on the same side of the kink, which is what lets a backward that reads the side off y be
+    compared with a reference that reads it off z.  (E is below KINK / 2 everywhere but on ``constant``, where
+    4u |a mean| reaches 6e-4 while no |z| = |beta| is below 0.1; elements short of 2 E are nudged like those short
+    of KINK, and none is exempt.)  ``exact_zero``: channels with gamma = beta = 0, whose z is exactly 0 in any
+    arithmetic (E = 0 there, nothing to disagree about); they are required to be exactly that and are the only
+    elements excepted.  ``storage = (round, spacing)`` for a half-precision case: x and dy are rounded to the
+    storage type (fp32 arrays of half values), every nudge is at least two spacings of the type at the element
+    and is rounded again."""
+    rng = np.random.default_rng(seed)
+    C = shape[-1]
+    if isinstance(kind, str):
+        x = gn_inputs(kind, shape, groups, seed)
+    else:
+        assert len(kind) == shape[0]
+        x = np.concatenate([gn_inputs(k, (1,) + tuple(shape[1:]), groups, seed + 1 + i) for i, k in enumerate(kind)])
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    dy = rng.standard_normal(shape).astype(np.float32)
+    if storage is not None:
+        x, dy = storage[0](x), storage[0](dy)
+    if gamma is None:
+        gamma = rng.uniform(0.5, 1.5, C).astype(np.float32)
+        gamma[::2] *= -1
+    if beta is None:
+        beta = (rng.uniform(0.1, 0.5, C) * rng.choice([-1.0, 1.0], C)).astype(np.float32)
+    live = np.ones(C, dtype=bool)
+    live[list(exact_zero)] = False
+    assert np.all(gamma[~live] == 0) and np.all(beta[~live] == 0)
+    cpg = C // groups
+    for _ in range(100):
+        z, E, var = _preact_parts(x, groups, gamma, beta)
+        bad = (np.abs(z) < np.maximum(KINK, 2 * E)) & live
+        if not bad.any():
+            break
+        step = np.repeat(np.sqrt(var) / 32, cpg, axis=1).reshape(shape[0], *(1,) * (len(shape) - 2), C)
+        step = np.broadcast_to(step, shape)[bad]
+        if storage is not None:
+            step = np.maximum(step, 2 * storage[1](x[bad]))
+        x[bad] += step.astype(np.float32)
+        if storage is not None:
+            x = storage[0](x)
+    assert not bad.any(), (kind, int(np.count_nonzero(bad)), float(E.max()))     # z, E: those of the final x
+    assert np.all(z[..., ~live] == 0) and np.all(E[..., ~live] == 0)
+    return x, dy, gamma, beta
 
 
 def pool_tie_input(shape, seed):

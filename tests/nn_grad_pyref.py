@@ -11,33 +11,48 @@ import numpy as np
 import nn_pyref
 
 
-def group_norm_lrelu_backward(x, dy, groups, gamma=None, beta=None, eps=1e-5, slope=0.01):
+def group_norm_lrelu_backward(x, dy, groups, gamma=None, beta=None, eps=1e-5, slope=0.01, stats=None):
     """Gradients of ``y = leaky_relu(group_norm(x))``: a dict with ``dx`` (shape of x), ``dgamma``, ``dbeta``
     ([C]; the parameter gradients of the affine module whether or not gamma is given), their ``S_dx``,
     ``S_dgamma``, ``S_dbeta``, and the pre-activation ``z``.
       dz = dy (z > 0 ? 1 : slope)      xh = (x - mean) rstd
       dbeta = sum_{b,s} dz             dgamma = sum_{b,s} dz xh
-      dx = rstd (gamma dz - m1 - xh m2), m1, m2 = means over a (sample, group) of gamma dz and gamma dz xh"""
+      dx = rstd (gamma dz - m1 - xh m2), m1, m2 = means over a (sample, group) of gamma dz and gamma dz xh
+    ``stats = (mean[b, g], rstd[b, g])``: the conditional reference -- these values stand in the formulas
+    instead of the statistics of x (what a backward pass that is handed a forward's statistics should give, to
+    fp64).  The side of the kink is the true fp64 z's either way.  Also returned, for bounds on how an error of
+    the statistics propagates: ``mean``, ``rstd``, ``m1``, ``m2`` ([b, g], as used), ``xh`` (shape of x) and the
+    per-sample summands ``dgamma_b``, ``dbeta_b`` ([b, C])."""
     x = np.asarray(x)
     B, C = x.shape[0], x.shape[-1]
     cpg = C // groups
     mean, var, _, z = nn_pyref.group_norm_parts(x, groups, gamma, beta, eps)
+    rstd_g = 1.0 / np.sqrt(var + eps)
+    if stats is not None:
+        mean, rstd_g = (np.asarray(s, dtype=np.float64).reshape(B, groups) for s in stats)
     v = x.astype(np.float64).reshape(B, -1, C)
     g = np.ones(C) if gamma is None else np.asarray(gamma, dtype=np.float64)
-    rstd = np.repeat(1.0 / np.sqrt(var + eps), cpg, axis=1)[:, None, :]          # [B, 1, C]
+    rstd = np.repeat(rstd_g, cpg, axis=1)[:, None, :]                            # [B, 1, C]
     xh = (v - np.repeat(mean, cpg, axis=1)[:, None, :]) * rstd
     dz = np.asarray(dy, dtype=np.float64).reshape(B, -1, C) * np.where(z.reshape(B, -1, C) > 0, 1.0, slope)
 
-    def group_mean(t):                                                           # [B, S, C] -> [B, 1, C]
-        m = t.reshape(B, t.shape[1], groups, cpg).mean(axis=(1, 3))
+    def group_mean(t):                                                           # [B, S, C] -> [B, G]
+        return t.reshape(B, t.shape[1], groups, cpg).mean(axis=(1, 3))
+
+    def per_channel(m):                                                          # [B, G] -> [B, 1, C]
         return np.repeat(m, cpg, axis=1)[:, None, :]
 
     gdz = g * dz
-    dx = rstd * (gdz - group_mean(gdz) - xh * group_mean(gdz * xh))
-    s_dx = rstd * (np.abs(gdz) + group_mean(np.abs(gdz)) + np.abs(xh) * group_mean(np.abs(gdz * xh)))
+    m1, m2 = group_mean(gdz), group_mean(gdz * xh)
+    dx = rstd * (gdz - per_channel(m1) - xh * per_channel(m2))
+    s_dx = rstd * (np.abs(gdz) + per_channel(group_mean(np.abs(gdz)))
+                   + np.abs(xh) * per_channel(group_mean(np.abs(gdz * xh))))
+    dgamma_b, dbeta_b = (dz * xh).sum(axis=1), dz.sum(axis=1)
     return {"dx": dx.reshape(x.shape), "S_dx": s_dx.reshape(x.shape),
             "dgamma": (dz * xh).sum(axis=(0, 1)), "S_dgamma": np.abs(dz * xh).sum(axis=(0, 1)),
-            "dbeta": dz.sum(axis=(0, 1)), "S_dbeta": np.abs(dz).sum(axis=(0, 1)), "z": z}
+            "dbeta": dz.sum(axis=(0, 1)), "S_dbeta": np.abs(dz).sum(axis=(0, 1)), "z": z,
+            "mean": mean, "rstd": rstd_g, "m1": m1, "m2": m2, "xh": xh.reshape(x.shape),
+            "dgamma_b": dgamma_b, "dbeta_b": dbeta_b}
 
 
 def maxpool2_argmax(x):

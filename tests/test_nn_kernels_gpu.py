@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import nn_pyref as R
+from nn_grad_cases import GN_LAYERS, POOL_LAYERS, UP_LAYERS, U, gn_inputs, gn_preact_bound
 from test_inference_gpu import TF_CFG
 
 from aind_exaspim_image_compression import _native, inference
@@ -22,11 +23,6 @@ from aind_exaspim_image_compression.machine_learning import transforms as T
 from aind_exaspim_image_compression.machine_learning import unet3d
 
 pytestmark = pytest.mark.gpu
-U = 2.0 ** -24                         # fp32 unit round-off
-
-GN_LAYERS = [(32, 64), (64, 32), (128, 16), (256, 8), (256, 4), (128, 8), (64, 16), (32, 32)]
-POOL_LAYERS = [(32, 64), (64, 32), (128, 16), (256, 8)]
-UP_LAYERS = [(256, 4), (128, 8), (64, 16), (32, 32)]
 
 
 def to_dev(a):
@@ -41,24 +37,6 @@ def to_host(t):
 
 
 # ---- GroupNorm + LeakyReLU --------------------------------------------------------------------------------
-
-def gn_inputs(kind, shape, groups, seed):
-    """Channels-last fp32 data [b, d, h, w, c] of one named distribution (per channel unless said)."""
-    rng = np.random.default_rng(seed)
-    b, c = shape[0], shape[-1]
-    n = rng.standard_normal(shape, dtype=np.float32)
-    if kind == "today":
-        return n * 3 + 1.5
-    if kind.startswith("mean"):                               # mean<m>: m + N(0, 1), mean/std = m
-        return n + np.float32(float(kind[4:]))
-    if kind.startswith("std"):                                # std<s>: 1 + s N(0, 1)
-        return 1 + np.float32(float(kind[3:])) * n
-    if kind == "constant":
-        return np.full(shape, 5.3, np.float32)
-    if kind == "spread":                                      # the channels of a group far apart, each narrow
-        return n * 0.5 + (rng.standard_normal(c) * 300).astype(np.float32)
-    raise ValueError(kind)
-
 
 def gn_bound(x, groups, gamma, beta, eps, slope, cbias):
     """Per-element bound on |y - y64| that the fused fp32 form can meet when its statistics are right.
@@ -77,15 +55,7 @@ def gn_bound(x, groups, gamma, beta, eps, slope, cbias):
     multiplies E by the slope where z < -E (plus the rounding of that product, u |y|) and passes it where
     |z| <= E (a sign change moves y by at most max(1, slope) E).  What the bound rejects: a relative error of
     rstd growing like (mean / std)^2 u, the cancellation of sums of squares formed around zero."""
-    c = x.shape[-1]
-    mean, var, a, z = R.group_norm_parts(x, groups, gamma, beta, eps, cbias)
-    b, g = x.shape[0], groups
-    mu = np.repeat(mean, c // g, axis=1)                                     # [b, c]
-    cb = np.zeros(c) if cbias is None else np.abs(np.asarray(cbias, np.float64))
-    ga = np.ones(c) if gamma is None else np.abs(np.asarray(gamma, np.float64))
-    be = np.zeros(c) if beta is None else np.abs(np.asarray(beta, np.float64))
-    lead = (4 * np.abs(a * mu) + 4 * np.abs(a) * cb + 16 * (be + ga)).reshape(b, *(1,) * (x.ndim - 2), c)
-    E = U * (lead + 16 * np.abs(z))
+    z, E = gn_preact_bound(x, groups, gamma, beta, eps, cbias)
     y = R.leaky_relu(z, slope)
     scale = np.where(z < -E, slope, max(1.0, slope))
     return y, scale * E + U * np.abs(y)
