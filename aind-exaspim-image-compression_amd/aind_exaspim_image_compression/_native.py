@@ -40,6 +40,7 @@ EVAL_PRED_NAN, EVAL_RAW_NAN, EVAL_TARGET_NAN = 13, 14, 15
 # exabm4d.h label element types
 LABEL_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.uint32): 1, np.dtype(np.uint64): 2,
                 np.dtype(np.int32): 3, np.dtype(np.int64): 4}
+DIFF_BINS = 131071          # exabm4d.h EXABM4D_DIFF_BINS: bins of a signed difference table (test - ref + 65535)
 DATA_EXP_AUTO = -2 ** 31    # exabm4d.h EXABM4D_DATA_EXP_AUTO: E per volume from the data (fp32 entry points)
 DATA_EXP_U16 = 17           # exabm4d.h EXABM4D_DATA_EXP_U16: the uint16 pipelines' fixed E
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2   # exabm4d.h exabm4d_dtype: element types of the *_dt_dev entries
@@ -253,6 +254,10 @@ SIGNATURES = {
                                             ctypes.c_double, c_vp]),
     "exabm4d_ssim3d_dev": (_I, [_CTX, c_vp, c_vp, _I, _I, _I, _I, _I, ctypes.c_double,
                                 ctypes.c_double, c_vp]),
+    "exabm4d_diff_histogram_u16_dev": (_I, [_CTX, c_vp, c_vp, c_vp, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _I, c_vp]),
+    "exabm4d_mip3_u16_dev": (_I, [_CTX, c_vp, c_vp, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_vp]),
+    "exabm4d_ssim3d_box_dev": (_I, [_CTX, c_vp, c_vp, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _I, ctypes.c_double,
+                                    ctypes.c_double, c_vp]),
     "exabm4d_noise_table_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp, c_vp, c_vp]),
     "exabm4d_foreground_masks_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, _F, _I, c_vp, c_vp]),
     "exabm4d_binary_dilate_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp]),
@@ -908,6 +913,38 @@ class Context:
                                              float(c1), float(c2), out.ctypes.data_as(c_vp)))
         return float(out[0])
 
+    # -- scoring a box inside a window -------------------------------------------
+    @staticmethod
+    def _box_geometry(vol_dims, win_origin, win_dims, box_origin, box_dims):
+        return [(ctypes.c_int32 * 3)(*(int(v) for v in t))
+                for t in (vol_dims, win_origin, win_dims, box_origin, box_dims)]
+
+    def diff_histogram_u16(self, ref_win, test_win, mask_win, vol_dims, win_origin, win_dims, box_origin, box_dims,
+                           hist, zero_first=False):
+        """``hist[(test - ref) + 65535] += 1`` over the box ``box_origin + [0, box_dims)`` of two uint16 windows
+        that hold ``win_origin + [0, win_dims)`` of a volume of ``vol_dims`` (all z, y, x).  ``hist``: ``DIFF_BINS``
+        uint64 counters on the device, added to (``zero_first`` zeroes them before); with ``mask_win`` (uint16,
+        non-zero = foreground) two tables, foreground then background.  Asynchronous."""
+        tri = self._box_geometry(vol_dims, win_origin, win_dims, box_origin, box_dims)
+        self._check(lib().exabm4d_diff_histogram_u16_dev(self.handle, _ptr(ref_win), _ptr(test_win), _ptr(mask_win),
+                                                         *tri, 1 if zero_first else 0, _ptr(hist)))
+
+    def mip3_u16(self, ref_win, test_win, vol_dims, win_origin, win_dims, box_origin, box_dims, planes):
+        """Folds the box's maxima over z, y and x of ref, test and ``|test - ref|`` into ``planes``: 3 x
+        ``mip_plane_words(vol_dims)`` uint32 words on the device, zeroed by the caller once (``split_mip_planes``
+        names them).  Asynchronous."""
+        tri = self._box_geometry(vol_dims, win_origin, win_dims, box_origin, box_dims)
+        self._check(lib().exabm4d_mip3_u16_dev(self.handle, _ptr(ref_win), _ptr(test_win), *tri, _ptr(planes)))
+
+    def ssim3d_box_sum(self, ref_win, test_win, vol_dims, win_origin, win_dims, box_origin, box_dims, window, c1, c2):
+        """The sum of ``ssim3d_sum``'s map over the box only, read from two uint16 windows; ValueError when the
+        windows do not cover the box and its halo."""
+        out = np.empty(1, dtype=np.float64)
+        tri = self._box_geometry(vol_dims, win_origin, win_dims, box_origin, box_dims)
+        self._check(lib().exabm4d_ssim3d_box_dev(self.handle, _ptr(ref_win), _ptr(test_win), *tri, int(window),
+                                                 float(c1), float(c2), out.ctypes.data_as(c_vp)))
+        return float(out[0])
+
     # -- noise table (DESIGN.md 5.9) -----------------------------------------------------------
     def noise_table(self, vol, dtype, shape, shift=0):
         """(hist[NOISE_LEVELS, NOISE_BINS], sum_s[NOISE_LEVELS], skipped) of a uint16 or float32 volume of
@@ -1264,6 +1301,25 @@ def default_device(count=None):
 
 
 # -- host-only helpers (no GPU) -----------------------------------------------------------------
+def mip_plane_words(vol_dims):
+    """32-bit words of the three projection planes (y, x), (z, x), (z, y) of one volume (``Context.mip3_u16``)."""
+    nz, ny, nx = (int(v) for v in vol_dims)
+    return ny * nx + nz * nx + nz * ny
+
+
+def split_mip_planes(words, vol_dims):
+    """The downloaded words of ``Context.mip3_u16`` -> ``{"ref" | "test" | "abs_diff": (yx, zx, zy)}`` as uint16."""
+    nz, ny, nx = (int(v) for v in vol_dims)
+    per = mip_plane_words(vol_dims)
+    out = {}
+    for i, name in enumerate(("ref", "test", "abs_diff")):
+        w = np.asarray(words[i * per:(i + 1) * per])
+        out[name] = (w[:ny * nx].reshape(ny, nx).astype(np.uint16),
+                     w[ny * nx:ny * nx + nz * nx].reshape(nz, nx).astype(np.uint16),
+                     w[ny * nx + nz * nx:].reshape(nz, ny).astype(np.uint16))
+    return out
+
+
 def codec_chunk_bound(n, typesize):
     return int(lib().exabm4d_codec_chunk_bound(int(n), int(typesize)))
 

@@ -15,14 +15,24 @@ changes nothing per patch (volumes of a batch are independent: tests/test_bm4d_g
 ``evaluate.py:40``); without one the byte-shuffled order-0 entropy proxy of
 ``utils.img_util.shuffled_entropy_cratio`` is reported under the same keys (a rate proxy, not a
 Blosc byte count).
+
+``compare_stores`` is that per-block scoring -- compression ratio, SSIM, maximum-intensity projections of the noisy and
+the denoised block, plus the error statistics of ``compare_with_bm4d`` -- for two *stored* volumes of any size, brick
+by brick; ``compare_volumes`` is the same for arrays in memory.
+
 File handling, plotting and CSV output of the reference classes are out of scope.
 """
+import os
+import time
+
 import numpy as np
 
 from aind_exaspim_image_compression import bm4d as _bm4d
 from aind_exaspim_image_compression import inference
 from aind_exaspim_image_compression.machine_learning import transforms as _transforms
-from aind_exaspim_image_compression.utils import img_util
+from aind_exaspim_image_compression import _native
+from aind_exaspim_image_compression.utils import img_util, store_compare
+from aind_exaspim_image_compression.utils.store_compare import abs_error_percentile  # noqa: F401  (public here)
 
 
 def _cratio(img, codec):
@@ -82,3 +92,272 @@ def compare_with_bm4d(patches, model, transform, codec=None, offset=None, sigma=
             out.setdefault("denoised_gt", []).append(gt[i])
             out.setdefault("denoised", []).append(denoised)
     return out
+
+
+# ---- scoring one volume against another brick by brick ------------------------------------------
+_COMPARE_PHASES = ("read", "histogram", "mips", "minmax", "ssim", "download")
+
+
+class _StoreWindows:
+    """Windows of two or three stores: one region read per store and brick, in z slabs of about a chunk of the
+    reference store so that each reader's pool of decoded chunks stays under its cap; the slabs lie one after another
+    in one allocation, and layers past the volume's last hold 65535 (never the minimum, never scored)."""
+
+    def __init__(self, arrs, chunk_z):
+        self.arrs, self.chunk_z = arrs, chunk_z
+
+    def read(self, origin, extent):
+        slabs, slab = store_compare.window_slabs(extent[0], self.chunk_z)
+        starts = [(origin[0] + j * slab, origin[1], origin[2]) for j in range(slabs)]
+        wins = []
+        try:
+            for arr in self.arrs:
+                wins.append(arr.read_patches(starts, (slab, extent[1], extent[2]), is_center=False, out="device",
+                                             fill=65535))
+        except BaseException:
+            self.release(wins)
+            raise
+        return wins, (slabs * slab, extent[1], extent[2])
+
+    @staticmethod
+    def release(wins):
+        for w in wins:
+            w.free()
+
+    def close(self):
+        pass
+
+
+class _ArrayWindows:
+    """Arrays in memory as their own windows: uploaded once, one brick."""
+
+    def __init__(self, ctx, arrays):
+        self.shape = arrays[0].shape
+        self.bufs = []
+        try:
+            for a in arrays:
+                self.bufs.append(ctx.to_device(a))
+        except BaseException:
+            self.close()
+            raise
+
+    def read(self, origin, extent):
+        return self.bufs, self.shape
+
+    @staticmethod
+    def release(wins):
+        pass
+
+    def close(self):
+        for b in self.bufs:
+            b.free()
+
+
+def _score(ctx, shape, bricks, source, with_mask, data_range, window_size, stats):
+    """The loop of ``compare_stores`` / ``compare_volumes`` over ``bricks``; ``source.read(origin, extent)`` gives the
+    windows (ref, test[, mask]) and their extent as held."""
+    n = shape[0] * shape[1] * shape[2]
+    tables = 2 if with_mask else 1
+    words = 3 * _native.mip_plane_words(shape)
+    seconds = dict.fromkeys(_COMPARE_PHASES, 0.0)
+    timed = stats is not None
+    held = {"now": 0, "most": 0}
+
+    def hold(nbytes):
+        held["now"] += nbytes
+        held["most"] = max(held["most"], held["now"])
+
+    def clock():
+        if timed:
+            ctx.sync()
+        return time.perf_counter()
+
+    two_pass = data_range is None
+    lows = [65535, 65535]
+    ssim_sum, voxels_read = 0.0, 0
+    d_hist = d_planes = None
+    try:
+        d_hist = ctx.alloc(8 * tables * store_compare.DIFF_BINS)
+        d_planes = ctx.alloc(4 * words).zero()
+        hold(8 * tables * store_compare.DIFF_BINS + 4 * words)
+
+        def sweep(first):
+            """One pass over the bricks.  The first builds the table, the planes and the minima; the SSIM needs the
+            data range, so it runs in the first pass when the range is given and in a second one otherwise.  A pass
+            without SSIM reads the bricks alone, without their halos."""
+            nonlocal ssim_sum, voxels_read
+            with_ssim = not (first and two_pass)
+            c1, c2 = ((0.01 * data_range) ** 2, (0.03 * data_range) ** 2) if with_ssim else (None, None)
+            for k, brick in enumerate(bricks):
+                w0, wn = (brick.win_origin, brick.win_extent) if with_ssim else (brick.origin, brick.extent)
+                t0 = time.perf_counter()
+                wins, dims = source.read(w0, wn)
+                nbytes = 2 * len(wins) * dims[0] * dims[1] * dims[2]
+                hold(nbytes)
+                voxels_read += wn[0] * wn[1] * wn[2]
+                try:
+                    t1 = clock()
+                    geometry = (shape, w0, dims, brick.origin, brick.extent)
+                    if first:
+                        ctx.diff_histogram_u16(wins[0], wins[1], wins[2] if with_mask else None, *geometry, d_hist,
+                                               zero_first=k == 0)
+                        t2 = clock()
+                        ctx.mip3_u16(wins[0], wins[1], *geometry, d_planes)
+                        t3 = clock()
+                        for i in (0, 1):
+                            lows[i] = min(lows[i], int(ctx.minmax(wins[i], np.uint16, dims[0] * dims[1] * dims[2])[0]))
+                        t4 = clock()
+                        seconds["histogram"] += t2 - t1
+                        seconds["mips"] += t3 - t2
+                        seconds["minmax"] += t4 - t3
+                    else:
+                        t4 = t1
+                    if with_ssim:
+                        ssim_sum += ctx.ssim3d_box_sum(wins[0], wins[1], *geometry, window_size, c1, c2)
+                        seconds["ssim"] += clock() - t4
+                    seconds["read"] += t1 - t0
+                finally:
+                    source.release(wins)             # (freeing a buffer waits for the stream)
+                    hold(-nbytes)
+
+        sweep(True)
+        t0 = time.perf_counter()
+        hist = d_hist.download((tables, store_compare.DIFF_BINS), np.uint64)
+        planes = d_planes.download((words,), np.uint32)
+        seconds["download"] += time.perf_counter() - t0
+        mips = _native.split_mip_planes(planes, shape)
+        highs = [int(mips[name][0].max()) for name in ("ref", "test")]
+        if two_pass:
+            # ssim3D's default (reference utils/img_util.py:985-988), in its arithmetic
+            data_range = max(float(highs[0]) - float(lows[0]), float(highs[1]) - float(lows[1]))
+            sweep(False)
+    finally:
+        for buf in (d_hist, d_planes):
+            if buf is not None:
+                buf.free()
+
+    total = hist.sum(axis=0, dtype=np.uint64)
+    out = {"n": n, "error_hist": total}
+    whole = store_compare.error_stats(total, data_range)
+    assert whole["n"] == n, "the bricks do not partition the volume"
+    out.update({k: whole[k] for k in ("mae", "mse", "bias", "lmax", "psnr")})
+    if with_mask:
+        fg, bg = store_compare.error_stats(hist[0]), store_compare.error_stats(hist[1])
+        out.update(error_hist_fg=hist[0], error_hist_bg=hist[1], n_fg=fg["n"], mae_fg=fg["mae"], mae_bg=bg["mae"],
+                   lmax_fg=fg["lmax"], lmax_bg=bg["lmax"])
+    out.update(ssim=float(np.float64(ssim_sum) / n), data_range=float(data_range),
+               min={"ref": lows[0], "test": lows[1]}, max={"ref": highs[0], "test": highs[1]}, mips=mips)
+    if stats is not None:
+        stats.update(seconds=seconds, bricks=len(bricks), voxels_read=voxels_read, largest_alloc=held["most"],
+                     passes=2 if two_pass else 1)
+    return out
+
+
+def _check_compare_args(window_size, data_range, budget_bytes):
+    window_size, budget = int(window_size), int(budget_bytes)
+    if not 1 <= window_size <= 32:
+        raise ValueError("the ssim window must be 1..32")
+    if budget < 1:
+        raise ValueError("budget_bytes must be positive")
+    if data_range is not None and not float(data_range) > 0.0:
+        raise ValueError("data_range must be positive")
+    return window_size, budget
+
+
+def _stored_bytes(arr):
+    """The bytes of a store's chunk files: what ``write_zarr`` divides the raw bytes by."""
+    from aind_exaspim_image_compression.utils import chunk_store
+    grid = [-(-s // c) for s, c in zip(arr.shape[2:], arr.chunks[2:])]
+    return sum(os.path.getsize(os.path.join(arr.path, chunk_store.chunk_key(*idx))) for idx in np.ndindex(*grid))
+
+
+def compare_stores(ref, test, mask=None, data_range=None, window_size=16, budget_bytes=4 << 30, device=None,
+                   stats=None):
+    """Scores the stored volume ``test`` against the stored volume ``ref`` without ever holding either: what
+    ``compare_volumes(read_zarr(ref)[0, 0], read_zarr(test)[0, 0], ...)`` returns, for volumes of any size
+    (DESIGN.md 5.17).
+
+    ``ref``, ``test`` and ``mask`` (non-zero = foreground) are paths or ``StoredArray``s of uint16 and one shape,
+    opened for the device used here.  Their chunk shapes may differ: bricks are boxes of whole chunks of ``ref``
+    (``utils.store_compare.plan_compare``, each at most ``budget_bytes`` of device memory; a single chunk is taken
+    whatever it costs), and ``test`` and ``mask`` are read by region, whatever chunks that touches.  Per brick the
+    stores' windows -- the brick and the halo its SSIM reads -- come from region reads that stay on the device, and
+    three kernels score the brick inside them: the signed difference table, the maximum projections and the SSIM sum
+    of the box.  Nothing is carried between bricks: a halo is read again by every brick that needs it.
+
+    ``data_range``: the ``L`` of SSIM's constants and of the PSNR.  With one given the stores are read once
+    (``evaluate_blocks`` passes ``max(ref)``).  With ``None`` it is ``ssim3D``'s default, ``max(hi_ref - lo_ref,
+    hi_test - lo_test)``, which is only known after all of both volumes has been seen: a first pass builds the table,
+    the projections and the extremes from the bricks alone, and a second pass over the windows computes the SSIM --
+    **every chunk is read and decoded twice** (the halos only in the second pass).
+
+    Returns a dict: ``n`` (voxels); ``error_hist`` (131071 uint64 bins, ``test - ref + 65535``), and with a mask
+    ``error_hist_fg`` / ``error_hist_bg``; from the table, in exact integer arithmetic and one float64 division
+    each, ``mae``, ``mse``, ``bias`` (mean signed error), ``lmax`` and ``psnr`` (``10 log10(data_range^2 / mse)``,
+    ``inf`` for equal stores), with a mask also ``mae_fg``, ``mae_bg``, ``lmax_fg``, ``lmax_bg``, ``n_fg``
+    (``abs_error_percentile`` gives any percentile of the error from the table); ``ssim`` and ``data_range``; ``min``
+    and ``max`` (``{"ref", "test"}``); ``cratio_ref`` / ``cratio_test`` (raw bytes over chunk-file bytes, what
+    ``write_zarr`` returned); and ``mips``: ``{"ref" | "test" | "abs_diff": (yx, zx, zy)}``, host uint16 planes
+    (``img_util.mip_to_uint8`` stretches one for viewing).  Everything but ``ssim`` is independent of the brick plan;
+    ``ssim`` changes with it only by the order of the final fp64 sum.
+
+    ``stats`` (a dict) receives ``seconds`` per phase (read, histogram, mips, minmax, ssim, download; the stream is
+    synchronised around the phases only when ``stats`` is given), ``bricks``, ``passes``, ``voxels_read`` -- per store,
+    halos included, so ``voxels_read / n`` shows the share read more than once -- and ``largest_alloc``, the most
+    device bytes held here at one time (the readers' pools of decoded chunks are theirs and are not counted)."""
+    from aind_exaspim_image_compression.utils import chunk_store
+    window_size, budget = _check_compare_args(window_size, data_range, budget_bytes)
+    index = int(device) if device is not None else _native.default_device()
+    arrs = []
+    for name, src in (("ref", ref), ("test", test), ("mask", mask)):
+        if src is None:
+            continue
+        try:
+            arr = src if hasattr(src, "read_patches") else chunk_store.open_zarr(src, device=index)
+        except NotImplementedError as e:
+            raise ValueError("compare_stores: %s must hold uint16 (%s)" % (name, e)) from None
+        if np.dtype(arr.dtype) != np.uint16:
+            raise ValueError("compare_stores: %s must hold uint16" % name)
+        if int(arr.device if arr.device is not None else _native.default_device()) != index:
+            raise ValueError("compare_stores: %s was opened for another device than %d, the one used here" % (name, index))
+        if arrs and tuple(arr.shape) != tuple(arrs[0].shape):
+            raise ValueError("compare_stores: ref, test and mask must have one shape")
+        arrs.append(arr)
+    shape = tuple(int(s) for s in arrs[0].shape[2:])
+    chunks = tuple(int(c) for c in arrs[0].chunks[2:])
+    with_mask = mask is not None
+    bricks = store_compare.plan_compare(shape, chunks, window_size, budget, with_mask)
+    ctx = _native.context(index)
+    caps = [a.max_pool_bytes for a in arrs]
+    for a in arrs:
+        a.max_pool_bytes = max(1, min(a.max_pool_bytes, budget // store_compare.READER_SHARE))
+    try:
+        out = _score(ctx, shape, bricks, _StoreWindows(arrs, chunks[0]), with_mask, data_range, window_size, stats)
+    finally:
+        for a, cap in zip(arrs, caps):
+            a.max_pool_bytes = cap
+    raw = 2 * shape[0] * shape[1] * shape[2]
+    out.update(cratio_ref=raw / _stored_bytes(arrs[0]), cratio_test=raw / _stored_bytes(arrs[1]))
+    return out
+
+
+def compare_volumes(ref, test, mask=None, data_range=None, window_size=16, device=None, stats=None):
+    """``compare_stores`` for uint16 arrays in memory: the volumes are uploaded whole and scored as one brick.  The
+    same dict without the compression ratios; ``mask``: any array of the volumes' shape, non-zero = foreground."""
+    window_size, _ = _check_compare_args(window_size, data_range, 1)
+    arrays = [np.asarray(ref), np.asarray(test)]
+    for a in arrays:
+        if a.dtype != np.uint16 or a.ndim != 3:
+            raise ValueError("compare_volumes: ref and test are 3-D uint16 arrays")
+    if mask is not None:
+        arrays.append((np.asarray(mask) != 0).astype(np.uint16))
+    if any(a.shape != arrays[0].shape for a in arrays) or 0 in arrays[0].shape:
+        raise ValueError("compare_volumes: ref, test and mask must have one shape, without an empty axis")
+    shape = tuple(int(s) for s in arrays[0].shape)
+    ctx = _native.context(device)
+    brick = store_compare.Brick((0, 0, 0), shape, (0, 0, 0), shape, 2 * len(arrays) * int(np.prod(shape)))
+    source = _ArrayWindows(ctx, [np.ascontiguousarray(a) for a in arrays])
+    try:
+        return _score(ctx, shape, [brick], source, mask is not None, data_range, window_size, stats)
+    finally:
+        source.close()

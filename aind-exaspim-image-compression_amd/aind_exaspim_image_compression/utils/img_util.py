@@ -173,6 +173,20 @@ def compute_lmax(img1, img2):
     return float(out[6])
 
 
+def mip_to_uint8(mip, low_pct=1.0, high_pct=99.9):
+    """A projection plane stretched to 8 bits for viewing: the arithmetic of the reference's ``save_mip_png``
+    (``machine_learning/train.py:464-488``) without the file.  The plane is taken as float32; its ``low_pct``-th
+    percentile maps to 0 and its ``high_pct``-th to 255 (when the upper one does not exceed the lower one it is the
+    lower one plus 1), values between them linearly, rounded half to even, and everything outside is clipped.
+    Writing the image stays with the caller."""
+    plane = np.asarray(mip).astype(np.float32)
+    black, white = np.percentile(plane, (low_pct, high_pct))
+    if white <= black:
+        white = black + 1.0
+    stretched = np.clip((plane - black) / (white - black), 0.0, 1.0)
+    return np.rint(stretched * 255).astype(np.uint8)
+
+
 # -- patch coordinates (reference ``utils/img_util.py`` get_patch / get_start_end / get_slices / is_inbounds) ------
 def _half_extent(shape):
     """The three half edge lengths, rounded down: what the reference's patch arithmetic is made of."""

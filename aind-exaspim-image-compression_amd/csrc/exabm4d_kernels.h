@@ -98,6 +98,23 @@ int ssim3d_partials(int nz, int ny, int nx);
 int ssim3d_max_window();
 hipError_t launch_ssim3d(const void* a, const void* b, int dtype, int nz, int ny, int nx, int w,
                          double C1, double C2, double* partials, double* out1, hipStream_t s);
+// ---- store comparison (compare_kernels.hip, the SSIM of a box in metrics_kernels.hip) ----
+// A box inside a window (all z, y, x): the dense window buffer holds w0 + [0, wd) of a volume of n voxels per axis,
+// the box b0 + [0, bd) lies inside it.  The host layer checks all of that before a launch.
+struct BoxGeom {
+    int n[3], w0[3], wd[3], b0[3], bd[3];
+};
+constexpr int DIFF_BINS = 131071;   // bins of a signed difference table (exabm4d.h EXABM4D_DIFF_BINS)
+// hist[(test - ref) + 65535] += 1 over the box; with a mask two tables, foreground then background
+hipError_t launch_diff_hist_u16(const uint16_t* ref, const uint16_t* test, const uint16_t* mask, const BoxGeom& g,
+                                unsigned long long* hist, hipStream_t s);
+size_t mip3_plane_words(const BoxGeom& g);     // ny nx + nz nx + nz ny: the three planes of one volume
+// planes: 3 x mip3_plane_words() 32-bit words, (yx, zx, zy) of ref, of test and of |test - ref|; max is folded in
+hipError_t launch_mip3_u16(const uint16_t* ref, const uint16_t* test, const BoxGeom& g, uint32_t* planes,
+                           hipStream_t s);
+// partials: ssim3d_partials(bd) doubles
+hipError_t launch_ssim3d_box(const uint16_t* a, const uint16_t* b, const BoxGeom& g, int w, double C1,
+                             double C2, double* partials, double* out1, hipStream_t s);
 // Options of block matching (per context since round 4; exabm4d_set_option "bm_xcd_mode" / "bm_carry" / "bm_carry_fault")
 struct BmOpts {
     int xcd_mode = 2;       // workgroup order: 0 = contiguous per XCD, 1 = all XCDs in one z slab of tiles (raster), n >= 2 = in strips of n tile rows

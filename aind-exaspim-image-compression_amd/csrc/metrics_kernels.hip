@@ -332,9 +332,17 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
     return i < n ? i : p - 1 - i;
 }
 
+//
+// The outputs are those of the box g.b0 + [0, g.bd) and the samples come from a window buffer that
+// holds g.w0 + [0, g.wd) of the volume g.n: sample (z, y, x) of the volume, an index after
+// reflection at the VOLUME's faces, is element ((z - w0z) wdy + (y - w0y)) wdx + (x - w0x).  The
+// whole-volume entry passes box = window = volume; exabm4d_ssim3d_box_dev checks
+// on the host that every index the box's outputs read lies in the window.  A tile at the box's
+// upper faces stages rows and columns past the last one an output of the box reads; those are
+// zeros, not loads (only outputs outside the box would have used them).
 template <class T>
 __global__ __launch_bounds__(SS_T) void ssim3d_kernel(const T* __restrict__ A, const T* __restrict__ B,
-                                                      int nz, int ny, int nx, int w, int zc, double C1,
+                                                      BoxGeom g, int w, int zc, double C1,
                                                       double C2, double* __restrict__ partials) {
     extern __shared__ double ss_lds[];
     const int RW = SS_TX + w - 1, RH = SS_TY + w - 1;
@@ -342,10 +350,14 @@ __global__ __launch_bounds__(SS_T) void ssim3d_kernel(const T* __restrict__ A, c
     T* ra = reinterpret_cast<T*>(ys + 5 * SS_TY * RW);     // [RH][RW]
     T* rb = ra + RH * RW;
     const int left = w / 2;
-    const int tiles_x = (nx + SS_TX - 1) / SS_TX, tiles_y = (ny + SS_TY - 1) / SS_TY;
+    const int nz = g.n[0], ny = g.n[1], nx = g.n[2];
+    const int tiles_x = (g.bd[2] + SS_TX - 1) / SS_TX, tiles_y = (g.bd[1] + SS_TY - 1) / SS_TY;
     const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y;
     const int tz = blockIdx.x / (tiles_x * tiles_y);
-    const int x0 = tx * SS_TX, y0 = ty * SS_TY, zs = tz * zc, ze = min(nz, zs + zc);
+    const int xe = g.b0[2] + g.bd[2], ye = g.b0[1] + g.bd[1];      // the box's end in x and y
+    const int x0 = g.b0[2] + tx * SS_TX, y0 = g.b0[1] + ty * SS_TY;
+    const int zs = g.b0[0] + tz * zc, ze = min(g.b0[0] + g.bd[0], zs + zc);
+    const int xhi = xe + w - left - 2, yhi = ye + w - left - 2;   // the last column / row an output of the box reads
     const int lane = threadIdx.x;
     const int ox = lane % SS_TX, oy = lane / SS_TX;   // outputs (oy + 4 j, ox), j < 4
     double acc[4][5];
@@ -357,12 +369,18 @@ __global__ __launch_bounds__(SS_T) void ssim3d_kernel(const T* __restrict__ A, c
     double total = 0.0;
 
     auto plane = [&](int p, bool add) {
-        const size_t src = (size_t)reflect_idx(p, nz) * ny;
+        const size_t src = (size_t)(reflect_idx(p, nz) - g.w0[0]) * g.wd[1];
         for (int it = lane; it < RH * RW; it += SS_T) {
             const int r = it / RW, c = it - r * RW;
-            const size_t g = (src + reflect_idx(y0 - left + r, ny)) * nx + reflect_idx(x0 - left + c, nx);
-            ra[it] = A[g];
-            rb[it] = B[g];
+            const int gy = y0 - left + r, gx = x0 - left + c;
+            if (gy <= yhi && gx <= xhi) {
+                const size_t i = (src + (reflect_idx(gy, ny) - g.w0[1])) * g.wd[2] + (reflect_idx(gx, nx) - g.w0[2]);
+                ra[it] = A[i];
+                rb[it] = B[i];
+            } else {
+                ra[it] = T(0);
+                rb[it] = T(0);
+            }
         }
         __syncthreads();
         for (int it = lane; it < SS_TY * RW; it += SS_T) {
@@ -407,7 +425,7 @@ __global__ __launch_bounds__(SS_T) void ssim3d_kernel(const T* __restrict__ A, c
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int y = y0 + oy + 4 * j, x = x0 + ox;
-            if (y < ny && x < nx) {
+            if (y < ye && x < xe) {
                 const double mu1 = acc[j][0] / w3, mu2 = acc[j][1] / w3;
                 const double s1 = acc[j][2] / w3 - mu1 * mu1;
                 const double s2 = acc[j][3] / w3 - mu2 * mu2;
@@ -434,31 +452,36 @@ int ssim3d_partials(int nz, int ny, int nx) {
     return ((nx + SS_TX - 1) / SS_TX) * ((ny + SS_TY - 1) / SS_TY) * ((nz + zc - 1) / zc);
 }
 
+// tiles and z chunks follow the BOX: a box equal to the volume launches what the whole-volume entry launches
 template <class T>
-static hipError_t launch_ssim_t(const T* a, const T* b, int nz, int ny, int nx, int w, double C1,
-                                double C2, double* partials, int blocks, int zc, hipStream_t s) {
+static hipError_t launch_ssim_t(const T* a, const T* b, const BoxGeom& g, int w, double C1, double C2,
+                                double* partials, double* out1, hipStream_t s) {
+    const int zc = ssim_zchunk(g.bd[0], g.bd[1], g.bd[2]);
+    const int blocks = ssim3d_partials(g.bd[0], g.bd[1], g.bd[2]);
     const int RW = SS_TX + w - 1, RH = SS_TY + w - 1;
     const size_t lds = (size_t)5 * SS_TY * RW * sizeof(double) + (size_t)2 * RH * RW * sizeof(T);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ssim3d_kernel<T>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ssim3d_kernel<T>, dim3(blocks), dim3(SS_T), lds, s, a, b, nz, ny, nx, w, zc, C1,
-                       C2, partials);
-    return hipGetLastError();
+    hipLaunchKernelGGL(ssim3d_kernel<T>, dim3(blocks), dim3(SS_T), lds, s, a, b, g, w, zc, C1, C2, partials);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_reduce_partials(partials, blocks, 1, 0u, 0u, out1, s);
 }
 
 hipError_t launch_ssim3d(const void* a, const void* b, int dtype, int nz, int ny, int nx, int w,
                          double C1, double C2, double* partials, double* out1, hipStream_t s) {
-    const int zc = ssim_zchunk(nz, ny, nx);
-    const int blocks = ssim3d_partials(nz, ny, nx);
-    hipError_t e;
+    const BoxGeom g{{nz, ny, nx}, {0, 0, 0}, {nz, ny, nx}, {0, 0, 0}, {nz, ny, nx}};
     switch (dtype) {
-        case 0: e = launch_ssim_t((const uint16_t*)a, (const uint16_t*)b, nz, ny, nx, w, C1, C2, partials, blocks, zc, s); break;
-        case 1: e = launch_ssim_t((const float*)a, (const float*)b, nz, ny, nx, w, C1, C2, partials, blocks, zc, s); break;
-        default: e = launch_ssim_t((const double*)a, (const double*)b, nz, ny, nx, w, C1, C2, partials, blocks, zc, s);
+        case 0: return launch_ssim_t((const uint16_t*)a, (const uint16_t*)b, g, w, C1, C2, partials, out1, s);
+        case 1: return launch_ssim_t((const float*)a, (const float*)b, g, w, C1, C2, partials, out1, s);
+        default: return launch_ssim_t((const double*)a, (const double*)b, g, w, C1, C2, partials, out1, s);
     }
-    if (e != hipSuccess) return e;
-    return launch_reduce_partials(partials, blocks, 1, 0u, 0u, out1, s);
+}
+
+hipError_t launch_ssim3d_box(const uint16_t* a, const uint16_t* b, const BoxGeom& g, int w, double C1,
+                             double C2, double* partials, double* out1, hipStream_t s) {
+    return launch_ssim_t(a, b, g, w, C1, C2, partials, out1, s);
 }
 
 int ssim3d_max_window() { return SS_MAXW; }

@@ -817,6 +817,53 @@ int exabm4d_masked_error_stats_dev(exabm4d_ctx* ctx, const void* pred, int pred_
 int exabm4d_ssim3d_dev(exabm4d_ctx* ctx, const void* a, const void* b, int dtype, int nz, int ny,
                        int nx, int window, double c1, double c2, double* sum_host);
 
+/* ---- scoring one volume against another brick by brick ---------------------------- */
+/* The three entries below work on a box inside a window.  A window is a dense uint16 device buffer that holds
+ * the part win_origin_zyx + [0, win_dims_zyx) of a volume of vol_dims_zyx voxels (z, y, x; x fastest); the box
+ * box_origin_zyx + [0, box_dims_zyx), in the volume's coordinates, lies inside the window and is what is scored.
+ * ref_win, test_win (and mask_win) are windows of one geometry.  The five triples are host memory.  Every entry
+ * checks the geometry on the host before anything is launched -- every extent >= 1, the volume at most 2^20 per
+ * axis and 2^40 voxels, the window's origin inside the volume, the box inside the window and inside the volume --
+ * and returns EXABM4D_ERR_INVALID otherwise.  A window may run past the volume's upper faces (a region read's
+ * padding): nothing there is ever read.  Device buffers need the natural alignment of their element type only. */
+#define EXABM4D_DIFF_BINS 131071      /* bins of a signed difference table: test - ref = -65535 .. 65535 */
+
+/* hist_dev[(test - ref) + 65535] += 1 for every voxel of the box.  hist_dev: EXABM4D_DIFF_BINS uint64 counters
+ * resident on the device, which the call ADDS to, so that the calls of all bricks of a volume build one table;
+ * zero_first != 0 zeroes them before this box is counted.  With mask_win (uint16, non-zero = foreground) hist_dev
+ * holds two such tables, foreground then background (2 * EXABM4D_DIFF_BINS counters), and a voxel counts in the
+ * one its mask names; mask_win may be NULL.  All counters are integers: the table depends neither on the launch nor
+ * on how the volume was cut into boxes.  Asynchronous on the context's stream. */
+int exabm4d_diff_histogram_u16_dev(exabm4d_ctx* ctx, const uint16_t* ref_win, const uint16_t* test_win,
+                                   const uint16_t* mask_win, const int32_t* vol_dims_zyx,
+                                   const int32_t* win_origin_zyx, const int32_t* win_dims_zyx,
+                                   const int32_t* box_origin_zyx, const int32_t* box_dims_zyx, int zero_first,
+                                   uint64_t* hist_dev);
+
+/* Maximum projections of the box along z, y and x, of ref, of test and of |test - ref|, folded (max) into nine
+ * planes of the WHOLE volume's extents at the box's position.  planes_dev: 3 x (ny nx + nz nx + nz ny) 32-bit words
+ * resident on the device (the device has no 16-bit atomic maximum; every value is <= 65535) -- for ref, then test,
+ * then |test - ref|, the planes (y, x), (z, x) and (z, y) one after another, each dense with its last axis fastest.
+ * The caller zeroes them once; max does not depend on the order, so the planes are exact for any set of boxes
+ * that covers the volume.  Asynchronous on the context's stream. */
+int exabm4d_mip3_u16_dev(exabm4d_ctx* ctx, const uint16_t* ref_win, const uint16_t* test_win,
+                         const int32_t* vol_dims_zyx, const int32_t* win_origin_zyx, const int32_t* win_dims_zyx,
+                         const int32_t* box_origin_zyx, const int32_t* box_dims_zyx, uint32_t* planes_dev);
+
+/* exabm4d_ssim3d_dev's map summed over the box only: the same window (1..32, left = window / 2), the same
+ * "reflect" boundary AT THE VOLUME'S FACES ONLY, c1 and c2 from the caller, fp64.  The sample at volume index i
+ * (per axis, after reflection in [0, n)) is read from the window at i - win_origin.  The entry verifies on the
+ * host that every index the box's voxels read -- box_origin - window / 2 .. box_origin + box_dims - 1 + window -
+ * window / 2 - 1 per axis, reflected -- lies inside the window, and that an axis shorter than `window` is in the
+ * window whole; EXABM4D_ERR_INVALID otherwise, nothing launched.  For uint16 input every running sum is an exact
+ * integer, so a voxel's map value does not depend on the box it was computed in: the sums of boxes that
+ * partition a volume add up to exabm4d_ssim3d_dev's but for the order of the fp64 additions, and the box equal
+ * to the volume gives it bit for bit.  *sum_host is host memory; the call synchronises the context's stream. */
+int exabm4d_ssim3d_box_dev(exabm4d_ctx* ctx, const uint16_t* ref_win, const uint16_t* test_win,
+                           const int32_t* vol_dims_zyx, const int32_t* win_origin_zyx, const int32_t* win_dims_zyx,
+                           const int32_t* box_origin_zyx, const int32_t* box_dims_zyx, int window, double c1,
+                           double c2, double* sum_host);
+
 /* ---- noise table: sigma and Poisson-Gaussian parameters from the data -------------- */
 #define EXABM4D_NOISE_LEVELS 49       /* quarter-octave intensity levels of exabm4d_noise_table_dev */
 #define EXABM4D_NOISE_BINS 4096       /* magnitude bins per level of exabm4d_noise_table_dev */
