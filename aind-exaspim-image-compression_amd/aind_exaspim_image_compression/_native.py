@@ -33,6 +33,8 @@ SEG_STATS_K = 23            # exabm4d.h EXABM4D_SEG_STATS_K
 GAUSS_MAX_RADIUS = 64       # exabm4d.h EXABM4D_GAUSS_MAX_RADIUS
 NOISE_LEVELS = 49           # exabm4d.h EXABM4D_NOISE_LEVELS
 NOISE_BINS = 4096           # exabm4d.h EXABM4D_NOISE_BINS
+NOISE_WIDE_BINS = 16384     # exabm4d.h EXABM4D_NOISE_WIDE_BINS: wide bins per level of Context.measure_box_u16
+COUNT_BINS = 65536          # exabm4d.h EXABM4D_COUNT_BINS: counters of a table of the uint16 counts
 EVAL_K = 16                 # exabm4d.h EXABM4D_EVAL_K: doubles per patch of Context.evaluate_batch
 # exabm4d.h EXABM4D_EVAL_*: the columns of such a row after those of masked_error_stats (0..5)
 EVAL_MED, EVAL_MAD, EVAL_THR, EVAL_RAW_LO, EVAL_RAW_HI, EVAL_PRED_LO, EVAL_PRED_HI = 6, 7, 8, 9, 10, 11, 12
@@ -259,6 +261,7 @@ SIGNATURES = {
     "exabm4d_ssim3d_box_dev": (_I, [_CTX, c_vp, c_vp, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _I, ctypes.c_double,
                                     ctypes.c_double, c_vp]),
     "exabm4d_noise_table_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp, c_vp, c_vp]),
+    "exabm4d_measure_box_u16_dev": (_I, [_CTX, c_vp, c_vp, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _I, c_vp, c_vp]),
     "exabm4d_foreground_masks_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, _F, _I, c_vp, c_vp]),
     "exabm4d_binary_dilate_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp]),
     "exabm4d_gaussian_filter3d_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp, _I, c_vp]),
@@ -961,6 +964,19 @@ class Context:
             hist.ctypes.data_as(c_vp), sum_s.ctypes.data_as(c_vp), skipped.ctypes.data_as(c_vp)))
         return hist, sum_s, int(skipped[0])
 
+    # -- measuring a box inside a window ---------------------------------------
+    def measure_box_u16(self, win, mask_win, vol_dims, win_origin, win_dims, box_origin, box_dims, counts, noise,
+                        zero_first=False):
+        """Adds the box ``box_origin + [0, box_dims)`` of a uint16 window that holds ``win_origin + [0, win_dims)`` of a
+        volume of ``vol_dims`` (all z, y, x) to two tables on the device: ``counts`` (``COUNT_BINS`` uint64, one per
+        value) and ``noise`` (``measure_noise_words()`` uint64: the wide noise table ``[NOISE_LEVELS,
+        NOISE_WIDE_BINS]`` of the cells whose origins lie in the box, then ``sum_s``); ``zero_first`` zeroes them
+        before.  With ``mask_win`` (uint16, non-zero = foreground) two tables each, foreground then background.
+        ValueError when the window misses the far corner of a cell that begins in the box.  Asynchronous."""
+        tri = self._box_geometry(vol_dims, win_origin, win_dims, box_origin, box_dims)
+        self._check(lib().exabm4d_measure_box_u16_dev(self.handle, _ptr(win), _ptr(mask_win), *tri,
+                                                      1 if zero_first else 0, _ptr(counts), _ptr(noise)))
+
     # -- patch-cache masks and coherence gate (DESIGN.md 5.8); batches of (nz, ny, nx) patches --
     def foreground_masks(self, raw, dtype, batch, shape, k, dilate, mask):
         """Masks into the device bytes ``mask``; returns the per-patch fp32 thresholds."""
@@ -1318,6 +1334,11 @@ def split_mip_planes(words, vol_dims):
                      w[ny * nx:ny * nx + nz * nx].reshape(nz, nx).astype(np.uint16),
                      w[ny * nx + nz * nx:].reshape(nz, ny).astype(np.uint16))
     return out
+
+
+def measure_noise_words():
+    """uint64 words of one noise block of ``Context.measure_box_u16``: the wide table, then ``sum_s``."""
+    return NOISE_LEVELS * NOISE_WIDE_BINS + NOISE_LEVELS
 
 
 def codec_chunk_bound(n, typesize):

@@ -389,8 +389,8 @@ def denoise_store(src, dst_path, sigma=None, offset=0.0, chunk=256, halo=8, prof
     every destination chunk lies in one core and none is read back.
 
     ``sigma`` / ``offset`` / ``noise`` / ``inverse`` as in ``denoise_chunked``, except that "auto" is rejected: nothing
-    here sees the whole volume.  Measure a region instead -- ``utils.noise.estimate_sigma(arr[0, 0, z0:z1, y0:y1,
-    x0:x1])`` or ``utils.noise.estimate_poisson_gaussian`` on such a read -- and pass the result.
+    here sees the whole volume.  Measure the store first, in one pass out of core -- ``m =
+    utils.noise.measure_store(src)`` -- and pass ``sigma=m.sigma()`` or ``noise=m.poisson_gaussian()``.
 
     Returns raw bytes / stored chunk bytes, like ``write_zarr``.  ``stats`` (a dict) receives ``seconds`` per phase
     (read, denoise, scatter, encode, files_write), ``bricks``, ``windows`` and ``largest_alloc``, the largest device
@@ -399,8 +399,8 @@ def denoise_store(src, dst_path, sigma=None, offset=0.0, chunk=256, halo=8, prof
     from aind_exaspim_image_compression.utils.chunk_codec import ExacCodec
     # -- every argument check, before a context exists
     if isinstance(sigma, str) or isinstance(noise, str):
-        raise ValueError("denoise_store: 'auto' is not available, nothing here sees the whole volume; measure a region "
-                         "read (utils.noise.estimate_sigma / estimate_poisson_gaussian) and pass the result")
+        raise ValueError("denoise_store: 'auto' is not available, nothing here sees the whole volume; measure the "
+                         "store first (m = utils.noise.measure_store(src)) and pass m.sigma() or m.poisson_gaussian()")
     nz_model = _pg_noise(noise, inverse, sigma, offset)
     chunk, halo, stages = int(chunk), int(halo), int(stages)
     if chunk < 1 or not 0 <= halo <= 64:

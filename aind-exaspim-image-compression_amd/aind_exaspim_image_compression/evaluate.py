@@ -32,6 +32,7 @@ from aind_exaspim_image_compression import inference
 from aind_exaspim_image_compression.machine_learning import transforms as _transforms
 from aind_exaspim_image_compression import _native
 from aind_exaspim_image_compression.utils import img_util, store_compare
+from aind_exaspim_image_compression.utils.store_windows import ArrayWindows, StoreWindows, capped_pools, open_u16_stores
 from aind_exaspim_image_compression.utils.store_compare import abs_error_percentile  # noqa: F401  (public here)
 
 
@@ -96,61 +97,6 @@ def compare_with_bm4d(patches, model, transform, codec=None, offset=None, sigma=
 
 # ---- scoring one volume against another brick by brick ------------------------------------------
 _COMPARE_PHASES = ("read", "histogram", "mips", "minmax", "ssim", "download")
-
-
-class _StoreWindows:
-    """Windows of two or three stores: one region read per store and brick, in z slabs of about a chunk of the
-    reference store so that each reader's pool of decoded chunks stays under its cap; the slabs lie one after another
-    in one allocation, and layers past the volume's last hold 65535 (never the minimum, never scored)."""
-
-    def __init__(self, arrs, chunk_z):
-        self.arrs, self.chunk_z = arrs, chunk_z
-
-    def read(self, origin, extent):
-        slabs, slab = store_compare.window_slabs(extent[0], self.chunk_z)
-        starts = [(origin[0] + j * slab, origin[1], origin[2]) for j in range(slabs)]
-        wins = []
-        try:
-            for arr in self.arrs:
-                wins.append(arr.read_patches(starts, (slab, extent[1], extent[2]), is_center=False, out="device",
-                                             fill=65535))
-        except BaseException:
-            self.release(wins)
-            raise
-        return wins, (slabs * slab, extent[1], extent[2])
-
-    @staticmethod
-    def release(wins):
-        for w in wins:
-            w.free()
-
-    def close(self):
-        pass
-
-
-class _ArrayWindows:
-    """Arrays in memory as their own windows: uploaded once, one brick."""
-
-    def __init__(self, ctx, arrays):
-        self.shape = arrays[0].shape
-        self.bufs = []
-        try:
-            for a in arrays:
-                self.bufs.append(ctx.to_device(a))
-        except BaseException:
-            self.close()
-            raise
-
-    def read(self, origin, extent):
-        return self.bufs, self.shape
-
-    @staticmethod
-    def release(wins):
-        pass
-
-    def close(self):
-        for b in self.bufs:
-            b.free()
 
 
 def _score(ctx, shape, bricks, source, with_mask, data_range, window_size, stats):
@@ -305,37 +251,16 @@ def compare_stores(ref, test, mask=None, data_range=None, window_size=16, budget
     synchronised around the phases only when ``stats`` is given), ``bricks``, ``passes``, ``voxels_read`` -- per store,
     halos included, so ``voxels_read / n`` shows the share read more than once -- and ``largest_alloc``, the most
     device bytes held here at one time (the readers' pools of decoded chunks are theirs and are not counted)."""
-    from aind_exaspim_image_compression.utils import chunk_store
     window_size, budget = _check_compare_args(window_size, data_range, budget_bytes)
     index = int(device) if device is not None else _native.default_device()
-    arrs = []
-    for name, src in (("ref", ref), ("test", test), ("mask", mask)):
-        if src is None:
-            continue
-        try:
-            arr = src if hasattr(src, "read_patches") else chunk_store.open_zarr(src, device=index)
-        except NotImplementedError as e:
-            raise ValueError("compare_stores: %s must hold uint16 (%s)" % (name, e)) from None
-        if np.dtype(arr.dtype) != np.uint16:
-            raise ValueError("compare_stores: %s must hold uint16" % name)
-        if int(arr.device if arr.device is not None else _native.default_device()) != index:
-            raise ValueError("compare_stores: %s was opened for another device than %d, the one used here" % (name, index))
-        if arrs and tuple(arr.shape) != tuple(arrs[0].shape):
-            raise ValueError("compare_stores: ref, test and mask must have one shape")
-        arrs.append(arr)
+    arrs = open_u16_stores("compare_stores", (("ref", ref), ("test", test), ("mask", mask)), index)
     shape = tuple(int(s) for s in arrs[0].shape[2:])
     chunks = tuple(int(c) for c in arrs[0].chunks[2:])
     with_mask = mask is not None
     bricks = store_compare.plan_compare(shape, chunks, window_size, budget, with_mask)
     ctx = _native.context(index)
-    caps = [a.max_pool_bytes for a in arrs]
-    for a in arrs:
-        a.max_pool_bytes = max(1, min(a.max_pool_bytes, budget // store_compare.READER_SHARE))
-    try:
-        out = _score(ctx, shape, bricks, _StoreWindows(arrs, chunks[0]), with_mask, data_range, window_size, stats)
-    finally:
-        for a, cap in zip(arrs, caps):
-            a.max_pool_bytes = cap
+    with capped_pools(arrs, budget):
+        out = _score(ctx, shape, bricks, StoreWindows(arrs, chunks[0]), with_mask, data_range, window_size, stats)
     raw = 2 * shape[0] * shape[1] * shape[2]
     out.update(cratio_ref=raw / _stored_bytes(arrs[0]), cratio_test=raw / _stored_bytes(arrs[1]))
     return out
@@ -356,7 +281,7 @@ def compare_volumes(ref, test, mask=None, data_range=None, window_size=16, devic
     shape = tuple(int(s) for s in arrays[0].shape)
     ctx = _native.context(device)
     brick = store_compare.Brick((0, 0, 0), shape, (0, 0, 0), shape, 2 * len(arrays) * int(np.prod(shape)))
-    source = _ArrayWindows(ctx, [np.ascontiguousarray(a) for a in arrays])
+    source = ArrayWindows(ctx, [np.ascontiguousarray(a) for a in arrays])
     try:
         return _score(ctx, shape, [brick], source, mask is not None, data_range, window_size, stats)
     finally:

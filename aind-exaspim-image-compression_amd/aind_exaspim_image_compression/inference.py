@@ -538,9 +538,9 @@ def predict_store(src, dst_path, model, transform, batch_size=32, patch_size=64,
     the rest of the batch the store is therefore chunk file for chunk file what the whole-volume call gives.  Nothing
     is carried between bricks: a patch whose core meets several bricks runs once for each.
 
-    ``transform`` is used as given: no per-volume offset is estimated, nothing here sees the whole volume.  Measure a
-    region read instead -- ``estimate_offset(arr[0, 0, z0:z1, y0:y1, x0:x1])`` -- and pass
-    ``build_volume_transform(base, offset=...)``.
+    ``transform`` is used as given: no per-volume offset is estimated, nothing here sees the whole volume.  Measure the
+    store first -- ``m = utils.noise.measure_store(src)``, one pass out of core -- and pass
+    ``build_volume_transform(base, img=m)``, which takes the offset the whole volume gives.
 
     Returns raw bytes / stored chunk bytes, like ``write_zarr``.  ``stats`` (a dict) receives ``seconds`` per phase
     (read, gather, forward, stitch, scatter, encode, files_write; the stream is synchronised around the phases, per
@@ -778,11 +778,16 @@ def load_model(path, device="cuda"):
 def build_volume_transform(base_transform, img=None, percentile=0.1, offset=None):
     """Inference transform carrying a per-volume background offset (reference
     inference.py:302-337): a supplied ``offset`` is used as is, otherwise it is estimated from
-    ``img``; ``ValueError`` if neither is given."""
+    ``img``; ``ValueError`` if neither is given.  ``img`` may be the ``StoreMeasure`` of a stored volume
+    (``utils.noise.measure_store``), whose ``offset`` is the estimate of the whole volume."""
     if offset is None:
         if img is None:
             raise ValueError("img is required when offset is not supplied")
-        offset = estimate_offset(img, percentile=percentile, ignore_zeros=True)
+        from aind_exaspim_image_compression.utils.store_measure import StoreMeasure
+        if isinstance(img, StoreMeasure):
+            offset = img.offset(percentile=percentile, ignore_zeros=True)
+        else:
+            offset = estimate_offset(img, percentile=percentile, ignore_zeros=True)
     return with_offset(base_transform, offset)
 
 

@@ -260,6 +260,12 @@ def background_offset_statistics(sample, percentile=0.1):
         hist = ctx.u16_histogram(buf, flat.size)
     finally:
         buf.free()
+    return background_offset_statistics_of_hist(hist, percentile)
+
+
+def background_offset_statistics_of_hist(hist, percentile=0.1):
+    """``background_offset_statistics`` from the 65536-bin histogram of the volume's counts."""
+    hist = np.asarray(hist)
     n = int(hist.sum())
     nonzero = n - int(hist[0])
     every = order_stats.from_u16_hist(hist, dtype=np.uint16)

@@ -232,6 +232,109 @@ def anscombe_cfg(vol, **kw):
     return {"kind": "anscombe", "params": estimate_poisson_gaussian(vol, **kw)}
 
 
+# ---- measuring a stored volume out of core ------------------------------------------------------
+def _measure(ctx, shape, bricks, source, with_mask, stats):
+    """The loop of ``measure_store`` / ``measure_volume`` over ``bricks``; ``source.read(origin, extent)`` gives the
+    windows (volume[, mask]) and their extent as held."""
+    import time
+    from aind_exaspim_image_compression.utils.store_measure import StoreMeasure
+    tables = 2 if with_mask else 1
+    table_bytes = 8 * tables * (_native.COUNT_BINS + _native.measure_noise_words())
+    seconds = {"read": 0.0, "measure": 0.0, "download": 0.0}
+    timed = stats is not None
+    voxels_read, most = 0, 0
+
+    def clock():
+        if timed:
+            ctx.sync()
+        return time.perf_counter()
+
+    d_counts = d_noise = None
+    try:
+        d_counts = ctx.alloc(8 * tables * _native.COUNT_BINS)
+        d_noise = ctx.alloc(8 * tables * _native.measure_noise_words())
+        for k, brick in enumerate(bricks):
+            t0 = time.perf_counter()
+            wins, dims = source.read(brick.win_origin, brick.win_extent)
+            most = max(most, table_bytes + 2 * len(wins) * dims[0] * dims[1] * dims[2])
+            voxels_read += brick.window_voxels
+            try:
+                t1 = clock()
+                ctx.measure_box_u16(wins[0], wins[1] if with_mask else None, shape, brick.win_origin, dims,
+                                    brick.origin, brick.extent, d_counts, d_noise, zero_first=k == 0)
+                seconds["measure"] += clock() - t1
+                seconds["read"] += t1 - t0
+            finally:
+                source.release(wins)                 # (freeing a buffer waits for the stream)
+        t0 = time.perf_counter()
+        counts = d_counts.download((tables, _native.COUNT_BINS), np.uint64)
+        tab = d_noise.download((tables, _native.measure_noise_words()), np.uint64)
+        seconds["download"] += time.perf_counter() - t0
+    finally:
+        for buf in (d_counts, d_noise):
+            if buf is not None:
+                buf.free()
+    if stats is not None:
+        stats.update(seconds=seconds, bricks=len(bricks), voxels_read=voxels_read, largest_alloc=most, passes=1)
+    return StoreMeasure.from_tables(shape, counts, tab)
+
+
+def measure_store(src, mask=None, budget_bytes=4 << 30, device=None, stats=None):
+    """Measures the stored uint16 volume ``src`` without ever holding it: what ``measure_volume(read_zarr(src)[0, 0])``
+    returns, for a volume of any size.  The ``StoreMeasure`` that comes back gives, as host scalar
+    work and bit for bit as the in-memory functions give them on the whole array, ``offset()``
+    (``transforms.estimate_offset``), ``background_offset_statistics()``, ``noise_table()``, ``sigma()``
+    (``estimate_sigma``), ``noise_curve()``, ``poisson_gaussian()`` (``estimate_poisson_gaussian``) and
+    ``anscombe_cfg()`` -- the ``sigma=`` / ``noise=`` of ``bm4d.denoise_store`` and the offset of
+    ``inference.build_volume_transform`` for ``predict_store``.
+
+    ``src`` and ``mask`` (non-zero = foreground) are paths or ``StoredArray``s of uint16 and one shape, opened for the
+    device used here.  Bricks are boxes of whole chunks of ``src`` (``utils.store_measure.plan_measure``, each at most
+    ``budget_bytes`` of device memory; a single chunk is taken whatever it costs).  Per brick one region read per store
+    stays on the device and one kernel adds the brick to two integer tables there -- the counts of every value, and a
+    wide noise table from which the table of every shift follows -- which are downloaded once at the end.  **Every
+    chunk is read and decoded once**, whatever shift the noise needs.  With a mask the tables come for the foreground
+    and the background as well (``noise_table(which="bg")``: the noise away from structure).
+
+    ``stats`` (a dict) receives ``seconds`` per phase (read, measure, download; the stream is synchronised around the
+    phases only when ``stats`` is given), ``bricks``, ``passes`` (always 1), ``voxels_read`` -- per store, with the
+    one-voxel halos -- and ``largest_alloc``, the most device bytes held here at one time (the readers' pools of
+    decoded chunks are theirs and are not counted)."""
+    from aind_exaspim_image_compression.utils import store_measure, store_windows
+    budget = int(budget_bytes)
+    if budget < 1:
+        raise ValueError("budget_bytes must be positive")
+    index = int(device) if device is not None else _native.default_device()
+    arrs = store_windows.open_u16_stores("measure_store", (("src", src), ("mask", mask)), index)
+    shape = tuple(int(s) for s in arrs[0].shape[2:])
+    chunks = tuple(int(c) for c in arrs[0].chunks[2:])
+    bricks = store_measure.plan_measure(shape, chunks, budget, mask is not None)
+    ctx = _native.context(index)
+    with store_windows.capped_pools(arrs, budget):
+        return _measure(ctx, shape, bricks, store_windows.StoreWindows(arrs, chunks[0]), mask is not None, stats)
+
+
+def measure_volume(vol, mask=None, device=None, stats=None):
+    """``measure_store`` for a 3-D uint16 array in memory: uploaded whole and measured as one brick.  ``mask``: any
+    array of the volume's shape, non-zero = foreground."""
+    from aind_exaspim_image_compression.utils import store_compare, store_windows
+    arrays = [np.asarray(vol)]
+    if arrays[0].dtype != np.uint16 or arrays[0].ndim != 3 or 0 in arrays[0].shape:
+        raise ValueError("measure_volume: vol is a 3-D uint16 array without an empty axis")
+    if mask is not None:
+        arrays.append((np.asarray(mask) != 0).astype(np.uint16))
+        if arrays[1].shape != arrays[0].shape:
+            raise ValueError("measure_volume: vol and mask must have one shape")
+    shape = tuple(int(s) for s in arrays[0].shape)
+    ctx = _native.context(device)
+    brick = store_compare.Brick((0, 0, 0), shape, (0, 0, 0), shape, 2 * len(arrays) * int(np.prod(shape)))
+    source = store_windows.ArrayWindows(ctx, [np.ascontiguousarray(a) for a in arrays])
+    try:
+        return _measure(ctx, shape, [brick], source, mask is not None, stats)
+    finally:
+        source.close()
+
+
 def pg_params(noise):
     """``{"gain", "read_noise", "offset"}`` as floats from what the denoisers' ``noise=`` accepts: that dict (the
     return value of ``estimate_poisson_gaussian``) or an anscombe transform cfg (``anscombe_cfg``)."""

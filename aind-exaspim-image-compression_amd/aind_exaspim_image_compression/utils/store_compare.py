@@ -79,11 +79,17 @@ def plan_compare(shape, chunks_zyx, window, budget_bytes, with_mask=False):
         raise ValueError("plan_compare: shape and chunks are three positive sizes each")
     if not 1 <= window <= 32 or budget < 1:
         raise ValueError("plan_compare: 1 <= window <= 32 and budget_bytes >= 1")
+    return plan_bricks(shape, chunk, budget, stores, lambda b0, bd, dim: halo_range(b0, bd, dim, window))
+
+
+def plan_bricks(shape, chunk, budget, stores, axis_window):
+    """``plan_compare``'s rule for any window: ``axis_window(b0, bd, dim) -> (start, extent)`` is what a brick that
+    covers ``[b0, b0 + bd)`` of an axis of ``dim`` voxels has to read there; ``stores`` windows are held at a time."""
     grid = [-(-s // c) for s, c in zip(shape, chunk)]
 
     def axes(a, n):
         """The bricks' (o0, o1, w0, wn) along axis a when a brick is n chunks long."""
-        return [(o0, o1) + halo_range(o0, o1 - o0, shape[a], window) for o0, o1 in _runs(shape[a], n * chunk[a])]
+        return [(o0, o1) + tuple(axis_window(o0, o1 - o0, shape[a])) for o0, o1 in _runs(shape[a], n * chunk[a])]
 
     def bound(per_axis):
         widest = [max(r[3] for r in ax) for ax in per_axis]

@@ -6,33 +6,6 @@ using namespace exabm4d;
 
 static_assert(DIFF_BINS == EXABM4D_DIFF_BINS, "exabm4d.h and exabm4d_kernels.h differ");
 
-// The geometry every entry shares, checked before anything is launched.
-static int box_geometry(exabm4d_ctx* ctx, const char* who, const int32_t* vol, const int32_t* w0, const int32_t* wd,
-                        const int32_t* b0, const int32_t* bd, BoxGeom& g) {
-    const std::string name(who);
-    if (!vol || !w0 || !wd || !b0 || !bd) return fail(ctx, EXABM4D_ERR_INVALID, name + ": NULL argument");
-    long long voxels = 1;
-    for (int a = 0; a < 3; a++) {
-        g.n[a] = vol[a];
-        g.w0[a] = w0[a];
-        g.wd[a] = wd[a];
-        g.b0[a] = b0[a];
-        g.bd[a] = bd[a];
-        if (vol[a] < 1 || wd[a] < 1 || bd[a] < 1) return fail(ctx, EXABM4D_ERR_INVALID, name + ": every extent must be >= 1");
-        if (vol[a] > (1 << 20)) return fail(ctx, EXABM4D_ERR_INVALID, name + ": volume too large");
-        voxels *= vol[a];
-        // a window may run past the volume's upper faces (a reader's padding): nothing there is ever read
-        if (w0[a] < 0 || w0[a] >= vol[a] || wd[a] > (1 << 21))
-            return fail(ctx, EXABM4D_ERR_INVALID, name + ": the window does not begin inside the volume");
-        if (b0[a] < w0[a] || (long long)b0[a] + bd[a] > (long long)w0[a] + wd[a])
-            return fail(ctx, EXABM4D_ERR_INVALID, name + ": the box does not lie inside the window");
-        if ((long long)b0[a] + bd[a] > vol[a])
-            return fail(ctx, EXABM4D_ERR_INVALID, name + ": the box does not lie inside the volume");
-    }
-    if (voxels > (1ll << 40)) return fail(ctx, EXABM4D_ERR_INVALID, name + ": volume too large");
-    return EXABM4D_OK;
-}
-
 // scipy's "reflect" of an index into [0, n): what reflect_idx of metrics_kernels.hip computes
 static int reflect_host(int i, int n) {
     const int p = 2 * n;

@@ -84,6 +84,34 @@ inline int check_patches(exabm4d_ctx* ctx, int batch, int nz, int ny, int nx) {
 }
 inline bool bad_label_dtype(int d) { return d < EXABM4D_LBL_U8 || d > EXABM4D_LBL_I64; }
 
+// A box inside a window: the geometry every such entry shares, checked before anything is
+// launched.
+inline int box_geometry(exabm4d_ctx* ctx, const char* who, const int32_t* vol, const int32_t* w0, const int32_t* wd,
+                        const int32_t* b0, const int32_t* bd, BoxGeom& g) {
+    const std::string name(who);
+    if (!vol || !w0 || !wd || !b0 || !bd) return fail(ctx, EXABM4D_ERR_INVALID, name + ": NULL argument");
+    long long voxels = 1;
+    for (int a = 0; a < 3; a++) {
+        g.n[a] = vol[a];
+        g.w0[a] = w0[a];
+        g.wd[a] = wd[a];
+        g.b0[a] = b0[a];
+        g.bd[a] = bd[a];
+        if (vol[a] < 1 || wd[a] < 1 || bd[a] < 1) return fail(ctx, EXABM4D_ERR_INVALID, name + ": every extent must be >= 1");
+        if (vol[a] > (1 << 20)) return fail(ctx, EXABM4D_ERR_INVALID, name + ": volume too large");
+        voxels *= vol[a];
+        // a window may run past the volume's upper faces (a reader's padding): nothing there is ever read
+        if (w0[a] < 0 || w0[a] >= vol[a] || wd[a] > (1 << 21))
+            return fail(ctx, EXABM4D_ERR_INVALID, name + ": the window does not begin inside the volume");
+        if (b0[a] < w0[a] || (long long)b0[a] + bd[a] > (long long)w0[a] + wd[a])
+            return fail(ctx, EXABM4D_ERR_INVALID, name + ": the box does not lie inside the window");
+        if ((long long)b0[a] + bd[a] > vol[a])
+            return fail(ctx, EXABM4D_ERR_INVALID, name + ": the box does not lie inside the volume");
+    }
+    if (voxels > (1ll << 40)) return fail(ctx, EXABM4D_ERR_INVALID, name + ": volume too large");
+    return EXABM4D_OK;
+}
+
 }  // namespace exabm4d
 
 struct exabm4d_ctx {
@@ -107,6 +135,7 @@ struct exabm4d_ctx {
     size_t region_host_bytes = 0;
     hipEvent_t region_ev = nullptr;
     int noise_wgs = 0;         // noise table: workgroups per launch (one per CU); 0 = noise_table_prepare() not yet run
+    int measure_wgs = 0;       // measuring a box: the same; 0 = measure_prepare() not yet run
     int force_generic_bm = 0;  // exabm4d_set_option("force_generic_bm")
     int bm_guarded_copy = 0;   // exabm4d_set_option("bm_guarded_copy"): staged block matching on a guarded copy
     exabm4d::StageOpts stage;  // exabm4d_set_option("stage_pairvol" / "stage_strip" / "stage_chunks")

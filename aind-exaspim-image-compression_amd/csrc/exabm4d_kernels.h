@@ -115,6 +115,25 @@ hipError_t launch_mip3_u16(const uint16_t* ref, const uint16_t* test, const BoxG
 // partials: ssim3d_partials(bd) doubles
 hipError_t launch_ssim3d_box(const uint16_t* a, const uint16_t* b, const BoxGeom& g, int w, double C1,
                              double C2, double* partials, double* out1, hipStream_t s);
+// ---- measuring a box (measure_kernels.hip) ----
+constexpr int COUNT_BINS = 65536;        // counters of a table of the uint16 counts (exabm4d.h EXABM4D_COUNT_BINS)
+constexpr int NOISE_WIDE_BINS = 16384;   // wide bins of |d| per level (exabm4d.h EXABM4D_NOISE_WIDE_BINS)
+size_t measure_counts_bytes(int tables);     // tables x COUNT_BINS 64-bit counters
+size_t measure_noise_bytes(int tables);      // tables x (wide[NOISE_LEVELS][NOISE_WIDE_BINS], sum_s[NOISE_LEVELS])
+// once per device, on the current device: raises the kernels' LDS limit; *wgs = workgroups to launch (one per CU)
+hipError_t measure_prepare(int device, int* wgs);
+// How a box is walked: 16-byte loads or element loads, the first x of a lane's groups of eight, the groups per
+// row, the lanes per pair of rows, the workgroups.  false: more than 2^31 pairs of cell rows, or 2^32 voxels in one
+// workgroup's share (its counters are 32-bit).
+struct MeasurePlan {
+    int vector_ok, xs, ngx, lx_log2;
+    unsigned blocks;
+};
+bool measure_box_plan(const uint16_t* win, const uint16_t* mask, const BoxGeom& g, int wgs, MeasurePlan& p);
+// ADDS the box's voxels to counts and the cells whose origins lie in the box to noise; with a mask window two
+// tables each, foreground then background.
+hipError_t launch_measure_box_u16(const uint16_t* win, const uint16_t* mask, const BoxGeom& g, const MeasurePlan& p,
+                                  unsigned long long* counts, unsigned long long* noise, hipStream_t s);
 // Options of block matching (per context since round 4; exabm4d_set_option "bm_xcd_mode" / "bm_carry" / "bm_carry_fault")
 struct BmOpts {
     int xcd_mode = 2;       // workgroup order: 0 = contiguous per XCD, 1 = all XCDs in one z slab of tiles (raster), n >= 2 = in strips of n tile rows

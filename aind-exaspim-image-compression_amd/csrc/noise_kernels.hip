@@ -9,6 +9,7 @@
 //
 // All counters are integers: the table does not depend on the launch shape or the order of the updates.
 #include "exabm4d_kernels.h"
+#include "noise_cell.h"
 
 namespace exabm4d {
 
@@ -23,12 +24,6 @@ constexpr int NT_SLOTS = 8;
 constexpr int NT_COLS = 32;
 constexpr size_t NT_LDS = (size_t)NOISE_LEVELS * NT_COLS * 8 + (size_t)NT_SLOTS * NOISE_BINS * 4 + 64;
 constexpr uint32_t NT_S_MAX = 8u * 65535u;
-
-__device__ __forceinline__ int noise_level(uint32_t s) {
-    const uint32_t t = (s >> 3) + 16u;
-    const int e = 31 - __clz(t);                                   // 4 .. 16
-    return 4 * (e - 4) + (int)((t >> (e - 2)) & 3u);               // 0 .. 48
-}
 
 struct NoiseLds {
     unsigned long long* sums;   // [NOISE_LEVELS][NT_COLS]
@@ -53,15 +48,12 @@ struct NoiseLds {
     }
 };
 
-// One cell of uint16 voxels: a, b, c, d are the dwords (x, x + 1) of the rows (z, y), (z, y + 1), (z + 1, y),
-// (z + 1, y + 1).
+// One cell of uint16 voxels (cell_u16_sm of noise_cell.h names the four dwords).
 __device__ __forceinline__ void cell_u16(const NoiseLds& L, uint32_t a, uint32_t b, uint32_t c, uint32_t d, int shift,
                                          unsigned long long* __restrict__ hist) {
-    const int a0 = a & 0xFFFFu, a1 = a >> 16, b0 = b & 0xFFFFu, b1 = b >> 16;
-    const int c0 = c & 0xFFFFu, c1 = c >> 16, d0 = d & 0xFFFFu, d1 = d >> 16;
-    const uint32_t s = (uint32_t)(a0 + a1 + b0 + b1 + c0 + c1 + d0 + d1);
-    const int det = (a0 - a1) - (b0 - b1) - (c0 - c1) + (d0 - d1);
-    L.count(s, (uint32_t)abs(det), shift, hist);
+    uint32_t s, m;
+    cell_u16_sm(a, b, c, d, s, m);
+    L.count(s, m, shift, hist);
 }
 
 // One cell of fp32 voxels v[dz][dy][dx], with the association the specification fixes.

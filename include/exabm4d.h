@@ -885,6 +885,42 @@ int exabm4d_ssim3d_box_dev(exabm4d_ctx* ctx, const uint16_t* ref_win, const uint
 int exabm4d_noise_table_dev(exabm4d_ctx* ctx, const void* vol, int dtype, int nz, int ny, int nx, int shift,
                             uint64_t* hist_host, uint64_t* sum_s_host, uint64_t* skipped_host);
 
+/* ---- measuring a volume brick by brick: the counts and every shift's noise table in one pass -- */
+#define EXABM4D_COUNT_BINS 65536      /* counters of a table of the uint16 counts */
+#define EXABM4D_NOISE_WIDE_BINS 16384 /* wide magnitude bins per level of exabm4d_measure_box_u16_dev */
+
+/* One pass over a box inside a window (the geometry, its checks and its limits are those of the three entries of
+ * DESIGN.md 5.17 above) that ADDS to two tables resident on the device, so that the calls of all bricks of a volume
+ * build the tables of the volume; zero_first != 0 zeroes both before this box is counted.  Asynchronous on the
+ * context's stream.
+ *
+ * counts_dev: EXABM4D_COUNT_BINS uint64 counters, counts_dev[v] += 1 for every voxel of the box: what
+ * exabm4d_u16_histogram_dev gives for the volume once every box of a partition has been counted.
+ *
+ * noise_dev: EXABM4D_NOISE_LEVELS x EXABM4D_NOISE_WIDE_BINS uint64 counters wide[level][w], then
+ * sum_s[EXABM4D_NOISE_LEVELS].  The cells are exabm4d_noise_table_dev's for the whole volume -- the 2x2x2 cells at even
+ * coordinates of the VOLUME whose origin is below (dim & ~1) on every axis -- with its s, d and level bit for bit; a
+ * cell is counted by the box that contains its ORIGIN, so boxes may begin and end at odd coordinates and any partition
+ * of the volume counts every cell once.  The far corner of such a cell may lie one voxel outside the box: the entry
+ * verifies on the host that the window contains it and returns EXABM4D_ERR_INVALID, nothing launched, otherwise.
+ * The wide bin of m = |d| (< 2^18): w = m for m < 4096; otherwise, with j = floor(log2 m) - 11 (1..6),
+ * w = 4096 + (j - 1) 2048 + ((m >> j) - 2048).  Its lowest value is v0(w) = w for w < 4096, else (2048 + r) << j with
+ * j = (w - 4096) / 2048 + 1 and r = (w - 4096) % 2048, and exabm4d_noise_table_dev's table at any shift k = 0..6 is
+ * hist_k[level][min(v0(w) >> k, EXABM4D_NOISE_BINS - 1)] += wide[level][w], exactly; sum_s does not depend on k.
+ *
+ * With mask_win (uint16, non-zero = foreground; a window of the same geometry) both come twice, foreground then
+ * background: counts_dev holds 2 x EXABM4D_COUNT_BINS counters, noise_dev two blocks of (wide, sum_s) one after the
+ * other.  A voxel counts in the table its mask names; a cell is background only if all eight of its voxels are.
+ * mask_win may be NULL (one table each).  All counters are integers: the tables depend neither on the launch nor on how
+ * the volume was cut into boxes.  Further limits (EXABM4D_ERR_INVALID): at most 2^31 pairs of cell rows in the box, and
+ * 2^32 voxels in the share of one workgroup (one per compute unit).  Device buffers need the natural alignment of
+ * their element type only; rows are read with 16-byte loads where the window's pitch, its address and its x origin
+ * allow. */
+int exabm4d_measure_box_u16_dev(exabm4d_ctx* ctx, const uint16_t* win, const uint16_t* mask_win,
+                                const int32_t* vol_dims_zyx, const int32_t* win_origin_zyx,
+                                const int32_t* win_dims_zyx, const int32_t* box_origin_zyx, const int32_t* box_dims_zyx,
+                                int zero_first, uint64_t* counts_dev, uint64_t* noise_dev);
+
 /* ---- patch-cache foreground masks and coherence gate --
  * Batches of `batch` patches of nz x ny x nx voxels, contiguous in HBM.  Every entry point
  * synchronises the context's stream; floating-point results are deterministic (fixed mappings and
