@@ -33,6 +33,7 @@ SEG_STATS_K = 23            # exabm4d.h EXABM4D_SEG_STATS_K
 GAUSS_MAX_RADIUS = 64       # exabm4d.h EXABM4D_GAUSS_MAX_RADIUS
 NOISE_LEVELS = 49           # exabm4d.h EXABM4D_NOISE_LEVELS
 NOISE_BINS = 4096           # exabm4d.h EXABM4D_NOISE_BINS
+FG_MAX_RADIUS = 8           # exabm4d.h EXABM4D_FG_MAX_RADIUS: iterations of Context.foreground_box_u16
 NOISE_WIDE_BINS = 16384     # exabm4d.h EXABM4D_NOISE_WIDE_BINS: wide bins per level of Context.measure_box_u16
 COUNT_BINS = 65536          # exabm4d.h EXABM4D_COUNT_BINS: counters of a table of the uint16 counts
 EVAL_K = 16                 # exabm4d.h EXABM4D_EVAL_K: doubles per patch of Context.evaluate_batch
@@ -262,6 +263,9 @@ SIGNATURES = {
                                     ctypes.c_double, c_vp]),
     "exabm4d_noise_table_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp, c_vp, c_vp]),
     "exabm4d_measure_box_u16_dev": (_I, [_CTX, c_vp, c_vp, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _I, c_vp, c_vp]),
+    "exabm4d_foreground_box_u16_dev": (_I, [_CTX, c_vp, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _I, _I, _I, c_vp, c_vp,
+                                            c_vp, _I]),
+    "exabm4d_nonzero_u8_dev": (_I, [_CTX, c_vp, _SZ, c_vp]),
     "exabm4d_foreground_masks_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, _F, _I, c_vp, c_vp]),
     "exabm4d_binary_dilate_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp]),
     "exabm4d_gaussian_filter3d_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp, _I, c_vp]),
@@ -976,6 +980,26 @@ class Context:
         tri = self._box_geometry(vol_dims, win_origin, win_dims, box_origin, box_dims)
         self._check(lib().exabm4d_measure_box_u16_dev(self.handle, _ptr(win), _ptr(mask_win), *tri,
                                                       1 if zero_first else 0, _ptr(counts), _ptr(noise)))
+
+    # -- the foreground mask of a box inside a window ----------------------------
+    def foreground_box_u16(self, win, vol_dims, win_origin, win_dims, box_origin, box_dims, cut, radius, value=1,
+                           out_u16=None, out_u8=None, counts=None, zero_first=False):
+        """The mask of the box ``box_origin + [0, box_dims)`` of a uint16 window that holds ``win_origin + [0,
+        win_dims)`` of a volume of ``vol_dims`` (all z, y, x): ``value`` where a voxel of the VOLUME with a count
+        ``>= cut`` (0..65536) lies within the L1 distance ``radius`` (0..``FG_MAX_RADIUS``), else 0 -- ``radius``
+        iterations of the 6-neighbour cross on ``vol >= cut``.  ``out_u16`` (``value`` / 0) and ``out_u8`` (1 / 0):
+        dense device arrays of ``box_dims``, one at least.  ``counts``: two uint64 on the device, to which the seeds
+        and the mask voxels of the box are added (``zero_first`` zeroes them before).  What the window holds past the
+        volume's faces is never a seed.  ValueError when the window misses the box grown by ``radius`` (cut at the
+        volume).  Asynchronous."""
+        tri = self._box_geometry(vol_dims, win_origin, win_dims, box_origin, box_dims)
+        self._check(lib().exabm4d_foreground_box_u16_dev(self.handle, _ptr(win), *tri, int(cut), int(radius),
+                                                         int(value), _ptr(out_u16), _ptr(out_u8), _ptr(counts),
+                                                         1 if zero_first else 0))
+
+    def nonzero_u8(self, src, n, dst):
+        """``dst[i] = src[i] != 0`` for ``n`` uint16 elements on the device, as bytes.  Asynchronous."""
+        self._check(lib().exabm4d_nonzero_u8_dev(self.handle, _ptr(src), int(n), _ptr(dst)))
 
     # -- patch-cache masks and coherence gate (DESIGN.md 5.8); batches of (nz, ny, nx) patches --
     def foreground_masks(self, raw, dtype, batch, shape, k, dilate, mask):

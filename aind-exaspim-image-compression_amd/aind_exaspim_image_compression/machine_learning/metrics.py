@@ -26,6 +26,7 @@ import numpy as np
 
 from aind_exaspim_image_compression import _native
 from aind_exaspim_image_compression.utils import order_stats
+from aind_exaspim_image_compression.utils.store_foreground import foreground_store, foreground_volume  # noqa: F401
 
 # reference metrics.py:24-29
 DEFAULT_CHECKPOINT_WEIGHTS = {

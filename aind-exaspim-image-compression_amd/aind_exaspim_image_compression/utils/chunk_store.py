@@ -33,6 +33,7 @@ import numpy as np
 from aind_exaspim_image_compression.utils.block_bounded_codec import BlockBoundedCodec
 from aind_exaspim_image_compression.utils.bounded_codec import BoundedDctCodec
 from aind_exaspim_image_compression.utils.chunk_codec import EncodedVolume, ExacCodec
+from aind_exaspim_image_compression.utils.store_recode import recode_store  # noqa: F401  (re-exported)
 
 FORMAT_NOTE = ("EXAC chunk streams (aind-exaspim-image-compression_amd, DESIGN.md 3.11b); edge chunks truncated to "
                "the array; decode with utils.chunk_codec.ExacCodec.decode or utils.chunk_store.read_zarr")

@@ -82,9 +82,11 @@ def plan_compare(shape, chunks_zyx, window, budget_bytes, with_mask=False):
     return plan_bricks(shape, chunk, budget, stores, lambda b0, bd, dim: halo_range(b0, bd, dim, window))
 
 
-def plan_bricks(shape, chunk, budget, stores, axis_window):
+def plan_bricks(shape, chunk, budget, stores, axis_window, brick_bytes=0):
     """``plan_compare``'s rule for any window: ``axis_window(b0, bd, dim) -> (start, extent)`` is what a brick that
-    covers ``[b0, b0 + bd)`` of an axis of ``dim`` voxels has to read there; ``stores`` windows are held at a time."""
+    covers ``[b0, b0 + bd)`` of an axis of ``dim`` voxels has to read there; ``stores`` windows are held at a time.
+    ``brick_bytes``: what a loop holds besides the windows, per voxel of the brick itself (a result, a pool of
+    destination chunks)."""
     grid = [-(-s // c) for s, c in zip(shape, chunk)]
 
     def axes(a, n):
@@ -93,7 +95,9 @@ def plan_bricks(shape, chunk, budget, stores, axis_window):
 
     def bound(per_axis):
         widest = [max(r[3] for r in ax) for ax in per_axis]
-        return _cost((_held_z(widest[0], chunk[0]), widest[1], widest[2]), stores, budget)
+        longest = [max(r[1] - r[0] for r in ax) for ax in per_axis]
+        return (_cost((_held_z(widest[0], chunk[0]), widest[1], widest[2]), stores, budget) +
+                brick_bytes * longest[0] * longest[1] * longest[2])
 
     n = [1, 1, 1]
     per_axis = [axes(a, 1) for a in range(3)]
@@ -112,8 +116,10 @@ def plan_bricks(shape, chunk, budget, stores, axis_window):
     bricks = []
     for r in itertools.product(*per_axis):
         wn = tuple(q[3] for q in r)
-        bricks.append(Brick(tuple(q[0] for q in r), tuple(q[1] - q[0] for q in r), tuple(q[2] for q in r), wn,
-                            _cost((_held_z(wn[0], chunk[0]), wn[1], wn[2]), stores, budget)))
+        ext = tuple(q[1] - q[0] for q in r)
+        bricks.append(Brick(tuple(q[0] for q in r), ext, tuple(q[2] for q in r), wn,
+                            _cost((_held_z(wn[0], chunk[0]), wn[1], wn[2]), stores, budget) +
+                            brick_bytes * ext[0] * ext[1] * ext[2]))
     return bricks
 
 

@@ -1,0 +1,219 @@
+"""The foreground mask of a stored volume, out of core: ``foreground_store`` makes
+``make_foreground_mask`` of the whole volume store to store, ``foreground_volume`` is its in-memory twin.
+
+Two facts carry it.  The whole-volume threshold follows exactly from the table of the counts that
+``utils.noise.measure_store`` makes (``StoreMeasure.foreground_threshold``), and for integer counts ``raw > thr`` is the
+integer test ``raw >= cut``.  And ``dilate`` iterations of the 6-neighbour cross with border 0 are one dilation by the L1
+ball of radius ``dilate``, cut at the volume's faces: a brick read with a halo of ``dilate`` voxels gives the
+whole-volume mask exactly.  Per brick one kernel launch thresholds, packs and dilates
+(``exabm4d_foreground_box_u16_dev``, ``csrc/foreground_kernels.hip``).
+"""
+import time
+
+import numpy as np
+
+from aind_exaspim_image_compression import _native
+from aind_exaspim_image_compression.utils import store_compare
+from aind_exaspim_image_compression.utils.store_measure import StoreMeasure, cut_of_threshold
+from aind_exaspim_image_compression.utils.store_predict import BRICK_BYTES, POOL_BYTES
+
+MAX_DILATE = _native.FG_MAX_RADIUS
+
+
+def halo_window(radius):
+    """``axis_window`` of ``store_compare.plan_bricks``: ``[max(0, b0 - radius), min(dim, b0 + bd + radius))``."""
+    def axis_window(b0, bd, dim):
+        lo = max(0, b0 - radius)
+        return lo, min(dim, b0 + bd + radius) - lo
+    return axis_window
+
+
+def plan_foreground(shape, chunks_zyx, dilate, budget_bytes):
+    """The bricks (``store_compare.Brick``) of masking a volume of ``shape`` (z, y, x) into a store with chunks of
+    ``chunks_zyx``, in raster order: boxes of whole destination chunks that partition the volume, grown as
+    ``store_compare.plan_compare`` grows them.  A brick's window is the brick grown by ``dilate`` voxels per axis and
+    cut at the volume's faces.  A brick costs its window at 2 bytes a voxel as it is held, the reader's pool of decoded
+    chunks (``budget_bytes // READER_SHARE``), and per voxel of the brick the dense mask and the destination pool with
+    its coded streams.  A brick of a single chunk is accepted whatever it costs."""
+    shape = tuple(int(s) for s in shape)
+    chunk = tuple(int(c) for c in chunks_zyx)
+    dilate, budget = int(dilate), int(budget_bytes)
+    if len(shape) != 3 or len(chunk) != 3 or min(shape) < 1 or min(chunk) < 1:
+        raise ValueError("plan_foreground: shape and chunks are three positive sizes each")
+    if not 0 <= dilate <= MAX_DILATE or budget < 1:
+        raise ValueError("plan_foreground: 0 <= dilate <= %d and budget_bytes >= 1" % MAX_DILATE)
+    return store_compare.plan_bricks(shape, chunk, budget, 1, halo_window(dilate), BRICK_BYTES + POOL_BYTES)
+
+
+def _check_mask_args(who, k, dilate, threshold, value=1):
+    dilate = int(dilate)
+    if not 0 <= dilate <= MAX_DILATE:
+        raise ValueError("%s: dilate must be 0..%d" % (who, MAX_DILATE))
+    if not 1 <= int(value) <= 65535:
+        raise ValueError("%s: value must be 1..65535" % who)
+    if threshold is not None:
+        if not np.isfinite(float(threshold)):
+            raise ValueError("%s: threshold must be a finite number of counts" % who)
+    elif not np.isfinite(float(k)) or float(k) < 0.0:
+        raise ValueError("%s: k must be finite and >= 0" % who)
+    return dilate, int(value)
+
+
+def foreground_store(src, dst_path, k=6.0, dilate=1, threshold=None, measure=None, value=1, chunks=None, codec=None,
+                     attributes=None, budget_bytes=4 << 30, device=None, stats=None):
+    """The foreground mask of the stored uint16 volume ``src`` as a store of its own, without ever holding the volume:
+    ``dst_path`` is, chunk file for chunk file, ``write_zarr((make_foreground_mask(read_zarr(src)[0, 0], k, dilate) *
+    value).astype(uint16), dst_path, chunks, codec)`` -- a mask store (uint16, non-zero = foreground) as
+    ``measure_store(mask=)``, ``compare_stores(mask=)`` and ``recode_store(mask=)`` take it.
+
+    The threshold is the WHOLE volume's: ``threshold`` (a number in counts) if given; else
+    ``measure.foreground_cut(k)`` of a ``StoreMeasure`` of ``src``; else the function measures ``src`` itself first
+    (``measure_store``, one more pass: ``stats["passes"]`` is then 2, otherwise 1).  Seeds are the voxels above it
+    (``raw >= cut`` with ``cut = floor(threshold) + 1``, clamped to 0..65536), dilated ``dilate`` (0..8) times.
+
+    ``src``: a path or a ``StoredArray`` opened for the device used here.  The destination is made with
+    ``create_zarr`` (``chunks``: default the source's; ``codec``: default ``ExacCodec(2)``; ``attributes``).  Bricks
+    are boxes of whole destination chunks (``plan_foreground``, at most ``budget_bytes`` of device memory each; a
+    single chunk is taken whatever it costs).  Per brick: one region read of the brick and its halo of ``dilate``
+    voxels that stays on the device, one kernel launch into a dense brick, a scatter into the pool of destination
+    chunks, which is coded and committed.
+
+    Returns ``{"threshold", "cut", "n", "n_seed", "n_fg", "fraction", "cratio"}``: the voxels, those above the
+    threshold, those of the mask, ``n_fg / n`` and raw bytes / stored bytes.  ``stats`` (a dict) receives ``seconds``
+    per phase (measure, read, mask, scatter, encode, files_write; the stream is synchronised around the phases only
+    when ``stats`` is given), ``bricks``, ``passes``, ``voxels_read`` (with the halos; the measuring pass counts its
+    own) and ``largest_alloc``, the most device bytes held here at one time."""
+    from aind_exaspim_image_compression.utils import chunk_store, noise, store_windows, store_write
+    from aind_exaspim_image_compression.utils.chunk_codec import ExacCodec
+    # -- every argument check, before a context exists
+    dilate, value = _check_mask_args("foreground_store", k, dilate, threshold, value)
+    budget = int(budget_bytes)
+    if budget < 1:
+        raise ValueError("foreground_store: budget_bytes must be positive")
+    if chunks is not None:
+        try:
+            chunks = tuple(int(c) for c in chunks)
+        except TypeError:
+            raise ValueError("chunks must be (1, 1, cz, cy, cx)") from None
+        if len(chunks) != 5 or chunks[:2] != (1, 1) or min(chunks) < 1:
+            raise ValueError("chunks must be (1, 1, cz, cy, cx)")
+    if measure is not None and not isinstance(measure, StoreMeasure):
+        raise ValueError("foreground_store: measure is a StoreMeasure (utils.noise.measure_store)")
+    index = int(device) if device is not None else _native.default_device()
+    (arr,) = store_windows.open_u16_stores("foreground_store", (("src", src),), index)
+    shape = tuple(int(s) for s in arr.shape[2:])
+    if measure is not None and threshold is None and tuple(measure.shape) != shape:
+        raise ValueError("foreground_store: measure was made of another shape than src")
+    chunks = chunks if chunks is not None else tuple(int(c) for c in arr.chunks)
+    codec = codec or ExacCodec(2)
+    bricks = plan_foreground(shape, chunks[2:], dilate, budget)
+
+    seconds = dict.fromkeys(("measure", "read", "mask", "scatter", "encode", "files_write"), 0.0)
+    passes, voxels_read, most = 1, 0, 0
+    if threshold is not None:
+        thr = float(threshold)
+    else:
+        if measure is None:
+            t0 = time.perf_counter()
+            inner = {}
+            measure = noise.measure_store(arr, budget_bytes=budget, device=index, stats=inner)
+            seconds["measure"] = time.perf_counter() - t0
+            passes, voxels_read, most = 2, inner["voxels_read"], inner["largest_alloc"]
+        thr = float(measure.foreground_threshold(k))
+    cut = cut_of_threshold(thr)
+
+    ctx = _native.context(index)
+    out = chunk_store.create_zarr(dst_path, shape, chunks, codec=codec, attributes=attributes, overwrite=True,
+                                  device=index)
+    source = store_windows.StoreWindows([arr], int(arr.chunks[2]))
+    st = store_write._new_stats()
+    timed = stats is not None
+
+    def clock():
+        if timed:
+            ctx.sync()
+        return time.perf_counter()
+
+    written = 0
+    d_counts = d_table = None
+    try:
+        d_counts = ctx.alloc(16)
+        d_table = store_write.bound_table_on_device(out, ctx)
+        with store_windows.capped_pools([arr], budget):
+            for n_brick, brick in enumerate(bricks):
+                nvox = int(np.prod(brick.extent))
+                (g,) = store_write.plan_write(shape, chunks[2:], [brick.origin], [brick.extent], out._nominal,
+                                              exists=lambda *idx: False, max_pool_bytes=1 << 62)
+                if any(s != store_write.COVERED for s in g.states):
+                    raise RuntimeError("foreground_store: a destination chunk is not covered by one brick")
+                t0 = time.perf_counter()
+                wins, dims = source.read(brick.win_origin, brick.win_extent)
+                d_brick = pool = None
+                try:
+                    t1 = clock()
+                    try:
+                        d_brick = ctx.alloc(2 * nvox)
+                        most = max(most, 2 * int(np.prod(dims)) + 2 * nvox + 16)
+                        ctx.foreground_box_u16(wins[0], shape, brick.win_origin, dims, brick.origin, brick.extent, cut,
+                                               dilate, value, out_u16=d_brick, counts=d_counts,
+                                               zero_first=n_brick == 0)
+                        t2 = clock()
+                    finally:
+                        source.release(wins)             # (freeing a buffer waits for the stream)
+                    voxels_read += brick.window_voxels
+                    pool = store_write.open_pool(out, ctx, g, st)
+                    most = max(most, 2 * nvox + 2 * g.pool_elems + 16)
+                    store_write.scatter(ctx, g, pool, d_brick, nvox, np.uint16,
+                                        store_write.box_records([brick.origin], brick.extent))
+                    t3 = clock()
+                    d_brick.free()
+                    d_brick = None
+                    seconds["read"] += t1 - t0
+                    seconds["mask"] += t2 - t1
+                    seconds["scatter"] += t3 - t2
+                    written += store_write.encode_commit(out, ctx, g, pool, st, d_table)
+                finally:
+                    if d_brick is not None:
+                        d_brick.free()
+                    if pool is not None:
+                        pool.free()
+        n_seed, n_fg = (int(c) for c in d_counts.download((2,), np.uint64))
+    finally:
+        for buf in (d_counts, d_table):
+            if buf is not None:
+                buf.free()
+    seconds["encode"], seconds["files_write"] = st["seconds"]["encode"], st["seconds"]["files_write"]
+    n = shape[0] * shape[1] * shape[2]
+    if stats is not None:
+        stats.update(seconds=seconds, bricks=len(bricks), passes=passes, voxels_read=voxels_read, largest_alloc=most,
+                     chunks=st["chunks"], encode_calls=st["encode_calls"])
+    return {"threshold": thr, "cut": cut, "n": n, "n_seed": n_seed, "n_fg": n_fg, "fraction": n_fg / n,
+            "cratio": 2 * n / written}
+
+
+def foreground_volume(vol, k=6.0, dilate=1, threshold=None, device=None):
+    """``foreground_store`` for a 3-D uint16 array in memory: ``make_foreground_mask(vol, k, dilate)`` as a host
+    ``bool`` array.  The array is uploaded once and masked as one brick; the threshold comes from ``threshold``
+    (counts) or from the table of its counts (``measure_volume``)."""
+    vol = np.asarray(vol)
+    if vol.dtype != np.uint16 or vol.ndim != 3 or 0 in vol.shape:
+        raise ValueError("foreground_volume: vol is a 3-D uint16 array without an empty axis")
+    dilate, _ = _check_mask_args("foreground_volume", k, dilate, threshold)
+    shape = tuple(int(s) for s in vol.shape)
+    ctx = _native.context(device)
+    d_vol = d_out = None
+    try:
+        d_vol = ctx.to_device(np.ascontiguousarray(vol))
+        if threshold is not None:
+            cut = cut_of_threshold(float(threshold))
+        else:
+            hist = ctx.u16_histogram(d_vol, vol.size)
+            dummy = np.zeros((1, _native.measure_noise_words()), dtype=np.uint64)
+            cut = StoreMeasure.from_tables(shape, hist, dummy).foreground_cut(k)
+        d_out = ctx.alloc(vol.size)
+        ctx.foreground_box_u16(d_vol, shape, (0, 0, 0), shape, (0, 0, 0), shape, cut, dilate, 1, out_u8=d_out)
+        return d_out.download(shape, np.uint8).view(np.bool_)
+    finally:
+        for buf in (d_vol, d_out):
+            if buf is not None:
+                buf.free()

@@ -97,6 +97,27 @@ def _counts(a, name):
     return a.astype(np.uint64)
 
 
+def _twice_median(table):
+    """The sum of the two middle values of the population that holds the value ``i`` ``table[i]`` times."""
+    cum = np.cumsum(table, dtype=np.uint64)
+    n = int(cum[-1])
+    lo = np.searchsorted(cum, np.uint64((n - 1) // 2 + 1))
+    hi = np.searchsorted(cum, np.uint64(n // 2 + 1))
+    return int(lo) + int(hi)
+
+
+def cut_of_threshold(thr):
+    """The least integer count above the threshold ``thr`` (counts), clamped to 0..65536."""
+    thr = float(thr)
+    if np.isnan(thr):
+        raise ValueError("a foreground threshold is a number")
+    if thr < 0.0:
+        return 0
+    if thr >= COUNT_BINS - 1:
+        return COUNT_BINS
+    return int(np.floor(thr)) + 1
+
+
 @dataclass
 class StoreMeasure:
     """What one pass over a uint16 volume leaves: ``counts[v]`` voxels of every value, the wide noise table
@@ -165,6 +186,32 @@ class StoreMeasure:
         """``transforms.background_offset_statistics`` of the volume."""
         from aind_exaspim_image_compression.machine_learning.transforms import background_offset_statistics_of_hist
         return background_offset_statistics_of_hist(self.counts, percentile)
+
+    # -- the foreground threshold (DESIGN.md 5.19) ------------------------------------------------
+    def foreground_threshold(self, k=6.0):
+        """``make_foreground_mask``'s threshold ``med + k * 1.4826 * (MAD + 1e-6)`` of the whole volume as the
+        ``np.float32`` numpy's fp32 arithmetic gives, from the counts alone.  The median of integer counts is the mean
+        of the two middle ones, a multiple of 1/2 and exact in fp32; the deviations ``|v - med|`` are then exact as
+        well, and their median is that of the counts folded onto ``|2 v - 2 med|``, halved.  The four operations that
+        follow round to fp32 one by one (``order_stats`` works in fp64 and differs after the ``+ 1e-6``)."""
+        k = float(k)
+        if not np.isfinite(k) or k < 0.0:
+            raise ValueError("foreground_threshold: k must be finite and >= 0")
+        med2 = _twice_median(self.counts)
+        folded = np.zeros(2 * (COUNT_BINS - 1) + 1, dtype=np.uint64)
+        np.add.at(folded, np.abs(2 * np.arange(COUNT_BINS, dtype=np.int64) - med2), self.counts)
+        mad4 = _twice_median(folded)
+        f32 = np.float32
+        med = f32(med2) / f32(2)
+        mad = f32(mad4) / f32(4) + f32(1e-6)
+        sigma = f32(1.4826) * mad
+        with np.errstate(over="ignore"):
+            return f32(med + f32(k) * sigma)
+
+    def foreground_cut(self, k=6.0):
+        """The least count above ``foreground_threshold(k)``, 0..65536: for integer counts ``raw > thr`` is
+        ``raw >= cut``, and a cut of 65536 means that no voxel is foreground."""
+        return cut_of_threshold(self.foreground_threshold(k))
 
     # -- the noise table --------------------------------------------------------------------------
     def _wide(self, which):

@@ -316,6 +316,23 @@ struct OpLutForward {
     }
 };
 
+// dst[i] = src[i] != 0: a uint16 mask window (non-zero = foreground) as the bytes a mask pool takes
+struct OpNonzeroU8 {
+    const uint16_t* in;
+    uint8_t* out;
+    __device__ void one(size_t i) const { out[i] = in[i] ? 1 : 0; }
+    __device__ void eight(size_t i) const {
+        const uint4 r = *reinterpret_cast<const uint4*>(in + i);
+        const unsigned w[4] = {r.x, r.y, r.z, r.w};
+        uint2 q;
+        q.x = ((w[0] & 0xFFFFu) ? 1u : 0u) | ((w[0] >> 16) ? 1u << 8 : 0u) | ((w[1] & 0xFFFFu) ? 1u << 16 : 0u) |
+              ((w[1] >> 16) ? 1u << 24 : 0u);
+        q.y = ((w[2] & 0xFFFFu) ? 1u : 0u) | ((w[2] >> 16) ? 1u << 8 : 0u) | ((w[3] & 0xFFFFu) ? 1u << 16 : 0u) |
+              ((w[3] >> 16) ? 1u << 24 : 0u);
+        *reinterpret_cast<uint2*>(out + i) = q;
+    }
+};
+
 static inline unsigned ew_blocks(size_t n);
 static inline bool aligned16(const void* a, const void* b, const void* c = nullptr) {
     return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15u) == 0;
@@ -968,6 +985,10 @@ hipError_t launch_round_counts(const float* in, float* out_f32, uint16_t* out_u1
         return launch_stream(OpRoundCountsU16{in, out_u16x, offset}, n,
                              aligned16(in, in) && ((uintptr_t)out_u16x & 15) == 0, s);
     return launch_stream(OpRoundCountsF32{in, out_f32, offset}, n, aligned16(in, out_f32), s);
+}
+hipError_t launch_nonzero_u8(const uint16_t* src, uint8_t* dst, size_t n, hipStream_t s) {
+    if (!n) return hipSuccess;
+    return launch_stream(OpNonzeroU8{src, dst}, n, ((uintptr_t)src & 15u) == 0 && ((uintptr_t)dst & 7u) == 0, s);
 }
 hipError_t launch_normalize_u16(const float* num, const float* den, uint16_t* out, size_t n,
                                 float offset, hipStream_t s) {

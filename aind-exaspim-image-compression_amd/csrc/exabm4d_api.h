@@ -136,6 +136,7 @@ struct exabm4d_ctx {
     hipEvent_t region_ev = nullptr;
     int noise_wgs = 0;         // noise table: workgroups per launch (one per CU); 0 = noise_table_prepare() not yet run
     int measure_wgs = 0;       // measuring a box: the same; 0 = measure_prepare() not yet run
+    int foreground_ready = 0;  // the foreground mask of a box: foreground_prepare() has run
     int force_generic_bm = 0;  // exabm4d_set_option("force_generic_bm")
     int bm_guarded_copy = 0;   // exabm4d_set_option("bm_guarded_copy"): staged block matching on a guarded copy
     exabm4d::StageOpts stage;  // exabm4d_set_option("stage_pairvol" / "stage_strip" / "stage_chunks")

@@ -134,6 +134,30 @@ bool measure_box_plan(const uint16_t* win, const uint16_t* mask, const BoxGeom& 
 // tables each, foreground then background.
 hipError_t launch_measure_box_u16(const uint16_t* win, const uint16_t* mask, const BoxGeom& g, const MeasurePlan& p,
                                   unsigned long long* counts, unsigned long long* noise, hipStream_t s);
+// ---- the foreground mask of a box (foreground_kernels.hip) ----
+constexpr int FG_MAX_RADIUS = 8;         // dilation iterations one launch makes (exabm4d.h EXABM4D_FG_MAX_RADIUS)
+constexpr int FG_LANES_OUT = 61;         // output vectors of eight voxels per row of a region
+constexpr int FG_STRIDE_X = 8 * FG_LANES_OUT;
+// How a box is cut into regions: per axis the part [r0, r1) of the volume whose voxels may be seeds (inside the
+// volume, the window and box +- radius); xs, the x of region 0's first voxel; shift (0..7), the voxel of a lane at
+// which an output vector begins; whether rows are loaded / stored as vectors; the regions per axis (x, y, z).
+struct FgPlan {
+    int r0[3], r1[3];
+    int xs, shift;
+    int vec_in, vec_u16, vec_u8;
+    unsigned tiles[3];
+};
+hipError_t foreground_prepare();         // once per device, on the current device: raises the kernel's LDS limit
+// false: more regions than a launch takes
+bool foreground_box_plan(const uint16_t* win, const BoxGeom& g, int radius, const uint16_t* out16, const uint8_t* out8,
+                         FgPlan& p);
+// out16 / out8: dense box-shaped outputs, either may be NULL; counts: NULL, or {seeds in the box, mask voxels in the
+// box}, ADDED to once per workgroup
+hipError_t launch_foreground_box_u16(const uint16_t* win, const BoxGeom& g, const FgPlan& p, uint32_t cut, int radius,
+                                     uint32_t value, uint16_t* out16, uint8_t* out8, unsigned long long* counts,
+                                     hipStream_t s);
+// dst[i] = src[i] != 0 (elementwise_kernels.hip): a uint16 mask window as the bytes a mask pool takes
+hipError_t launch_nonzero_u8(const uint16_t* src, uint8_t* dst, size_t n, hipStream_t s);
 // Options of block matching (per context since round 4; exabm4d_set_option "bm_xcd_mode" / "bm_carry" / "bm_carry_fault")
 struct BmOpts {
     int xcd_mode = 2;       // workgroup order: 0 = contiguous per XCD, 1 = all XCDs in one z slab of tiles (raster), n >= 2 = in strips of n tile rows

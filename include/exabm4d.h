@@ -921,6 +921,40 @@ int exabm4d_measure_box_u16_dev(exabm4d_ctx* ctx, const uint16_t* win, const uin
                                 const int32_t* win_dims_zyx, const int32_t* box_origin_zyx, const int32_t* box_dims_zyx,
                                 int zero_first, uint64_t* counts_dev, uint64_t* noise_dev);
 
+/* ---- the foreground mask of a stored volume, box by box ------------------------------
+ * The geometry of exabm4d_measure_box_u16_dev: win (device, uint16, dense) holds win_origin + [0, win_dims) of a
+ * volume of vol_dims voxels, the box box_origin + [0, box_dims) lies inside both.  For every voxel b of the box
+ *     out[b] = value  if some voxel p of the VOLUME has vol[p] >= cut and |p - b|_1 <= radius,  else 0:
+ * `radius` iterations of the 6-neighbour cross with border 0 (scipy.ndimage.binary_dilation) of vol >= cut are one
+ * dilation by the L1 ball, cut at the volume's faces, so the mask of a box depends only on the voxels within `radius`
+ * of it along each axis, and a partition of a volume into boxes gives the whole-volume mask.  With
+ * cut = floor(thr) + 1 this is make_foreground_mask's raw > thr for integer counts; cut = 65536 makes no voxel a seed.
+ * The window may reach past the volume's upper faces (a reader's padding, whatever it holds): such positions are
+ * never seeds, whatever cut is.  The window must hold the box grown by `radius` per axis and cut at the volume's
+ * faces; that is checked on the host.
+ * out_u16 (value / 0) and out_u8 (1 / 0) are dense arrays of box_dims on the device; either may be NULL, not both.
+ * counts_dev: NULL, or two uint64 words on the device, to which the call ADDS the number of seeds (vol >= cut) in
+ * the box and the number of mask voxels in the box, once per workgroup; zero_first zeroes them before.  Integers:
+ * they depend neither on the launch nor on how a volume was cut into boxes.
+ * One launch: threshold, packing by ballot into 64-bit words in LDS, every iteration on those words, expansion.
+ * Checked on the host (EXABM4D_ERR_INVALID, nothing written): non-NULL ctx, win and geometry, one output at least,
+ * cut 0..65536, radius 0..EXABM4D_FG_MAX_RADIUS, value 1..65535, the geometry, at most 65535 regions of
+ * 32 - 2 radius rows along z and y.  Alignment: win and out_u16 2 bytes, out_u8 none, counts_dev 8 bytes; rows are
+ * loaded with 16-byte loads where win_dims[2] is a multiple of 8 (at any phase of the address), and stored with
+ * 16-byte (out_u8: 8-byte) stores where box_dims[2] is, out_u8 together with out_u16 only at the same phase of eight
+ * elements.  Asynchronous on the context's stream. */
+#define EXABM4D_FG_MAX_RADIUS 8
+int exabm4d_foreground_box_u16_dev(exabm4d_ctx* ctx, const uint16_t* win, const int32_t* vol_dims_zyx,
+                                   const int32_t* win_origin_zyx, const int32_t* win_dims_zyx,
+                                   const int32_t* box_origin_zyx, const int32_t* box_dims_zyx, int cut, int radius,
+                                   int value, uint16_t* out_u16, uint8_t* out_u8, uint64_t* counts_dev,
+                                   int zero_first);
+
+/* dst[i] = src[i] != 0 for n elements on the device: a uint16 mask window (non-zero = foreground) as the bytes a
+ * mask pool of exabm4d_scatter_boxes_dev takes.  src at an even address, dst at any; 16-byte loads and 8-byte stores
+ * where src is 16-byte and dst 8-byte aligned.  n == 0 succeeds without a launch.  Asynchronous. */
+int exabm4d_nonzero_u8_dev(exabm4d_ctx* ctx, const uint16_t* src, size_t n, uint8_t* dst);
+
 /* ---- patch-cache foreground masks and coherence gate --
  * Batches of `batch` patches of nz x ny x nx voxels, contiguous in HBM.  Every entry point
  * synchronises the context's stream; floating-point results are deterministic (fixed mappings and
