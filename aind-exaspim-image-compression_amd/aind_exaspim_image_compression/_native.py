@@ -34,6 +34,7 @@ GAUSS_MAX_RADIUS = 64       # exabm4d.h EXABM4D_GAUSS_MAX_RADIUS
 NOISE_LEVELS = 49           # exabm4d.h EXABM4D_NOISE_LEVELS
 NOISE_BINS = 4096           # exabm4d.h EXABM4D_NOISE_BINS
 FG_MAX_RADIUS = 8           # exabm4d.h EXABM4D_FG_MAX_RADIUS: iterations of Context.foreground_box_u16
+CC_TILE = (8, 8, 64)        # exabm4d.h EXABM4D_CC_TILE_Z / _Y / _X: the tile Context.component_seeds_u16 labels in LDS
 NOISE_WIDE_BINS = 16384     # exabm4d.h EXABM4D_NOISE_WIDE_BINS: wide bins per level of Context.measure_box_u16
 COUNT_BINS = 65536          # exabm4d.h EXABM4D_COUNT_BINS: counters of a table of the uint16 counts
 EVAL_K = 16                 # exabm4d.h EXABM4D_EVAL_K: doubles per patch of Context.evaluate_batch
@@ -265,6 +266,10 @@ SIGNATURES = {
     "exabm4d_measure_box_u16_dev": (_I, [_CTX, c_vp, c_vp, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _I, c_vp, c_vp]),
     "exabm4d_foreground_box_u16_dev": (_I, [_CTX, c_vp, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _I, _I, _I, c_vp, c_vp,
                                             c_vp, _I]),
+    "exabm4d_components_scratch_bytes": (_SZ, [c_i32p, _I]),
+    "exabm4d_component_seeds_u16_dev": (_I, [_CTX, c_vp, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _I, _I,
+                                             _I, c_vp, c_vp, c_vp, c_vp, _SZ, c_vp, _I]),
+    "exabm4d_label_components_dev": (_I, [_CTX, c_vp, _I, c_i32p, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, _SZ, c_vp]),
     "exabm4d_nonzero_u8_dev": (_I, [_CTX, c_vp, _SZ, c_vp]),
     "exabm4d_foreground_masks_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, _F, _I, c_vp, c_vp]),
     "exabm4d_binary_dilate_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp]),
@@ -361,6 +366,25 @@ def lib():
                 fn.argtypes = args
             _lib = L
     return _lib
+
+
+def components_scratch_bytes(win_dims, connectivity=26):
+    """Bytes of scratch ``Context.component_seeds_u16`` takes for a window of ``win_dims`` (z, y, x); ValueError for
+    bad arguments or 2^31 voxels and more.  No GPU needed."""
+    dims = (ctypes.c_int32 * 3)(*(int(v) for v in win_dims))
+    n = int(lib().exabm4d_components_scratch_bytes(dims, int(connectivity)))
+    if n == 0:
+        raise ValueError("components_scratch_bytes: dims >= 1 with fewer than 2^31 voxels, connectivity 6 or 26")
+    return n
+
+
+def components_region(vol_dims, box_origin, box_dims, min_voxels):
+    """(origin, dims) of the region ``Context.component_seeds_u16`` labels: the box grown by ``min_voxels - 1`` voxels
+    per axis and cut at the volume's faces (all z, y, x)."""
+    grow = max(0, int(min_voxels) - 1)
+    lo = tuple(max(0, int(b) - grow) for b in box_origin)
+    hi = tuple(min(int(n), int(b) + int(d) + grow) for n, b, d in zip(vol_dims, box_origin, box_dims))
+    return lo, tuple(h - l for h, l in zip(hi, lo))
 
 
 def default_params(**overrides):
@@ -996,6 +1020,58 @@ class Context:
         self._check(lib().exabm4d_foreground_box_u16_dev(self.handle, _ptr(win), *tri, int(cut), int(radius),
                                                          int(value), _ptr(out_u16), _ptr(out_u8), _ptr(counts),
                                                          1 if zero_first else 0))
+
+    # -- connected components of the seeds, and their filter by size -------------
+    def component_seeds_u16(self, win, vol_dims, win_origin, win_dims, box_origin, box_dims, cut, min_voxels,
+                            connectivity=26, count_origin=None, count_dims=None, seeds_u16=None, labels=None,
+                            sizes=None, scratch=None, counts=None, zero_first=False, scratch_bytes=None):
+        """The seeds (``>= cut``) of a uint16 window in the geometry of ``foreground_box_u16``, labelled by
+        connected component (``connectivity`` 6 or 26) inside ``components_region(...)`` -- the box grown by
+        ``min_voxels - 1`` and cut at the volume, which the window must hold -- and filtered: ``seeds_u16`` (dense
+        uint16 of ``box_dims``) gets 1 where a seed's component has at least ``min_voxels`` voxels, else 0.
+        ``labels`` / ``sizes``: uint32 per voxel of the region (label = 1 + region index of the component's first
+        voxel; its size at index label - 1).  ``counts``: three uint64 on the device to which the seeds, the kept
+        seeds and the dropped components (by first voxel) of ``count_origin + [0, count_dims)`` (default: the box)
+        are added (``zero_first`` zeroes them before).  ``scratch``: a device buffer of at least
+        ``components_scratch_bytes(win_dims)`` bytes (``scratch_bytes`` of them where it is a bare pointer); one
+        is allocated and freed here when None.  Asynchronous when ``scratch`` is given."""
+        tri = self._box_geometry(vol_dims, win_origin, win_dims, box_origin, box_dims)
+        cnt = [(ctypes.c_int32 * 3)(*(int(v) for v in t))
+               for t in (box_origin if count_origin is None else count_origin,
+                         box_dims if count_dims is None else count_dims)]
+        own = None
+        if scratch is None:
+            scratch = own = self.alloc(max(256, components_scratch_bytes(win_dims, connectivity)))
+        try:
+            self._check(lib().exabm4d_component_seeds_u16_dev(
+                self.handle, _ptr(win), *tri, *cnt, int(cut), int(min_voxels), int(connectivity), _ptr(seeds_u16),
+                _ptr(labels), _ptr(sizes), _ptr(scratch), int(scratch.nbytes if scratch_bytes is None else scratch_bytes),
+                _ptr(counts), 1 if zero_first else 0))
+        finally:
+            if own is not None:
+                own.free()                               # (freeing a buffer waits for the stream)
+
+    def label_components(self, src, dtype, shape, cut=1, min_voxels=1, connectivity=26, labels=None, sizes=None,
+                         kept_u8=None, scratch=None, counts=None, scratch_bytes=None):
+        """``component_seeds_u16`` for a dense uint8 (seed where non-zero) or uint16 (seed where ``>= cut``) array
+        of ``shape`` resident on the device, as box = window = volume: ``labels`` / ``sizes`` (uint32 per voxel),
+        ``kept_u8`` (1 where the voxel's component has at least ``min_voxels`` voxels, any number >= 1) and
+        ``counts`` (three uint64, zeroed first), each optional."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.uint8), np.dtype(np.bool_), np.dtype(np.uint16)):
+            raise ValueError("label_components: the array must be uint8, bool or uint16")
+        dims = (ctypes.c_int32 * 3)(*(int(v) for v in shape))
+        own = None
+        if scratch is None:
+            scratch = own = self.alloc(max(256, components_scratch_bytes(shape, connectivity)))
+        try:
+            self._check(lib().exabm4d_label_components_dev(
+                self.handle, _ptr(src), 1 if dt == np.dtype(np.uint16) else 0, dims, int(cut), int(min_voxels),
+                int(connectivity), _ptr(labels), _ptr(sizes), _ptr(kept_u8), _ptr(scratch),
+                int(scratch.nbytes if scratch_bytes is None else scratch_bytes), _ptr(counts)))
+        finally:
+            if own is not None:
+                own.free()
 
     def nonzero_u8(self, src, n, dst):
         """``dst[i] = src[i] != 0`` for ``n`` uint16 elements on the device, as bytes.  Asynchronous."""

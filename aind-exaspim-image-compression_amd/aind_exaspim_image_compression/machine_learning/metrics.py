@@ -26,7 +26,8 @@ import numpy as np
 
 from aind_exaspim_image_compression import _native
 from aind_exaspim_image_compression.utils import order_stats
-from aind_exaspim_image_compression.utils.store_foreground import foreground_store, foreground_volume  # noqa: F401
+from aind_exaspim_image_compression.utils.store_foreground import (  # noqa: F401
+    _check_filter_args, foreground_store, foreground_volume)
 
 # reference metrics.py:24-29
 DEFAULT_CHECKPOINT_WEIGHTS = {
@@ -451,10 +452,60 @@ def _dilate(masks, iterations):
         return d_out.download(m.shape, np.uint8).view(bool)
 
 
-def make_foreground_mask(raw, k=6.0, dilate=1):
+def _binary_volume(who, mask):
+    mask = np.asarray(mask)
+    if mask.ndim != 3 or 0 in mask.shape or mask.size >= 2 ** 31:
+        raise ValueError("%s: mask is a 3-D array without an empty axis and with fewer than 2^31 voxels" % who)
+    return np.ascontiguousarray(mask != 0).view(np.uint8)
+
+
+def label_components(mask, connectivity=26, relabel=False):
+    """The connected components of the non-zero voxels of a 3-D ``mask`` on the device:
+    ``(labels, n)``, int32 labels and the number of components.  A component's label is 1 + the linear (z, y, x)
+    index of its first voxel in raster order, background 0; ``relabel=True`` renumbers them 1..n in that order on the
+    host, which is ``scipy.ndimage.label``'s numbering.  ``connectivity``: 6 (faces) or 26 (faces, edges, corners)."""
+    _check_filter_args("label_components", 1, connectivity)
+    m = _binary_volume("label_components", mask)
+    ctx = _native.context()
+    with ctx.to_device(m) as d_mask, ctx.alloc(4 * m.size) as d_labels, ctx.alloc(24) as d_counts:
+        # no component has 2^31 - 1 voxels unless it is the whole array: every one counts as dropped, or one as kept
+        ctx.label_components(d_mask, np.uint8, m.shape, min_voxels=2 ** 31 - 1, connectivity=connectivity,
+                             labels=d_labels, counts=d_counts)
+        labels = d_labels.download(m.shape, np.uint32).view(np.int32)
+        _, kept, dropped = (int(c) for c in d_counts.download((3,), np.uint64))
+    n = dropped + (1 if kept else 0)
+    if relabel and n:
+        flat = labels.reshape(-1)
+        firsts = np.flatnonzero(flat == np.arange(1, flat.size + 1, dtype=np.int64))     # roots, in raster order
+        table = np.zeros(flat.size + 1, dtype=np.int32)
+        table[firsts + 1] = np.arange(1, firsts.size + 1, dtype=np.int32)
+        labels = table[flat].reshape(labels.shape)
+    return labels, n
+
+
+def remove_small_components(mask, min_voxels, connectivity=26):
+    """``mask`` (3-D) without the connected components of fewer than ``min_voxels`` voxels, as a bool array, on the
+    device.  The array is resident and the sizes are the whole array's, so ``min_voxels`` is any integer >= 1."""
+    min_voxels = _check_filter_args("remove_small_components", min_voxels, connectivity, least=1)
+    m = _binary_volume("remove_small_components", mask)
+    ctx = _native.context()
+    with ctx.to_device(m) as d_mask, ctx.alloc(m.size) as d_kept:
+        ctx.label_components(d_mask, np.uint8, m.shape, min_voxels=min_voxels, connectivity=connectivity,
+                             kept_u8=d_kept)
+        return d_kept.download(m.shape, np.uint8).view(bool)
+
+
+def make_foreground_mask(raw, k=6.0, dilate=1, min_voxels=0, connectivity=26):
     """Robust intensity foreground mask, raw > median + k * 1.4826 * MAD, then ``dilate`` binary
-    dilations (reference metrics.py:32-62): ``foreground_masks`` with B = 1."""
-    return foreground_masks(_patches(raw, 3, "raw")[None], k, dilate)[0]
+    dilations (reference metrics.py:32-62): ``foreground_masks`` with B = 1.  With ``min_voxels`` > 0 the voxels above
+    the threshold are filtered first: only connected components (``connectivity`` 6 or 26) of at least ``min_voxels``
+    voxels are dilated (threshold, filter, dilate)."""
+    min_voxels = _check_filter_args("make_foreground_mask", min_voxels, connectivity)
+    raw = _patches(raw, 3, "raw")
+    if min_voxels == 0:
+        return foreground_masks(raw[None], k, dilate)[0]
+    seeds = remove_small_components(foreground_masks(raw[None], k, 0)[0], min_voxels, connectivity)
+    return _dilate(seeds[None], dilate)[0]
 
 
 def make_segmentation_mask(labels, dilate=0):

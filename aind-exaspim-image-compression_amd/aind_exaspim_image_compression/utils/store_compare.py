@@ -49,9 +49,9 @@ def halo_range(b0, bd, dim, window):
     return lo, hi - lo + 1
 
 
-def _cost(windows_held, stores, budget):
+def _cost(windows_held, stores, budget, window_bytes=WINDOW_BYTES):
     """``windows_held``: the window as held, (z, y, x)."""
-    return stores * (WINDOW_BYTES * windows_held[0] * windows_held[1] * windows_held[2] + budget // READER_SHARE)
+    return stores * (window_bytes * windows_held[0] * windows_held[1] * windows_held[2] + budget // READER_SHARE)
 
 
 def _held_z(wz, chunk_z):
@@ -82,11 +82,12 @@ def plan_compare(shape, chunks_zyx, window, budget_bytes, with_mask=False):
     return plan_bricks(shape, chunk, budget, stores, lambda b0, bd, dim: halo_range(b0, bd, dim, window))
 
 
-def plan_bricks(shape, chunk, budget, stores, axis_window, brick_bytes=0):
+def plan_bricks(shape, chunk, budget, stores, axis_window, brick_bytes=0, window_bytes=WINDOW_BYTES, fixed_bytes=0):
     """``plan_compare``'s rule for any window: ``axis_window(b0, bd, dim) -> (start, extent)`` is what a brick that
     covers ``[b0, b0 + bd)`` of an axis of ``dim`` voxels has to read there; ``stores`` windows are held at a time.
     ``brick_bytes``: what a loop holds besides the windows, per voxel of the brick itself (a result, a pool of
-    destination chunks)."""
+    destination chunks); ``window_bytes``: what it holds per voxel of a window as held, the window itself included;
+    ``fixed_bytes``: and per brick."""
     grid = [-(-s // c) for s, c in zip(shape, chunk)]
 
     def axes(a, n):
@@ -96,8 +97,8 @@ def plan_bricks(shape, chunk, budget, stores, axis_window, brick_bytes=0):
     def bound(per_axis):
         widest = [max(r[3] for r in ax) for ax in per_axis]
         longest = [max(r[1] - r[0] for r in ax) for ax in per_axis]
-        return (_cost((_held_z(widest[0], chunk[0]), widest[1], widest[2]), stores, budget) +
-                brick_bytes * longest[0] * longest[1] * longest[2])
+        return (_cost((_held_z(widest[0], chunk[0]), widest[1], widest[2]), stores, budget, window_bytes) +
+                brick_bytes * longest[0] * longest[1] * longest[2] + fixed_bytes)
 
     n = [1, 1, 1]
     per_axis = [axes(a, 1) for a in range(3)]
@@ -118,8 +119,8 @@ def plan_bricks(shape, chunk, budget, stores, axis_window, brick_bytes=0):
         wn = tuple(q[3] for q in r)
         ext = tuple(q[1] - q[0] for q in r)
         bricks.append(Brick(tuple(q[0] for q in r), ext, tuple(q[2] for q in r), wn,
-                            _cost((_held_z(wn[0], chunk[0]), wn[1], wn[2]), stores, budget) +
-                            brick_bytes * ext[0] * ext[1] * ext[2]))
+                            _cost((_held_z(wn[0], chunk[0]), wn[1], wn[2]), stores, budget, window_bytes) +
+                            brick_bytes * ext[0] * ext[1] * ext[2] + fixed_bytes))
     return bricks
 
 

@@ -156,6 +156,24 @@ bool foreground_box_plan(const uint16_t* win, const BoxGeom& g, int radius, cons
 hipError_t launch_foreground_box_u16(const uint16_t* win, const BoxGeom& g, const FgPlan& p, uint32_t cut, int radius,
                                      uint32_t value, uint16_t* out16, uint8_t* out8, unsigned long long* counts,
                                      hipStream_t s);
+// ---- connected components of the seeds of a window (component_kernels.hip) ----
+constexpr int CC_TZ = 8, CC_TY = 8, CC_TX = 64;     // a tile, labelled in LDS (exabm4d.h EXABM4D_CC_TILE_*)
+// The window w0 + [0, wd), the labelled region r0 + [0, rd) (the box grown by min_voxels - 1, cut at the volume), the
+// box b0 + [0, bd) the filtered seeds are written for and the sub-box c0 + [0, cd) the counters count in (all volume
+// coordinates, z y x); the tiles of the region per axis; the voxels of the region (< 2^31) and of the box.
+struct CcGeom {
+    int w0[3], wd[3], r0[3], rd[3], b0[3], bd[3], c0[3], cd[3];
+    unsigned tiles[3];
+    long long voxels, box_voxels;
+};
+// false: 2^31 labelled voxels or more.  grow: min_voxels - 1, clamped by the caller to what an int holds
+bool components_geometry(const BoxGeom& b, const int* count0, const int* countd, long long grow, CcGeom& g);
+size_t components_scratch_bytes(long long voxels);   // three 256-byte aligned arrays of 32-bit words
+// parent, labels, sizes: g.voxels 32-bit words each (region-shaped); out16 / out8: dense box-shaped 1 / 0, either or
+// both may be NULL; counts: NULL, or {seeds, kept seeds, dropped components}, ADDED to once per workgroup
+hipError_t launch_components(const void* win, bool win_u8, const CcGeom& g, uint32_t cut, uint32_t min_voxels,
+                             int connectivity, uint32_t* parent, uint32_t* labels, uint32_t* sizes, uint16_t* out16,
+                             uint8_t* out8, unsigned long long* counts, hipStream_t s);
 // dst[i] = src[i] != 0 (elementwise_kernels.hip): a uint16 mask window as the bytes a mask pool takes
 hipError_t launch_nonzero_u8(const uint16_t* src, uint8_t* dst, size_t n, hipStream_t s);
 // Options of block matching (per context since round 4; exabm4d_set_option "bm_xcd_mode" / "bm_carry" / "bm_carry_fault")

@@ -950,6 +950,52 @@ int exabm4d_foreground_box_u16_dev(exabm4d_ctx* ctx, const uint16_t* win, const 
                                    int value, uint16_t* out_u16, uint8_t* out_u8, uint64_t* counts_dev,
                                    int zero_first);
 
+/* ---- connected components of the seeds, and their filter by size ----------------------
+ * The geometry of exabm4d_foreground_box_u16_dev.  A voxel is a SEED where win >= cut and it lies inside the
+ * LABELLED REGION: the box grown by min_voxels - 1 voxels per axis and cut at the volume's faces, which the window
+ * must hold (checked on the host).  What the window holds elsewhere -- a reader's padding past the faces included --
+ * is never a seed and connects nothing.  Seeds are connected through faces (connectivity 6) or through faces, edges
+ * and corners (26).  The label of a component is 1 + the linear (z, y, x) index WITHIN THE REGION of its first voxel
+ * in raster order, background 0: a pure function of the input, bit-identical between launches, like the sizes.
+ * A seed is KEPT where its component in the region has >= min_voxels voxels.  For the seeds of the box that equals
+ * the same test on the components of the whole volume: a smaller component lies whole inside the region, and of a
+ * larger one the region holds min_voxels voxels connected to the seed.
+ *   seeds_u16   NULL, or a dense uint16 array of box_dims: 1 where the voxel is a kept seed, else 0 -- the window of
+ *               a following exabm4d_foreground_box_u16_dev with cut = 1 (window = this box), which dilates it
+ *   labels      NULL, or uint32 per voxel of the region (region-shaped, dense)
+ *   sizes       NULL, or uint32 per voxel of the region: at index label - 1 the voxels of that component, else 0
+ *   counts_dev  NULL, or three uint64 words on the device to which the call ADDS, for the count box
+ *               count_origin + [0, count_dims) inside the box: its seeds, its kept seeds, and the dropped components
+ *               whose first voxel lies in it; zero_first zeroes them before.  A dropped component lies whole in the
+ *               region, so over a partition of a volume into count boxes the three sums are the whole volume's.
+ *   scratch     device memory of scratch_bytes >= exabm4d_components_scratch_bytes(win_dims, connectivity) bytes
+ *               (0: bad arguments or 2^31 voxels or more), 4-byte aligned; its contents are not kept.
+ * Four launches (a tile of EXABM4D_CC_TILE_Z x _Y x _X voxels by union-find in LDS; the tile faces by atomic min on
+ * the parents; roots and sizes; the filter); no workgroup waits for another.
+ * Checked on the host (EXABM4D_ERR_INVALID, nothing written): non-NULL ctx, win, geometry and scratch, connectivity 6
+ * or 26, min_voxels >= 1, cut 0..65536, the count box inside the box, the window holding the region, fewer than 2^31
+ * labelled voxels, the scratch size; alignment: win and seeds_u16 2 bytes, labels, sizes and scratch 4, counts_dev 8.
+ * Asynchronous on the context's stream. */
+#define EXABM4D_CC_TILE_Z 8
+#define EXABM4D_CC_TILE_Y 8
+#define EXABM4D_CC_TILE_X 64
+size_t exabm4d_components_scratch_bytes(const int32_t* win_dims_zyx, int connectivity);
+int exabm4d_component_seeds_u16_dev(exabm4d_ctx* ctx, const uint16_t* win, const int32_t* vol_dims_zyx,
+                                    const int32_t* win_origin_zyx, const int32_t* win_dims_zyx,
+                                    const int32_t* box_origin_zyx, const int32_t* box_dims_zyx,
+                                    const int32_t* count_origin_zyx, const int32_t* count_dims_zyx, int cut,
+                                    int min_voxels, int connectivity, uint16_t* seeds_u16, uint32_t* labels,
+                                    uint32_t* sizes, void* scratch, size_t scratch_bytes, uint64_t* counts_dev,
+                                    int zero_first);
+
+/* The same for a dense array of dims_zyx resident on the device, as box = window = volume: src is uint8 (seed where
+ * non-zero; cut is ignored) or, with src_u16, uint16 (seed where >= cut).  labels, sizes: as above, of dims_zyx,
+ * either may be NULL; kept_u8: NULL, or 1 / 0 bytes of dims_zyx -- the sizes are the whole array's, so min_voxels is
+ * any number >= 1.  counts_dev: NULL, or the three words above for the whole array, zeroed first.  Asynchronous. */
+int exabm4d_label_components_dev(exabm4d_ctx* ctx, const void* src, int src_u16, const int32_t* dims_zyx, int cut,
+                                 int min_voxels, int connectivity, uint32_t* labels, uint32_t* sizes,
+                                 uint8_t* kept_u8, void* scratch, size_t scratch_bytes, uint64_t* counts_dev);
+
 /* dst[i] = src[i] != 0 for n elements on the device: a uint16 mask window (non-zero = foreground) as the bytes a
  * mask pool of exabm4d_scatter_boxes_dev takes.  src at an even address, dst at any; 16-byte loads and 8-byte stores
  * where src is 16-byte and dst 8-byte aligned.  n == 0 succeeds without a launch.  Asynchronous. */
