@@ -34,6 +34,8 @@ GAUSS_MAX_RADIUS = 64       # exabm4d.h EXABM4D_GAUSS_MAX_RADIUS
 NOISE_LEVELS = 49           # exabm4d.h EXABM4D_NOISE_LEVELS
 NOISE_BINS = 4096           # exabm4d.h EXABM4D_NOISE_BINS
 FG_MAX_RADIUS = 8           # exabm4d.h EXABM4D_FG_MAX_RADIUS: iterations of Context.foreground_box_u16
+DS_METHODS = {"mode": 0, "mean": 1, "max": 2}   # exabm4d.h EXABM4D_DS_MODE / _MEAN / _MAX: Context.downsample_box_u16
+DS_EDGES = {"crop": 0, "partial": 1}            # exabm4d.h EXABM4D_DS_CROP / _PARTIAL
 CC_TILE = (8, 8, 64)        # exabm4d.h EXABM4D_CC_TILE_Z / _Y / _X: the tile Context.component_seeds_u16 labels in LDS
 NOISE_WIDE_BINS = 16384     # exabm4d.h EXABM4D_NOISE_WIDE_BINS: wide bins per level of Context.measure_box_u16
 COUNT_BINS = 65536          # exabm4d.h EXABM4D_COUNT_BINS: counters of a table of the uint16 counts
@@ -271,6 +273,7 @@ SIGNATURES = {
                                              _I, c_vp, c_vp, c_vp, c_vp, _SZ, c_vp, _I]),
     "exabm4d_label_components_dev": (_I, [_CTX, c_vp, _I, c_i32p, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, _SZ, c_vp]),
     "exabm4d_nonzero_u8_dev": (_I, [_CTX, c_vp, _SZ, c_vp]),
+    "exabm4d_downsample_box_u16_dev": (_I, [_CTX, c_vp, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _I, _I, c_vp]),
     "exabm4d_foreground_masks_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, _F, _I, c_vp, c_vp]),
     "exabm4d_binary_dilate_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp]),
     "exabm4d_gaussian_filter3d_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp, _I, c_vp]),
@@ -1076,6 +1079,23 @@ class Context:
     def nonzero_u8(self, src, n, dst):
         """``dst[i] = src[i] != 0`` for ``n`` uint16 elements on the device, as bytes.  Asynchronous."""
         self._check(lib().exabm4d_nonzero_u8_dev(self.handle, _ptr(src), int(n), _ptr(dst)))
+
+    # -- one pyramid level of a box inside a window (DESIGN.md 5.21) -------------------------------
+    def downsample_box_u16(self, win, vol_dims, win_origin, win_dims, box_origin, box_dims, factors, method="mode",
+                           edge="crop", out_u16=None):
+        """The box ``box_origin + [0, box_dims)`` of one pyramid level -- LEVEL coordinates -- of a SOURCE volume of
+        ``vol_dims``, read from a uint16 window that holds ``win_origin + [0, win_dims)`` of the source (all z, y, x):
+        every level voxel reduces its window of ``factors`` (1 or 2 each, one at least 2) source voxels, cut at the
+        volume's faces, by ``method`` (``"mode"``: ties to the smallest value; ``"mean"``: half to even; ``"max"``).
+        ``edge``: ``"crop"`` (the level has ``n // f`` voxels per axis) or ``"partial"`` (``ceil(n / f)``).
+        ``out_u16``: a dense device array of ``box_dims``.  What the window holds past the volume's faces never enters
+        a result.  ValueError when the box leaves the level or the window misses ``[box_origin f, min(vol,
+        (box_origin + box_dims) f))``.  Asynchronous."""
+        tri = self._box_geometry(vol_dims, win_origin, win_dims, box_origin, box_dims)
+        fac = (ctypes.c_int32 * 3)(*(int(f) for f in factors))
+        self._check(lib().exabm4d_downsample_box_u16_dev(
+            self.handle, _ptr(win), *tri, fac, DS_METHODS.get(method, -1) if isinstance(method, str) else int(method),
+            DS_EDGES.get(edge, -1) if isinstance(edge, str) else int(edge), _ptr(out_u16)))
 
     # -- patch-cache masks and coherence gate (DESIGN.md 5.8); batches of (nz, ny, nx) patches --
     def foreground_masks(self, raw, dtype, batch, shape, k, dilate, mask):

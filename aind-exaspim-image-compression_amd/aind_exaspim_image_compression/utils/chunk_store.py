@@ -33,6 +33,8 @@ import numpy as np
 from aind_exaspim_image_compression.utils.block_bounded_codec import BlockBoundedCodec
 from aind_exaspim_image_compression.utils.bounded_codec import BoundedDctCodec
 from aind_exaspim_image_compression.utils.chunk_codec import EncodedVolume, ExacCodec
+from aind_exaspim_image_compression.utils.store_pyramid import (  # noqa: F401  (re-exported)
+    downsample_store, open_multiscale, pyramid_store)
 from aind_exaspim_image_compression.utils.store_recode import recode_store  # noqa: F401  (re-exported)
 
 FORMAT_NOTE = ("EXAC chunk streams (aind-exaspim-image-compression_amd, DESIGN.md 3.11b); edge chunks truncated to "

@@ -87,12 +87,14 @@ def plan_bricks(shape, chunk, budget, stores, axis_window, brick_bytes=0, window
     covers ``[b0, b0 + bd)`` of an axis of ``dim`` voxels has to read there; ``stores`` windows are held at a time.
     ``brick_bytes``: what a loop holds besides the windows, per voxel of the brick itself (a result, a pool of
     destination chunks); ``window_bytes``: what it holds per voxel of a window as held, the window itself included;
-    ``fixed_bytes``: and per brick."""
+    ``fixed_bytes``: and per brick.  ``axis_window`` may also be three such functions, one per axis (z, y, x): a
+    window in other coordinates than the bricks', as a pyramid level's in its source (``store_pyramid``)."""
     grid = [-(-s // c) for s, c in zip(shape, chunk)]
+    windows = tuple(axis_window) if isinstance(axis_window, (tuple, list)) else (axis_window,) * 3
 
     def axes(a, n):
         """The bricks' (o0, o1, w0, wn) along axis a when a brick is n chunks long."""
-        return [(o0, o1) + tuple(axis_window(o0, o1 - o0, shape[a])) for o0, o1 in _runs(shape[a], n * chunk[a])]
+        return [(o0, o1) + tuple(windows[a](o0, o1 - o0, shape[a])) for o0, o1 in _runs(shape[a], n * chunk[a])]
 
     def bound(per_axis):
         widest = [max(r[3] for r in ax) for ax in per_axis]

@@ -176,6 +176,22 @@ hipError_t launch_components(const void* win, bool win_u8, const CcGeom& g, uint
                              uint8_t* out8, unsigned long long* counts, hipStream_t s);
 // dst[i] = src[i] != 0 (elementwise_kernels.hip): a uint16 mask window as the bytes a mask pool takes
 hipError_t launch_nonzero_u8(const uint16_t* src, uint8_t* dst, size_t n, hipStream_t s);
+// ---- one pyramid level of a box (downsample_kernels.hip) ----
+constexpr int DS_MODE = 0, DS_MEAN = 1, DS_MAX = 2;     // exabm4d.h EXABM4D_DS_MODE / _MEAN / _MAX
+constexpr int DS_CROP = 0, DS_PARTIAL = 1;              // exabm4d.h EXABM4D_DS_CROP / _PARTIAL
+// Here a BoxGeom holds the SOURCE volume's n and the window w0 + [0, wd) in source coordinates, and the box b0 + [0, bd)
+// in LEVEL coordinates.  How the box is walked: the factors; ox, the level x at which piece 0 of every row begins
+// (<= b0[2]); the pieces (8 source voxels each) per row; whether pieces are loaded / stored as vectors; block and grid.
+struct DsPlan {
+    int f[3];
+    int ox, pieces;
+    int vec_in, vec_out;
+    unsigned block[2], grid[3];
+};
+void downsample_box_plan(const uint16_t* win, const BoxGeom& g, const int* factors, const uint16_t* out, DsPlan& p);
+// out: a dense array of g.bd
+hipError_t launch_downsample_box_u16(const uint16_t* win, const BoxGeom& g, const DsPlan& p, int method, uint16_t* out,
+                                     hipStream_t s);
 // Options of block matching (per context since round 4; exabm4d_set_option "bm_xcd_mode" / "bm_carry" / "bm_carry_fault")
 struct BmOpts {
     int xcd_mode = 2;       // workgroup order: 0 = contiguous per XCD, 1 = all XCDs in one z slab of tiles (raster), n >= 2 = in strips of n tile rows

@@ -1001,6 +1001,35 @@ int exabm4d_label_components_dev(exabm4d_ctx* ctx, const void* src, int src_u16,
  * where src is 16-byte and dst 8-byte aligned.  n == 0 succeeds without a launch.  Asynchronous. */
 int exabm4d_nonzero_u8_dev(exabm4d_ctx* ctx, const uint16_t* src, size_t n, uint8_t* dst);
 
+/* ---- one pyramid level of a box inside a window ----------------------------------------
+ * win (device, uint16, dense) holds win_origin + [0, win_dims) of a SOURCE volume of vol_dims voxels; factors_zyx are
+ * 1 or 2 each, one at least 2.  The LEVEL has floor(n / f) voxels per axis (edge = EXABM4D_DS_CROP) or ceil(n / f)
+ * (EXABM4D_DS_PARTIAL), and its voxel (z, y, x) reduces the source voxels [z fz, min(nz, (z + 1) fz)) x ... -- 1, 2, 4
+ * or 8 of them; under CROP no window is ever cut -- by
+ *     EXABM4D_DS_MODE   their most frequent value; of values equally frequent the smallest
+ *     EXABM4D_DS_MEAN   sum / count rounded half to even (count is a power of two: integer arithmetic, exact)
+ *     EXABM4D_DS_MAX    their largest value ("any voxel set" for a mask; the mask's value survives)
+ * box_origin / box_dims are in LEVEL coordinates; out_u16 is a dense array of box_dims on the device.  The window
+ * must hold [box_origin f, min(vol, (box_origin + box_dims) f)) per axis.  It may reach past the volume's upper faces
+ * (a reader's padding, whatever it holds): nothing there ever enters a result.  A partition of a level into boxes
+ * gives the whole level.
+ * Checked on the host (EXABM4D_ERR_INVALID, nothing written): non-NULL pointers, factors, method, edge, every extent
+ * >= 1, at most 2^20 voxels per axis and 2^40 in all, the window begins inside the volume, the box lies inside the
+ * level, the window holds its source voxels.  Alignment: win and out_u16 2 bytes.  A lane takes 8 source voxels of a
+ * row: 16-byte loads where win_dims[2] is a multiple of 8 and (factor 2 along x) the box's first source voxel lies at
+ * an even element of the window's allocation; 8-byte (16-byte with a factor of 1 along x) stores where box_dims[2] is
+ * a multiple of 4 (8) and out_u16 is at the phase the loads fixed; element loads and stores otherwise.
+ * Asynchronous on the context's stream. */
+#define EXABM4D_DS_MODE 0
+#define EXABM4D_DS_MEAN 1
+#define EXABM4D_DS_MAX 2
+#define EXABM4D_DS_CROP 0
+#define EXABM4D_DS_PARTIAL 1
+int exabm4d_downsample_box_u16_dev(exabm4d_ctx* ctx, const uint16_t* win, const int32_t* vol_dims_zyx,
+                                   const int32_t* win_origin_zyx, const int32_t* win_dims_zyx,
+                                   const int32_t* box_origin_zyx, const int32_t* box_dims_zyx,
+                                   const int32_t* factors_zyx, int method, int edge, uint16_t* out_u16);
+
 /* ---- patch-cache foreground masks and coherence gate --
  * Batches of `batch` patches of nz x ny x nx voxels, contiguous in HBM.  Every entry point
  * synchronises the context's stream; floating-point results are deterministic (fixed mappings and
