@@ -287,11 +287,20 @@ SIGNATURES = {
     "exabm4d_gather_boxes_dev": (_I, [_CTX, c_vp, _SZ, c_vp, _I, c_vp, _I, c_vp, _I, _I, _I, _I, _I, _F,
                                       ctypes.c_double, c_vp]),
     "exabm4d_scatter_boxes_dev": (_I, [_CTX, c_vp, _SZ, _I, c_vp, _I, c_vp, _SZ, _I, c_vp, _I, c_vp, _I, _F]),
+    "exabm4d_label_encode_bound": (_SZ, [_I, _I, _I, _I, _I, _I, _I]),
+    "exabm4d_label_encode_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, _I, _I, c_vp, _SZ, c_vp, c_vp, c_vp]),
+    "exabm4d_label_decode_dev": (_I, [_CTX, c_vp, _SZ, c_vp, _I, _I, _I, _I, _I, _I, _I, c_vp]),
+    "exabm4d_label_gather_boxes_dev": (_I, [_CTX, c_vp, _SZ, _I, c_vp, _I, c_vp, _I, c_vp, _I, _I, _I, _I, c_i32p,
+                                            c_i32p, c_vp]),
 }
 
 # ``exabm4d_box_src`` (include/exabm4d.h): a decoded chunk in the pool ``Context.gather_boxes`` reads
 BOX_SRC = np.dtype([("base", "<u8"), ("stride_y", "<u8"), ("stride_z", "<u8"), ("z0", "<i4"), ("y0", "<i4"),
                     ("x0", "<i4"), ("ez", "<i4"), ("ey", "<i4"), ("ex", "<i4")])
+
+# ``exabm4d_label_src`` (include/exabm4d.h): a coded chunk in the container ``Context.label_gather_boxes`` reads
+LABEL_SRC = np.dtype([("offset", "<u8"), ("bytes", "<u8"), ("z0", "<i4"), ("y0", "<i4"), ("x0", "<i4"),
+                      ("ez", "<i4"), ("ey", "<i4"), ("ex", "<i4")])
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -1226,6 +1235,46 @@ class Context:
             _ptr(pool), int(pool_elems), self.SCATTER_DTYPES[pdt], dsts.ctypes.data_as(c_vp), len(dsts),
             dst_boxes.ctypes.data_as(c_vp), dst_boxes.shape[1], float(offset)))
 
+    # -- label codec ---------------------------------------------------------
+    def label_encode(self, vol, typesize, shape, chunk, out=None, out_capacity=0, offsets=None, sizes=None,
+                     totals=True):
+        """Code every chunk of a device uint32 / uint64 volume as ``exac-labels`` streams.  -> (sum of stream
+        lengths, container bytes) when `totals` (synchronises), else None."""
+        nz, ny, nx = shape
+        tot = np.zeros(2, dtype=np.uint64)
+        self._check(lib().exabm4d_label_encode_dev(
+            self.handle, _ptr(vol), int(typesize), nz, ny, nx, int(chunk[0]), int(chunk[1]), int(chunk[2]),
+            _ptr(out), int(out_capacity), _ptr(offsets), _ptr(sizes), tot.ctypes.data_as(c_vp) if totals else None))
+        return (int(tot[0]), int(tot[1])) if totals else None
+
+    def label_decode(self, data, nbytes, offsets, typesize, shape, chunk, vol):
+        """``data``: ``nbytes`` bytes of ``exac-labels`` streams on the device -> ``vol``; a malformed stream or a
+        palette index past its palette raises ValueError, without a read outside ``data`` or a write outside
+        ``vol``."""
+        nz, ny, nx = shape
+        self._check(lib().exabm4d_label_decode_dev(
+            self.handle, _ptr(data), int(nbytes), _ptr(offsets), int(typesize), nz, ny, nx, int(chunk[0]),
+            int(chunk[1]), int(chunk[2]), _ptr(vol)))
+
+    def label_gather_boxes(self, data, nbytes, typesize, srcs, box_srcs, starts, box, shape, chunk, out):
+        """out[n][z][y][x] <- the label at starts[n] + (z, y, x) of the array ``shape`` in chunks ``chunk``, read
+        from the coded chunks in the device container ``data``; 0 outside the array.  ``srcs``: host array of
+        ``LABEL_SRC``; ``box_srcs``: host int32 (nbox, per_box), per box the rows of ``srcs`` of its chunk range in
+        raster order; ``starts``: host int32 (nbox, 3); ``out``: device, nbox * prod(box) elements.  Checked on the
+        host (ValueError, nothing written); synchronises."""
+        srcs = np.ascontiguousarray(srcs, dtype=LABEL_SRC).reshape(-1)
+        starts = np.ascontiguousarray(starts, dtype=np.int32).reshape(-1, 3)
+        box_srcs = np.ascontiguousarray(box_srcs, dtype=np.int32)
+        if box_srcs.ndim != 2 or box_srcs.shape[0] != len(starts):
+            raise ValueError("label_gather_boxes: box_srcs must be (nbox, per_box)")
+        bz, by, bx = (int(b) for b in box)
+        shape3 = (ctypes.c_int32 * 3)(*[int(v) for v in shape])
+        chunk3 = (ctypes.c_int32 * 3)(*[int(v) for v in chunk])
+        self._check(lib().exabm4d_label_gather_boxes_dev(
+            self.handle, _ptr(data), int(nbytes), int(typesize), srcs.ctypes.data_as(c_vp), len(srcs),
+            box_srcs.ctypes.data_as(c_vp), box_srcs.shape[1], starts.ctypes.data_as(c_vp), len(starts), bz, by, bx,
+            shape3, chunk3, _ptr(out)))
+
     def close(self):
         if self.handle and os.getpid() == self.pid:
             lib().exabm4d_destroy(self.handle)
@@ -1473,6 +1522,14 @@ def codec_volume_bound(typesize, shape, chunk):
         raise ValueError("codec: typesize must be 2 or 4 and every size >= 1")
     return b
 
+
+
+def label_encode_bound(typesize, shape, chunk):
+    """Bytes that hold the ``exac-labels`` container of any volume of this geometry."""
+    b = lib().exabm4d_label_encode_bound(int(typesize), *[int(v) for v in shape], *[int(v) for v in chunk])
+    if b == 0:
+        raise ValueError("label codec: typesize must be 4 or 8, sizes >= 1, chunk <= 2^27 voxels, volume <= 2^40")
+    return int(b)
 
 
 def bounded_volume_bound(shape, chunk):

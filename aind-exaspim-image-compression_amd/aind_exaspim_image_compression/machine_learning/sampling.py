@@ -38,8 +38,8 @@ SCORE_ROUNDS = 6                # the searches stop after ``cnt > 5`` (data_hand
 
 class BrainSource:
     """What the samplers read of one brain: ``image`` (a ``StoredArray``, (1, 1, z, y, x) uint16),
-    ``labels`` (None, or a (z, y, x) integer array-like that takes a basic slice: ``np.memmap``,
-    ``ndarray``), ``skeleton`` (None, or (N, 3) integer zyx voxels), the brain's background ``offset``
+    ``labels`` (None, a (z, y, x) integer array-like that takes a basic slice -- ``np.memmap``, ``ndarray`` -- or
+    a ``LabelArray``: a (1, 1, z, y, x) ``exac-labels`` store, read by regions on the device), ``skeleton`` (None, or (N, 3) integer zyx voxels), the brain's background ``offset``
     and ``val_image`` (None, or the store the ``val`` split reads its counts from)."""
 
     def __init__(self, image, labels=None, skeleton=None, offset=0.0, val_image=None):
@@ -49,7 +49,10 @@ class BrainSource:
             raise ValueError("BrainSource: the image is (1, 1, z, y, x)")
         if val_image is not None and tuple(val_image.shape) != tuple(image.shape):
             raise ValueError("BrainSource: the validation image must have the image's shape")
-        if labels is not None:
+        if _is_label_store(labels):
+            if tuple(labels.shape) != (1, 1) + tuple(image.shape[2:]):
+                raise ValueError("BrainSource: a label store is (1, 1, z, y, x) of the image's extent")
+        elif labels is not None:
             if len(labels.shape) != 3 or tuple(labels.shape) != tuple(image.shape[2:]):
                 raise ValueError("BrainSource: labels are (z, y, x) of the image's extent")
             if np.dtype(labels.dtype).kind not in "iub":
@@ -64,6 +67,11 @@ class BrainSource:
                 raise ValueError("BrainSource: skeleton points outside the int32 range")
         self.image, self.labels, self.skeleton = image, labels, skeleton
         self.offset, self.val_image = float(offset), val_image
+
+
+def _is_label_store(labels):
+    from aind_exaspim_image_compression.utils.store_labels import LabelArray
+    return isinstance(labels, LabelArray)
 
 
 class TaskRng:
@@ -138,6 +146,8 @@ class DeviceScorer:
     def segmentation(self, brain_id, voxels):
         from aind_exaspim_image_compression import _native
         from aind_exaspim_image_compression.machine_learning import metrics
+        if _is_label_store(self.s.brains[brain_id].labels):
+            return self._segmentation_of_store(brain_id, voxels)
         labels = self.labels(brain_id, voxels)
         n = int(np.prod(self.s.patch_shape))
         out = [None] * len(labels)
@@ -156,12 +166,38 @@ class DeviceScorer:
                 out[b] = volume_from_label_list(counts, n)
         return out
 
+    def _segmentation_of_store(self, brain_id, voxels):
+        """``segmentation`` for a ``LabelArray`` brain: the candidates' label patches go from the coded chunks to the
+        device set without a visit to the host (only a patch the set cannot hold is downloaded and counted there)."""
+        from aind_exaspim_image_compression import _native
+        store = self.s.brains[brain_id].labels
+        n = int(np.prod(self.s.patch_shape))
+        patches = store.read_patches(voxels, self.s.patch_shape, out="device")
+        try:
+            ctx = _native.context(store.device)
+            keys, counts, held, status = ctx.label_set(patches.buf, store.dtype, len(voxels), self.s.patch_shape)
+            host = patches.download() if status.any() else None
+        finally:
+            patches.free()
+        out = []
+        for b in range(len(voxels)):
+            if status[b]:
+                lb = host[b]
+                c = np.unique(lb[lb > 0], return_counts=True)[1]
+            else:
+                c = counts[b, :held[b]][np.argsort(keys[b, :held[b]], kind="stable")]
+            out.append(volume_from_label_list(c, n))
+        return out
+
     def raw_counts(self, brain_id, voxels, split):
         return self._image(brain_id, split).read_patches(voxels, self.s.patch_shape, dtype=np.float32,
                                                          offset=self.s.brains[brain_id].offset)
 
     def labels(self, brain_id, voxels):
-        return read_label_patches(self.s.brains[brain_id].labels, voxels, self.s.patch_shape)
+        labels = self.s.brains[brain_id].labels
+        if _is_label_store(labels):
+            return labels.read_patches(voxels, self.s.patch_shape)
+        return read_label_patches(labels, voxels, self.s.patch_shape)
 
     def incoherent(self, labels, raws):
         from aind_exaspim_image_compression.machine_learning import metrics
@@ -179,7 +215,11 @@ class DeviceScorer:
         d_labels = d_mask = None
         try:
             lab = None
-            if labels is not None:
+            if labels is not None and _is_label_store(src.labels):
+                # the patches at these voxels, from the coded chunks to the kernel (``labels`` holds the same values)
+                lab = src.labels.read_patches(voxels, self.s.patch_shape, out="device")
+                d_labels = lab.buf
+            elif labels is not None:
                 lab = metrics._labels_dev(np.asarray(labels))
                 d_labels = ctx.to_device(lab)
             pts, npts = (None, 0)

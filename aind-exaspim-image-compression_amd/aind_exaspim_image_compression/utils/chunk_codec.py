@@ -81,7 +81,8 @@ class EncodedVolume:
 class VolumeCodec:
     """A chunk codec whose arithmetic runs on the GPU: volume in, ``EncodedVolume`` out, and back.  A codec states
 
-    * ``typesize`` (of its elements), ``_check_dtype(dtype, what)`` and ``_check_typesize(enc)``: what it codes;
+    * ``typesize`` (of its elements), ``_check_dtype(dtype, what)`` and ``_check_typesize(enc)``: what it codes
+      (``_element_dtype()`` where that is not uint16 / int32);
     * ``nominal_chunks``: its streams keep the nominal chunk shape (else the chunk clamped to the array);
     * ``_bound(shape, chunk, want_bytes)``: its volume bound, where the codec needs it (for the container, or because
       it is also the format's size check);
@@ -98,6 +99,9 @@ class VolumeCodec:
     nominal_chunks = False
     takes_mask = False
     device = None
+
+    def _element_dtype(self):
+        return _DTYPES[self.typesize]
 
     def _chunk(self, shape, chunk):
         chunk = tuple(int(c) for c in _shape3(chunk))
@@ -190,7 +194,7 @@ class VolumeCodec:
         d_vol = ctx.alloc(self.typesize * int(np.prod(shape)))
         try:
             self.decode_device(ctx, enc, d_vol)
-            return d_vol.download(shape, _DTYPES[self.typesize])
+            return d_vol.download(shape, self._element_dtype())
         finally:
             d_vol.free()
 

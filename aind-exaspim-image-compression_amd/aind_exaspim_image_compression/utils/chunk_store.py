@@ -33,6 +33,7 @@ import numpy as np
 from aind_exaspim_image_compression.utils.block_bounded_codec import BlockBoundedCodec
 from aind_exaspim_image_compression.utils.bounded_codec import BoundedDctCodec
 from aind_exaspim_image_compression.utils.chunk_codec import EncodedVolume, ExacCodec
+from aind_exaspim_image_compression.utils.label_codec import LabelCodec
 from aind_exaspim_image_compression.utils.store_pyramid import (  # noqa: F401  (re-exported)
     downsample_store, open_multiscale, pyramid_store)
 from aind_exaspim_image_compression.utils.store_recode import recode_store  # noqa: F401  (re-exported)
@@ -51,7 +52,13 @@ def chunk_key(iz, iy, ix):
 
 
 # codec id in ``zarr.json`` -> the class that states the entry's configuration, validates one and decodes its streams
-CODECS = {cls.codec_id: cls for cls in (ExacCodec, BoundedDctCodec, BlockBoundedCodec)}
+CODECS = {cls.codec_id: cls for cls in (ExacCodec, BoundedDctCodec, BlockBoundedCodec, LabelCodec)}
+
+
+def _data_type(codec, typesize):
+    """``data_type`` of a store of ``codec`` (an instance or a class): uint16 / int32 for the image codecs; the label
+    codec states its own (uint32 / uint64)."""
+    return getattr(codec, "data_types", {2: "uint16", 4: "int32"})[typesize]
 
 
 def metadata(shape3, chunk3, typesize=2, version=2, attributes=None, codec=None):
@@ -63,7 +70,7 @@ def metadata(shape3, chunk3, typesize=2, version=2, attributes=None, codec=None)
         "zarr_format": 3,
         "node_type": "array",
         "shape": [1, 1] + [int(s) for s in shape3],
-        "data_type": {2: "uint16", 4: "int32"}[codec.typesize],
+        "data_type": _data_type(codec, codec.typesize),
         "chunk_grid": {"name": "regular", "configuration": {"chunk_shape": [1, 1] + [int(c) for c in chunk3]}},
         "chunk_key_encoding": {"name": "default", "configuration": {"separator": "/"}},
         "fill_value": 0,
@@ -110,13 +117,13 @@ def check_metadata(meta):
             raise ValueError("not a Zarr v3 array")
         codecs = meta["codecs"]
         if len(codecs) != 1 or codecs[0]["name"] not in CODECS:
-            raise ValueError("the array's codec chain is not [exac], [exac-dctq] or [exac-dctq-block]")
+            raise ValueError("the array's codec chain is not [exac], [exac-dctq], [exac-dctq-block] or [exac-labels]")
         cls = CODECS[codecs[0]["name"]]
         typesize = cls.check_config(codecs[0]["configuration"])
         shape5, chunk5 = meta["shape"], meta["chunk_grid"]["configuration"]["chunk_shape"]
         if len(shape5) != 5 or shape5[:2] != [1, 1] or len(chunk5) != 5 or chunk5[:2] != [1, 1]:
             raise ValueError("only (1, 1, z, y, x) arrays with (1, 1, cz, cy, cx) chunks are stored this way")
-        if meta["data_type"] != {2: "uint16", 4: "int32"}[typesize]:
+        if meta["data_type"] != _data_type(cls, typesize):
             raise ValueError("data_type does not match the codec's typesize")
         if meta["chunk_key_encoding"]["name"] != "default" or \
                 meta["chunk_key_encoding"]["configuration"].get("separator", "/") != "/":
@@ -214,6 +221,15 @@ def open_zarr(path, device=None, max_pool_bytes=1 << 30, mode="r", codec=None):
     ``"r"`` writes raise.  ``codec``: needed only to write a block-bounded store with a bound table, which the file
     does not hold; a codec whose ``config_entry()`` differs from the stored one raises ``ValueError``."""
     from aind_exaspim_image_compression.utils.store_read import StoredArray
+    with open(os.path.join(path, "zarr.json")) as f:
+        meta = json.load(f)
+    try:
+        labels = meta["codecs"][0]["name"] == LabelCodec.codec_id
+    except (KeyError, IndexError, TypeError):
+        labels = False                              # StoredArray says what is wrong with the document
+    if labels:
+        from aind_exaspim_image_compression.utils.store_labels import LabelArray
+        return LabelArray(path, device=device, max_pool_bytes=max_pool_bytes, mode=mode, codec=codec)
     return StoredArray(path, device=device, max_pool_bytes=max_pool_bytes, mode=mode, codec=codec)
 
 
@@ -230,7 +246,7 @@ def create_zarr(path, shape, chunks=(1, 1, 64, 64, 64), codec=None, attributes=N
     if len(chunks) != 5 or tuple(chunks[:2]) != (1, 1) or min(int(c) for c in chunks) < 1:
         raise ValueError("chunks must be (1, 1, cz, cy, cx)")
     codec = codec or ExacCodec(2)
-    if codec.typesize != 2:
+    if codec.typesize != 2 and not isinstance(codec, LabelCodec):
         raise NotImplementedError("region writes of int32 (index) stores are not implemented")
     if os.path.exists(os.path.join(path, "zarr.json")) and not overwrite:
         raise FileExistsError(path)

@@ -528,4 +528,39 @@ hipError_t launch_scatter_boxes(const void* src, int kind, const BoxSrc* boxes, 
                                 const unsigned long long* row0, int ndst, const int32_t* lists, int per_dst,
                                 unsigned long long rows, float offset, void* pool, hipStream_t s);
 
+// ---- label codec (label_codec_kernels.hip) ------------------------------------------
+constexpr uint32_t LB_MAGIC = 0x424C5845u;      // "EXLB", little-endian
+constexpr int LB_HEADER = 32;                   // bytes of a stream's header; the block table follows
+constexpr uint32_t LB_ST_MALFORMED = 1u;        // status bits of the decoders: a header or table entry was rejected,
+constexpr uint32_t LB_ST_CLAMPED = 2u;          // a palette index >= k was clamped
+struct LabelGeom {
+    int ts;                  // element bytes: 4 (uint32) or 8 (uint64)
+    int nz, ny, nx;          // volume
+    int cz, cy, cx;          // chunk shape, clamped to the volume
+    int gz, gy, gx;          // chunks per axis
+    int nchunks;
+    int nb;                  // 8^3 blocks of a full chunk: the stride of a chunk in the per-block scratch
+};
+int make_label_geom(int ts, int nz, int ny, int nx, int cz, int cy, int cx, LabelGeom& g);
+size_t label_volume_bound(const LabelGeom& g);
+// units, blockoff: nchunks * g.nb words of scratch each; sizes[nchunks], offsets[nchunks + 1], totals[2] as
+// launch_codec_scan makes them; out == nullptr stops after the sizes
+hipError_t launch_label_encode(const void* vol, const LabelGeom& g, uint32_t* units, uint32_t* blockoff, uint32_t* sizes,
+                               unsigned long long* offsets, unsigned long long* totals, uint8_t* out, hipStream_t s);
+// Never reads outside [in, in + in_bytes) nor writes outside the volume, whatever the bytes; *status |= LB_ST_*
+hipError_t launch_label_decode(const uint8_t* in, size_t in_bytes, const unsigned long long* offsets, const LabelGeom& g,
+                               void* vol, uint32_t* status, hipStream_t s);
+// A coded chunk in the container: exabm4d_label_src of exabm4d.h, field for field.
+struct LabelChunkSrc {
+    unsigned long long offset, bytes;               // of its stream in the container
+    int32_t z0, y0, x0;                             // origin in the array
+    int32_t ez, ey, ex;                             // extent
+};
+// out[n][z][y][x] <- the label at starts[n] + (z, y, x), 0 outside the array.  lists[n] holds the chunks box n
+// touches, in raster order of its chunk range, as rows of srcs; the caller has checked every record against the
+// container and every list against the geometry.  *status |= LB_ST_*
+hipError_t launch_label_gather(const uint8_t* data, int ts, const LabelChunkSrc* srcs, const int32_t* lists, int per_box,
+                               const int32_t* starts, int nbox, int bz, int by, int bx, const int* shape,
+                               const int* chunk, void* out, uint32_t* status, hipStream_t s);
+
 }  // namespace exabm4d

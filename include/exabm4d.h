@@ -1211,6 +1211,54 @@ int exabm4d_scatter_boxes_dev(exabm4d_ctx* ctx, const void* src, size_t src_elem
                               int pool_dtype, const exabm4d_box_src* dsts_host, int ndst,
                               const int32_t* dst_boxes_host, int per_dst, float offset);
 
+/* ---- label codec `exac-labels`: segmentation volumes coded per 8^3 block --------
+ * Lossless, for unsigned labels of typesize 4 (uint32) or 8 (uint64).  The volume (nz, ny, nx) is cut into chunks
+ * (cz, cy, cx), clamped to the volume and truncated at its high faces; each chunk becomes one position-independent
+ * stream: a 32-byte header, one 8-byte table entry per 8^3 block, and per block an ascending palette with packed
+ * indices, or the raw values (DESIGN.md 3.13 is the specification; the stream is a pure function of the chunk).
+ * A chunk holds at most 2^27 voxels, a volume at most 2^40.
+ *
+ * exabm4d_label_encode_bound: bytes that hold the container of any volume of this geometry (every block raw, tables,
+ * headers, every stream padded to 16 bytes); 0 for a bad geometry.
+ *
+ * exabm4d_label_encode_dev: vol (device, C order, natural alignment) -> the container `out` (device, 16-byte aligned,
+ * out_capacity >= the bound; NULL: sizes only), every stream at a multiple of 16 bytes, in chunk raster order;
+ * offsets_dev[nchunks + 1] (required with out) and sizes_dev[nchunks] (optional) are device arrays;
+ * totals_host[2] (optional; synchronises) = {sum of stream lengths, container bytes}.  The bytes do not depend on
+ * the launch geometry, and no workgroup waits for another.
+ *
+ * exabm4d_label_decode_dev: the container (`in`, device, 16-byte aligned, in_bytes; offsets_dev as the encoder made
+ * them) -> vol.  The kernel reads nothing outside [in, in + in_bytes) and writes nothing outside vol, whatever the
+ * bytes: a stream, header or table entry that does not fit its bounds decodes to zeros, a palette index >= k is
+ * clamped to k - 1 before the palette is read, and either makes the call return EXABM4D_ERR_INVALID (after it has
+ * synchronised).
+ *
+ * exabm4d_label_gather_boxes_dev: boxes straight from coded chunks, with no decoded copy.  data (device, 16-byte
+ * aligned, data_bytes) holds the streams of the touched chunks; srcs_host[nsrc] say where each lies (offset a
+ * multiple of 8, offset + bytes <= data_bytes), its origin in the array (a multiple of the chunk shape) and its
+ * extent (the chunk truncated to the array).  Box n is the voxels starts_host[n] + [0, bz) x [0, by) x [0, bx) of
+ * the array shape3_host in chunks chunk3_host; box_srcs_host[n][0 .. per_box) lists the rows of srcs_host of the
+ * chunks it touches, in raster order over its chunk range (floor(max(start, 0) / c) .. floor((min(start + b, n) - 1)
+ * / c) per axis); entries past that count are ignored.  out[n][z][y][x] (device, typesize elements, natural
+ * alignment) is the label there, 0 outside the array.  Every table is checked on the host before anything is
+ * launched (EXABM4D_ERR_INVALID, nothing written); the kernel opens every block under its stream's bounds as the
+ * decoder does and the call returns EXABM4D_ERR_INVALID for a rejected entry or a clamped index.  Synchronises. */
+typedef struct exabm4d_label_src {
+    uint64_t offset, bytes;        /* of the chunk's stream in data */
+    int32_t  z0, y0, x0;           /* its origin in the array */
+    int32_t  ez, ey, ex;           /* its extent, >= 1 */
+} exabm4d_label_src;
+size_t exabm4d_label_encode_bound(int typesize, int nz, int ny, int nx, int cz, int cy, int cx);
+int exabm4d_label_encode_dev(exabm4d_ctx* ctx, const void* vol, int typesize, int nz, int ny, int nx, int cz, int cy,
+                             int cx, uint8_t* out, size_t out_capacity, uint64_t* offsets_dev, uint32_t* sizes_dev,
+                             uint64_t* totals_host);
+int exabm4d_label_decode_dev(exabm4d_ctx* ctx, const uint8_t* in, size_t in_bytes, const uint64_t* offsets_dev,
+                             int typesize, int nz, int ny, int nx, int cz, int cy, int cx, void* vol);
+int exabm4d_label_gather_boxes_dev(exabm4d_ctx* ctx, const uint8_t* data, size_t data_bytes, int typesize,
+                                   const exabm4d_label_src* srcs_host, int nsrc, const int32_t* box_srcs_host,
+                                   int per_box, const int32_t* starts_host, int nbox, int bz, int by, int bx,
+                                   const int32_t* shape3_host, const int32_t* chunk3_host, void* out);
+
 #ifdef __cplusplus
 }
 #endif
