@@ -272,6 +272,10 @@ SIGNATURES = {
     "exabm4d_component_seeds_u16_dev": (_I, [_CTX, c_vp, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _I, _I,
                                              _I, c_vp, c_vp, c_vp, c_vp, _SZ, c_vp, _I]),
     "exabm4d_label_components_dev": (_I, [_CTX, c_vp, _I, c_i32p, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, _SZ, c_vp]),
+    "exabm4d_segment_collect_dev": (_I, [_CTX, c_vp, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_vp, c_vp, _SZ, c_vp, _SZ,
+                                         c_vp, _SZ, c_vp]),
+    "exabm4d_segment_relabel_dev": (_I, [_CTX, c_vp, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_vp, c_vp, _SZ, _I, c_vp,
+                                         c_vp]),
     "exabm4d_nonzero_u8_dev": (_I, [_CTX, c_vp, _SZ, c_vp]),
     "exabm4d_downsample_box_u16_dev": (_I, [_CTX, c_vp, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _I, _I, c_vp]),
     "exabm4d_foreground_masks_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, _F, _I, c_vp, c_vp]),
@@ -397,6 +401,15 @@ def components_region(vol_dims, box_origin, box_dims, min_voxels):
     lo = tuple(max(0, int(b) - grow) for b in box_origin)
     hi = tuple(min(int(n), int(b) + int(d) + grow) for n, b, d in zip(vol_dims, box_origin, box_dims))
     return lo, tuple(h - l for h, l in zip(hi, lo))
+
+
+def segment_record_capacities(win_dims, brick_origin, brick_dims):
+    """(halo, face): the most halo and face records ``Context.segment_collect`` can write -- the voxels of the window
+    outside the brick, and the voxels of the brick on a low face whose brick origin on that axis is > 0."""
+    win = int(np.prod([int(v) for v in win_dims], dtype=np.int64))
+    brick = int(np.prod([int(v) for v in brick_dims], dtype=np.int64))
+    inner = int(np.prod([int(d) - (1 if int(o) > 0 else 0) for o, d in zip(brick_origin, brick_dims)], dtype=np.int64))
+    return win - brick, brick - inner
 
 
 def default_params(**overrides):
@@ -1084,6 +1097,33 @@ class Context:
         finally:
             if own is not None:
                 own.free()
+
+    # -- the components of a volume from those of its bricks' windows -----------
+    def segment_collect(self, labels, vol_dims, win_origin, win_dims, brick_origin, brick_dims, own, halo, halo_capacity,
+                        face, face_capacity, size, size_capacity, counts):
+        """What a merge over all bricks needs of one window's ``labels`` (uint32, ``component_seeds_u16`` with region
+        = window): ``own`` (uint32 per voxel of the window, zeroed here) gets the voxels of each component inside the
+        brick at index label - 1; ``halo`` / ``face`` / ``size`` (pairs of uint64, capacities in records) get the
+        (volume index, provisional label) of the seeds outside the brick and of the brick's seeds on its low faces
+        with a brick before them, and (provisional label, own count) per component with an own count; ``counts``
+        (three uint64, zeroed here): the records there are of each kind.  ``segment_record_capacities`` states the
+        least halo and face capacities; size records past ``size_capacity`` are counted and not stored.
+        Asynchronous."""
+        tri = self._box_geometry(vol_dims, win_origin, win_dims, brick_origin, brick_dims)
+        self._check(lib().exabm4d_segment_collect_dev(
+            self.handle, _ptr(labels), *tri, _ptr(own), _ptr(halo), int(halo_capacity), _ptr(face), int(face_capacity),
+            _ptr(size), int(size_capacity), _ptr(counts)))
+
+    def segment_relabel(self, labels, vol_dims, win_origin, win_dims, brick_origin, brick_dims, keys, vals, n_keys,
+                        typesize, final, out):
+        """The dense brick ``out`` (``typesize`` 4 or 8 bytes an element) of a window's ``labels``: ``vals[k]`` where
+        ``keys[k]`` (uint64 on the device, ascending; None with ``n_keys`` 0) is the component's provisional label,
+        else the provisional label, background 0.  ``final``: ``typesize`` bytes per voxel of the window, not kept.
+        Asynchronous."""
+        tri = self._box_geometry(vol_dims, win_origin, win_dims, brick_origin, brick_dims)
+        self._check(lib().exabm4d_segment_relabel_dev(
+            self.handle, _ptr(labels), *tri, _ptr(keys), _ptr(vals), int(n_keys), int(typesize), _ptr(final),
+            _ptr(out)))
 
     def nonzero_u8(self, src, n, dst):
         """``dst[i] = src[i] != 0`` for ``n`` uint16 elements on the device, as bytes.  Asynchronous."""

@@ -28,6 +28,7 @@ from aind_exaspim_image_compression import _native
 from aind_exaspim_image_compression.utils import order_stats
 from aind_exaspim_image_compression.utils.store_foreground import (  # noqa: F401
     _check_filter_args, foreground_store, foreground_volume)
+from aind_exaspim_image_compression.utils.store_segment import components_store, components_volume  # noqa: F401
 
 # reference metrics.py:24-29
 DEFAULT_CHECKPOINT_WEIGHTS = {

@@ -174,6 +174,25 @@ size_t components_scratch_bytes(long long voxels);   // three 256-byte aligned a
 hipError_t launch_components(const void* win, bool win_u8, const CcGeom& g, uint32_t cut, uint32_t min_voxels,
                              int connectivity, uint32_t* parent, uint32_t* labels, uint32_t* sizes, uint16_t* out16,
                              uint8_t* out8, unsigned long long* counts, hipStream_t s);
+// ---- the components of a volume from those of its bricks' windows (segment_kernels.hip) ----
+// The volume n, the labelled window w0 + [0, wd) inside it and the brick b0 + [0, bd) inside the window (z y x); the
+// voxels of the window (< 2^31) and of the brick.  The host layer checks all of that before a launch.
+struct SegGeom {
+    int n[3], w0[3], wd[3], b0[3], bd[3];
+    long long voxels, brick_voxels;
+};
+long long segment_halo_records(const SegGeom& g);    // the voxels of the window outside the brick
+long long segment_face_records(const SegGeom& g);    // the voxels of the brick on a low face with b0 > 0
+// own: g.voxels words, zeroed by the caller; halo / face / size: pairs of 64-bit words; counts: {halo, face, size
+// records}, zeroed by the caller.  size records past size_cap are counted and not stored.
+hipError_t launch_segment_collect(const uint32_t* labels, const SegGeom& g, uint32_t* own, unsigned long long* halo,
+                                  unsigned long long halo_cap, unsigned long long* face, unsigned long long face_cap,
+                                  unsigned long long* size, unsigned long long size_cap, unsigned long long* counts,
+                                  hipStream_t s);
+// final: g.voxels elements of typesize (4 or 8); out: g.brick_voxels of them
+hipError_t launch_segment_relabel(const uint32_t* labels, const SegGeom& g, const unsigned long long* keys,
+                                  const unsigned long long* vals, unsigned long long n_keys, int typesize, void* final,
+                                  void* out, hipStream_t s);
 // dst[i] = src[i] != 0 (elementwise_kernels.hip): a uint16 mask window as the bytes a mask pool takes
 hipError_t launch_nonzero_u8(const uint16_t* src, uint8_t* dst, size_t n, hipStream_t s);
 // ---- one pyramid level of a box (downsample_kernels.hip) ----

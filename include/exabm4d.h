@@ -996,6 +996,51 @@ int exabm4d_label_components_dev(exabm4d_ctx* ctx, const void* src, int src_u16,
                                  int min_voxels, int connectivity, uint32_t* labels, uint32_t* sizes,
                                  uint8_t* kept_u8, void* scratch, size_t scratch_bytes, uint64_t* counts_dev);
 
+/* ---- the components of a whole volume from those of its bricks' windows ------------------
+ * labels (device, uint32, dense) holds the labels exabm4d_component_seeds_u16_dev made of the WINDOW win_origin + [0,
+ * win_dims) of a volume of vol_dims voxels (region = window: label = 1 + the window index of the component's first
+ * voxel, background 0); the BRICK brick_origin + [0, brick_dims) lies inside the window, the window inside the
+ * volume, and the window has fewer than 2^31 voxels (all z, y, x).  A PROVISIONAL label is such a label in volume
+ * coordinates: 1 + the linear index IN THE VOLUME of the voxel at window index label - 1, a 64-bit number.
+ *
+ * exabm4d_segment_collect_dev writes what a merge over all bricks needs, as pairs of uint64:
+ *   own         uint32 per voxel of the window, zeroed here: at index label - 1 the voxels of that component that lie
+ *               INSIDE THE BRICK (what a partition of the volume into bricks may add up)
+ *   halo        (volume index of the voxel, provisional label) of every seed of the window outside the brick
+ *   face        the same of every seed of the brick that lies on a low face of the brick whose brick_origin on that
+ *               axis is > 0 -- a voxel that the window of the brick before it on that axis holds as halo
+ *   size        (provisional label, own count) of every component with an own count > 0
+ *   counts_dev  three uint64 words, zeroed here: the halo, face and size records there are
+ * halo_capacity and face_capacity (records) must be at least the geometric worst case -- the voxels of the window
+ * outside the brick, and the voxels of the brick on such low faces -- so those two cannot overflow.  size records are
+ * always all COUNTED, and stored only below size_capacity (>= 1): where counts_dev[2] > size_capacity the buffer holds
+ * size_capacity of them and the caller repeats the call with a capacity of counts_dev[2].  The order of the records
+ * is not determined; their sets are.  Two launches (own counts with halo and face records, one atomic add per wave and
+ * record kind; then the size records); no workgroup waits for another and no loop is without a bound.
+ *
+ * exabm4d_segment_relabel_dev writes the dense brick out (brick_dims elements of typesize 4 or 8 bytes): for a seed
+ * the value vals[k] where keys[k] is its component's provisional label, the provisional label itself where no key
+ * is, and 0 for background.  keys (ascending, distinct) and vals: n_keys uint64 each on the device; n_keys == 0
+ * takes NULL.  The table is searched once per component, by the component's first voxel, into final (device,
+ * typesize bytes per voxel of the window, contents not kept); a second pass streams the brick, with 16-byte loads and
+ * stores for the voxels at which the address allows them.  With typesize 4 the volume has at most 2^32 - 1 voxels and
+ * the caller sees to it that every val fits.
+ *
+ * Checked on the host (EXABM4D_ERR_INVALID, nothing written): non-NULL ctx, labels, geometry, own / final, the record
+ * buffers, counts_dev and out; keys and vals unless n_keys == 0; the window inside the volume with fewer than 2^31
+ * voxels and the brick inside the window; the capacities; typesize, and the volume's size with typesize 4;
+ * alignment: labels and own 4 bytes, the record buffers 16, counts_dev, keys and vals 8, final and out typesize.
+ * Asynchronous on the context's stream. */
+int exabm4d_segment_collect_dev(exabm4d_ctx* ctx, const uint32_t* labels, const int32_t* vol_dims_zyx,
+                                const int32_t* win_origin_zyx, const int32_t* win_dims_zyx,
+                                const int32_t* brick_origin_zyx, const int32_t* brick_dims_zyx, uint32_t* own,
+                                uint64_t* halo, size_t halo_capacity, uint64_t* face, size_t face_capacity,
+                                uint64_t* size, size_t size_capacity, uint64_t* counts_dev);
+int exabm4d_segment_relabel_dev(exabm4d_ctx* ctx, const uint32_t* labels, const int32_t* vol_dims_zyx,
+                                const int32_t* win_origin_zyx, const int32_t* win_dims_zyx,
+                                const int32_t* brick_origin_zyx, const int32_t* brick_dims_zyx, const uint64_t* keys,
+                                const uint64_t* vals, size_t n_keys, int typesize, void* final, void* out);
+
 /* dst[i] = src[i] != 0 for n elements on the device: a uint16 mask window (non-zero = foreground) as the bytes a
  * mask pool of exabm4d_scatter_boxes_dev takes.  src at an even address, dst at any; 16-byte loads and 8-byte stores
  * where src is 16-byte and dst 8-byte aligned.  n == 0 succeeds without a launch.  Asynchronous. */
