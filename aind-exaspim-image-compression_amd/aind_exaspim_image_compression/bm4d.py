@@ -395,7 +395,7 @@ def denoise_store(src, dst_path, sigma=None, offset=0.0, chunk=256, halo=8, prof
     Returns raw bytes / stored chunk bytes, like ``write_zarr``.  ``stats`` (a dict) receives ``seconds`` per phase
     (read, denoise, scatter, encode, files_write), ``bricks``, ``windows`` and ``largest_alloc``, the largest device
     allocation made here (the pipeline's scratch is the context's and is not counted)."""
-    from aind_exaspim_image_compression.utils import chunk_store, store_write
+    from aind_exaspim_image_compression.utils import chunk_store, store_windows
     from aind_exaspim_image_compression.utils.chunk_codec import ExacCodec
     # -- every argument check, before a context exists
     if isinstance(sigma, str) or isinstance(noise, str):
@@ -409,11 +409,10 @@ def denoise_store(src, dst_path, sigma=None, offset=0.0, chunk=256, halo=8, prof
         raise ValueError("denoise_store: stages must be 1 or 2")
     if int(budget_bytes) < 1:
         raise ValueError("denoise_store: budget_bytes must be positive")
+    chunks = store_windows.check_chunks(chunks)
     arr = src if hasattr(src, "read_patches") else chunk_store.open_zarr(src, device=device)
     shape = arr.shape[2:]
-    chunks = tuple(int(c) for c in (chunks if chunks is not None else arr.chunks))
-    if len(chunks) != 5 or chunks[:2] != (1, 1) or min(chunks) < 1:
-        raise ValueError("chunks must be (1, 1, cz, cy, cx)")
+    chunks = chunks if chunks is not None else tuple(int(c) for c in arr.chunks)
     if any(chunk % c for c in chunks[2:]):
         raise ValueError("denoise_store: chunk=%d is not a multiple of the destination's chunk shape %s on every "
                          "axis" % (chunk, chunks[2:]))
@@ -435,83 +434,63 @@ def denoise_store(src, dst_path, sigma=None, offset=0.0, chunk=256, halo=8, prof
                               (z0, y0, x0), (ez, ey, ex)))
     cost = [_STORE_WINDOW_BYTES * int(np.prod(c[1])) + _STORE_CORE_BYTES * int(np.prod(c[4])) for c in cores]
     budget = int(budget_bytes)
-    arr_pool_cap, arr.max_pool_bytes = arr.max_pool_bytes, max(1, min(arr.max_pool_bytes, budget // 8))
+    reader = budget // store_windows.READER_SHARE
     bricks, first, held = [], 0, 0
     for n, c in enumerate(cost):
-        if n > first and held + c > budget - budget // 8:
+        if n > first and held + c > budget - reader:
             bricks.append((first, n))
             first, held = n, 0
         held += c
     bricks.append((first, len(cores)))
 
-    st = store_write._new_stats()
-    seconds = {"read": 0.0, "denoise": 0.0, "scatter": 0.0, "encode": 0.0, "files_write": 0.0}
-    largest, written, windows = 0, 0, 0
-    d_table = None
-    try:
+    largest, windows = 0, 0
+    with store_windows.capped_pools([arr], budget):
         ctx = _native.context(device)
-        d_table = store_write.bound_table_on_device(out, ctx)
-        for b0, b1 in bricks:
-            brick = cores[b0:b1]
-            plan = store_write.plan_write(shape, chunks[2:], [c[3] for c in brick], [c[4] for c in brick],
-                                          out._nominal, exists=lambda *idx: False, max_pool_bytes=1 << 62)
-            (g,) = plan
-            if any(s != store_write.COVERED for s in g.states):
-                raise RuntimeError("denoise_store: a destination chunk is not covered by one core")
-            classes = {}
-            for k, c in enumerate(brick):
-                classes.setdefault(c[1], []).append(k)
-            pool = store_write.open_pool(out, ctx, g, st)
-            largest = max(largest, 2 * g.pool_elems)
-            try:
-                for win, members in classes.items():
-                    nvox = int(np.prod(win))
-                    t0 = time.perf_counter()
-                    d_in = arr.read_patches([brick[k][0] for k in members], win, is_center=False, out="device")
-                    d_res = None
-                    try:
-                        d_res = ctx.alloc(2 * nvox * len(members))
-                        largest = max(largest, 2 * nvox * len(members))
-                        t1 = time.perf_counter()
-                        if nz_model is not None:
-                            ctx.denoise_pg_u16(d_in, d_res, win, nz_model, params=prof, stages=stages,
-                                               batch=len(members))
-                        else:
-                            ctx.denoise_u16(d_in, d_res, win, sigma, float(offset), params=prof, stages=stages,
-                                            batch=len(members))
-                        ctx.sync()
-                        t2 = time.perf_counter()
-                        # the cores: the inner part of each window, its front offset its own
-                        rec = np.zeros(len(members), dtype=_native.BOX_SRC)
-                        remap = np.full(len(brick) + 1, -1, dtype=np.int32)      # [-1] stays -1
-                        for j, k in enumerate(members):
-                            _, _, (lz, ly, lx), org, ext = brick[k]
-                            rec[j]["base"] = j * nvox + (lz * win[1] + ly) * win[2] + lx
-                            rec[j]["stride_z"], rec[j]["stride_y"] = win[1] * win[2], win[2]
-                            rec[j]["z0"], rec[j]["y0"], rec[j]["x0"] = org
-                            rec[j]["ez"], rec[j]["ey"], rec[j]["ex"] = ext
-                            remap[k] = j
-                        store_write.scatter(ctx, g, pool, d_res, nvox * len(members), np.uint16, rec,
-                                            dst_boxes=remap[g.dst_boxes])
-                        ctx.sync()
-                        t3 = time.perf_counter()
-                    finally:
-                        d_in.free()
-                        if d_res is not None:
-                            d_res.free()
-                    seconds["read"] += t1 - t0
-                    seconds["denoise"] += t2 - t1
-                    seconds["scatter"] += t3 - t2
-                    windows += len(members)
-                written += store_write.encode_commit(out, ctx, g, pool, st, d_table)
-            finally:
-                pool.free()
-    finally:
-        arr.max_pool_bytes = arr_pool_cap
-        if d_table is not None:
-            d_table.free()
-    seconds["encode"], seconds["files_write"] = st["seconds"]["encode"], st["seconds"]["files_write"]
+        clock = store_windows.PhaseClock(("read", "denoise", "scatter", "encode", "files_write"), True, ctx.sync)
+        seconds = clock.seconds
+        with store_windows.BrickSink("denoise_store", out, ctx, shape, chunks, box="core") as sink:
+            for b0, b1 in bricks:
+                brick = cores[b0:b1]
+                classes = {}
+                for k, c in enumerate(brick):
+                    classes.setdefault(c[1], []).append(k)
+                with sink.pool([c[3] for c in brick], [c[4] for c in brick]) as pool:
+                    largest = max(largest, 2 * pool.g.pool_elems)
+                    for win, members in classes.items():
+                        nvox = int(np.prod(win))
+                        t0 = time.perf_counter()
+                        d_in = arr.read_patches([brick[k][0] for k in members], win, is_center=False, out="device")
+                        try:
+                            with ctx.alloc(2 * nvox * len(members)) as d_res:
+                                largest = max(largest, 2 * nvox * len(members))
+                                t1 = time.perf_counter()
+                                if nz_model is not None:
+                                    ctx.denoise_pg_u16(d_in, d_res, win, nz_model, params=prof, stages=stages,
+                                                       batch=len(members))
+                                else:
+                                    ctx.denoise_u16(d_in, d_res, win, sigma, float(offset), params=prof, stages=stages,
+                                                    batch=len(members))
+                                t2 = clock()
+                                # the cores: the inner part of each window, its front offset its own
+                                rec = np.zeros(len(members), dtype=_native.BOX_SRC)
+                                remap = np.full(len(brick) + 1, -1, dtype=np.int32)      # [-1] stays -1
+                                for j, k in enumerate(members):
+                                    _, _, (lz, ly, lx), org, ext = brick[k]
+                                    rec[j]["base"] = j * nvox + (lz * win[1] + ly) * win[2] + lx
+                                    rec[j]["stride_z"], rec[j]["stride_y"] = win[1] * win[2], win[2]
+                                    rec[j]["z0"], rec[j]["y0"], rec[j]["x0"] = org
+                                    rec[j]["ez"], rec[j]["ey"], rec[j]["ex"] = ext
+                                    remap[k] = j
+                                pool.scatter(d_res, nvox * len(members), np.uint16, rec,
+                                             dst_boxes=remap[pool.g.dst_boxes])
+                                t3 = clock()
+                        finally:
+                            d_in.free()
+                        seconds["read"] += t1 - t0
+                        seconds["denoise"] += t2 - t1
+                        seconds["scatter"] += t3 - t2
+                        windows += len(members)
+                    pool.commit()
     if stats is not None:
-        stats.update(seconds=seconds, bricks=len(bricks), windows=windows, largest_alloc=largest,
-                     chunks=st["chunks"], encode_calls=st["encode_calls"])
-    return 2 * int(np.prod(shape)) / written
+        stats.update(sink.finish(seconds), seconds=seconds, bricks=len(bricks), windows=windows, largest_alloc=largest)
+    return 2 * int(np.prod(shape)) / sink.written

@@ -32,7 +32,8 @@ from aind_exaspim_image_compression import inference
 from aind_exaspim_image_compression.machine_learning import transforms as _transforms
 from aind_exaspim_image_compression import _native
 from aind_exaspim_image_compression.utils import img_util, store_compare
-from aind_exaspim_image_compression.utils.store_windows import ArrayWindows, StoreWindows, capped_pools, open_u16_stores
+from aind_exaspim_image_compression.utils.store_windows import (ArrayWindows, PhaseClock, StoreWindows, capped_pools,
+                                                                open_u16_stores)
 from aind_exaspim_image_compression.utils.store_compare import abs_error_percentile  # noqa: F401  (public here)
 
 
@@ -105,18 +106,13 @@ def _score(ctx, shape, bricks, source, with_mask, data_range, window_size, stats
     n = shape[0] * shape[1] * shape[2]
     tables = 2 if with_mask else 1
     words = 3 * _native.mip_plane_words(shape)
-    seconds = dict.fromkeys(_COMPARE_PHASES, 0.0)
-    timed = stats is not None
+    clock = PhaseClock(_COMPARE_PHASES, stats is not None, ctx.sync)
+    seconds = clock.seconds
     held = {"now": 0, "most": 0}
 
     def hold(nbytes):
         held["now"] += nbytes
         held["most"] = max(held["most"], held["now"])
-
-    def clock():
-        if timed:
-            ctx.sync()
-        return time.perf_counter()
 
     two_pass = data_range is None
     lows = [65535, 65535]

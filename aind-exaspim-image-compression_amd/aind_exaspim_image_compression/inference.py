@@ -548,7 +548,7 @@ def predict_store(src, dst_path, model, transform, batch_size=32, patch_size=64,
     waits for it), ``bricks``, ``patches_run``, ``patches_unique`` (``count_patches`` of
     the volume) and ``largest_alloc``, the most device bytes held here at one time (the model's activations are the
     framework's and are not counted)."""
-    from aind_exaspim_image_compression.utils import chunk_store, store_predict, store_write
+    from aind_exaspim_image_compression.utils import chunk_store, store_predict, store_windows, store_write
     from aind_exaspim_image_compression.utils.chunk_codec import ExacCodec
     # -- every argument check, before a context exists
     if precision not in PRECISIONS:
@@ -564,22 +564,11 @@ def predict_store(src, dst_path, model, transform, batch_size=32, patch_size=64,
     budget = int(budget_bytes)
     if budget < 1:
         raise ValueError("predict_store: budget_bytes must be positive")
-    if chunks is not None:
-        chunks = tuple(int(c) for c in chunks)
-        if len(chunks) != 5 or chunks[:2] != (1, 1) or min(chunks) < 1:
-            raise ValueError("chunks must be (1, 1, cz, cy, cx)")
+    chunks = store_windows.check_chunks(chunks)
     # the device: the caller's, else the model's (no context is needed to tell); a path is opened for it
     dev = torch.device("cuda", int(device)) if device is not None else _model_device(model)
     index = dev.index or 0
-    try:
-        arr = src if hasattr(src, "read_patches") else chunk_store.open_zarr(src, device=index)
-    except NotImplementedError as e:
-        raise ValueError("predict_store: the source must hold uint16 (%s)" % e) from None
-    if np.dtype(arr.dtype) != np.uint16:
-        raise ValueError("predict_store: the source must hold uint16")
-    if int(arr.device if arr.device is not None else _native.default_device()) != index:
-        raise ValueError("predict_store: the source was opened for another device than cuda:%d, the one used here"
-                         % index)
+    (arr,) = store_windows.open_u16_stores("predict_store", (("src", src),), index)
     shape = tuple(int(s) for s in arr.shape[2:])
     chunks = chunks if chunks is not None else tuple(int(c) for c in arr.chunks)
     codec = codec or ExacCodec(2)
@@ -594,9 +583,7 @@ def predict_store(src, dst_path, model, transform, batch_size=32, patch_size=64,
     run, loop_amp, call_amp = _forward_plan(model, fast, amp_dtype)
     tf = transform.native_struct()
     pv = patch_size ** 3
-    st = store_write._new_stats()
-    seconds = dict.fromkeys(("read", "gather", "forward", "stitch", "scatter", "encode", "files_write"), 0.0)
-    timed = stats is not None
+    source = store_windows.StoreWindows([arr], chunks[2], fill=0)       # (in z slabs of a destination chunk)
     held = {"now": 0, "most": 0}
 
     def hold(nbytes):
@@ -607,109 +594,83 @@ def predict_store(src, dst_path, model, transform, batch_size=32, patch_size=64,
     if verbose:
         from tqdm import tqdm
         pbar = tqdm(total=sum(b.n_patches for b in bricks), desc="Denoise")
-    arr_pool_cap, arr.max_pool_bytes = arr.max_pool_bytes, max(1, min(arr.max_pool_bytes,
-                                                                    budget // store_predict.READER_SHARE))
-    written, patches_run, seen_batch = 0, 0, False
-    d_table = None
+    patches_run, seen_batch = 0, False
     try:
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev), store_windows.capped_pools([arr], budget):
             stream = torch.cuda.current_stream(dev)
             ctx.set_stream(stream.cuda_stream)       # kernels, the codecs and the model share one stream
-
-            def clock(sync):
-                if sync:
-                    stream.synchronize()
-                return time.perf_counter()
-
+            clock = store_windows.PhaseClock(
+                ("read", "gather", "forward", "stitch", "scatter", "encode", "files_write"), stats is not None,
+                stream.synchronize)
+            seconds = clock.seconds
             # one input batch and one buffer of predictions, sized for the largest brick, for the whole call
             batch = torch.zeros((batch_size, 1, patch_size, patch_size, patch_size), dtype=torch.float32, device=dev)
             preds = torch.empty((max(most, 1), 1, patch_size, patch_size, patch_size), dtype=torch.float32,
                                 device=dev)
             hold(4 * pv * (batch_size + max(most, 1)))
-            d_table = store_write.bound_table_on_device(out, ctx)
-            for brick in bricks:
-                n_patches = brick.n_patches
-                grid = _native.patch_grid(brick.first, brick.count, patch_size - overlap, patch_size)
-                if n_patches:
-                    # the window in z slabs, so that the reader's pool stays under its cap; the slabs lie one after
-                    # another: one window, as tall as the plan priced it
-                    wz, wy, wx = brick.win_extent
-                    slabs, slab = store_predict.window_slabs(wz, chunks[2])
-                    win_dims = (slabs * slab, wy, wx)
-                    t0 = time.perf_counter()
-                    d_win = arr.read_patches([(brick.win_origin[0] + j * slab,) + tuple(brick.win_origin[1:])
-                                              for j in range(slabs)], (slab, wy, wx), is_center=False, out="device")
-                    hold(2 * int(np.prod(win_dims)))
-                    seconds["read"] += time.perf_counter() - t0
-                    try:
-                        with loop_amp():
-                            for k0 in range(0, n_patches, batch_size):
-                                nb = min(batch_size, n_patches - k0)
-                                t0 = clock(timed)
-                                ctx.tile_gather_u16(tf, d_win, brick.win_origin, win_dims, shape, grid, k0, nb, batch)
-                                t1 = clock(timed)
-                                # predict's rule for a short batch: at full size once the tensor holds earlier rows
-                                # (MIOpen sees ONE shape), for eval-mode modules only; the call's first batch as it is
-                                full = nb < batch_size and seen_batch and not getattr(model, "training", True)
-                                with torch.no_grad(), call_amp():
-                                    res = run(batch if full else batch[:nb])[:nb]
-                                preds[k0:k0 + nb].copy_(res)
-                                del res
-                                t2 = clock(timed)
-                                seconds["gather"] += t1 - t0
-                                seconds["forward"] += t2 - t1
-                                seen_batch = True
-                                patches_run += nb
-                                if pbar is not None:
-                                    pbar.update(nb)
-                    finally:                                 # (freeing a buffer waits for the stream)
-                        d_win.free()
-                        hold(-2 * int(np.prod(win_dims)))
-                nvox = int(np.prod(brick.extent))
-                (g,) = store_write.plan_write(shape, chunks[2:], [brick.origin], [brick.extent], out._nominal,
-                                              exists=lambda *idx: False, max_pool_bytes=1 << 62)
-                if any(s != store_write.COVERED for s in g.states):
-                    raise RuntimeError("predict_store: a destination chunk is not covered by one brick")
-                d_res = pool = None
-                try:
-                    t0 = clock(timed)
-                    d_res = ctx.alloc(2 * nvox)
-                    hold(2 * nvox)
-                    ctx.tile_stitch_u16(tf, preds if n_patches else None, n_patches, grid, trim, brick.origin,
-                                        brick.extent, shape, d_res)
-                    t1 = clock(timed)
-                    pool = store_write.open_pool(out, ctx, g, st)
-                    hold(2 * g.pool_elems)
-                    store_write.scatter(ctx, g, pool, d_res, nvox, np.uint16,
-                                        store_write.box_records([brick.origin], brick.extent))
-                    t2 = clock(timed)
-                    d_res.free()
-                    d_res = None
-                    hold(-2 * nvox)
-                    seconds["stitch"] += t1 - t0
-                    seconds["scatter"] += t2 - t1
-                    written += store_write.encode_commit(out, ctx, g, pool, st, d_table)
-                finally:
-                    if d_res is not None:
-                        d_res.free()
-                        hold(-2 * nvox)
-                    if pool is not None:
-                        pool.free()
-                        hold(-2 * g.pool_elems)
+            with store_windows.BrickSink("predict_store", out, ctx, shape, chunks) as sink:
+                for brick in bricks:
+                    n_patches = brick.n_patches
+                    grid = _native.patch_grid(brick.first, brick.count, patch_size - overlap, patch_size)
+                    if n_patches:
+                        t0 = time.perf_counter()
+                        (d_win,), win_dims = source.read(brick.win_origin, brick.win_extent)
+                        hold(2 * int(np.prod(win_dims)))
+                        seconds["read"] += time.perf_counter() - t0
+                        try:
+                            with loop_amp():
+                                for k0 in range(0, n_patches, batch_size):
+                                    nb = min(batch_size, n_patches - k0)
+                                    t0 = clock()
+                                    ctx.tile_gather_u16(tf, d_win, brick.win_origin, win_dims, shape, grid, k0, nb,
+                                                        batch)
+                                    t1 = clock()
+                                    # predict's rule for a short batch: at full size once the tensor holds earlier
+                                    # rows (MIOpen sees ONE shape), for eval-mode modules only; the call's first batch
+                                    # as it is
+                                    full = nb < batch_size and seen_batch and not getattr(model, "training", True)
+                                    with torch.no_grad(), call_amp():
+                                        res = run(batch if full else batch[:nb])[:nb]
+                                    preds[k0:k0 + nb].copy_(res)
+                                    del res
+                                    t2 = clock()
+                                    seconds["gather"] += t1 - t0
+                                    seconds["forward"] += t2 - t1
+                                    seen_batch = True
+                                    patches_run += nb
+                                    if pbar is not None:
+                                        pbar.update(nb)
+                        finally:                                 # (freeing a buffer waits for the stream)
+                            d_win.free()
+                            hold(-2 * int(np.prod(win_dims)))
+                    nvox = int(np.prod(brick.extent))
+                    group = sink.pool([brick.origin], [brick.extent])
+                    t0 = clock()
+                    with ctx.alloc(2 * nvox) as d_res:
+                        hold(2 * nvox)
+                        ctx.tile_stitch_u16(tf, preds if n_patches else None, n_patches, grid, trim, brick.origin,
+                                            brick.extent, shape, d_res)
+                        t1 = clock()
+                        with group as pool:
+                            hold(2 * pool.g.pool_elems)
+                            pool.scatter(d_res, nvox, np.uint16, store_write.box_records([brick.origin], brick.extent))
+                            t2 = clock()
+                            d_res.free()
+                            hold(-2 * nvox)
+                            seconds["stitch"] += t1 - t0
+                            seconds["scatter"] += t2 - t1
+                            pool.commit()
+                        hold(-2 * pool.g.pool_elems)
             del batch, preds
     finally:
         ctx.reset_stream()
-        arr.max_pool_bytes = arr_pool_cap
-        if d_table is not None:
-            d_table.free()
         if pbar is not None:
             pbar.close()
     del run
-    seconds["encode"], seconds["files_write"] = st["seconds"]["encode"], st["seconds"]["files_write"]
     if stats is not None:
-        stats.update(seconds=seconds, bricks=len(bricks), patches_run=patches_run, patches_unique=unique,
-                     largest_alloc=held["most"], chunks=st["chunks"], encode_calls=st["encode_calls"])
-    return 2 * int(np.prod(shape)) / written
+        stats.update(sink.finish(seconds), seconds=seconds, bricks=len(bricks), patches_run=patches_run,
+                     patches_unique=unique, largest_alloc=held["most"])
+    return 2 * int(np.prod(shape)) / sink.written
 
 
 def predict_patch(patch, model, transform):

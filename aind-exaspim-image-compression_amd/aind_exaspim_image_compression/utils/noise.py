@@ -238,17 +238,12 @@ def _measure(ctx, shape, bricks, source, with_mask, stats):
     windows (volume[, mask]) and their extent as held."""
     import time
     from aind_exaspim_image_compression.utils.store_measure import StoreMeasure
+    from aind_exaspim_image_compression.utils.store_windows import PhaseClock
     tables = 2 if with_mask else 1
     table_bytes = 8 * tables * (_native.COUNT_BINS + _native.measure_noise_words())
-    seconds = {"read": 0.0, "measure": 0.0, "download": 0.0}
-    timed = stats is not None
+    clock = PhaseClock(("read", "measure", "download"), stats is not None, ctx.sync)
+    seconds = clock.seconds
     voxels_read, most = 0, 0
-
-    def clock():
-        if timed:
-            ctx.sync()
-        return time.perf_counter()
-
     d_counts = d_noise = None
     try:
         d_counts = ctx.alloc(8 * tables * _native.COUNT_BINS)

@@ -134,13 +134,7 @@ def foreground_store(src, dst_path, k=6.0, dilate=1, threshold=None, measure=Non
     budget = int(budget_bytes)
     if budget < 1:
         raise ValueError("foreground_store: budget_bytes must be positive")
-    if chunks is not None:
-        try:
-            chunks = tuple(int(c) for c in chunks)
-        except TypeError:
-            raise ValueError("chunks must be (1, 1, cz, cy, cx)") from None
-        if len(chunks) != 5 or chunks[:2] != (1, 1) or min(chunks) < 1:
-            raise ValueError("chunks must be (1, 1, cz, cy, cx)")
+    chunks = store_windows.check_chunks(chunks)
     if measure is not None and not isinstance(measure, StoreMeasure):
         raise ValueError("foreground_store: measure is a StoreMeasure (utils.noise.measure_store)")
     index = int(device) if device is not None else _native.default_device()
@@ -152,8 +146,7 @@ def foreground_store(src, dst_path, k=6.0, dilate=1, threshold=None, measure=Non
     codec = codec or ExacCodec(2)
     bricks = plan_foreground(shape, chunks[2:], dilate, budget, min_voxels)
 
-    seconds = dict.fromkeys(("measure", "read", "mask", "scatter", "encode", "files_write"), 0.0)
-    passes, voxels_read, most = 1, 0, 0
+    passes, voxels_read, most, measuring = 1, 0, 0, 0.0
     if threshold is not None:
         thr = float(threshold)
     else:
@@ -161,7 +154,7 @@ def foreground_store(src, dst_path, k=6.0, dilate=1, threshold=None, measure=Non
             t0 = time.perf_counter()
             inner = {}
             measure = noise.measure_store(arr, budget_bytes=budget, device=index, stats=inner)
-            seconds["measure"] = time.perf_counter() - t0
+            measuring = time.perf_counter() - t0
             passes, voxels_read, most = 2, inner["voxels_read"], inner["largest_alloc"]
         thr = float(measure.foreground_threshold(k))
     cut = cut_of_threshold(thr)
@@ -170,31 +163,23 @@ def foreground_store(src, dst_path, k=6.0, dilate=1, threshold=None, measure=Non
     out = chunk_store.create_zarr(dst_path, shape, chunks, codec=codec, attributes=attributes, overwrite=True,
                                   device=index)
     source = store_windows.StoreWindows([arr], int(arr.chunks[2]))
-    st = store_write._new_stats()
-    timed = stats is not None
-
-    def clock():
-        if timed:
-            ctx.sync()
-        return time.perf_counter()
-
-    written = 0
-    d_counts = d_table = d_kept = None
+    clock = store_windows.PhaseClock(("measure", "read", "mask", "scatter", "encode", "files_write"), stats is not None,
+                                     ctx.sync)
+    seconds = clock.seconds
+    seconds["measure"] = measuring
+    d_counts = d_kept = None
     try:
         d_counts = ctx.alloc(16)
         if min_voxels:
             d_kept = ctx.alloc(24)
-        d_table = store_write.bound_table_on_device(out, ctx)
-        with store_windows.capped_pools([arr], budget):
+        with store_windows.BrickSink("foreground_store", out, ctx, shape, chunks) as sink, \
+                store_windows.capped_pools([arr], budget):
             for n_brick, brick in enumerate(bricks):
                 nvox = int(np.prod(brick.extent))
-                (g,) = store_write.plan_write(shape, chunks[2:], [brick.origin], [brick.extent], out._nominal,
-                                              exists=lambda *idx: False, max_pool_bytes=1 << 62)
-                if any(s != store_write.COVERED for s in g.states):
-                    raise RuntimeError("foreground_store: a destination chunk is not covered by one brick")
+                group = sink.pool([brick.origin], [brick.extent])
                 t0 = time.perf_counter()
                 wins, dims = source.read(brick.win_origin, brick.win_extent)
-                d_brick = pool = d_seeds = None
+                d_brick = d_seeds = None
                 try:
                     t1 = clock()
                     try:
@@ -228,37 +213,32 @@ def foreground_store(src, dst_path, k=6.0, dilate=1, threshold=None, measure=Non
                         if d_seeds is not None:
                             d_seeds.free()
                     voxels_read += brick.window_voxels
-                    pool = store_write.open_pool(out, ctx, g, st)
-                    most = max(most, 2 * nvox + 2 * g.pool_elems + 16)
-                    store_write.scatter(ctx, g, pool, d_brick, nvox, np.uint16,
-                                        store_write.box_records([brick.origin], brick.extent))
-                    t3 = clock()
-                    d_brick.free()
-                    d_brick = None
-                    seconds["read"] += t1 - t0
-                    seconds["mask"] += t2 - t1
-                    seconds["scatter"] += t3 - t2
-                    written += store_write.encode_commit(out, ctx, g, pool, st, d_table)
+                    with group as pool:
+                        most = max(most, 2 * nvox + 2 * pool.g.pool_elems + 16)
+                        pool.scatter(d_brick, nvox, np.uint16, store_write.box_records([brick.origin], brick.extent))
+                        t3 = clock()
+                        d_brick.free()
+                        seconds["read"] += t1 - t0
+                        seconds["mask"] += t2 - t1
+                        seconds["scatter"] += t3 - t2
+                        pool.commit()
                 finally:
                     if d_brick is not None:
                         d_brick.free()
-                    if pool is not None:
-                        pool.free()
         n_seed, n_fg = (int(c) for c in d_counts.download((2,), np.uint64))
         n_kept, n_dropped = n_seed, 0
         if min_voxels:                                   # (the mask kernel counted the kept seeds as its seeds)
             n_seed, n_kept, n_dropped = (int(c) for c in d_kept.download((3,), np.uint64))
     finally:
-        for buf in (d_counts, d_table, d_kept):
+        for buf in (d_counts, d_kept):
             if buf is not None:
                 buf.free()
-    seconds["encode"], seconds["files_write"] = st["seconds"]["encode"], st["seconds"]["files_write"]
     n = shape[0] * shape[1] * shape[2]
     if stats is not None:
-        stats.update(seconds=seconds, bricks=len(bricks), passes=passes, voxels_read=voxels_read, largest_alloc=most,
-                     chunks=st["chunks"], encode_calls=st["encode_calls"])
+        stats.update(sink.finish(seconds), seconds=seconds, bricks=len(bricks), passes=passes, voxels_read=voxels_read,
+                     largest_alloc=most)
     return {"threshold": thr, "cut": cut, "n": n, "n_seed": n_seed, "n_kept": n_kept,
-            "n_dropped_components": n_dropped, "n_fg": n_fg, "fraction": n_fg / n, "cratio": 2 * n / written}
+            "n_dropped_components": n_dropped, "n_fg": n_fg, "fraction": n_fg / n, "cratio": 2 * n / sink.written}
 
 
 def foreground_volume(vol, k=6.0, dilate=1, threshold=None, device=None, min_voxels=0, connectivity=26):

@@ -48,24 +48,6 @@ def _check_rule(who, factors, method, edge):
     return _check_factors(who, factors)
 
 
-def _check_store_args(who, chunks, codec, budget_bytes):
-    from aind_exaspim_image_compression.utils.chunk_codec import ExacCodec
-    budget = int(budget_bytes)
-    if budget < 1:
-        raise ValueError("%s: budget_bytes must be positive" % who)
-    if chunks is not None:
-        try:
-            chunks = tuple(int(c) for c in chunks)
-        except TypeError:
-            raise ValueError("chunks must be (1, 1, cz, cy, cx)") from None
-        if len(chunks) != 5 or chunks[:2] != (1, 1) or min(chunks) < 1:
-            raise ValueError("chunks must be (1, 1, cz, cy, cx)")
-    codec = codec or ExacCodec(2)
-    if not hasattr(codec, "config_entry") or getattr(codec, "typesize", None) != 2:
-        raise ValueError("%s: codec must be a codec of uint16 volumes that create_zarr takes" % who)
-    return chunks, codec, budget
-
-
 def level_shape(shape, factors, edge="crop"):
     """The (z, y, x) shape of the level that ``factors`` make of a volume of ``shape``: ``n // f`` per axis under
     ``edge="crop"`` (an axis may come out empty), ``ceil(n / f)`` under ``"partial"``."""
@@ -131,7 +113,7 @@ def downsample_store(src, dst_path, factors=(2, 2, 2), method="mode", edge="crop
     from aind_exaspim_image_compression.utils import chunk_store, store_windows, store_write
     # -- every argument check, before a context exists
     f = _check_rule("downsample_store", factors, method, edge)
-    chunks, codec, budget = _check_store_args("downsample_store", chunks, codec, budget_bytes)
+    chunks, codec, budget = store_windows.check_store_args("downsample_store", chunks, codec, budget_bytes)
     index = int(device) if device is not None else _native.default_device()
     (arr,) = store_windows.open_u16_stores("downsample_store", (("src", src),), index)
     src_shape = tuple(int(s) for s in arr.shape[2:])
@@ -142,65 +124,42 @@ def downsample_store(src, dst_path, factors=(2, 2, 2), method="mode", edge="crop
     out = chunk_store.create_zarr(dst_path, shape, chunks, codec=codec, attributes=attributes, overwrite=True,
                                   device=index)
     source = store_windows.StoreWindows([arr], int(chunks[2]))
-    st = store_write._new_stats()
-    seconds = dict.fromkeys(("read", "reduce", "scatter", "encode", "files_write"), 0.0)
-    timed = stats is not None
-
-    def clock():
-        if timed:
-            ctx.sync()
-        return time.perf_counter()
-
-    written, voxels_read, most = 0, 0, 0
-    d_table = None
-    try:
-        d_table = store_write.bound_table_on_device(out, ctx)
-        with store_windows.capped_pools([arr], budget):
-            for brick in bricks:
-                nvox = int(np.prod(brick.extent))
-                (g,) = store_write.plan_write(shape, chunks[2:], [brick.origin], [brick.extent], out._nominal,
-                                              exists=lambda *idx: False, max_pool_bytes=1 << 62)
-                if any(s != store_write.COVERED for s in g.states):
-                    raise RuntimeError("downsample_store: a destination chunk is not covered by one brick")
-                t0 = time.perf_counter()
-                wins, dims = source.read(brick.win_origin, brick.win_extent)
-                d_brick = pool = None
-                try:
-                    t1 = clock()
-                    try:
-                        d_brick = ctx.alloc(2 * nvox)
-                        most = max(most, 2 * int(np.prod(dims)) + 2 * nvox)
-                        ctx.downsample_box_u16(wins[0], src_shape, brick.win_origin, dims, brick.origin, brick.extent,
-                                               f, method, edge, out_u16=d_brick)
-                        t2 = clock()
-                    finally:
-                        source.release(wins)             # (freeing a buffer waits for the stream)
+    clock = store_windows.PhaseClock(("read", "reduce", "scatter", "encode", "files_write"), stats is not None,
+                                     ctx.sync)
+    seconds = clock.seconds
+    voxels_read, most = 0, 0
+    with store_windows.BrickSink("downsample_store", out, ctx, shape, chunks) as sink, \
+            store_windows.capped_pools([arr], budget):
+        for brick in bricks:
+            nvox = int(np.prod(brick.extent))
+            group = sink.pool([brick.origin], [brick.extent])
+            t0 = time.perf_counter()
+            wins, dims = source.read(brick.win_origin, brick.win_extent)
+            try:
+                t1 = clock()
+                with ctx.alloc(2 * nvox) as d_brick:
+                    most = max(most, 2 * int(np.prod(dims)) + 2 * nvox)
+                    ctx.downsample_box_u16(wins[0], src_shape, brick.win_origin, dims, brick.origin, brick.extent,
+                                           f, method, edge, out_u16=d_brick)
+                    t2 = clock()
+                    source.release(wins)                 # (freeing a buffer waits for the stream)
                     voxels_read += brick.window_voxels
-                    pool = store_write.open_pool(out, ctx, g, st)
-                    most = max(most, 2 * nvox + 2 * g.pool_elems)
-                    store_write.scatter(ctx, g, pool, d_brick, nvox, np.uint16,
-                                        store_write.box_records([brick.origin], brick.extent))
-                    t3 = clock()
-                    d_brick.free()
-                    d_brick = None
-                    seconds["read"] += t1 - t0
-                    seconds["reduce"] += t2 - t1
-                    seconds["scatter"] += t3 - t2
-                    written += store_write.encode_commit(out, ctx, g, pool, st, d_table)
-                finally:
-                    if d_brick is not None:
+                    with group as pool:
+                        most = max(most, 2 * nvox + 2 * pool.g.pool_elems)
+                        pool.scatter(d_brick, nvox, np.uint16, store_write.box_records([brick.origin], brick.extent))
+                        t3 = clock()
                         d_brick.free()
-                    if pool is not None:
-                        pool.free()
-    finally:
-        if d_table is not None:
-            d_table.free()
-    seconds["encode"], seconds["files_write"] = st["seconds"]["encode"], st["seconds"]["files_write"]
+                        seconds["read"] += t1 - t0
+                        seconds["reduce"] += t2 - t1
+                        seconds["scatter"] += t3 - t2
+                        pool.commit()
+            finally:
+                source.release(wins)
     n = shape[0] * shape[1] * shape[2]
     if stats is not None:
-        stats.update(seconds=seconds, bricks=len(bricks), voxels_read=voxels_read, largest_alloc=most,
-                     chunks=st["chunks"], encode_calls=st["encode_calls"])
-    return {"shape": shape, "n": n, "cratio": 2 * n / written}
+        stats.update(sink.finish(seconds), seconds=seconds, bricks=len(bricks), voxels_read=voxels_read,
+                     largest_alloc=most)
+    return {"shape": shape, "n": n, "cratio": 2 * n / sink.written}
 
 
 def downsample_volume(vol, factors=(2, 2, 2), method="mode", edge="crop", device=None):
@@ -310,7 +269,7 @@ def pyramid_store(src, dst_path, n_levels, factors=(2, 2, 2), method="mode", edg
     # -- every argument check, before a context exists and before anything is written
     steps = _level_factors(n_levels, factors)
     _check_rule("pyramid_store", (2, 2, 2), method, edge)
-    chunks, codec, budget = _check_store_args("pyramid_store", chunks, codec, budget_bytes)
+    chunks, codec, budget = store_windows.check_store_args("pyramid_store", chunks, codec, budget_bytes)
     transforms = level_transforms(steps, voxel_size, scale, translation)
     if not isinstance(spatial_unit, str):
         raise ValueError("pyramid_store: spatial_unit is a string")

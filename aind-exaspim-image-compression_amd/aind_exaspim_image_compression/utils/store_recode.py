@@ -58,13 +58,7 @@ def recode_store(src, dst_path, codec=None, mask=None, chunks=None, attributes=N
     budget = int(budget_bytes)
     if budget < 1:
         raise ValueError("recode_store: budget_bytes must be positive")
-    if chunks is not None:
-        try:
-            chunks = tuple(int(c) for c in chunks)
-        except TypeError:
-            raise ValueError("chunks must be (1, 1, cz, cy, cx)") from None
-        if len(chunks) != 5 or chunks[:2] != (1, 1) or min(chunks) < 1:
-            raise ValueError("chunks must be (1, 1, cz, cy, cx)")
+    chunks = store_windows.check_chunks(chunks)
     index = int(device) if device is not None else _native.default_device()
     arrs = store_windows.open_u16_stores("recode_store", (("src", src), ("mask", mask)), index)
     shape = tuple(int(s) for s in arrs[0].shape[2:])
@@ -76,60 +70,40 @@ def recode_store(src, dst_path, codec=None, mask=None, chunks=None, attributes=N
     out = chunk_store.create_zarr(dst_path, shape, chunks, codec=codec, attributes=attributes, overwrite=True,
                                   device=index)
     source = store_windows.StoreWindows(arrs, int(arrs[0].chunks[2]))
-    st = store_write._new_stats()
-    seconds = dict.fromkeys(("read", "scatter", "encode", "files_write"), 0.0)
-    timed = stats is not None
-
-    def clock():
-        if timed:
-            ctx.sync()
-        return time.perf_counter()
-
-    written, voxels_read, most = 0, 0, 0
-    d_table = None
-    try:
-        d_table = store_write.bound_table_on_device(out, ctx)
-        with store_windows.capped_pools(arrs, budget):
-            for brick in bricks:
-                (g,) = store_write.plan_write(shape, chunks[2:], [brick.origin], [brick.extent], out._nominal,
-                                              exists=lambda *idx: False, max_pool_bytes=1 << 62)
-                if any(s != store_write.COVERED for s in g.states):
-                    raise RuntimeError("recode_store: a destination chunk is not covered by one brick")
-                t0 = time.perf_counter()
-                wins, dims = source.read(brick.win_origin, brick.win_extent)
-                voxels_read += brick.window_voxels
-                n_win = int(np.prod(dims))
-                d_bytes = pool = None
-                try:
-                    try:
-                        t1 = clock()
-                        pool = store_write.open_pool(out, ctx, g, st, want_mask=with_mask)
-                        # the window may be taller than the brick (whole z slabs): its first brick.extent layers count
-                        record = store_write.box_records([brick.origin], brick.extent)
-                        record["stride_z"], record["stride_y"] = dims[1] * dims[2], dims[2]
-                        store_write.scatter(ctx, g, pool, wins[0], n_win, np.uint16, record)
-                        if with_mask:
-                            d_bytes = ctx.alloc(n_win)
-                            ctx.nonzero_u8(wins[1], n_win, d_bytes)
-                            store_write.scatter(ctx, g, pool, d_bytes, n_win, np.uint8, record, mask=True)
-                        most = max(most, (2 * len(wins) + (1 if with_mask else 0)) * n_win +
-                                   (3 if with_mask else 2) * g.pool_elems)
-                        t2 = clock()
-                    finally:
-                        source.release(wins)             # (freeing a buffer waits for the stream)
-                        if d_bytes is not None:
-                            d_bytes.free()
+    clock = store_windows.PhaseClock(("read", "scatter", "encode", "files_write"), stats is not None, ctx.sync)
+    seconds = clock.seconds
+    voxels_read, most = 0, 0
+    with store_windows.BrickSink("recode_store", out, ctx, shape, chunks) as sink, \
+            store_windows.capped_pools(arrs, budget):
+        for brick in bricks:
+            group = sink.pool([brick.origin], [brick.extent], want_mask=with_mask)
+            t0 = time.perf_counter()
+            wins, dims = source.read(brick.win_origin, brick.win_extent)
+            voxels_read += brick.window_voxels
+            n_win = int(np.prod(dims))
+            held = list(wins)                            # and the mask as bytes
+            try:
+                t1 = clock()
+                with group as pool:
+                    # the window may be taller than the brick (whole z slabs): its first brick.extent layers count
+                    record = store_write.box_records([brick.origin], brick.extent)
+                    record["stride_z"], record["stride_y"] = dims[1] * dims[2], dims[2]
+                    pool.scatter(wins[0], n_win, np.uint16, record)
+                    if with_mask:
+                        d_bytes = ctx.alloc(n_win)
+                        held.append(d_bytes)
+                        ctx.nonzero_u8(wins[1], n_win, d_bytes)
+                        pool.scatter(d_bytes, n_win, np.uint8, record, mask=True)
+                    most = max(most, (2 * len(wins) + (1 if with_mask else 0)) * n_win +
+                               (3 if with_mask else 2) * pool.g.pool_elems)
+                    t2 = clock()
+                    source.release(held)                 # before the pool is coded (freeing waits for the stream)
                     seconds["read"] += t1 - t0
                     seconds["scatter"] += t2 - t1
-                    written += store_write.encode_commit(out, ctx, g, pool, st, d_table)
-                finally:
-                    if pool is not None:
-                        pool.free()
-    finally:
-        if d_table is not None:
-            d_table.free()
-    seconds["encode"], seconds["files_write"] = st["seconds"]["encode"], st["seconds"]["files_write"]
+                    pool.commit()
+            finally:
+                source.release(held)
     if stats is not None:
-        stats.update(seconds=seconds, bricks=len(bricks), voxels_read=voxels_read, largest_alloc=most,
-                     chunks=st["chunks"], encode_calls=st["encode_calls"])
-    return 2 * shape[0] * shape[1] * shape[2] / written
+        stats.update(sink.finish(seconds), seconds=seconds, bricks=len(bricks), voxels_read=voxels_read,
+                     largest_alloc=most)
+    return 2 * shape[0] * shape[1] * shape[2] / sink.written

@@ -21,7 +21,6 @@ every provisional label is 1 + the index of a voxel of its component, and the co
 voxel of the window component of the brick that owns it: the minimum over a set is 1 + the volume index of the
 component's first voxel, ``metrics.label_components``' label without its 2^31 limit.
 """
-import os
 import time
 
 import numpy as np
@@ -30,6 +29,7 @@ from aind_exaspim_image_compression import _native
 from aind_exaspim_image_compression.utils import store_compare
 from aind_exaspim_image_compression.utils.store_foreground import _check_filter_args, _check_mask_args
 from aind_exaspim_image_compression.utils.store_measure import StoreMeasure, cut_of_threshold
+from aind_exaspim_image_compression.utils.store_windows import PhaseClock
 
 # The byte account of a brick (``plan_segment``), per voxel of its window W and of the brick B:
 #   window          2 W    the uint16 counts as read
@@ -164,15 +164,11 @@ class _Run:
 
     def __init__(self, ctx, shape, bricks, cut, connectivity, typesize, read, timed):
         self.ctx, self.shape, self.bricks, self.cut, self.connectivity = ctx, shape, bricks, cut, connectivity
-        self.typesize, self.read, self.timed = typesize, read, timed
-        self.seconds = dict.fromkeys(("read", "label", "collect", "merge", "relabel"), 0.0)
+        self.typesize, self.read = typesize, read
+        self.clock = PhaseClock(("read", "label", "collect", "merge", "relabel"), timed, ctx.sync)
+        self.seconds = self.clock.seconds
         self.most, self.voxels_read, self.repeats = 0, 0, 0
         self.records = {"halo": 0, "face": 0, "size": 0}
-
-    def clock(self):
-        if self.timed:
-            self.ctx.sync()
-        return time.perf_counter()
 
     def _label(self, brick):
         """(d_labels, d_scratch) of the brick's window; the caller frees both."""
@@ -324,8 +320,9 @@ def _check_common(who, k, threshold, measure, connectivity, min_voxels, budget_b
 
 
 def _commit(out, brick, chunk3, enc):
-    """The streams of a coded brick as the chunk files of ``out``, each through a temporary name and ``os.replace``.
-    Returns the bytes written."""
+    """The streams of a coded brick as the chunk files of ``out``, each replaced atomically.  Returns the bytes
+    written."""
+    from aind_exaspim_image_compression.utils import store_write
     first = [o // c for o, c in zip(brick.origin, chunk3)]
     grid = [-(-e // c) for e, c in zip(brick.extent, chunk3)]
     if len(enc.sizes) != grid[0] * grid[1] * grid[2]:
@@ -335,17 +332,7 @@ def _commit(out, brick, chunk3, enc):
         for iy in range(grid[1]):
             for ix in range(grid[2]):
                 blob = enc.chunk_bytes(k)
-                final = out._chunk_path((first[0] + iz, first[1] + iy, first[2] + ix))
-                os.makedirs(os.path.dirname(final), exist_ok=True)
-                tmp = os.path.join(os.path.dirname(final), ".%s.%d.tmp" % (os.path.basename(final), os.getpid()))
-                try:
-                    with open(tmp, "wb") as f:
-                        f.write(blob)
-                    os.replace(tmp, final)
-                except BaseException:
-                    if os.path.exists(tmp):
-                        os.remove(tmp)
-                    raise
+                store_write.replace_chunk_file(out._chunk_path((first[0] + iz, first[1] + iy, first[2] + ix)), blob)
                 total += len(blob)
                 k += 1
     return total
@@ -386,13 +373,7 @@ def components_store(src, dst_path, threshold=None, measure=None, k=6.0, connect
     # -- every argument check, before a context exists
     min_voxels = _check_common(who, k, threshold, measure, connectivity, min_voxels, budget_bytes)
     budget = int(budget_bytes)
-    if chunks is not None:
-        try:
-            chunks = tuple(int(c) for c in chunks)
-        except TypeError:
-            raise ValueError("chunks must be (1, 1, cz, cy, cx)") from None
-        if len(chunks) != 5 or chunks[:2] != (1, 1) or min(chunks) < 1:
-            raise ValueError("chunks must be (1, 1, cz, cy, cx)")
+    chunks = store_windows.check_chunks(chunks)
     if dtype is not None:
         _label_dtype(who, dtype, 1, relabel)
     index = int(device) if device is not None else _native.default_device()

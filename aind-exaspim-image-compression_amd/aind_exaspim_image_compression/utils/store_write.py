@@ -212,6 +212,21 @@ def scatter(ctx, g, pool, src, src_elems, src_dtype, boxes, dst_boxes=None, offs
         ctx.scatter_boxes(src, src_elems, src_dtype, boxes, pool.buf, pool.elems, np.uint16, g.dsts, lists, offset)
 
 
+def replace_chunk_file(final, blob):
+    """Replace a chunk file atomically: ``blob`` goes to a temporary name in the file's directory and then takes the
+    file's name (``os.replace``), so the file is always the old or the new stream."""
+    os.makedirs(os.path.dirname(final), exist_ok=True)
+    tmp = os.path.join(os.path.dirname(final), ".%s.%d.tmp" % (os.path.basename(final), os.getpid()))
+    try:
+        with open(tmp, "wb") as f:
+            f.write(blob)
+        os.replace(tmp, final)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+
+
 def encode_commit(arr, ctx, g, pool, stats, d_table=None):
     """Step 3: every stack coded with one ``encode_device`` call, then the chunk files replaced.  Nothing is written
     before every stack of the group has been coded.  Returns the bytes written."""
@@ -232,17 +247,7 @@ def encode_commit(arr, ctx, g, pool, stats, d_table=None):
     t1 = time.perf_counter()
     total = 0
     for idx, blob in zip(g.chunks, blobs):
-        final = os.path.join(arr.path, chunk_store.chunk_key(*idx))
-        os.makedirs(os.path.dirname(final), exist_ok=True)
-        tmp = os.path.join(os.path.dirname(final), ".%s.%d.tmp" % (os.path.basename(final), os.getpid()))
-        try:
-            with open(tmp, "wb") as f:
-                f.write(blob)
-            os.replace(tmp, final)
-        except BaseException:
-            if os.path.exists(tmp):
-                os.remove(tmp)
-            raise
+        replace_chunk_file(os.path.join(arr.path, chunk_store.chunk_key(*idx)), blob)
         total += len(blob)
     stats["seconds"]["encode"] += t1 - t0
     stats["seconds"]["files_write"] += time.perf_counter() - t1
