@@ -36,6 +36,7 @@ NOISE_BINS = 4096           # exabm4d.h EXABM4D_NOISE_BINS
 FG_MAX_RADIUS = 8           # exabm4d.h EXABM4D_FG_MAX_RADIUS: iterations of Context.foreground_box_u16
 DS_METHODS = {"mode": 0, "mean": 1, "max": 2}   # exabm4d.h EXABM4D_DS_MODE / _MEAN / _MAX: Context.downsample_box_u16
 DS_EDGES = {"crop": 0, "partial": 1}            # exabm4d.h EXABM4D_DS_CROP / _PARTIAL
+LABEL_ZEROS = {"count": 0, "ignore": 1}         # exabm4d.h EXABM4D_LABEL_ZEROS_COUNT / _IGNORE: Context.downsample_box_labels
 CC_TILE = (8, 8, 64)        # exabm4d.h EXABM4D_CC_TILE_Z / _Y / _X: the tile Context.component_seeds_u16 labels in LDS
 NOISE_WIDE_BINS = 16384     # exabm4d.h EXABM4D_NOISE_WIDE_BINS: wide bins per level of Context.measure_box_u16
 COUNT_BINS = 65536          # exabm4d.h EXABM4D_COUNT_BINS: counters of a table of the uint16 counts
@@ -278,6 +279,8 @@ SIGNATURES = {
                                          c_vp]),
     "exabm4d_nonzero_u8_dev": (_I, [_CTX, c_vp, _SZ, c_vp]),
     "exabm4d_downsample_box_u16_dev": (_I, [_CTX, c_vp, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _I, _I, c_vp]),
+    "exabm4d_downsample_box_labels_dev": (_I, [_CTX, c_vp, _I, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, _I, _I,
+                                               c_vp]),
     "exabm4d_foreground_masks_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, _F, _I, c_vp, c_vp]),
     "exabm4d_binary_dilate_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp]),
     "exabm4d_gaussian_filter3d_dev": (_I, [_CTX, c_vp, _I, _I, _I, _I, _I, c_vp, _I, c_vp]),
@@ -1145,6 +1148,20 @@ class Context:
         self._check(lib().exabm4d_downsample_box_u16_dev(
             self.handle, _ptr(win), *tri, fac, DS_METHODS.get(method, -1) if isinstance(method, str) else int(method),
             DS_EDGES.get(edge, -1) if isinstance(edge, str) else int(edge), _ptr(out_u16)))
+
+    def downsample_box_labels(self, win, dtype, vol_dims, win_origin, win_dims, box_origin, box_dims, factors,
+                              edge="crop", zeros="count", out=None):
+        """``downsample_box_u16`` for a window of uint32 / uint64 ids (``dtype``), which compare as unsigned integers
+        (DESIGN.md 5.24): every level voxel becomes the most frequent value of its window of source voxels, ties to the
+        smallest value; with ``zeros="ignore"`` the most frequent non-zero value, 0 only where every voxel present is
+        0 (``"count"``: 0 is a value like any other).  ``out``: a dense device array of ``box_dims`` of ``dtype``.
+        ValueError as there, and for another dtype or a pointer not aligned to it.  Asynchronous."""
+        tri = self._box_geometry(vol_dims, win_origin, win_dims, box_origin, box_dims)
+        fac = (ctypes.c_int32 * 3)(*(int(f) for f in factors))
+        self._check(lib().exabm4d_downsample_box_labels_dev(
+            self.handle, _ptr(win), int(np.dtype(dtype).itemsize) if np.dtype(dtype).kind == "u" else -1, *tri, fac,
+            DS_EDGES.get(edge, -1) if isinstance(edge, str) else int(edge),
+            LABEL_ZEROS.get(zeros, -1) if isinstance(zeros, str) else int(zeros), _ptr(out)))
 
     # -- patch-cache masks and coherence gate (DESIGN.md 5.8); batches of (nz, ny, nx) patches --
     def foreground_masks(self, raw, dtype, batch, shape, k, dilate, mask):

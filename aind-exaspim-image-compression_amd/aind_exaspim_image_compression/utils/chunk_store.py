@@ -36,6 +36,8 @@ from aind_exaspim_image_compression.utils.chunk_codec import EncodedVolume, Exac
 from aind_exaspim_image_compression.utils.label_codec import LabelCodec
 from aind_exaspim_image_compression.utils.store_pyramid import (  # noqa: F401  (re-exported)
     downsample_store, open_multiscale, pyramid_store)
+from aind_exaspim_image_compression.utils.store_label_pyramid import (  # noqa: F401  (re-exported)
+    downsample_label_store, downsample_label_volume, plan_label_downsample, pyramid_label_store)
 from aind_exaspim_image_compression.utils.store_recode import recode_store  # noqa: F401  (re-exported)
 
 FORMAT_NOTE = ("EXAC chunk streams (aind-exaspim-image-compression_amd, DESIGN.md 3.11b); edge chunks truncated to "

@@ -198,19 +198,19 @@ def _five(name, values):
     return v
 
 
-def _level_factors(n_levels, factors):
+def _level_factors(n_levels, factors, who="pyramid_store"):
     """``n_levels - 1`` checked triples from one triple or from one per step."""
     if isinstance(n_levels, (bool, float)) or int(n_levels) != n_levels or n_levels < 1:
-        raise ValueError("pyramid_store: n_levels must be an integer >= 1")
+        raise ValueError("%s: n_levels must be an integer >= 1" % who)
     try:
         nested = len(factors) > 0 and all(hasattr(t, "__len__") for t in factors)
     except TypeError:
         nested = False
     if not nested:
-        return [_check_factors("pyramid_store", factors)] * (int(n_levels) - 1)
+        return [_check_factors(who, factors)] * (int(n_levels) - 1)
     if len(factors) != n_levels - 1:
-        raise ValueError("pyramid_store: factors are one triple, or n_levels - 1 triples, one per step")
-    return [_check_factors("pyramid_store", t) for t in factors]
+        raise ValueError("%s: factors are one triple, or n_levels - 1 triples, one per step" % who)
+    return [_check_factors(who, t) for t in factors]
 
 
 def level_transforms(steps, voxel_size=(748, 748, 1000), scale=None, translation=None):

@@ -319,25 +319,6 @@ def _check_common(who, k, threshold, measure, connectivity, min_voxels, budget_b
     return min_voxels
 
 
-def _commit(out, brick, chunk3, enc):
-    """The streams of a coded brick as the chunk files of ``out``, each replaced atomically.  Returns the bytes
-    written."""
-    from aind_exaspim_image_compression.utils import store_write
-    first = [o // c for o, c in zip(brick.origin, chunk3)]
-    grid = [-(-e // c) for e, c in zip(brick.extent, chunk3)]
-    if len(enc.sizes) != grid[0] * grid[1] * grid[2]:
-        raise RuntimeError("components_store: encode_device returned another number of chunks than the brick holds")
-    total = k = 0
-    for iz in range(grid[0]):
-        for iy in range(grid[1]):
-            for ix in range(grid[2]):
-                blob = enc.chunk_bytes(k)
-                store_write.replace_chunk_file(out._chunk_path((first[0] + iz, first[1] + iy, first[2] + ix)), blob)
-                total += len(blob)
-                k += 1
-    return total
-
-
 def components_store(src, dst_path, threshold=None, measure=None, k=6.0, connectivity=26, min_voxels=0, relabel=False,
                      dtype=None, chunks=None, attributes=None, budget_bytes=4 << 30, device=None, stats=None):
     """The connected components of the seeds of the stored uint16 volume ``src`` as a label store, without ever holding
@@ -367,7 +348,7 @@ def components_store(src, dst_path, threshold=None, measure=None, k=6.0, connect
     read, label, collect, merge, relabel, encode, files_write; the stream is synchronised around the phases only when
     ``stats`` is given), ``bricks``, ``passes``, ``voxels_read``, ``largest_alloc``, ``records`` (halo, face, size) and
     ``collect_repeats``, the bricks whose size records took a second collection."""
-    from aind_exaspim_image_compression.utils import chunk_store, noise, store_windows
+    from aind_exaspim_image_compression.utils import chunk_store, noise, store_windows, store_write
     from aind_exaspim_image_compression.utils.label_codec import LabelCodec
     who = "components_store"
     # -- every argument check, before a context exists
@@ -419,7 +400,7 @@ def components_store(src, dst_path, threshold=None, measure=None, k=6.0, connect
             brick.extent, chunk3)))
         enc = codec.encode_device(ctx, d_out, brick.extent, chunk3)
         t1 = time.perf_counter()
-        written[0] += _commit(out, brick, chunk3, enc)
+        written[0] += store_write.commit_coded_brick(who, out, brick, chunk3, enc)
         seconds["encode"] += t1 - t0
         seconds["files_write"] += time.perf_counter() - t1
 

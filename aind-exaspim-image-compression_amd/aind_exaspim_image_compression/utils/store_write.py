@@ -227,6 +227,25 @@ def replace_chunk_file(final, blob):
         raise
 
 
+def commit_coded_brick(who, out, brick, chunk3, enc):
+    """The streams of a coded brick (``enc``: an ``EncodedVolume`` of ``brick.extent`` in chunks of ``chunk3``, the
+    brick a box of whole chunks of ``out``) as the chunk files of ``out``, each replaced atomically.  Returns the bytes
+    written."""
+    first = [o // c for o, c in zip(brick.origin, chunk3)]
+    grid = [-(-e // c) for e, c in zip(brick.extent, chunk3)]
+    if len(enc.sizes) != grid[0] * grid[1] * grid[2]:
+        raise RuntimeError("%s: encode_device returned another number of chunks than the brick holds" % who)
+    total = k = 0
+    for iz in range(grid[0]):
+        for iy in range(grid[1]):
+            for ix in range(grid[2]):
+                blob = enc.chunk_bytes(k)
+                replace_chunk_file(out._chunk_path((first[0] + iz, first[1] + iy, first[2] + ix)), blob)
+                total += len(blob)
+                k += 1
+    return total
+
+
 def encode_commit(arr, ctx, g, pool, stats, d_table=None):
     """Step 3: every stack coded with one ``encode_device`` call, then the chunk files replaced.  Nothing is written
     before every stack of the group has been coded.  Returns the bytes written."""

@@ -21,35 +21,12 @@
 // pieces that lie whole inside the box.  Everything else goes element by element.
 #include <algorithm>
 
+#include "ds_sort.h"
 #include "exabm4d_kernels.h"
 
 namespace exabm4d {
 
 constexpr int DS_T = 256;
-
-template <int N>
-__device__ __forceinline__ void ds_sort(uint32_t (&v)[N]) {
-#define DS_CE(a, b)                                  \
-    {                                                \
-        const uint32_t lo = min(v[a], v[b]);         \
-        v[b] = max(v[a], v[b]);                      \
-        v[a] = lo;                                   \
-    }
-    if constexpr (N == 8) {                          // 19 compare-exchanges, 6 layers
-        DS_CE(0, 2) DS_CE(1, 3) DS_CE(4, 6) DS_CE(5, 7)
-        DS_CE(0, 4) DS_CE(1, 5) DS_CE(2, 6) DS_CE(3, 7)
-        DS_CE(0, 1) DS_CE(2, 3) DS_CE(4, 5) DS_CE(6, 7)
-        DS_CE(2, 4) DS_CE(3, 5)
-        DS_CE(1, 4) DS_CE(3, 6)
-        DS_CE(1, 2) DS_CE(3, 4) DS_CE(5, 6)
-    } else {
-        static_assert(N == 4, "windows of 4 or 8 values");
-        DS_CE(0, 1) DS_CE(2, 3)
-        DS_CE(0, 2) DS_CE(1, 3)
-        DS_CE(1, 2)
-    }
-#undef DS_CE
-}
 
 // the reduction of N = 4 or 8 values (repeats included)
 template <int METHOD, int N>
@@ -66,7 +43,7 @@ __device__ __forceinline__ uint32_t ds_reduce(uint32_t (&v)[N]) {
         for (int i = 0; i < N; i++) s += v[i];
         return (s + ((1u << (SH - 1)) - 1u) + ((s >> SH) & 1u)) >> SH;        // sum / N, half to even
     } else {
-        ds_sort<N>(v);
+        ds_sort(v);
         uint32_t best = v[0], best_len = 1, run = 1;
 #pragma unroll
         for (int i = 1; i < N; i++) {

@@ -211,6 +211,13 @@ void downsample_box_plan(const uint16_t* win, const BoxGeom& g, const int* facto
 // out: a dense array of g.bd
 hipError_t launch_downsample_box_u16(const uint16_t* win, const BoxGeom& g, const DsPlan& p, int method, uint16_t* out,
                                      hipStream_t s);
+// ---- one pyramid level of a box of labels (label_downsample_kernels.hip) ----
+constexpr int LABEL_ZEROS_COUNT = 0, LABEL_ZEROS_IGNORE = 1;    // exabm4d.h EXABM4D_LABEL_ZEROS_COUNT / _IGNORE
+// The same BoxGeom and DsPlan for elements of `typesize` 4 or 8 bytes; a piece is 16 bytes of a source row.
+void label_downsample_box_plan(const void* win, int typesize, const BoxGeom& g, const int* factors, const void* out,
+                               DsPlan& p);
+hipError_t launch_downsample_box_labels(const void* win, int typesize, const BoxGeom& g, const DsPlan& p, int zeros,
+                                        void* out, hipStream_t s);
 // Options of block matching (per context since round 4; exabm4d_set_option "bm_xcd_mode" / "bm_carry" / "bm_carry_fault")
 struct BmOpts {
     int xcd_mode = 2;       // workgroup order: 0 = contiguous per XCD, 1 = all XCDs in one z slab of tiles (raster), n >= 2 = in strips of n tile rows

@@ -1075,6 +1075,26 @@ int exabm4d_downsample_box_u16_dev(exabm4d_ctx* ctx, const uint16_t* win, const 
                                    const int32_t* box_origin_zyx, const int32_t* box_dims_zyx,
                                    const int32_t* factors_zyx, int method, int edge, uint16_t* out_u16);
 
+/* ---- one pyramid level of a box of labels ------------------------------------------------
+ * exabm4d_downsample_box_u16_dev's contract for a window of uint32 (typesize 4) or uint64 (typesize 8) ids, which
+ * compare as UNSIGNED integers; out is a dense array of box_dims of the same type.  The reduction is a mode:
+ *     EXABM4D_LABEL_ZEROS_COUNT    the most frequent value of the voxels present, of values equally frequent the
+ *                                  smallest: 0 is a value like any other (EXABM4D_DS_MODE on wider values)
+ *     EXABM4D_LABEL_ZEROS_IGNORE   the most frequent NON-ZERO value, of equally frequent ones the smallest; 0 only
+ *                                  where every voxel present is 0
+ * Checked on the host as there (EXABM4D_ERR_INVALID, nothing written), and: typesize 4 or 8, zeros, win and out
+ * aligned to typesize.  A lane takes 16 bytes of a row (4 or 2 source voxels): 16-byte loads where win_dims[2] is a
+ * multiple of 16 / typesize and the box's first source voxel lies at a multiple of the x factor in the window's
+ * allocation (counted in elements, modulo 16 / typesize); stores of 16 / fx bytes where box_dims[2] is a multiple of
+ * 16 / (typesize fx) and out is at the phase the loads fixed; element loads and stores otherwise.
+ * Asynchronous on the context's stream. */
+#define EXABM4D_LABEL_ZEROS_COUNT 0
+#define EXABM4D_LABEL_ZEROS_IGNORE 1
+int exabm4d_downsample_box_labels_dev(exabm4d_ctx* ctx, const void* win, int typesize, const int32_t* vol_dims_zyx,
+                                      const int32_t* win_origin_zyx, const int32_t* win_dims_zyx,
+                                      const int32_t* box_origin_zyx, const int32_t* box_dims_zyx,
+                                      const int32_t* factors_zyx, int edge, int zeros, void* out);
+
 /* ---- patch-cache foreground masks and coherence gate --
  * Batches of `batch` patches of nz x ny x nx voxels, contiguous in HBM.  Every entry point
  * synchronises the context's stream; floating-point results are deterministic (fixed mappings and
