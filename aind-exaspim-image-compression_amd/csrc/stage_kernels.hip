@@ -9,7 +9,8 @@
 //     workgroups or launches add: the GPU equals the oracle bit for bit and itself run for run.
 //   * Two waves process one group (half groups, below).  A half group's spectrum lives in registers;
 //     each block goes through gather -> DCT(y) -> LDS transpose -> DCT(x) -> LDS transpose -> DCT(z);
-//     the Haar transform along the group and the shrinkage then run in registers.
+//     the Haar transform along the group and the shrinkage then run in registers, on the register pairs
+//     the DCT leaves (two blocks of one coefficient plane): no repacking in between.
 //   * Lane layouts of one 8^3 block (8 values per lane):
 //       L1: lane = (z,x), regs = y    gather / scatter (LDS adds conflict-free: bank = 8z + x)
 //       L2: lane = (z,y), regs = x
@@ -30,7 +31,6 @@
 
 namespace exabm4d {
 
-typedef float f16v __attribute__((ext_vector_type(16)));
 
 #ifdef EXABM4D_STAMPS
 // Diagnostic build only: per-phase cycle sums (s_memtime) accumulated over all waves.
@@ -53,34 +53,75 @@ __device__ __forceinline__ void gather8v(__amdgpu_buffer_rsrc_t rsrc, int corner
         v[y] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)voff[y], corner, 0));
 }
 
-// Packed Haar along the group axis: v[k] holds two independent sequences in .x / .y.
-template <int K>
-__device__ __forceinline__ void haar_fwd2(f2 (&v)[MAXG]) {
+// Haar along the group axis on the DCT's register pairs: pair_fwd / pair_inv keep blocks
+// (kl, kl + 1) of one coefficient plane in a 64-bit register pair -- exactly the two values a Haar butterfly
+// combines.  One v_pk_add_f32 whose operand-half selectors pick component SA of `a` and component SB of `b`
+// for BOTH result lanes, the second operand negated in the upper lane, yields (a[SA] + b[SB], a[SA] - b[SB]):
+// the IEEE add and subtract (x0 + (-x1)) of DESIGN.md 3.5 on the same operands, and no register move to
+// bring the operands into a common pair first.  (hipcc does not fold a shufflevector into op_sel.)
+template <int SA, int SB>
+__device__ __forceinline__ f2 bfly(f2 a, f2 b) {
+    f2 r;
+    if constexpr (SA == 0 && SB == 0)
+        asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+    else if constexpr (SA == 0 && SB == 1)
+        asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+    else if constexpr (SA == 1 && SB == 0)
+        asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+    else
+        asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// (selectors known once the surrounding loop is unrolled)
+__device__ __forceinline__ f2 bfly_sel(int sa, int sb, f2 a, f2 b) {
+    return sa ? (sb ? bfly<1, 1>(a, b) : bfly<1, 0>(a, b)) : (sb ? bfly<0, 1>(a, b) : bfly<0, 0>(a, b));
+}
+// First level, blocks (2m, 2m + 1) of a plane in one pair: (x0, x1) -> ((x0 + x1) c, (x0 - x1) c).
+__device__ __forceinline__ f2 haar_l1(f2 v) { return bfly<0, 1>(v, v) * HAAR_C; }
+// Register pairs of one coefficient plane of a half group of KH blocks.
+constexpr int haar_pairs(int KH) { return KH > 1 ? KH / 2 : 1; }
+// Levels above the first, in place.  In: q[m] = (a_m, d_m), approximation and detail of blocks (2m, 2m + 1).
+// Out, in the oracle's order (0,1), (2,3), then the sums: q[0] = (approximation, top detail) and whole pairs
+// of details -- KH = 4: q[1] = (d_0, d_1); KH = 8: q[2] = second-level details, q[1] = (d_0, d_1),
+// q[3] = (d_2, d_3).  `det` sees every detail as it moves to its final slot (the hard threshold selects
+// there, so that the move is the select), except the top one, which stays where the butterfly put it.
+template <int KH, class F>
+__device__ __forceinline__ void haar_fwd_upper(f2 (&q)[haar_pairs(KH)], F&& det) {
+    if constexpr (KH >= 4) {
 #pragma unroll
-    for (int len = K; len > 1; len >>= 1) {
-        const int half = len >> 1;
-        f2 t[MAXG];
-#pragma unroll
-        for (int i = 0; i < half; i++) {
-            t[i] = (v[2 * i] + v[2 * i + 1]) * HAAR_C;
-            t[half + i] = (v[2 * i] - v[2 * i + 1]) * HAAR_C;
+        for (int i = 0; i < KH / 4; i++) {
+            const f2 r = bfly<0, 0>(q[2 * i], q[2 * i + 1]) * HAAR_C;
+            const float d0 = det(q[2 * i].y), d1 = det(q[2 * i + 1].y);
+            q[2 * i + 1] = mk2(d0, d1);
+            q[2 * i] = r;
         }
-#pragma unroll
-        for (int i = 0; i < len; i++) v[i] = t[i];
+    }
+    if constexpr (KH == 8) {
+        const f2 r = bfly<0, 0>(q[0], q[2]) * HAAR_C;
+        const float d0 = det(q[0].y), d1 = det(q[2].y);
+        q[2] = mk2(d0, d1);
+        q[0] = r;
     }
 }
-template <int K>
-__device__ __forceinline__ void haar_inv2(f2 (&v)[MAXG]) {
-#pragma unroll
-    for (int len = 1; len < K; len <<= 1) {
-        f2 t[MAXG];
-#pragma unroll
-        for (int i = 0; i < len; i++) {
-            t[2 * i] = (v[i] + v[len + i]) * HAAR_C;
-            t[2 * i + 1] = (v[i] - v[len + i]) * HAAR_C;
-        }
-#pragma unroll
-        for (int i = 0; i < 2 * len; i++) v[i] = t[i];
+// Inverse levels below the top one: `a` = the two approximations the top inverse butterfly produced (KH = 2:
+// the two blocks themselves).  Every butterfly takes its approximation and its detail from where they lie
+// and writes blocks (2m, 2m + 1) as a pair: out q[m] in the layout pair_inv wants.
+template <int KH>
+__device__ __forceinline__ void haar_inv_lower(f2 (&q)[haar_pairs(KH)], f2 a) {
+    if constexpr (KH == 2) {
+        q[0] = a;
+    } else if constexpr (KH == 4) {
+        const f2 p0 = bfly<0, 0>(a, q[1]) * HAAR_C, p1 = bfly<1, 1>(a, q[1]) * HAAR_C;
+        q[0] = p0;
+        q[1] = p1;
+    } else {
+        const f2 v0 = bfly<0, 0>(a, q[2]) * HAAR_C, v1 = bfly<1, 1>(a, q[2]) * HAAR_C;
+        const f2 p0 = bfly<0, 0>(v0, q[1]) * HAAR_C, p1 = bfly<1, 1>(v0, q[1]) * HAAR_C;
+        const f2 p2 = bfly<0, 0>(v1, q[3]) * HAAR_C, p3 = bfly<1, 1>(v1, q[3]) * HAAR_C;
+        q[0] = p0;
+        q[1] = p1;
+        q[2] = p2;
+        q[3] = p3;
     }
 }
 
@@ -192,12 +233,10 @@ __device__ __forceinline__ long long magic_bits(double m) {
 // multiply-adds (v_pk_fma_f32) -- IEEE operations only, so the oracle produces the same bits (v_rcp_f32 is a
 // table the CPU does not have), and about what two quarter-rate v_rcp_f32 cost.  Measured at 1024^3, Wiener
 // stage, A/B on one box each: v_rcp_f32 233.1 ms, two Newton steps 232.1, three 239.6; with the chains of two
-// coefficient pairs interleaved (EXABM4D_WIE_ILV) 239.6 -> 235.4.  A five-operation form -- one cubic step
+// coefficient pairs interleaved 239.6 -> 235.4.  (That limit, a scheduling barrier every two chains, went with the
+// pair layout of the spectrum: there hipcc spills 24 registers with it and 4 without.)  A five-operation form -- one cubic step
 // r (1 + t + t^2) and one Newton step, 0.8 ulp -- was built into specification, oracle and kernel and measured
 // SLOWER than the six operations of three Newton steps (235.9 against 233.8, A/B/A/B): reverted.
-#ifndef EXABM4D_WIE_ILV
-#define EXABM4D_WIE_ILV 2                      // Newton chains interleaved per scheduling region (0: no limit)
-#endif
 __device__ __forceinline__ f2 rcp_nr2(f2 d) {
     f2 r = mk2(__uint_as_float(0x7EF311C7u - __float_as_uint(d.x)), __uint_as_float(0x7EF311C7u - __float_as_uint(d.y)));
 #pragma unroll
@@ -231,54 +270,26 @@ __device__ __forceinline__ void raise_flag(int* flag, int value, int lane) {
     cbar();
 }
 
-// Local part of the hard-threshold shrinkage on a half group of KH blocks: forward Haar over the
-// half, threshold and count the detail coefficients, hand back the approximation pairs.
-// Spectrum layout as in shrink_ht with the local block index: S[jp][2 kl + c] = coefficient plane
-// 2 jp + c of local block kl, so that two planes run through the Haar transform as one packed
-// stream.  (Whole-vector loads and stores only: element-wise stores into S at constant offsets
-// get merged with neighbouring accesses into wider ones, after which the array can no longer be
-// split into registers and ends up in scratch.)
-template <int KH>
-__device__ __forceinline__ void half_shrink_local(f16v (&S)[4], float thr, int& nnz, f2 (&approx)[4]) {
-#pragma unroll
-    for (int jp = 0; jp < 4; jp++) {
-        f16v A = S[jp];
-        f2 x[MAXG];
-#pragma unroll
-        for (int k = 0; k < KH; k++) x[k] = mk2(A[2 * k], A[2 * k + 1]);
-        haar_fwd2<KH>(x);
-        approx[jp] = x[0];
-#pragma unroll
-        for (int k = 1; k < KH; k++) {
-            const bool k0 = fabsf(x[k].x) >= thr, k1 = fabsf(x[k].y) >= thr;
-            nnz += (k0 ? 1 : 0) + (k1 ? 1 : 0);
-            float f0 = k0 ? x[k].x : 0.0f, f1 = k1 ? x[k].y : 0.0f;
-            // select now: left to itself hipcc keeps the 64-bit compare masks of a whole half group
-            // alive in scalar registers until the inverse transforms and spills 64 of them per group
-            asm volatile("" : "+v"(f0), "+v"(f1));
-            A[2 * k] = f0;
-            A[2 * k + 1] = f1;
-        }
-        S[jp] = A;
-    }
+// Hard threshold of one coefficient, counted.
+__device__ __forceinline__ float ht_keep(float v, float thr, int& nnz) {
+    const bool k = fabsf(v) >= thr;
+    nnz += k ? 1 : 0;
+    float f = k ? v : 0.0f;
+    // select now: left to itself hipcc keeps the 64-bit compare masks of a whole half group
+    // alive in scalar registers until the inverse transforms and spills 64 of them per group
+    asm volatile("" : "+v"(f));
+    return f;
 }
-// Inverse Haar over the half once the filtered approximation coefficients are known.
+// Local part of the hard-threshold shrinkage on a half group of KH blocks: the Haar levels above the
+// first (the first ran as the spectrum left the DCT), threshold and count the detail coefficients.
+// Spectrum layout: X[j][m] = register pair of coefficient plane j (haar_fwd_upper); the approximation
+// of plane j is left in X[j][0].x.
 template <int KH>
-__device__ __forceinline__ void half_unshrink_local(f16v (&S)[4], const f2 (&approx)[4]) {
+__device__ __forceinline__ void half_shrink_local(f2 (&X)[8][haar_pairs(KH)], float thr, int& nnz) {
 #pragma unroll
-    for (int jp = 0; jp < 4; jp++) {
-        f16v A = S[jp];
-        f2 x[MAXG];
-        x[0] = approx[jp];
-#pragma unroll
-        for (int k = 1; k < KH; k++) x[k] = mk2(A[2 * k], A[2 * k + 1]);
-        haar_inv2<KH>(x);
-#pragma unroll
-        for (int k = 0; k < KH; k++) {
-            A[2 * k] = x[k].x;
-            A[2 * k + 1] = x[k].y;
-        }
-        S[jp] = A;
+    for (int j = 0; j < 8; j++) {
+        haar_fwd_upper<KH>(X[j], [&](float v) { return ht_keep(v, thr, nnz); });
+        if constexpr (KH > 1) X[j][0].y = ht_keep(X[j][0].y, thr, nnz);
     }
 }
 
@@ -377,52 +388,47 @@ __device__ __forceinline__ bool flush_take(int* lock, ring_t* ring, long long* _
     return true;
 }
 
-// Wiener counterparts.  The noisy and the basic-estimate groups keep separate spectra, both in the
-// hard-threshold layout (S[jp][2 kl + c] = coefficient plane 2 jp + c of local block kl), so that
-// (i) blocks (kl, kl + 1) of one volume are the two packed streams of a transform, exactly as in
-// the hard-threshold kernel, (ii) the basic spectrum is dead once the weights are known -- a wave
-// holds 128 spectrum registers only between the forward transforms and the local shrinkage, 64
-// afterwards -- and (iii) the inverse half is the hard-threshold code.  (The first version
-// interleaved noisy and basic in one 128-register array that stayed live to the end and spilled
+// Wiener counterparts.  The noisy and the basic-estimate groups keep separate spectra, X and Y, both in the
+// hard-threshold layout (X[j][m] = register pair of coefficient plane j), so that (i) the basic spectrum is
+// dead once the weights are known -- a wave holds 128 spectrum registers only between the forward transforms
+// and the local shrinkage, 64 afterwards -- and (ii) the inverse half is the hard-threshold code.  (The first
+// version interleaved noisy and basic in one 128-register array that stayed live to the end and spilled
 // 54 registers per lane: 280 GB of scratch traffic per 1024^3 launch.)
-// Local part: Haar over the half of both spectra, Wiener-filter the detail coefficients
-// (W = e R(e + sigma^2) from the basic estimate), hand back the approximation pairs.  The
-// filtered details stay in S; `sw` collects the lane's share of sum W^2 as biased integers (wiener_w2).
+// Local part: the upper Haar levels of both spectra, Wiener-filter the detail coefficients
+// (W = e R(e + sigma^2) from the basic estimate).  Both spectra have the same layout, so a
+// pair of weights meets the pair of noisy coefficients in the same slots; the top details, alone in their
+// pairs, go two planes at a time.  The filtered details stay in X, the approximations in X[j][0].x and
+// Y[j][0].x; `sw` collects the lane's share of sum W^2 as biased integers (wiener_w2), 4 (KH - 1) calls.
 template <int KH>
-__device__ __forceinline__ void wiener_half_local(f16v (&S)[4], const f16v (&SB)[4], float sigma2,
-                                                  unsigned& sw, f2 (&approx)[8]) {
+__device__ __forceinline__ void wiener_half_local(f2 (&X)[8][haar_pairs(KH)], f2 (&Y)[8][haar_pairs(KH)],
+                                                  float sigma2, unsigned& sw) {
+    auto same = [](float v) { return v; };
 #pragma unroll
-    for (int jp = 0; jp < 4; jp++) {
-        f16v A = S[jp];
-        const f16v B = SB[jp];
-        f2 x[MAXG], y[MAXG];
+    for (int j = 0; j < 8; j++) {
+        haar_fwd_upper<KH>(X[j], same);
+        haar_fwd_upper<KH>(Y[j], same);
 #pragma unroll
-        for (int k = 0; k < KH; k++) {
-            x[k] = mk2(A[2 * k], A[2 * k + 1]);
-            y[k] = mk2(B[2 * k], B[2 * k + 1]);
+        for (int m = 1; m < haar_pairs(KH); m++) {
+            const f2 W = wiener_w2(Y[j][m] * Y[j][m], sigma2, sw);
+            X[j][m] = W * X[j][m];
         }
-        haar_fwd2<KH>(x);
-        haar_fwd2<KH>(y);
-        approx[jp] = x[0];
-        approx[4 + jp] = y[0];
-#pragma unroll
-        for (int k = 1; k < KH; k++) {
-            const f2 W = wiener_w2(y[k] * y[k], sigma2, sw);
-            const f2 f = W * x[k];
-            A[2 * k] = f.x;
-            A[2 * k + 1] = f.y;
-            // EXABM4D_WIE_ILV coefficient pairs at a time: interleaving the Newton chains of ALL k for latency
-            // costs the registers the two spectra leave (30 spilled), one at a time exposes the chain
-            if (EXABM4D_WIE_ILV && (k % EXABM4D_WIE_ILV) == 0) __builtin_amdgcn_sched_barrier(0);
+        if constexpr (KH > 1) {
+            if (j & 1) {
+                const f2 W = wiener_w2(mk2(Y[j - 1][0].y * Y[j - 1][0].y, Y[j][0].y * Y[j][0].y), sigma2, sw);
+                X[j - 1][0].y = W.x * X[j - 1][0].y;
+                X[j][0].y = W.y * X[j][0].y;
+            }
         }
-        S[jp] = A;
     }
 }
 
 // One wave, one half of a group.  `sync` = int[2 * HNW]: ready[w], ack[w]; `seq` = exchanges this
 // pair has done so far (both waves of a pair count alike).  Returns true for the wave that
 // completes the layer.
-template <bool WIENER, typename TableT>
+// SEPVOL (Wiener only): the noisy and the basic volume are gathered separately, there is no interleaved
+// volume.  A kernel of its own (stage_half_sep_kernel), not a branch: with both gathers in one kernel the
+// forward transforms spill 30 registers per lane.
+template <bool WIENER, bool SEPVOL, typename TableT>
 __device__ __forceinline__ bool process_half_group(
     const float* __restrict__ noisy, const float* __restrict__ basic, const uint32_t* __restrict__ kk,
     int rz, int ry, int rx, const TileGeom& tg, size_t sy, size_t sz, const TableT& T,
@@ -440,6 +446,7 @@ __device__ __forceinline__ bool process_half_group(
     constexpr bool HELP_FLUSH = !WIENER;       // (the Wiener kernel has no registers for it
                                                //  and waits 1.5 % of its time at the gate)
     constexpr int NP = WIENER ? 8 : 4;         // f2 values per lane swapped with the partner
+    constexpr bool PAIRVOL = WIENER && !SEPVOL;
     const int hi = lane >> 3, lo = lane & 7;
     const int xl = tr_x<WIENER>(hi, lo);               // the block column this lane holds after the inverse transforms (dct_pairs.h)
     STAMP(t0);
@@ -459,14 +466,11 @@ __device__ __forceinline__ bool process_half_group(
     // v_mov / s_set_gpr_idx_off: three instructions per moved float, a fifth of the kernel.)
     auto body = [&](auto KHc) {
         constexpr int KH = decltype(KHc)::value;
-        f16v S[4];                             // (noisy) spectrum of my blocks
-        f16v SB[WIENER ? 4 : 1];               // Wiener: basic-estimate spectrum, dead after the local step
-#pragma unroll
-        for (int j = 0; j < 4; j++) S[j] = (f16v)(0.0f);
-        if constexpr (WIENER) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) SB[j] = (f16v)(0.0f);
-        }
+        // (noisy) spectrum of my blocks, in the DCT's register pairs: X[j][m] = blocks (2m, 2m + 1) of
+        // coefficient plane j, which the first Haar level turns into (approximation, detail) on the spot
+        constexpr int HP = haar_pairs(KH);
+        f2 X[8][HP];
+        f2 Y[WIENER ? 8 : 1][HP];              // Wiener: basic-estimate spectrum, dead after the top level
 
         int my_dz, my_dy, my_dx;
         code_to_disp(mykey & KEY_CMASK, my_dz, my_dy, my_dx);
@@ -488,7 +492,7 @@ __device__ __forceinline__ bool process_half_group(
         auto corner_of = [&](int k) -> int { return __builtin_amdgcn_readlane(my_rel, k); };
         // Wiener with the interleaved volume: 8-byte elements, the same window
         const __amdgpu_buffer_rsrc_t pair_r = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<f2*>((WIENER && pair ? pair : reinterpret_cast<const f2*>(noisy)) + (WIENER && pair ? win_off : 0)), 0,
+            const_cast<f2*>((PAIRVOL ? pair : reinterpret_cast<const f2*>(noisy)) + (PAIRVOL ? win_off : 0)), 0,
             (int)min(win_left * sizeof(f2), (size_t)0x7FFFFFFFu * 2u), 0x00020000);
         // Forward transforms of my blocks, two streams per transform: blocks (kl, kl + 1) of one
         // volume (a half of one block pairs the noisy block with the basic one in the Wiener
@@ -523,10 +527,8 @@ __device__ __forceinline__ bool process_half_group(
                 pair_fwd_x2<WIENER>(T, tb, hi, lo, v2, w2);
 #pragma unroll
                 for (int j = 0; j < 8; j++) {
-                    S[j >> 1][2 * kl + (j & 1)] = v2[j].x;
-                    S[j >> 1][2 * kl + 2 + (j & 1)] = v2[j].y;
-                    S[j >> 1][2 * kl + 4 + (j & 1)] = w2[j].x;
-                    S[j >> 1][2 * kl + 6 + (j & 1)] = w2[j].y;
+                    X[j][kl / 2] = haar_l1(v2[j]);
+                    X[j][kl / 2 + 1] = haar_l1(w2[j]);
                 }
             }
         } else if constexpr (!WIENER) {
@@ -542,15 +544,11 @@ __device__ __forceinline__ bool process_half_group(
                 }
                 pair_fwd<WIENER>(T, tb, hi, lo, v2);
 #pragma unroll
-                for (int j = 0; j < 8; j++) S[j >> 1][2 * kl + (j & 1)] = v2[j].x;
-                if constexpr (KH > 1) {
-#pragma unroll
-                    for (int j = 0; j < 8; j++) S[j >> 1][2 * kl + 2 + (j & 1)] = v2[j].y;
-                }
+                for (int j = 0; j < 8; j++) X[j][kl / 2] = KH > 1 ? haar_l1(v2[j]) : v2[j];
             }
         } else if constexpr (KH == 1) {
             const size_t c0 = corner_of(kb);
-            if (pair) {
+            if constexpr (PAIRVOL) {
                 gather8v2(pair_r, 2 * (int)c0, voff, a, b);
             } else {
                 gather8v(noisy_r, c0, voff, a);
@@ -561,52 +559,49 @@ __device__ __forceinline__ bool process_half_group(
             pair_fwd<WIENER>(T, tb, hi, lo, v2);
 #pragma unroll
             for (int j = 0; j < 8; j++) {
-                S[j >> 1][j & 1] = v2[j].x;
-                SB[j >> 1][j & 1] = v2[j].y;
+                X[j][0] = v2[j];
+                Y[j][0] = mk2(v2[j].y, v2[j].y);
             }
-        } else if (pair) {
-            // interleaved volume: block k's noisy and basic values arrive together and are the two
-            // packed streams of its transform (same arithmetic per stream as the other pairing)
-            gather8v2(pair_r, 2 * corner_of(kb), voff, a, b);
+        } else {
+            // A pair is (noisy, basic) of ONE block -- with the interleaved volume they arrive together,
+            // without it from two gathers -- so the first Haar level takes its two blocks from two pairs:
+            // component 0 of both for the noisy spectrum, component 1 for the basic one.
+            f2 ab[8];
+            auto gather_nb = [&](int k) {
+                if constexpr (PAIRVOL) {
+                    const int c2 = 2 * corner_of(k);
+#pragma unroll
+                    for (int y = 0; y < 8; y++) {
+                        const u2v t = __builtin_amdgcn_raw_buffer_load_b64(pair_r, (int)(2u * voff[y]), c2, 0);
+                        ab[y] = mk2(__uint_as_float(t.x), __uint_as_float(t.y));
+                    }
+                } else {
+                    const int c = corner_of(k);
+#pragma unroll
+                    for (int y = 0; y < 8; y++)
+                        ab[y] = mk2(__int_as_float(__builtin_amdgcn_raw_buffer_load_b32(noisy_r, (int)voff[y], c, 0)),
+                                    __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(basic_r, (int)voff[y], c, 0)));
+                }
+            };
+            gather_nb(kb);
+            f2 z0[8];
 #pragma unroll
             for (int kl = 0; kl < KH; kl++) {
 #pragma unroll
-                for (int j = 0; j < 8; j++) v2[j] = mk2(a[j], b[j]);
-                if (kl + 1 < KH) gather8v2(pair_r, 2 * corner_of(kb + kl + 1), voff, a, b);
+                for (int j = 0; j < 8; j++) v2[j] = ab[j];
+                if (kl + 1 < KH) gather_nb(kb + kl + 1);
                 pair_fwd<WIENER>(T, tb, hi, lo, v2);
+                if ((kl & 1) == 0) {
 #pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    S[j >> 1][2 * kl + (j & 1)] = v2[j].x;
-                    SB[j >> 1][2 * kl + (j & 1)] = v2[j].y;
+                    for (int j = 0; j < 8; j++) z0[j] = v2[j];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 8; j++) {
+                        X[j][kl / 2] = bfly<0, 0>(z0[j], v2[j]) * HAAR_C;
+                        Y[j][kl / 2] = bfly<1, 1>(z0[j], v2[j]) * HAAR_C;
+                    }
                 }
-            }
-        } else {
-            gather8v(noisy_r, corner_of(kb), voff, a);
-            gather8v(noisy_r, corner_of(kb + 1), voff, b);
-#pragma unroll
-            for (int kl = 0; kl < KH; kl += 2) {
-#pragma unroll
-                for (int j = 0; j < 8; j++) v2[j] = mk2(a[j], b[j]);
-                gather8v(basic_r, corner_of(kb + kl), voff, a);
-                gather8v(basic_r, corner_of(kb + kl + 1), voff, b);
-                pair_fwd<WIENER>(T, tb, hi, lo, v2);
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    S[j >> 1][2 * kl + (j & 1)] = v2[j].x;
-                    S[j >> 1][2 * kl + 2 + (j & 1)] = v2[j].y;
-                }
-#pragma unroll
-                for (int j = 0; j < 8; j++) v2[j] = mk2(a[j], b[j]);
-                if (kl + 2 < KH) {
-                    gather8v(noisy_r, corner_of(kb + kl + 2), voff, a);
-                    gather8v(noisy_r, corner_of(kb + kl + 3), voff, b);
-                }
-                pair_fwd<WIENER>(T, tb, hi, lo, v2);
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    SB[j >> 1][2 * kl + (j & 1)] = v2[j].x;
-                    SB[j >> 1][2 * kl + 2 + (j & 1)] = v2[j].y;
-                }
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
 
@@ -617,27 +612,43 @@ __device__ __forceinline__ bool process_half_group(
         // coefficients (hard threshold, as int bits) or the sum of squared Wiener weights.
         int nnz = 0;
         unsigned sw = 0;               // Wiener: sum of bits(fl(1 + W^2)), see wiener_w2
-        f2 approx[NP];                 // Wiener: [0, 4) noisy plane pairs, [4, 8) basic plane pairs
         if constexpr (WIENER)
-            wiener_half_local<KH>(S, SB, sigma2, sw, approx);
+            wiener_half_local<KH>(X, Y, sigma2, sw);
         else
-            half_shrink_local<KH>(S, thr, nnz, approx);
-        f2 top[4];                     // filtered approximation pairs of my half, per plane pair
-        if (K > 1) {
+            half_shrink_local<KH>(X, thr, nnz);
+        // Top level: the filtered approximation of my half goes back into X[j][0].x, where the approximation
+        // of plane j came from.  Half h needs (t0 + t1) c or (t0 - t1) c: t0 + (+-t1) with the sign bit of t1
+        // flipped for the second half -- the same IEEE add or subtract, and neither a branch nor a select.
+        const unsigned smask = half ? 0x80000000u : 0u;
+        if (KH > 1 || K > 1) {
             seq++;
             // my transpose buffer is free (forward transforms done; the partner acknowledged the
             // previous exchange before my last inverse transforms started)
+            // (the approximations go out one by one from where they lie: as pairs they would be put together
+            // by register moves, early, and wait for this store in scratch)
+            float* const tbf = reinterpret_cast<float*>(tb);
 #pragma unroll
-            for (int jp = 0; jp < NP; jp++) tb[jp * 64 + lane] = approx[jp];
+            for (int j = 0; j < 8; j++) {
+                tbf[(j >> 1) * 128 + 2 * lane + (j & 1)] = X[j][0].x;
+                if constexpr (WIENER) tbf[(4 + (j >> 1)) * 128 + 2 * lane + (j & 1)] = Y[j][0].x;
+            }
             tb[NP * 64 + lane] = mk2(__int_as_float(WIENER ? (int)sw : nnz), 0.0f);
             raise_flag(sync + wave, seq, lane);
             STAMP(te0);
             wait_flag(sync + partner, seq, lane);
             STAMP(te1);
             STAMP_ADD(2, te0, te1);
-            f2 other[NP];
+            // Both waves form (first half's approximation) +- (second half's) with the operands in that
+            // order, and both take them from the buffers -- a wave reads its own values back -- so that which
+            // buffer is whose is a scalar pointer select, not a select (or a branch) per coefficient.
+            const f2* const tb_lo = half ? partner_tb : tb;
+            const f2* const tb_hi = half ? tb : partner_tb;
+            f2 first[NP], second[NP];  // plane pair jp: approximations of planes (2 jp, 2 jp + 1); Wiener: + 4 basic
 #pragma unroll
-            for (int jp = 0; jp < NP; jp++) other[jp] = partner_tb[jp * 64 + lane];
+            for (int jp = 0; jp < NP; jp++) {
+                first[jp] = tb_lo[jp * 64 + lane];
+                second[jp] = tb_hi[jp * 64 + lane];
+            }
             const float theirs = partner_tb[NP * 64 + lane].x;
             cbar();
             raise_flag(sync + HNW + wave, seq, lane);          // partner may reuse its buffer
@@ -647,40 +658,47 @@ __device__ __forceinline__ bool process_half_group(
                 nnz += __float_as_int(theirs);
 #pragma unroll
             for (int jp = 0; jp < 4; jp++) {
-                const f2 a0 = half ? other[jp] : approx[jp], a1 = half ? approx[jp] : other[jp];
-                f2 t0 = (a0 + a1) * HAAR_C, t1 = (a0 - a1) * HAAR_C;
-                if constexpr (WIENER) {
-                    const f2 b0 = half ? other[4 + jp] : approx[4 + jp];
-                    const f2 b1 = half ? approx[4 + jp] : other[4 + jp];
-                    const f2 u0 = (b0 + b1) * HAAR_C, u1 = (b0 - b1) * HAAR_C;
-                    const f2 W0 = wiener_w2(u0 * u0, sigma2, sw);
-                    const f2 W1 = wiener_w2(u1 * u1, sigma2, sw);
-                    t0 = W0 * t0;
-                    t1 = W1 * t1;
-                } else {
-                    const bool p0 = fabsf(t0.x) >= thr, p1 = fabsf(t0.y) >= thr;
-                    const bool q0 = fabsf(t1.x) >= thr, q1 = fabsf(t1.y) >= thr;
-                    nnz += (p0 ? 1 : 0) + (p1 ? 1 : 0) + (q0 ? 1 : 0) + (q1 ? 1 : 0);
-                    t0 = mk2(p0 ? t0.x : 0.0f, p1 ? t0.y : 0.0f);
-                    t1 = mk2(q0 ? t1.x : 0.0f, q1 ? t1.y : 0.0f);
+                f2 t[2], u[2];
+#pragma unroll
+                for (int c = 0; c < 2; c++) {
+                    t[c] = bfly_sel(c, c, first[jp], second[jp]);
+                    if constexpr (WIENER) u[c] = bfly_sel(c, c, first[4 + jp], second[4 + jp]);
                 }
-                top[jp] = half ? (t0 - t1) * HAAR_C : (t0 + t1) * HAAR_C;
-                if constexpr (WIENER) __builtin_amdgcn_sched_barrier(0);      // as in wiener_half_local
+#pragma unroll
+                for (int c = 0; c < 2; c++) {
+                    f2 tt = t[c] * HAAR_C;
+                    if constexpr (WIENER) {
+                        const f2 uu = u[c] * HAAR_C;
+                        tt = wiener_w2(uu * uu, sigma2, sw) * tt;
+                    } else {
+                        const float k0 = ht_keep(tt.x, thr, nnz), k1 = ht_keep(tt.y, thr, nnz);
+                        tt = mk2(k0, k1);
+                    }
+                    X[2 * jp + c][0].x = (tt.x + __uint_as_float(__float_as_uint(tt.y) ^ smask)) * HAAR_C;
+                }
+                if constexpr (WIENER) __builtin_amdgcn_sched_barrier(0);      // two Newton chains at a time
             }
         } else {
+            // one-block group: the block's own coefficients, two planes per weight pair
 #pragma unroll
             for (int jp = 0; jp < 4; jp++) {
+                const float x0 = X[2 * jp][0].x, x1 = X[2 * jp + 1][0].x;
                 if constexpr (WIENER) {
-                    const f2 W = wiener_w2(approx[4 + jp] * approx[4 + jp], sigma2, sw);
-                    top[jp] = W * approx[jp];
+                    const float y0 = Y[2 * jp][0].x, y1 = Y[2 * jp + 1][0].x;
+                    const f2 W = wiener_w2(mk2(y0 * y0, y1 * y1), sigma2, sw);
+                    X[2 * jp][0].x = W.x * x0;
+                    X[2 * jp + 1][0].x = W.y * x1;
                 } else {
-                    const bool p0 = fabsf(approx[jp].x) >= thr, p1 = fabsf(approx[jp].y) >= thr;
-                    nnz += (p0 ? 1 : 0) + (p1 ? 1 : 0);
-                    top[jp] = mk2(p0 ? approx[jp].x : 0.0f, p1 ? approx[jp].y : 0.0f);
+                    X[2 * jp][0].x = ht_keep(x0, thr, nnz);
+                    X[2 * jp + 1][0].x = ht_keep(x1, thr, nnz);
                 }
             }
         }
-        half_unshrink_local<KH>(S, top);
+        // Inverse Haar over the half: X[j][0] = (approximation, top detail) again.
+        if constexpr (KH > 1) {
+#pragma unroll
+            for (int j = 0; j < 8; j++) haar_inv_lower<KH>(X[j], haar_l1(X[j][0]));
+        }
         // group weight u = 1 / max(statistic, 1) (IEEE division).  Both statistics are
         // integers, so neither the split into halves nor the order of the lane reduction matters.
         float w;
@@ -791,8 +809,8 @@ __device__ __forceinline__ bool process_half_group(
             for (int kl = 0; kl < KH; kl += 4) {
 #pragma unroll
                 for (int j = 0; j < 8; j++) {
-                    v2[j] = mk2(S[j >> 1][2 * kl + (j & 1)], S[j >> 1][2 * kl + 2 + (j & 1)]);
-                    w2[j] = mk2(S[j >> 1][2 * kl + 4 + (j & 1)], S[j >> 1][2 * kl + 6 + (j & 1)]);
+                    v2[j] = X[j][kl / 2];
+                    w2[j] = X[j][kl / 2 + 1];
                 }
                 pair_inv_x2<WIENER>(T, tb, hi, lo, v2, w2);
                 STAMP(tl1);
@@ -813,8 +831,7 @@ __device__ __forceinline__ bool process_half_group(
                 constexpr bool two = KH > 1;
                 const int kl2 = two ? kl + 1 : kl;
 #pragma unroll
-                for (int j = 0; j < 8; j++)
-                    v2[j] = mk2(S[j >> 1][2 * kl + (j & 1)], S[j >> 1][2 * kl2 + (j & 1)]);
+                for (int j = 0; j < 8; j++) v2[j] = two ? X[j][kl / 2] : mk2(X[j][0].x, X[j][0].x);
                 pair_inv<WIENER>(T, tb, hi, lo, v2);
                 STAMP(tl1);
                 gate(kb + kl);
@@ -856,10 +873,10 @@ __device__ __forceinline__ bool process_half_group(
 }
 
 typedef Dct7 HalfTable;       // seven scalars instead of a 64-entry table in SGPRs (dct_pairs.h)
-template <bool WIENER>
-__global__ __launch_bounds__(HalfCfg<WIENER>::NW * 64) void stage_half_kernel(
+template <bool WIENER, bool SEPVOL>
+__device__ __forceinline__ void stage_half_body(
     const float* __restrict__ noisy_all, const float* __restrict__ basic_all,
-    const uint32_t* __restrict__ keys_all, VolGeom g, HalfTable T, const float* __restrict__ win_g,
+    const uint32_t* __restrict__ keys_all, const VolGeom& g, const HalfTable& T, const float* __restrict__ win_g,
     float thr, float sigma2, const double* __restrict__ qscale, long long* __restrict__ num_all,
     unsigned long long* __restrict__ cvol_all, int tiles_x, int layers_per_chunk, const f2* __restrict__ pair_all,
     int strip) {
@@ -880,7 +897,7 @@ __global__ __launch_bounds__(HalfCfg<WIENER>::NW * 64) void stage_half_kernel(
     const size_t voff = (size_t)blockIdx.z * (size_t)g.nvox;
     const float* __restrict__ noisy = noisy_all + voff;
     const float* __restrict__ basic = WIENER ? basic_all + voff : nullptr;
-    const f2* __restrict__ pair = (WIENER && pair_all) ? pair_all + voff : nullptr;
+    const f2* __restrict__ pair = (WIENER && !SEPVOL) ? pair_all + voff : nullptr;
     long long* __restrict__ num = num_all + voff;
     unsigned long long* __restrict__ cvol = cvol_all + voff;
     const double up = qscale[2 * blockIdx.z];              // 2^(43 - E) of this volume
@@ -990,7 +1007,7 @@ __global__ __launch_bounds__(HalfCfg<WIENER>::NW * 64) void stage_half_kernel(
             else
                 __builtin_amdgcn_s_setprio(0);
         }
-        const bool closer = process_half_group<WIENER>(
+        const bool closer = process_half_group<WIENER, SEPVOL>(
             noisy, basic, kk, z0, ry, rx, tg, sy, sz, tab, win, win_g, thr, sigma2, up, ring, cvol, tb,
             partner_tb, lock, sync, cnt, wave, seq, seen, layer, 2 * nrefs, lane, g.nvox, num, g, izb, pair
 #ifdef EXABM4D_STAMPS
@@ -1067,6 +1084,27 @@ __global__ __launch_bounds__(256) void interleave_pair_kernel(const float* __res
         }
     }
 }
+template <bool WIENER>
+__global__ __launch_bounds__(HalfCfg<WIENER>::NW * 64) void stage_half_kernel(
+    const float* __restrict__ noisy_all, const float* __restrict__ basic_all,
+    const uint32_t* __restrict__ keys_all, VolGeom g, HalfTable T, const float* __restrict__ win_g,
+    float thr, float sigma2, const double* __restrict__ qscale, long long* __restrict__ num_all,
+    unsigned long long* __restrict__ cvol_all, int tiles_x, int layers_per_chunk, const f2* __restrict__ pair_all,
+    int strip) {
+    stage_half_body<WIENER, false>(noisy_all, basic_all, keys_all, g, T, win_g, thr, sigma2, qscale, num_all, cvol_all,
+                                   tiles_x, layers_per_chunk, pair_all, strip);
+}
+// Wiener stage without the interleaved volume (pair_all is not read).
+__global__ __launch_bounds__(HalfCfg<true>::NW * 64) void stage_half_sep_kernel(
+    const float* __restrict__ noisy_all, const float* __restrict__ basic_all,
+    const uint32_t* __restrict__ keys_all, VolGeom g, HalfTable T, const float* __restrict__ win_g,
+    float thr, float sigma2, const double* __restrict__ qscale, long long* __restrict__ num_all,
+    unsigned long long* __restrict__ cvol_all, int tiles_x, int layers_per_chunk, const f2* __restrict__ pair_all,
+    int strip) {
+    stage_half_body<true, true>(noisy_all, basic_all, keys_all, g, T, win_g, thr, sigma2, qscale, num_all, cvol_all,
+                                tiles_x, layers_per_chunk, pair_all, strip);
+}
+
 // One collaborative-filtering stage (basic == NULL: hard threshold; else Wiener).  Adds the numerator
 // terms to `num` (int64, units of 2^(43 - E) as qscale[2 b] says for volume b) and every block's weight
 // rint(u 2^40) to its corner voxel in `cw`; the caller zeroes both and turns cw into the denominator
@@ -1104,9 +1142,6 @@ hipError_t launch_stage(const float* noisy, const float* basic, const uint32_t* 
         hchunks = (g.gz + hlpc - 1) / hlpc;
         const dim3 hgrid((unsigned)(hty * htx), (unsigned)hchunks, (unsigned)batch);
         const size_t lds = sizeof(float) * C::LDS_FLOATS;
-        hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&stage_half_kernel<W>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err != hipSuccess) return err;
         const f2* pairvol = nullptr;
         // (the interleaving kernel reads both volumes with 16-byte loads: a caller's view that is only
         // float-aligned takes the separate gathers, which give the same bits)
@@ -1117,7 +1152,11 @@ hipError_t launch_stage(const float* noisy, const float* basic, const uint32_t* 
                 hipLaunchKernelGGL(interleave_pair_kernel, dim3(65536), dim3(256), 0, stream, noisy, basic, pv, n);
             pairvol = pv;
         }
-        hipLaunchKernelGGL(stage_half_kernel<W>, hgrid, dim3(C::NW * 64), lds, stream, noisy, basic, keys,
+        auto* kern = (W && !pairvol) ? &stage_half_sep_kernel : &stage_half_kernel<W>;
+        hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (err != hipSuccess) return err;
+        hipLaunchKernelGGL(kern, hgrid, dim3(C::NW * 64), lds, stream, noisy, basic, keys,
                            g, HT, win_dev, thr, sigma2, qscale, num, cw, htx, hlpc, pairvol, opt.strip);
         return hipGetLastError();
     };
