@@ -25,8 +25,10 @@ namespace exabm4d {
 // 4 exchange barriers, 5 selection, 6 carry waits (the poll and the tile's last drain), 7 wave lifetime.
 __device__ unsigned long long g_bm_stamps[8];
 // Slot 4 again, kept apart: [barrier of the (dz, pass): 2 round + (0 in front of / 1 behind the selection)][wave cz].
-// The wave that arrives last at a barrier waits least in it.
-__device__ unsigned long long g_bm_barrier_stamps[4][8];
+// The wave that arrives last at a barrier waits least in it.  Sized for the largest geometry (three rounds, twelve
+// waves); a geometry with fewer leaves the rest zero.
+constexpr int BM_STAMP_BARRIERS = 6, BM_STAMP_WAVES = 12;
+__device__ unsigned long long g_bm_barrier_stamps[BM_STAMP_BARRIERS][BM_STAMP_WAVES];
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -44,7 +46,7 @@ __device__ __forceinline__ void static_for(F&& f, std::integer_sequence<int, I..
     (f(std::integral_constant<int, I>{}), ...);
 }
 
-constexpr int TCZ = 8;       // cell layers per tile = waves per workgroup
+constexpr int TCZ = 8;       // cell layers per tile = waves per workgroup (the integer kernel: TileShape16::LAYERS)
 constexpr int NE = 6;        // dy values per pass (two passes: dy = -5..0 and 1..6, 6 is masked)
 constexpr int NSTEP = SWIN * 2 * 4;             // (dz, pass, z) steps
 // A wave is one z-layer of TCY x TCX cells (64 lanes).  8 x 8 is the shape for volumes; 4 x 16
@@ -94,10 +96,16 @@ struct TileShape : TilePlan<TCY_, TCX_> {
 // void -- and the host reports EXABM4D_ERR_HIP at its next synchronisation and switches the carry off for
 // the context (exabm4d_api.hip: check_async_status); never a hang.  All carry traffic is system-scope (stores written through,
 // loads and the LDS-DMA prefetch with sc0 sc1): no assumption about which XCD's L2 a tile runs on.  Wave 0
-// fetches a (dz, pass)'s two rounds by LDS-DMA one plane ahead of their use: no registers, no wait in
+// fetches a (dz, pass)'s whole slot by LDS-DMA one plane ahead of its use: no registers, no wait in
 // front of the exchange barriers.  The same sums enter the same adds: tables are unchanged.
-constexpr int CARRY_ROUND = (NE / 2) * SWIN * 64;                 // elements of one exchange round (33 x 64)
-constexpr int CARRY_TILE = (NSTEP / 4) * 2 * CARRY_ROUND;         // one tile's top layer: 22 (dz, pass) x 2 rounds
+// SLOT LAYOUT.  The slot of a (dz, pass) is linear [dy row e = 0 .. 5][d = 0 .. 10][64 cells], 2 * CARRY_ROUND
+// elements, in global memory and in lower0 alike: dy row e lies at e * SWIN * 64 however many rows an exchange round
+// publishes.  The 8-layer tiles exchange three rows per round (two rounds, the second at CARRY_ROUND), the integer
+// kernel's 12-layer tiles two rows (three rounds, at 0, 2 and 4 * SWIN * 64; TileShape16::XROWS): the carrying wave
+// stores and wave 0 reads round e0 at e0 * SWIN * 64 in both, so the slot's size, the prefetch of a whole slot and
+// the done[] protocol do not depend on the round size (tests/test_bm_layers_gpu.py forces the carry in both).
+constexpr int CARRY_ROUND = (NE / 2) * SWIN * 64;                 // half a (dz, pass): three dy rows of 11 sums x 64 cells
+constexpr int CARRY_TILE = (NSTEP / 4) * 2 * CARRY_ROUND;         // one tile's top layer: 22 (dz, pass) x 6 dy rows
 struct Carry {
     int on;                  // 1: tiles advance by TCZ cell layers and carry their top layer
     int strip;               // tile order inside a slab: strips of this many tile rows, column-major (0 = raster)
@@ -108,11 +116,11 @@ struct Carry {
     int fault;               // debug option "bm_carry_fault": every wait counts as run out (tests of the error path)
 };
 constexpr int CARRY_POLL_LIMIT = 1 << 23;       // x s_sleep(32) = 2048 cycles: ~7 s at 2.4 GHz
-// Both rounds of one (dz, pass) into `dst` (2 * CARRY_ROUND elements, linear): 16 full 1 KB transfers
+// The whole slot of one (dz, pass) into `dst` (2 * CARRY_ROUND elements, linear): 16 full 1 KB transfers
 // and one of 512 bytes.
 template <class T, class D>
 __device__ __forceinline__ void carry_prefetch(const T* src, D* dst, int lane) {
-    static_assert(2 * CARRY_ROUND == 16 * 256 + 128, "two rounds = 16.5 KB");
+    static_assert(2 * CARRY_ROUND == 16 * 256 + 128, "a slot = 16.5 KB");
 #pragma unroll
     for (int i = 0; i < 16; i++)
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 256 * i + 4 * lane),
@@ -563,9 +571,20 @@ __global__ __launch_bounds__(512) void bm_tile_kernel(const float* __restrict__ 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-template <int TCY_, int TCX_>
+// LAYERS: cell layers per tile = waves per workgroup, 8 or 12.  The fp32 kernel needs 249-252
+// registers and stays at TCZ = 8, two waves per SIMD; the integer kernel's 166 fit three (168 at most), and its LDS
+// does not stand in the way either: what made a plane buffer 2112 dwords was never the plane (PLANE_DW = 1280) but
+// the cell-sum exchange of HALF a pass at a time, three dy rows of 11 sums for 64 cells.  The exchange round is
+// therefore a constant of the shape, XROWS dy rows: the most whose sums fit a wave's share of the CU's 160 KB next
+// to lower0 -- 3 rows for 8 waves, as before, and 2 rows for 12 (12 x 2 x 1408 dwords = 8 x 2 x 2112: the same LDS
+// to the byte).  A pass of 6 / 5 rows then takes rounds of 3 + 3 / 3 + 2 rows, or of 2 + 2 + 2 / 2 + 2 + 1.
+// Nothing else moves: the sums, the order of the adds and of the candidates are those of the 8-layer tile.
+constexpr int LDS_CU_BYTES = 160 * 1024;
+constexpr int LOWER0_DW = 2 * CARRY_ROUND + 64;           // wave 0's lower cell layer: a whole (dz, pass) + the y overhang
+template <int TCY_, int TCX_, int LAYERS_ = TCZ>
 struct TileShape16 : TilePlan<TCY_, TCX_> {
     using Plan = TilePlan<TCY_, TCX_>;
+    static constexpr int LAYERS = LAYERS_;
     static constexpr int PCOLS = ((4 * TCX_ + 10 + 7) / 8) * 8;   // staged uint16 columns (48 / 80)
     // row stride in uint16: two cell rows of a 32-lane ds_read_b64 group must fall into different
     // 16-bank windows (8 x 8: 56 = 24 mod 32), one 16-lane cell row is 32 banks (4 x 16: 80 = 16 mod 32)
@@ -573,20 +592,36 @@ struct TileShape16 : TilePlan<TCY_, TCX_> {
     static constexpr int PCH = PSTR / 8;                          // 16-byte chunks per staged row
     static constexpr int NDMA = (Plan::PROWS * PCH + 63) / 64;
     static constexpr int PLANE_DW = NDMA * 256;                   // dwords of one plane buffer
-    static constexpr int XCH_DW = (NE / 2) * SWIN * 64;           // cell-sum exchange: 33 sums x 64 cells
+    // dwords a wave's plane buffer may take: the CU's LDS less lower0 and the launch position, over 2 LAYERS buffers
+    static constexpr int BUF_BUDGET_DW = ((LDS_CU_BYTES - 16) / 4 - LOWER0_DW) / (2 * LAYERS);
+    static constexpr int XROWS_FIT = BUF_BUDGET_DW / (SWIN * 64);
+    static constexpr int XROWS = XROWS_FIT < NE / 2 ? XROWS_FIT : NE / 2;     // dy rows per exchange round (3 / 2)
+    static constexpr int XCH_DW = XROWS * SWIN * 64;              // cell-sum exchange: 33 / 22 sums x 64 cells
     static constexpr int PBUF = PLANE_DW > XCH_DW ? PLANE_DW : XCH_DW;
+    // an upper bound, not the compiler's figure: 16 bytes stand for launch_position's 4-byte s_pos and any padding
+    // (8 and 12 layers: 152 336 here, 152 324 in the code object)
+    static constexpr int LDS_BYTES = (LAYERS * 2 * PBUF + LOWER0_DW) * 4 + 16;
+    // Exchange rounds of a pass of `rows` dy values, and the workgroup barriers of a tile: two per round, around
+    // the selection.  The waves that work and the idle waves of a column's last tile take their counts from HERE,
+    // both of them: a wave that passes one barrier fewer than the others leaves them waiting for ever.
+    static constexpr int rounds(int rows) { return (rows + XROWS - 1) / XROWS; }
+    static constexpr int TILE_BARRIERS = SWIN * 2 * (rounds(NE) + rounds(NE - 1));
     static_assert(PCOLS <= PSTR, "staged columns fit the row");
+    static_assert(XROWS >= 1 && PBUF >= PLANE_DW && PBUF >= XCH_DW, "a buffer holds a plane and an exchange round");
+    static_assert(LDS_BYTES <= LDS_CU_BYTES, "one workgroup's LDS fits the CU");
+    static_assert(64 * LAYERS <= 1024, "one wave per cell layer");
 };
 
 template <class TS>
-__global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restrict__ vol_all, VolGeom g,
+__global__ __launch_bounds__(64 * TS::LAYERS) void bm_tile16_kernel(const uint16_t* __restrict__ vol_all, VolGeom g,
                                                         uint32_t keymax,
                                                         uint32_t* __restrict__ keys_all, int tiles_y,
                                                         int tiles_x, int xcd_q, int nbatch, Carry carry) {
     constexpr int TCX = TS::TCX, TRX = TS::TRX, TRY = TS::TRY, PROWS = TS::PROWS, PCOLS = TS::PCOLS,
-                  PSTR = TS::PSTR, PCH = TS::PCH, NDMA = TS::NDMA, PBUF = TS::PBUF;
-    __shared__ __align__(16) uint32_t pbuf_all[TCZ][2][PBUF];
-    __shared__ __align__(16) uint32_t lower0[2 * CARRY_ROUND + 64];   // wave 0's lower cell layer (from the carry), both rounds
+                  PSTR = TS::PSTR, PCH = TS::PCH, NDMA = TS::NDMA, PBUF = TS::PBUF, LAYERS = TS::LAYERS,
+                  XROWS = TS::XROWS;
+    __shared__ __align__(16) uint32_t pbuf_all[LAYERS][2][PBUF];
+    __shared__ __align__(16) uint32_t lower0[LOWER0_DW];   // wave 0's lower cell layer (from the carry), all rounds of a (dz, pass)
 
     TileId id;
     if (!tile_id(id, tiles_y, tiles_x, xcd_q, nbatch, carry)) return;
@@ -599,12 +634,12 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     const int ix = TRX * tx + cx, iy = TRY * ty + cy;
     const size_t sy = (size_t)g.nx, sz = (size_t)g.nx * (size_t)g.ny;
 #ifdef EXABM4D_BM_STAMPS
-    unsigned long long st[8] = {}, stb[4] = {};
+    unsigned long long st[8] = {}, stb[BM_STAMP_BARRIERS] = {};
     const unsigned long long tk0 = stamp();
 #endif
 
     // cell layers a tile advances by (CARRY above); this tile's column and its two carry slots
-    const int Ls = (carry.on ? TCZ : TCZ - 1) * tz;
+    const int Ls = (carry.on ? LAYERS : LAYERS - 1) * tz;
     const uint32_t* carry_rd = carry.buf + ((size_t)((tz + 1) & 1) * cols + col) * CARRY_TILE;
     uint32_t* carry_wr = carry.buf + ((size_t)(tz & 1) * cols + col) * CARRY_TILE;
     int* done_col = carry.done + col;
@@ -629,7 +664,7 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     const int qz = min(STEP * L, g.nz - STEP);
     const int Z0 = STEP * L;
     const bool lower_carried = carry.on && cz == 0 && tz > 0;          // the lower layer is the tile below's top layer
-    const bool carries = carry.on && cz == TCZ - 1 && L + 1 <= g.az;   // ... and this wave's sums are the next tile's
+    const bool carries = carry.on && cz == LAYERS - 1 && L + 1 <= g.az;   // ... and this wave's sums are the next tile's
     const bool ref_ok = ref_yx && active && (cz > 0 || lower_carried);
     {
         STAMP(c0);
@@ -727,8 +762,8 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
 
     if (!active) {
         // a wave whose cell layer lies beyond the last one any reference block uses only keeps the
-        // workgroup's barrier count: four per (dz, pass)
-        for (int i = 0; i < (NSTEP / 4) * 4; i++) __syncthreads();
+        // workgroup's barrier count: two per exchange round (TileShape16::TILE_BARRIERS, as pass_end below)
+        for (int i = 0; i < TS::TILE_BARRIERS; i++) __syncthreads();
         break;
     }
     issue_dma(0, pbuf(cz, 0));
@@ -851,7 +886,16 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     // The end of a pass, behind the accumulate block of its last step (z == 3): publish the sums, select, carry.
     auto pass_end = [&](auto NEc, const int step) {
         constexpr int NEP = decltype(NEc)::value;
-        constexpr int NR0 = (NEP + 1) / 2;                        // dy values of its first exchange round
+        // Exchange rounds of XROWS dy values, the last one of what is left.  The carry slot of a (dz, pass) -- in
+        // global memory and in lower0 alike -- is linear [dy row e][d][64 cells], whatever the rounds: round e0's
+        // sums lie at e0 * SWIN * 64 (CARRY_ROUND for the second round of three rows).  So the slot's size, the
+        // prefetch of a whole slot and the done[] protocol are the same for every round size.
+        // A round has two barriers; TS::rounds(NEP) is also what the idle waves' barrier count is made of.
+        constexpr int NR0 = XROWS, NROUND = TS::rounds(NEP);
+        static_assert((NROUND - 1) * NR0 < NEP && NROUND * NR0 >= NEP, "the rounds cover the pass's rows, none is empty");
+#ifdef EXABM4D_BM_STAMPS
+        static_assert(2 * NROUND <= BM_STAMP_BARRIERS, "a stamp slot per barrier");
+#endif
         const int dz = (step >> 3) - RAD;
         const int dylo = NEP == NE ? -RAD : 1;
         lds_u32* cur = pbuf(cz, step & 1);
@@ -871,7 +915,7 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
                 return c + right;
             };
 #pragma unroll
-            for (int e0 = 0; e0 < NEP; e0 += NR0) {
+            for (int e0 = 0; e0 < NEP; e0 += NR0) {         // NROUND rounds
 #pragma unroll
                 for (int e = e0; e < (e0 + NR0 < NEP ? e0 + NR0 : NEP); e++)
 #pragma unroll
@@ -889,7 +933,7 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
                         uint32_t Sv[1][SWIN];          // one dy row of sums at a time (registers)
 #pragma unroll
                         for (int d = 0; d < SWIN; d++) {
-                            const lds_u32* c0 = lo_w + (cz == 0 && e0 ? CARRY_ROUND : 0) + 64 * ((e - e0) * SWIN + d);
+                            const lds_u32* c0 = lo_w + (cz == 0 && e0 ? e0 * SWIN * 64 : 0) + 64 * ((e - e0) * SWIN + d);
                             const lds_u32* c1 = up_w + 64 * ((e - e0) * SWIN + d);
                             Sv[0][d] = (c0[0] + c0[TCX]) + (c1[0] + c1[TCX]);
                         }
@@ -917,13 +961,13 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
                 STAMP_ADD(5, b1, b2);
                 STAMP_ADD(4, b2, b3);
 #ifdef EXABM4D_BM_STAMPS
-                stb[e0 ? 2 : 0] += b1 - b0;
-                stb[e0 ? 3 : 1] += b3 - b2;
+                stb[2 * (e0 / NR0)] += b1 - b0;
+                stb[2 * (e0 / NR0) + 1] += b3 - b2;
 #endif
                 if (carries) {
                     // the top wave's sums are the next block's lowest layer (read there by wave 0 in
                     // this same round, i.e. before this slot is written again)
-                    uint32_t* cw = cslot + (size_t)(e0 ? CARRY_ROUND : 0);
+                    uint32_t* cw = cslot + (size_t)(e0 ? e0 * SWIN * 64 : 0);
 #pragma unroll
                     for (int e = e0; e < (e0 + NR0 < NEP ? e0 + NR0 : NEP); e++)
 #pragma unroll
@@ -942,6 +986,9 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     // pass, its end: each accumulate body is a loop of its own, so the two bodies' register assignments meet
     // at a pass boundary, twice per dz, and not in front of every step.
     static_assert(NSTEP == 8 * SWIN, "two passes of four planes per dz");
+    // ... and the barriers of all that: what an idle wave counts off above
+    static_assert(TS::TILE_BARRIERS == (NSTEP / 8) * 2 * (TS::rounds(NE) + TS::rounds(NE - 1)),
+                  "idle and working waves pass the same number of barriers");
 #pragma unroll 1
     for (int step0 = 0; step0 < NSTEP; step0 += 8) {
 #pragma unroll 1
@@ -956,7 +1003,7 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     } while (false);
 
     if (carry.on) {
-        // the tile is finished when wave 7's stores have been acknowledged and wave 0's last prefetch has landed
+        // the tile is finished when the top wave's stores have been acknowledged and wave 0's last prefetch has landed
         STAMP(c0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -969,7 +1016,7 @@ __global__ __launch_bounds__(512) void bm_tile16_kernel(const uint16_t* __restri
     if (lane == 0)
         for (int i = 0; i < 8; i++) atomicAdd(&g_bm_stamps[i], st[i]);
     if (lane == 0)
-        for (int i = 0; i < 4; i++) atomicAdd(&g_bm_barrier_stamps[i][tid >> 6], stb[i]);
+        for (int i = 0; i < BM_STAMP_BARRIERS; i++) atomicAdd(&g_bm_barrier_stamps[i][tid >> 6], stb[i]);
 #endif
 }
 
@@ -980,9 +1027,9 @@ extern "C" void exabm4d_debug_bm_stamps(unsigned long long* out, int reset) {
     (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bm_stamps), sizeof(z));
     if (reset) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bm_stamps), z, sizeof(z));
 }
-// out[4][8]: cycles in each of the four barriers of a (dz, pass), per wave index
+// out[6][12]: cycles in each of the (up to six) barriers of a (dz, pass), per wave index
 extern "C" void exabm4d_debug_bm_barrier_stamps(unsigned long long* out, int reset) {
-    unsigned long long z[4][8] = {};
+    unsigned long long z[BM_STAMP_BARRIERS][BM_STAMP_WAVES] = {};
     (void)hipDeviceSynchronize();
     (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bm_barrier_stamps), sizeof(z));
     if (reset) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bm_barrier_stamps), z, sizeof(z));
@@ -1089,6 +1136,12 @@ __global__ __launch_bounds__(64) void bm_generic_kernel(const float* __restrict_
 // Tile shape: fewer (y, x) tiles = fewer idle cell lanes (64^3 patches: 5 flat tiles against 9 cubes)
 using Cube = TilePlan<8, 8>;
 using Flat = TilePlan<4, 16>;
+// Cost of a cell layer in the 12-layer tile (three waves per SIMD, three exchange rounds per pass) over that in
+// the 8-layer tile.  Measured with the integer kernel at 1024^3 in slab order with the carry, A/B/A/B on one device,
+// twice (profiles/bmlayers/ab.json, "layer_cost_ratio"): 22 tiles x 12 layers in 86.9 ms against 32 x 8 in 91.6-91.8 ms,
+// (86.9 / 264) / (91.6 / 256) = 0.920, 0.920, 0.919, 0.919 in the four pairs.  Launches without the carry have not
+// been measured at 12 layers and keep 8.
+constexpr double BM_LAYER_COST_12_OVER_8 = 0.92;
 static bool flat_tiles(const VolGeom& g) {
     auto tiles = [&](int try_, int trx) {
         return (long long)((g.ay + try_ - 1) / try_) * ((g.ax + trx - 1) / trx);
@@ -1106,18 +1159,41 @@ BmPlan bm_plan(const VolGeom& g, int batch, const BmOpts& opt) {
     p.ty = (g.ay + try_ - 1) / try_;
     p.tx = (g.ax + trx - 1) / trx;
     const long long cols = (long long)p.ty * p.tx * batch;          // columns of tiles: (batch element, ty, tx)
-    const int tz7 = (g.az + TCZ - 2) / (TCZ - 1), tz8 = g.az / TCZ + 1;
+    // tiles of a column: of `l` cell layers without the carry (l - 1 reference layers each) and with it
+    auto tz7_of = [&](int l) { return (g.az + l - 2) / (l - 1); };
+    auto tz8_of = [&](int l) { return g.az / l + 1; };
     const bool slab = opt.xcd_mode != 0 && cols >= 512;
+    // Cell layers per tile of the integer kernel (bm_layers).  Automatic: 12 for the cube shape
+    // where the launch is in slab order with the carry on -- the large volumes -- and the 12-layer tiles of a column
+    // cost no more than its 8-layer tiles: a column's time is its tiles x layers x the geometry's cost per layer,
+    // and a column's last tile counts in full whatever part of it is idle.  BM_LAYER_COST_12_OVER_8 is that cost
+    // ratio as measured (see its comment).  Patches, small volumes and launches without the carry keep 8.
     // The carry pays where it saves a tile per column (a 64^3 patch: 15 reference layers = 3 tiles without,
     // 2 with) AND a slab is a couple of rounds of the 256 CUs: a tile waits for the tile below it, and when
     // both are resident together the upper one only spins on a CU (a single small volume gains nothing).
-    const bool worth = tz8 >= 2 && tz8 < tz7 && slab;
     // 744 KB per column (+ done[columns] + the ticket counter): beyond 16 GB the launch goes without
     const size_t need = 2 * (size_t)cols * CARRY_TILE * sizeof(uint32_t) + ((size_t)cols + 64) * sizeof(int);
-    p.carry = (opt.carry != 0 && (worth || (opt.carry == 2 && tz8 >= 2)) && need <= ((size_t)16 << 30)) ? 1 : 0;
+    const bool fits = need <= ((size_t)16 << 30);
+    auto worth_of = [&](int l) { return tz8_of(l) >= 2 && tz8_of(l) < tz7_of(l) && slab; };
+    int layers = TCZ;
+    if (opt.layers == 12 && !p.flat) layers = 12;
+    if (opt.layers == 0 && !p.flat && opt.carry != 0 && fits && worth_of(TCZ) && worth_of(12) &&
+        tz8_of(12) * 12 * BM_LAYER_COST_12_OVER_8 <= tz8_of(TCZ) * TCZ)
+        layers = 12;
+    p.layers = layers;
+    const int tz7 = tz7_of(layers), tz8 = tz8_of(layers);
+    const bool worth = worth_of(layers);
+    p.carry = (opt.carry != 0 && (worth || (opt.carry == 2 && tz8 >= 2)) && fits) ? 1 : 0;
     p.carry_bytes = p.carry ? need : 0;
     p.tz = p.carry ? tz8 : tz7;
-    p.xq = (p.carry || (slab && p.tz >= 2)) ? (int)((cols + 7) / 8) : 0;
+    // ONE plan serves the integer and the fp32 launch of a call.  The carry and the slab order are decided from the
+    // integer kernel's tile counts and hold for the fp32 kernel too, which launches tz_f32 slabs of TCZ layers: a
+    // FORCED bm_layers = 12 can therefore change the fp32 launch's carry and order as well (correct either way: the
+    // carry on means az >= 12, two 8-layer tiles at least; a one-tile column with the carry on carries nothing), and
+    // a one-slab 12-layer launch goes in slab order where its 8-layer form has two slabs.  The automatic rule asks
+    // for worth_of(8) AND worth_of(12): it changes neither for any launch.
+    p.tz_f32 = p.carry ? tz8_of(TCZ) : tz7_of(TCZ);
+    p.xq = (p.carry || (slab && (p.tz >= 2 || p.tz_f32 >= 2))) ? (int)((cols + 7) / 8) : 0;
     p.strip = (opt.xcd_mode >= 2 && p.xq) ? opt.xcd_mode : 0;
     p.fault = opt.carry_fault;
     return p;
@@ -1148,17 +1224,24 @@ hipError_t launch_blockmatch(const float* vol, const VolGeom& g, int batch, uint
         if (vol16 &&
             ((unsigned long long)Cube::PROWS * (unsigned long long)g.nx + 80ull) * 2ull >= (1ull << 32))
             return hipErrorInvalidValue;
-        const dim3 grid((unsigned)(p.xq ? 8 * p.xq * p.tz : p.tz * p.ty * p.tx), (unsigned)(p.xq ? 1 : batch));
+        if (p.layers != TCZ && (p.layers != 12 || p.flat)) return hipErrorInvalidValue;
+        const int tz = vol16 ? p.tz : p.tz_f32;       // the fp32 kernel's tiles have TCZ layers whatever the plan's
+        const dim3 grid((unsigned)(p.xq ? 8 * p.xq * tz : tz * p.ty * p.tx), (unsigned)(p.xq ? 1 : batch));
         auto launch = [&](auto plan) {          // the kernel for the volume's type, in the plan's tile shape
             using Shape16 = TileShape16<decltype(plan)::TCY, decltype(plan)::TCX>;
             using Shape = TileShape<decltype(plan)::TCY, decltype(plan)::TCX>;
             if (vol16)
-                hipLaunchKernelGGL(bm_tile16_kernel<Shape16>, grid, dim3(512), 0, stream, vol16, g, keymax, keys,
-                                   p.ty, p.tx, p.xq, batch, carry);
+                hipLaunchKernelGGL(bm_tile16_kernel<Shape16>, grid, dim3(64 * Shape16::LAYERS), 0, stream, vol16, g,
+                                   keymax, keys, p.ty, p.tx, p.xq, batch, carry);
             else
                 hipLaunchKernelGGL(bm_tile_kernel<Shape>, grid, dim3(512), 0, stream, vol, g, keymax, keys, p.ty,
                                    p.tx, guarded, p.xq, batch, carry);
         };
+        if (vol16 && p.layers == 12) {          // the cube's 12-layer tile, three waves per SIMD
+            using Shape12 = TileShape16<Cube::TCY, Cube::TCX, 12>;
+            hipLaunchKernelGGL(bm_tile16_kernel<Shape12>, grid, dim3(64 * Shape12::LAYERS), 0, stream, vol16, g, keymax,
+                               keys, p.ty, p.tx, p.xq, batch, carry);
+        } else
         if (p.flat)
             launch(Flat{});
         else

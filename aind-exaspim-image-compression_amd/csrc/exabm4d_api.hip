@@ -300,6 +300,11 @@ int exabm4d_set_option(exabm4d_ctx* ctx, const char* name, int value) {
         ctx->bm.carry = value;
         return EXABM4D_OK;
     }
+    if (std::strcmp(name, "bm_layers") == 0) {          // integer block matching: cell layers per tile (0 automatic, 8 or 12 forced)
+        if (value != 0 && value != 8 && value != 12) return fail(ctx, EXABM4D_ERR_INVALID, "bm_layers must be 0, 8 or 12");
+        ctx->bm.layers = value;
+        return EXABM4D_OK;
+    }
     if (std::strcmp(name, "host_pipeline") == 0) {      // exabm4d_denoise_f32_host: large batches in overlapped sub-batches
         ctx->host_pipeline = value ? 1 : 0;
         return EXABM4D_OK;
@@ -417,7 +422,9 @@ int exabm4d_blockmatch_plan(const exabm4d_ctx* ctx, int nz, int ny, int nx, int 
     const int rc = make_geom(nullptr, nz, ny, nx, batch, g);
     if (rc) return rc;
     const BmPlan p = bm_plan(g, batch, ctx ? ctx->bm : BmOpts());
-    plan[0] = p.tz; plan[1] = p.ty; plan[2] = p.tx; plan[3] = p.xq; plan[4] = p.carry; plan[5] = p.flat;
+    // plan[0] counts tiles of EIGHT cell layers, the fp32 kernel's launch of this plan, as it always has; where the
+    // integer kernel takes 12 layers per tile (bm_layers) its launch has fewer slabs (BmPlan::tz)
+    plan[0] = p.tz_f32; plan[1] = p.ty; plan[2] = p.tx; plan[3] = p.xq; plan[4] = p.carry; plan[5] = p.flat;
     *carry_bytes = (uint64_t)p.carry_bytes;
     return EXABM4D_OK;
 }

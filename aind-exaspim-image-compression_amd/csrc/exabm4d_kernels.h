@@ -218,15 +218,18 @@ void label_downsample_box_plan(const void* win, int typesize, const BoxGeom& g, 
                                DsPlan& p);
 hipError_t launch_downsample_box_labels(const void* win, int typesize, const BoxGeom& g, const DsPlan& p, int zeros,
                                         void* out, hipStream_t s);
-// Options of block matching (per context since round 4; exabm4d_set_option "bm_xcd_mode" / "bm_carry" / "bm_carry_fault")
+// Options of block matching (per context since round 4; exabm4d_set_option "bm_xcd_mode" / "bm_carry" / "bm_carry_fault" / "bm_layers")
 struct BmOpts {
     int xcd_mode = 2;       // workgroup order: 0 = contiguous per XCD, 1 = all XCDs in one z slab of tiles (raster), n >= 2 = in strips of n tile rows
     int carry = 1;          // tiles of a column hand their top cell layer upwards (0 off, 1 automatic, 2 forced)
     int carry_fault = 0;    // debug: every carry wait counts as run out (the error path's test)
+    int layers = 0;         // cell layers per tile of the integer kernel: 0 automatic, 8 or 12 forced
 };
 // The launch block matching chooses for a geometry (bm_kernels.hip: bm_plan), evaluated once per launch
 struct BmPlan {
     int tz, ty, tx;         // tile slabs, tile rows, tile columns
+    int layers;             // cell layers per tile of the integer kernel (8 or 12); `tz` counts tiles of that many
+    int tz_f32;             // tile slabs of the fp32 kernel, always 8 layers per tile (= tz when layers == 8)
     int xq;                 // slab-order parameter (0: every XCD walks its own contiguous range)
     int carry;              // carry between the tiles of a column on
     int flat;               // 4 x 16 tile shape instead of 8 x 8

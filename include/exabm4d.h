@@ -128,7 +128,9 @@ int exabm4d_default_params(exabm4d_params* p);
  * so the wait always ends, and it is bounded besides: should it ever run out, the kernel raises a status word
  * instead of hanging, the next synchronising call (exabm4d_sync, exabm4d_memcpy_d2h, *_host, ...) returns
  * EXABM4D_ERR_HIP, and the carry is off for that context from then on (exabm4d_denoise_f32_host repeats its
- * run without the carry by itself).  "bm_carry_fault" = 1 (debug) makes every such wait count as run out; "bm_xcd_mode" = 0 | 1 | n (default 2): workgroup order of
+ * run without the carry by itself).  "bm_carry_fault" = 1 (debug) makes every such wait count as run out; "bm_layers" = 0 | 8 | 12 (default 0):
+ * cell layers per tile of the integer block-matching kernel, 0 = 12 for large volumes in slab order with the carry, else 8
+ * (tables are identical; any other value is EXABM4D_ERR_INVALID); "bm_xcd_mode" = 0 | 1 | n (default 2): workgroup order of
  * block matching; "host_pipeline" = 0 | 1 (default 1): exabm4d_denoise_f32_host cuts batches of >= 2^27 voxels
  * into sub-batches and copies under the kernels; "zero_overlap" = 0 | 1 (default 1): the 8-byte sums are zeroed on a second
  * stream of the context's, under the block matching that precedes each stage kernel, instead of in line
@@ -180,10 +182,11 @@ int exabm4d_tables(const exabm4d_params* p, float* dct64, float* win512);
  * the default options; the uint16 entry points add the fp32 + uint16 counts (6 bytes per voxel). */
 size_t exabm4d_scratch_bytes(int nz, int ny, int nx, int batch, int stages);
 
-/* The launch block matching chooses for a geometry (host logic only, no device call): plan = {tile slabs in z,
+/* The launch block matching chooses for a geometry (host logic only, no device call): plan = {tile slabs in z
+ * (of eight cell layers, the fp32 kernel's; the integer kernel's tiles have 12 where "bm_layers" says so: fewer slabs),
  * tile rows, tile columns, slab-order parameter (0: every XCD walks its own contiguous range), carry between
  * tiles on, flat 4 x 16 tile shape}; carry_bytes = the part of the context's scratch the
- * carry takes (0 without).  Follows ctx's options "bm_carry" / "bm_xcd_mode"; ctx == NULL: the defaults. */
+ * carry takes (0 without).  Follows ctx's options "bm_carry" / "bm_xcd_mode" / "bm_layers"; ctx == NULL: the defaults. */
 int exabm4d_blockmatch_plan(const exabm4d_ctx* ctx, int nz, int ny, int nx, int batch, int32_t plan[6],
                             uint64_t* carry_bytes);
 
