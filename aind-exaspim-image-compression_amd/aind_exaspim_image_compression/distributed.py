@@ -205,13 +205,15 @@ class SlabDenoiser:
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
             ctx.set_stream(stream.cuda_stream)
-            ctx.blockmatch(match_on, self.shape, self.sigma, c_match, self.keys, self.params)
-            ctx.stage(noisy, basic, self.keys, self.shape, self.sigma, self.num, self.den,
-                      self.params, data_exp=self.data_exp)
-            out = torch.empty(self.shape, dtype=torch.float32, device=self.device)
-            ctx.normalize(self.num, self.den, out, n)
-            stream.synchronize()
-            ctx.reset_stream()
+            try:
+                ctx.blockmatch(match_on, self.shape, self.sigma, c_match, self.keys, self.params)
+                ctx.stage(noisy, basic, self.keys, self.shape, self.sigma, self.num, self.den,
+                          self.params, data_exp=self.data_exp)
+                out = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+                ctx.normalize(self.num, self.den, out, n)
+                stream.synchronize()
+            finally:                    # an exception must not leave the context on the caller's stream
+                ctx.reset_stream()
         return out
 
     def stage1(self, noisy):
@@ -230,20 +232,22 @@ class SlabDenoiser:
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
             ctx.set_stream(stream.cuda_stream)
-            noisy = torch.empty(self.shape, dtype=torch.float32, device=self.device)
-            basic = torch.empty(self.shape, dtype=torch.float32, device=self.device)
-            ctx.counts_from_u16(raw, noisy, n, float(offset))
-            if offset_exact_in_fp32(offset):
-                ctx.blockmatch_u16(raw, self.shape, self.sigma, self.params.c_match_ht, self.keys,
+            try:
+                noisy = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+                basic = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+                ctx.counts_from_u16(raw, noisy, n, float(offset))
+                if offset_exact_in_fp32(offset):
+                    ctx.blockmatch_u16(raw, self.shape, self.sigma, self.params.c_match_ht, self.keys,
+                                       self.params)
+                else:                       # (float)v - offset is rounded: match on what stage 1 filters
+                    ctx.blockmatch(noisy, self.shape, self.sigma, self.params.c_match_ht, self.keys,
                                    self.params)
-            else:                       # (float)v - offset is rounded: match on what stage 1 filters
-                ctx.blockmatch(noisy, self.shape, self.sigma, self.params.c_match_ht, self.keys,
-                               self.params)
-            ctx.stage(noisy, None, self.keys, self.shape, self.sigma, self.num, self.den, self.params,
-                      data_exp=self.u16_exp)
-            ctx.normalize(self.num, self.den, basic, n)
-            stream.synchronize()
-            ctx.reset_stream()
+                ctx.stage(noisy, None, self.keys, self.shape, self.sigma, self.num, self.den, self.params,
+                          data_exp=self.u16_exp)
+                ctx.normalize(self.num, self.den, basic, n)
+                stream.synchronize()
+            finally:                    # an exception must not leave the context on the caller's stream
+                ctx.reset_stream()
         return noisy, basic
 
     def stage2_u16(self, noisy, basic, offset):
@@ -254,17 +258,19 @@ class SlabDenoiser:
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
             ctx.set_stream(stream.cuda_stream)
-            # the uint16 pipelines match stage 2 on the basic estimate rounded to counts;
-            # self.den is free until the stage call writes it
-            ctx.round_counts(basic, self.den, n, float(offset))
-            ctx.blockmatch(self.den, self.shape, self.sigma, self.params.c_match_wie, self.keys,
-                           self.params)
-            ctx.stage(noisy, basic, self.keys, self.shape, self.sigma, self.num, self.den, self.params,
-                      data_exp=self.u16_exp)
-            out = torch.empty(self.shape, dtype=torch.int16, device=self.device)
-            ctx.normalize_u16(self.num, self.den, out, n, float(offset))
-            stream.synchronize()
-            ctx.reset_stream()
+            try:
+                # the uint16 pipelines match stage 2 on the basic estimate rounded to counts;
+                # self.den is free until the stage call writes it
+                ctx.round_counts(basic, self.den, n, float(offset))
+                ctx.blockmatch(self.den, self.shape, self.sigma, self.params.c_match_wie, self.keys,
+                               self.params)
+                ctx.stage(noisy, basic, self.keys, self.shape, self.sigma, self.num, self.den, self.params,
+                          data_exp=self.u16_exp)
+                out = torch.empty(self.shape, dtype=torch.int16, device=self.device)
+                ctx.normalize_u16(self.num, self.den, out, n, float(offset))
+                stream.synchronize()
+            finally:                    # an exception must not leave the context on the caller's stream
+                ctx.reset_stream()
         return out
 
 
@@ -323,10 +329,12 @@ class ChunkedSlabDenoiser:
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
             ctx.set_stream(stream.cuda_stream)
-            ctx.denoise_chunked_u16(raw, out, shape, self.sigma, self.offset, chunk=self.chunk,
-                                    halo=self.halo, core=core, params=self.params)
-            stream.synchronize()
-            ctx.reset_stream()
+            try:
+                ctx.denoise_chunked_u16(raw, out, shape, self.sigma, self.offset, chunk=self.chunk,
+                                        halo=self.halo, core=core, params=self.params)
+                stream.synchronize()
+            finally:                    # an exception must not leave the context on the caller's stream
+                ctx.reset_stream()
         return out
 
 

@@ -471,48 +471,50 @@ def predict(img, model, transform, batch_size=32, patch_size=64, overlap=12, tri
 
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
-        ctx.set_stream(stream.cuda_stream)       # kernels and the model share one stream
-        src_u16 = img.dtype == np.uint16
-        host = np.ascontiguousarray(img if src_u16 else img.astype(np.float32))
-        d_raw = torch.from_numpy(host.view(np.int16) if src_u16 else host).to(dev)
-        vol = torch.empty(shape, dtype=torch.float32, device=dev)
-        transform.forward_device(ctx, d_raw, vol, n, src_u16)          # inference.py:69
-        del d_raw
-
-        accum_pred = torch.zeros(shape, dtype=torch.float32, device=dev)   # inference.py:81-82
-        accum_wgt = torch.zeros(shape, dtype=torch.float32, device=dev)
-        starts = list(generate_patch_starts(_ShapeOnly((1, 1) + shape), patch_size, overlap))
         pbar = None
-        if verbose:
-            from tqdm import tqdm
-            pbar = tqdm(total=len(starts), desc="Denoise")
-        batch = torch.empty((batch_size, 1, patch_size, patch_size, patch_size),
-                            dtype=torch.float32, device=dev)
-        with loop_amp():
-            for b0 in range(0, len(starts), batch_size):
-                chunk = np.asarray(starts[b0:b0 + batch_size], dtype=np.int32)
-                nb = len(chunk)
-                ctx.tile_gather(vol, shape, chunk, patch_size, batch)      # inference.py:153-168
-                # A short last batch is run at full size (rows beyond nb hold the previous batch's
-                # patches and are dropped): MIOpen then sees ONE input shape per volume instead of
-                # paying a solver search -- seconds -- for the tail's.  Only for modules in eval mode,
-                # whose output rows do not depend on the rest of the batch.
-                full = nb < batch_size and b0 > 0 and not getattr(model, "training", True)
-                with torch.no_grad(), call_amp():
-                    out = run(batch if full else batch[:nb])[:nb]      # inference.py:171-173
-                out = out.to(torch.float32).contiguous()
-                ctx.tile_accumulate(out, chunk, patch_size, trim, accum_pred, accum_wgt, shape)
-                if pbar is not None:
-                    pbar.update(nb)
-        del vol
-        result = torch.empty(shape, dtype=torch.int16, device=dev)
-        ctx.tile_finalize(transform.native_struct(), accum_pred, accum_wgt, result, n)
-        stream.synchronize()
-        out = result.cpu().numpy().view(np.uint16)
-        ctx.reset_stream()
+        ctx.set_stream(stream.cuda_stream)       # kernels and the model share one stream
+        try:
+            src_u16 = img.dtype == np.uint16
+            host = np.ascontiguousarray(img if src_u16 else img.astype(np.float32))
+            d_raw = torch.from_numpy(host.view(np.int16) if src_u16 else host).to(dev)
+            vol = torch.empty(shape, dtype=torch.float32, device=dev)
+            transform.forward_device(ctx, d_raw, vol, n, src_u16)          # inference.py:69
+            del d_raw
+
+            accum_pred = torch.zeros(shape, dtype=torch.float32, device=dev)   # inference.py:81-82
+            accum_wgt = torch.zeros(shape, dtype=torch.float32, device=dev)
+            starts = list(generate_patch_starts(_ShapeOnly((1, 1) + shape), patch_size, overlap))
+            if verbose:
+                from tqdm import tqdm
+                pbar = tqdm(total=len(starts), desc="Denoise")
+            batch = torch.empty((batch_size, 1, patch_size, patch_size, patch_size),
+                                dtype=torch.float32, device=dev)
+            with loop_amp():
+                for b0 in range(0, len(starts), batch_size):
+                    chunk = np.asarray(starts[b0:b0 + batch_size], dtype=np.int32)
+                    nb = len(chunk)
+                    ctx.tile_gather(vol, shape, chunk, patch_size, batch)      # inference.py:153-168
+                    # A short last batch is run at full size (rows beyond nb hold the previous batch's
+                    # patches and are dropped): MIOpen then sees ONE input shape per volume instead of
+                    # paying a solver search -- seconds -- for the tail's.  Only for modules in eval mode,
+                    # whose output rows do not depend on the rest of the batch.
+                    full = nb < batch_size and b0 > 0 and not getattr(model, "training", True)
+                    with torch.no_grad(), call_amp():
+                        out = run(batch if full else batch[:nb])[:nb]      # inference.py:171-173
+                    out = out.to(torch.float32).contiguous()
+                    ctx.tile_accumulate(out, chunk, patch_size, trim, accum_pred, accum_wgt, shape)
+                    if pbar is not None:
+                        pbar.update(nb)
+            del vol
+            result = torch.empty(shape, dtype=torch.int16, device=dev)
+            ctx.tile_finalize(transform.native_struct(), accum_pred, accum_wgt, result, n)
+            stream.synchronize()
+            out = result.cpu().numpy().view(np.uint16)
+        finally:                                    # an exception must not leave the context on the caller's stream
+            ctx.reset_stream()
+            if pbar is not None:
+                pbar.close()
     del run
-    if pbar is not None:
-        pbar.close()
     return out
 
 
